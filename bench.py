@@ -2,11 +2,19 @@
 """Headline benchmark: greedy bs=1 decode tokens/s of a random-init Llama-2-7B whose linear
 layers are E8P12 2-bit QuantLinear (BASELINE.json configs[1]), on N GPUs of one node.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 * a "step" is one decoded token = one pass of the hot path (224 QuantLinear forwards, plus the
   attention / norm / lm_head glue) replayed from a captured hipGraph;
+* a plain run builds the model (seeded: the same weights in every run), captures the step, replays W
+  untimed steps, times EXACTLY K steps, and prints the line: `value` = tokens/s of those K steps,
+  `ms_per_step` = their time / K;
+* --dump-outputs DIR: after the timed steps, what the last one gave its caller -- DIR/logits.npy
+  (float32, (1, vocab)) and DIR/next_token.npy (float64, (1,)) -- for comparing two builds;
+* --full: the timed region three times over (`value` = the median region), and the extras below: the
+  `roofline` launch, the teacher-forced parity check, the configs[4] prefill, the configs[2] / [3]
+  configurations, long contexts, the HF harness and the `cpu_baseline`;
 * multi-GPU = independent replicas (the Hadamard transform precludes tensor parallelism, SURVEY
   8e): every rank decodes its own sequence, no data-path collective; value = all ranks' tokens /
   max-over-ranks time; scaling "weak";
@@ -19,7 +27,7 @@ layers are E8P12 2-bit QuantLinear (BASELINE.json configs[1]), on N GPUs of one 
 * `cpu_baseline`: the CPU oracle (a port of the reference semantics: the reference has no CPU
   inference path) timed on this host for one layer of each Llama-7B shape and extrapolated to
   tokens/s.
-Prints ONE JSON line on rank 0."""
+Prints ONE JSON line on rank 0 (the roofline and the CPU baseline with --full only)."""
 import argparse
 import json
 import os
@@ -854,6 +862,25 @@ def aggregate_tokens_per_s(world, steps, dt):
     return world * steps / dt
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """write {name: array} as dirname/<name>.npy: floating arrays as float32, integer ones (token ids) as float64 (exact up
+    to 2^53); the whole dump stays under DUMP_LIMIT_BYTES"""
+    conv = {}
+    for name, x in arrays.items():
+        x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+        conv[name] = x.astype(np.float32 if np.issubdtype(x.dtype, np.floating) else np.float64)
+    total = sum(x.nbytes for x in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("outputs of %d bytes exceed the %d-byte dump limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, x in conv.items():
+        np.save(os.path.join(dirname, name + ".npy"), x)
+    return sorted(conv)
+
+
 def dist_selftest(a, rank, world):
     """replica plumbing only, no GPU: every rank "decodes" for a rank-dependent synthetic time"""
     import torch.distributed as dist
@@ -880,10 +907,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--model", default="7b", choices=["7b", "70b", "tiny"])
     ap.add_argument("--codebook", default="E8P12")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prefill", action="store_true", help="skip the configs[4] prefill extra of the N=1 7B line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the last step's outputs (logits, next token id) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="time the region three times (value = median) and add the extras: roofline launch, parity check, "
+                         "prefill, other configurations, HF harness, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-prefill", action="store_true", help="with --full: skip the configs[4] prefill extra of the N=1 7B line")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the configs[2] / [3] extras (70B E8P12, 7B E8P12RVQ4B, 7B D4) of the N=1 7B line")
+                    help="with --full: skip the configs[2] / [3] extras (70B E8P12, 7B E8P12RVQ4B, 7B D4) of the N=1 7B line")
     ap.add_argument("--dist-selftest", action="store_true",
                     help="exercise only the replica plumbing (rendezvous, barrier, max-over-ranks, rank-0 line) "
                          "with a synthetic per-rank time; runs on CPU with gloo (tests/test_bench_replicas.py)")
@@ -916,6 +948,9 @@ def main():
     # a 2048-slot static cache, as the reference's harness sets up (example_generate.py:66); the timed tokens sit at
     # positions [warmup, warmup + steps) of it in every repeat (config.workload says so)
     max_len = max(2048, a.steps + a.warmup + 8)
+    # the weights' draws are seeded: the random Hadamard factors (get_hadK: scipy, numpy's global generator) as well
+    np.random.seed(rank)
+    torch.manual_seed(rank)
     dec = D.LlamaDecoder(shape, a.codebook, max_len=max_len, device=f"cuda:{local_rank}", seed=rank,
                          device_init=(a.model == "70b"))
     dec.capture()
@@ -929,10 +964,10 @@ def main():
     import gc
     gc.collect()
     gc.disable()            # no collector pause (and no freeing of device memory) inside the timed region
-    # the contract's region -- W untimed steps, then EXACTLY K steps between two barriers -- three times over (same start
-    # state each time); `value` is the median region, `runs_tokens_per_s` all three
+    # the contract's region -- W untimed steps, then EXACTLY K steps between two barriers -- once (--full: three times over,
+    # same start state each time; `value` is the median region, `runs_tokens_per_s` all three)
     dts = []
-    for rep in range(3):
+    for rep in range(3 if a.full else 1):
         dec.reset(first_token=1 + rank)
         with torch.no_grad():
             for _ in range(a.warmup):
@@ -945,10 +980,13 @@ def main():
         barrier()
         dts.append(max_over_ranks(dist, time.perf_counter() - t0, f"cuda:{local_rank}"))
     gc.enable()
-    dt = sorted(dts)[1]
+    dt = sorted(dts)[len(dts) // 2]
     status = dec.engine_status() if hasattr(dec, "engine_status") else 0
     if status:      # a persistent launch gave up on a hand-off: its tokens are not results, no line
         raise RuntimeError("rank %d: persistent decode launch gave up (code 0x%x)" % (rank, status))
+    if a.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the logits of position W + K - 1 and the greedy token after it
+        dump_outputs(a.dump_outputs, {"logits": dec.step_logits, "next_token": dec.tok})
 
     if rank == 0:
         tok_s = aggregate_tokens_per_s(world, a.steps, dt)
@@ -968,20 +1006,22 @@ def main():
                                "tokens_per_s_at_8TBps": round(HBM_PEAK_GBPS * 1e9 / algo_bytes, 1),
                                "frac": round(tok_s / world / (HBM_PEAK_GBPS * 1e9 / algo_bytes), 4)},
         }
-        if a.codebook == "E8P12":
+        # everything below takes runs of its own beside the headline: --full only
+        if a.full and a.codebook == "E8P12":
             out["roofline"] = engine_roofline(dec) if getattr(dec, "block_eng", False) else gemv_roofline(dec)
-        try:
-            out["parity"] = decode_parity_check(dec)
-        except Exception as e:      # (a transient failure of the check -- e.g. the launch giving a hand-off up on a shared
-            out["parity"] = {"ok": False, "error": repr(e)[:400]}          # device -- is reported as a failed check, not as a traceback)
-        if not out["parity"]["ok"]:      # a fast step whose logits differ from the unfused step's is not a result: no line
-            raise RuntimeError("parity check failed: %r" % (out["parity"],))
-        if a.model == "7b" and a.codebook == "E8P12" and world == 1 and not a.no_prefill:
+        if a.full:
+            try:
+                out["parity"] = decode_parity_check(dec)
+            except Exception as e:      # (a transient failure of the check -- e.g. the launch giving a hand-off up on a shared
+                out["parity"] = {"ok": False, "error": repr(e)[:400]}          # device -- is reported as a failed check, not as a traceback)
+            if not out["parity"]["ok"]:      # a fast step whose logits differ from the unfused step's is not a result: no line
+                raise RuntimeError("parity check failed: %r" % (out["parity"],))
+        if a.full and a.model == "7b" and a.codebook == "E8P12" and world == 1 and not a.no_prefill:
             try:
                 out["prefill"] = prefill_config5(dec)
             except Exception as e:  # an extra, never the headline
                 out["prefill"] = {"error": repr(e)}
-        if a.model == "7b" and a.codebook == "E8P12" and world == 1 and not a.no_extras:
+        if a.full and a.model == "7b" and a.codebook == "E8P12" and world == 1 and not a.no_extras:
             # BASELINE configs[2] and [3], timed by the same procedure after the headline (never part of `value`)
             del dec
             torch.cuda.empty_cache()
@@ -1009,7 +1049,7 @@ def main():
             gc.collect()
             torch.cuda.empty_cache()
             out["extras"] = extras
-        if not a.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only (bench contract)
+        if a.full and not a.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only (bench contract)
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # the checker must never take the bench down

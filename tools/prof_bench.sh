@@ -9,10 +9,10 @@ tag=$1; shift
 out=$R/gpurun_out/prof_bench_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-CMD="python $R/bench.py --steps 16 --warmup 4 --no-cpu-baseline $*"
+CMD="python $R/bench.py --full --steps 16 --warmup 4 --no-cpu-baseline $*"
 timeout 900 rocprofv3 --kernel-trace --stats -d $out/kt -o kt -- $CMD > $out/kt.log 2>&1
 grep "^{\"metric\"" $out/kt.log | tail -1 | cut -c1-1400 > $R/gpurun_out/${tag}_bench_line.json
-timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out/pmc -o pmc -- python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline "$@" > $out/pmc.log 2>&1
+timeout 900 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out/pmc -o pmc -- python $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline "$@" > $out/pmc.log 2>&1
 python - <<PY
 import glob, sqlite3, json
 out, R, tag = "$out", "$R", "$tag"
@@ -28,7 +28,7 @@ with open(f"{R}/gpurun_out/{tag}_bench_kernel_trace.txt", "w") as f:
         for name, n, s, avg, mn, mx in rows[:40]:
             print("%-100s %8d %12.1f %6.2f%% %10.2f %10.2f %10.2f" % (name[:100], n, s / 1e3, 100.0 * s / tot, avg / 1e3, mn / 1e3, mx / 1e3), file=f)
 with open(f"{R}/gpurun_out/{tag}_bench_fetch_size.txt", "w") as f:
-    print("# rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --steps 4 --warmup 2 --no-cpu-baseline (own pass)", file=f)
+    print("# rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline (own pass)", file=f)
     for p in glob.glob(out + "/pmc/**/*.db", recursive=True):
         c = sqlite3.connect(p)
         ccols = [r[1] for r in c.execute("pragma table_info(counters_collection)")]
