@@ -3,6 +3,8 @@
 // (origin_order.cu:557-788 have no dtype / shape / contiguity checks).
 #include <stdlib.h>
 
+#include <initializer_list>
+
 #include "quip_internal.h"
 
 namespace quip {
@@ -65,6 +67,135 @@ static int mm_common(CodebookId cb, const void* x, const void* q, const Codebook
   if (!aligned16(x)) return QUIP_ERR_MISALIGNED;
   return generic_mm_launch(cb, x, q, a, y, m, n, k, s);
 }
+
+// ---- the stand-alone bs=1 GEMV -----------------------------------------------------------------------------------------
+// Three kernels serve it: the first (e8p_gemv_mfma.hip: one-shot loads on 8 waves) and the K-splitting kernel
+// (e8p_gemv_v2.hip: whole-line loads) with byte tables or in nibble mode (e8p_gemv_v2n.hip), each in one of three table
+// modes (GemvTune::rep).  One argument check (gemv_launch) and one planner (gemv_plan) serve every entry point.
+namespace {
+struct GemvMode {
+  int rep;              // 0 = E8P12, 64 = the D4 table (HI through its virtual layout), 40 = E8P12RVQ3B
+  uintptr_t q_mask;     // Qidxs alignment - 1
+  int k_multiple;
+  uintptr_t grid_mask;  // grid alignment - 1 checked up front (0: left to the kernel that reads it)
+  bool grid2;           // the E81B table (int8 (256, 8)), 8-byte aligned
+  bool ws_required;     // a missing or short workspace: an error before the K-splitting kernel (else its own cue)
+};
+// E8P12RVQ3B: a 3-byte code behind a zero byte is (main16 << 16 | resid8 << 8), i.e. an RVQ4-style row of 2k virtual weights
+// whose low 16-bit codes index the E81B table instead of the E8P tables; its rows are 3 k / 8 bytes, dword aligned
+constexpr GemvMode kGemvE8P{0, 15, 8, 63, false, false};
+constexpr GemvMode kGemvD4{64, 15, 8, 0, false, false};
+constexpr GemvMode kGemvRVQ3{40, 3, 32, 0, true, true};
+
+enum GemvKernel { kGemvFirst, kGemvV2Bytes, kGemvV2Nibble };
+struct GemvPlan {
+  GemvKernel kernel[3];
+  int count = 0;
+  void add(GemvKernel k) { kernel[count++] = k; }
+};
+
+// QUIP_GEMV_V2 = 0 / 1 forces the first / the K-splitting kernel for E8P12; QUIP_GEMV_NIB = 0 keeps the byte tables.
+// Both are read once per process.
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+int gemv_v2_env() {
+  static const int v = [] { return env_int("QUIP_GEMV_V2", -1); }();
+  return v;
+}
+bool gemv_nibble_env() {
+  static const bool v = [] { return env_int("QUIP_GEMV_NIB", 1) != 0; }();
+  return v;
+}
+
+// nibble mode for rows whose digit image leaves the byte tables 16 copies only (k > 10240: two-way conflicts on every
+// look-up; the nibble tables are 64 KB and conflict free whatever k is: 8192 x 28672 -5..9 % on two boxes, level on a third;
+// at k = 8192 both are conflict free and the two kernels trade places from box to box: profiles/r06_gemv_v2_nibble.txt),
+// and for grouped launches (q / k / v of 8192: 11.5-11.9 against 13.3 us and the first kernel's 12.4; gate / up 24.6
+// against 27.5-28.2; at k = 4096 the byte tables win: 8.7 against 9.4 us for 2 x 11008)
+bool gemv_prefers_nibble(int count, int k) { return gemv_nibble_env() && (k > 10240 || (count >= 2 && k >= 8192)); }
+
+// the kernels a launch tries, in order (k: weights per row as the kernels see them).  E8P12 (measured on MI355X,
+// tools/gemv_v2_bench.py): the K-splitting kernel wins from Llama-70B sizes on -- k >= 8192 with >= 16 MB of codes, or
+// >= 20 MB of codes in the launch (7B gate / up group) -- and is the only one for rows longer than 28672 (E8P12RVQ4B's
+// 2k-wide virtual rows at 70B); short launches stay on the first kernel.  The other table modes take the first kernel
+// wherever it takes the shape (k <= 28672), else the K-splitting one (HI's / E8P12RVQ3B's virtual rows at the 70B
+// down_proj width: 2 k = 57344; E8P12RVQ3B: one problem only)
+GemvPlan gemv_plan(const GemvMode& mode, const int* ns, int count, int k) {
+  GemvPlan p;
+  if (mode.rep != 0) {
+    p.add(kGemvFirst);
+    if (mode.rep == 64 || count == 1) p.add(kGemvV2Bytes);
+    return p;
+  }
+  size_t bytes = 0;
+  for (int i = 0; i < count; ++i) bytes += (size_t)ns[i] * (size_t)k / 4;
+  const bool first_ok = e8p_gemv_mfma_group_supported(ns, count, k);
+  const int env = gemv_v2_env();
+  if (env == 1 || !first_ok || (env != 0 && ((k >= 8192 && bytes >= ((size_t)16 << 20)) || bytes >= ((size_t)20 << 20)))) {
+    if (gemv_prefers_nibble(count, k)) p.add(kGemvV2Nibble);
+    p.add(kGemvV2Bytes);
+  }
+  if (first_ok) p.add(kGemvFirst);
+  return p;
+}
+
+// the K-splitting kernel in the table mode of `t`; rep 0 takes nibble mode first where the planner would (unless the K
+// split is forced), rep 4 nibble mode only
+int gemv_v2_auto(const void* const* planes, const void* const* qidxs, const void* grid, void* const* ys, void* ws,
+                 const int* ns, int count, int k, const GemvTune& t, hipStream_t stream) {
+  if (t.rep == 0 && !t.waves_g && gemv_prefers_nibble(count, k)) {
+    GemvTune tn = t;
+    tn.rep = 4;
+    const int rc = e8p_gemv_v2_group_launch(planes, qidxs, grid, ys, ws, ns, count, k, tn, stream);
+    if (rc != QUIP_ERR_UNSUPPORTED && rc != QUIP_ERR_NULL_POINTER) return rc;
+  }
+  return e8p_gemv_v2_group_launch(planes, qidxs, grid, ys, ws, ns, count, k, t, stream);
+}
+
+int gemv_launch(const GemvMode& mode, const void* const* planes, const void* const* qidxs, const void* grid,
+                const void* grid2, void* const* ys, const int32_t* ns, int32_t count, int32_t k, void* ws, size_t ws_bytes,
+                quip_stream_t stream) {
+  if (!planes || !qidxs || !grid || (mode.grid2 && !grid2) || !ys || !ns) return QUIP_ERR_NULL_POINTER;
+  if (count < 1 || count > QUIP_MAX_GROUP) return QUIP_ERR_BAD_SHAPE;
+  int n32[QUIP_MAX_GROUP];
+  size_t need = 0;
+  for (int i = 0; i < count; ++i) {
+    if (!planes[i] || !qidxs[i] || !ys[i]) return QUIP_ERR_NULL_POINTER;
+    if (!aligned16(planes[i]) || (reinterpret_cast<uintptr_t>(qidxs[i]) & mode.q_mask) != 0) return QUIP_ERR_MISALIGNED;
+    if (ns[i] < 1) return QUIP_ERR_BAD_SHAPE;
+    n32[i] = ns[i];
+    need += e8p_gemv_v2_workspace_words(ns[i]) * 4;
+  }
+  if (k < 1 || k % mode.k_multiple != 0) return QUIP_ERR_BAD_SHAPE;
+  if ((reinterpret_cast<uintptr_t>(grid) & mode.grid_mask) != 0 ||
+      (mode.grid2 && (reinterpret_cast<uintptr_t>(grid2) & 7u) != 0) || (ws && !aligned16(ws)))
+    return QUIP_ERR_MISALIGNED;
+  if (ws_bytes < need) ws = nullptr;
+  GemvTune t;
+  t.rep = mode.rep;
+  t.grid2 = mode.grid2 ? grid2 : nullptr;
+  const int kv = mode.rep == 40 ? 2 * k : k;
+  const GemvPlan plan = gemv_plan(mode, n32, count, kv);
+  int rc = QUIP_ERR_UNSUPPORTED;
+  // next kernel: after the first one on QUIP_ERR_UNSUPPORTED (it does not take the shape), after the K-splitting one also
+  // on QUIP_ERR_NULL_POINTER (it needs a K split but has no workspace)
+  for (int i = 0; i < plan.count; ++i) {
+    if (plan.kernel[i] == kGemvFirst) {
+      rc = e8p_gemv_mfma_group_launch(planes, qidxs, grid, ys, n32, count, kv, t, (hipStream_t)stream);
+      if (rc != QUIP_ERR_UNSUPPORTED) return rc;
+      continue;
+    }
+    if (mode.ws_required && !ws) return QUIP_ERR_NULL_POINTER;
+    GemvTune tv = t;
+    if (plan.kernel[i] == kGemvV2Nibble) tv.rep = 4;
+    rc = e8p_gemv_v2_group_launch(planes, qidxs, grid, ys, ws, n32, count, kv, tv, (hipStream_t)stream);
+    if (rc != QUIP_ERR_UNSUPPORTED && rc != QUIP_ERR_NULL_POINTER) return rc;
+  }
+  return rc;
+}
+}  // namespace
 
 }  // namespace quip
 
@@ -247,181 +378,71 @@ int quip_gemv_planes_rows_mode(const void* planes, const void* qidxs, const void
   return e8p_gemv_mfma_rows_launch(planes, qidxs, grid, y, rows, n, k, t, (hipStream_t)stream);
 }
 
-// Which of the two matrix-core GEMVs serves a launch (measured on MI355X, tools/gemv_v2_bench.py): the second
-// generation (whole-line loads, K split) wins from Llama-70B sizes on -- K >= 8192 with >= 16 MB of codes, or >= 20 MB
-// of codes in the launch (7B gate / up group) -- and is the only one for rows longer than 28672 (E8P12RVQ4B's 2k-wide virtual rows at 70B);
-// short launches stay on the first kernel (one-shot loads on 8 waves).  QUIP_GEMV_V2=0 / 1 forces one of them.
-static int gemv_v2_mode() {
-  static int mode = -2;
-  if (mode == -2) {
-    const char* e = getenv("QUIP_GEMV_V2");
-    mode = e ? atoi(e) : -1;
-  }
-  return mode;
-}
-
-// which kernel a bs=1 E8P12 GEMV launch of `count` matrices takes first: the K-splitting kernel (e8p_gemv_v2.hip) when
-// the first one (e8p_gemv_mfma.hip) does not take the shape, or for long rows (k >= 8192) from 16 MB of codes, or from
-// 20 MB; QUIP_GEMV_V2 = 0 / 1 forces either
-static bool gemv_prefers_v2(const int* ns, int count, int k, bool* v1_ok_out) {
-  size_t bytes = 0;
-  for (int i = 0; i < count; ++i) bytes += (size_t)ns[i] * (size_t)k / 4;
-  const bool v1_ok = e8p_gemv_mfma_group_supported(ns, count, k);
-  const int mode = gemv_v2_mode();
-  if (v1_ok_out) *v1_ok_out = v1_ok;
-  return mode == 1 || !v1_ok || (mode != 0 && ((k >= 8192 && bytes >= ((size_t)16 << 20)) || bytes >= ((size_t)20 << 20)));
-}
-
+// 1 = the first kernel, 2 = the K-splitting kernel (either table mode): the first kernel of gemv_plan that takes the shape
 int quip_e8p_gemv_kernel_choice(const int32_t* ns, int32_t count, int32_t k) {
   if (!ns) return QUIP_ERR_NULL_POINTER;
   if (count < 1 || count > QUIP_MAX_GROUP || k < 1 || k % 8 != 0) return QUIP_ERR_BAD_SHAPE;
   int n32[QUIP_MAX_GROUP];
+  bool v2_ok = true;
   for (int i = 0; i < count; ++i) {
     if (ns[i] < 1) return QUIP_ERR_BAD_SHAPE;
     n32[i] = ns[i];
+    v2_ok = v2_ok && e8p_gemv_v2_supported(ns[i], k);
   }
-  bool v1_ok = false;
-  const bool v2 = gemv_prefers_v2(n32, count, k, &v1_ok);
-  if (v2) {
-    for (int i = 0; i < count; ++i)
-      if (!e8p_gemv_v2_supported(n32[i], k)) return v1_ok ? 1 : QUIP_ERR_UNSUPPORTED;
-    return 2;
+  const GemvPlan plan = gemv_plan(kGemvE8P, n32, count, k);
+  for (int i = 0; i < plan.count; ++i) {
+    if (plan.kernel[i] == kGemvFirst) return 1;      // (planned only where it takes the shape)
+    if (v2_ok) return 2;
   }
-  return 1;
-}
-
-static int e8p_gemv_dispatch(const void* const* planes, const void* const* qidxs, const void* grid, void* const* ys,
-                             const int* ns, int count, int k, void* ws, size_t ws_bytes, hipStream_t stream) {
-  size_t need = 0;
-  for (int i = 0; i < count; ++i) need += e8p_gemv_v2_workspace_words(ns[i]) * 4;
-  if (ws && ws_bytes < need) ws = nullptr;
-  bool v1_ok = false;
-  const bool v2 = gemv_prefers_v2(ns, count, k, &v1_ok);
-  if (v2) {
-    const int rc = e8p_gemv_v2_group_launch(planes, qidxs, grid, ys, ws, ns, count, k, GemvTune{}, stream);
-    if (rc == QUIP_OK || !v1_ok || (rc != QUIP_ERR_NULL_POINTER && rc != QUIP_ERR_UNSUPPORTED)) return rc;
-    // needs a K split but no workspace was given: the first kernel takes it
-  }
-  return e8p_gemv_mfma_group_launch(planes, qidxs, grid, ys, ns, count, k, GemvTune{}, stream);
+  return QUIP_ERR_UNSUPPORTED;
 }
 
 size_t quip_e8p_gemv_workspace_bytes(int32_t n_total) {
   return n_total < 1 ? 0 : (e8p_gemv_v2_workspace_words(n_total) + 2 * 64) * 4;
 }
 
-static int gemv_group_common(const void* const* planes, const void* const* qidxs, const void* grid_packed_abs,
-                             void* const* ys, const int32_t* ns, int32_t count, int32_t k, void* ws, size_t ws_bytes,
-                             quip_stream_t stream) {
-  if (!planes || !qidxs || !grid_packed_abs || !ys || !ns) return QUIP_ERR_NULL_POINTER;
-  if (count < 1 || count > QUIP_MAX_GROUP) return QUIP_ERR_BAD_SHAPE;
-  int n32[QUIP_MAX_GROUP];
-  for (int i = 0; i < count; ++i) {
-    if (!planes[i] || !qidxs[i] || !ys[i]) return QUIP_ERR_NULL_POINTER;
-    if (!aligned16(planes[i]) || !aligned16(qidxs[i])) return QUIP_ERR_MISALIGNED;
-    if (ns[i] < 1) return QUIP_ERR_BAD_SHAPE;
-    n32[i] = ns[i];
-  }
-  if (k < 1 || k % 8 != 0) return QUIP_ERR_BAD_SHAPE;
-  if (!aligned64(grid_packed_abs) || (ws && !aligned16(ws))) return QUIP_ERR_MISALIGNED;
-  return e8p_gemv_dispatch(planes, qidxs, grid_packed_abs, ys, n32, count, k, ws, ws_bytes, (hipStream_t)stream);
-}
-
 int quip_e8p_gemv_planes_group_ws(const void* const* planes, const void* const* qidxs, const void* grid_packed_abs,
                                   void* const* ys, const int32_t* ns, int32_t count, int32_t k, void* workspace,
                                   size_t workspace_bytes, quip_stream_t stream) {
-  return gemv_group_common(planes, qidxs, grid_packed_abs, ys, ns, count, k, workspace, workspace_bytes, stream);
+  return gemv_launch(kGemvE8P, planes, qidxs, grid_packed_abs, nullptr, ys, ns, count, k, workspace, workspace_bytes,
+                     stream);
 }
 
 int quip_e8p_gemv_planes_ws(const void* planes, const void* qidxs, const void* grid, void* y, int32_t n, int32_t k,
                             void* workspace, size_t workspace_bytes, quip_stream_t stream) {
   if (n == 0) return QUIP_OK;
-  return gemv_group_common(&planes, &qidxs, grid, &y, &n, 1, k, workspace, workspace_bytes, stream);
+  return gemv_launch(kGemvE8P, &planes, &qidxs, grid, nullptr, &y, &n, 1, k, workspace, workspace_bytes, stream);
 }
 
 int quip_e8p_gemv_planes_group(const void* const* planes, const void* const* qidxs,
                                const void* grid_packed_abs, void* const* ys, const int32_t* ns,
                                int32_t count, int32_t k, quip_stream_t stream) {
-  return gemv_group_common(planes, qidxs, grid_packed_abs, ys, ns, count, k, nullptr, 0, stream);
-}
-
-// E8P12RVQ3B on the matrix-core GEMV: a 3-byte code behind a zero byte is (main16 << 16 | resid8 << 8), i.e. an RVQ4-style row of
-// 2k virtual weights whose low 16-bit codes index the E81B table (T3) instead of the E8P tables
-static int e8prvq3_group_common(const void* const* planes, const void* const* qidxs, const void* grid_packed_abs,
-                                const void* e81b_i8, void* const* ys, const int32_t* ns, int32_t count, int32_t k,
-                                void* ws, size_t ws_bytes, quip_stream_t stream) {
-  if (!planes || !qidxs || !grid_packed_abs || !e81b_i8 || !ys || !ns) return QUIP_ERR_NULL_POINTER;
-  if (count < 1 || count > QUIP_MAX_GROUP) return QUIP_ERR_BAD_SHAPE;
-  int n32[QUIP_MAX_GROUP];
-  size_t need = 0;
-  for (int i = 0; i < count; ++i) {
-    if (!planes[i] || !qidxs[i] || !ys[i]) return QUIP_ERR_NULL_POINTER;
-    if (!aligned16(planes[i]) || (reinterpret_cast<uintptr_t>(qidxs[i]) & 3) != 0) return QUIP_ERR_MISALIGNED;
-    if (ns[i] < 1) return QUIP_ERR_BAD_SHAPE;
-    n32[i] = ns[i];
-    need += e8p_gemv_v2_workspace_words(ns[i]) * 4;
-  }
-  if (k < 1 || k % 32 != 0) return QUIP_ERR_BAD_SHAPE;   // rows of 3 k / 8 bytes, dword aligned
-  if ((reinterpret_cast<uintptr_t>(e81b_i8) & 7) != 0 || (ws && !aligned16(ws))) return QUIP_ERR_MISALIGNED;
-  GemvTune t;
-  t.rep = 40;
-  t.grid2 = e81b_i8;
-  const int rc = e8p_gemv_mfma_group_launch(planes, qidxs, grid_packed_abs, ys, n32, count, 2 * k, t, (hipStream_t)stream);
-  if (rc != QUIP_ERR_UNSUPPORTED) return rc;
-  // virtual rows beyond the first kernel's LDS budget (70B down_proj: 2k = 57344): the K-splitting kernel, one problem
-  if (count != 1) return QUIP_ERR_UNSUPPORTED;
-  if (!ws || ws_bytes < need) return QUIP_ERR_NULL_POINTER;
-  return e8p_gemv_v2_group_launch(planes, qidxs, grid_packed_abs, ys, ws, n32, 1, 2 * k, t, (hipStream_t)stream);
+  return gemv_launch(kGemvE8P, planes, qidxs, grid_packed_abs, nullptr, ys, ns, count, k, nullptr, 0, stream);
 }
 
 int quip_e8prvq3_gemv_planes_group(const void* const* planes, const void* const* qidxs,
                                    const void* grid_packed_abs, const void* e81b_i8, void* const* ys,
                                    const int32_t* ns, int32_t count, int32_t k, quip_stream_t stream) {
-  return e8prvq3_group_common(planes, qidxs, grid_packed_abs, e81b_i8, ys, ns, count, k, nullptr, 0, stream);
+  return gemv_launch(kGemvRVQ3, planes, qidxs, grid_packed_abs, e81b_i8, ys, ns, count, k, nullptr, 0, stream);
 }
 
 int quip_e8prvq3_gemv_planes_group_ws(const void* const* planes, const void* const* qidxs,
                                       const void* grid_packed_abs, const void* e81b_i8, void* const* ys,
                                       const int32_t* ns, int32_t count, int32_t k, void* workspace,
                                       size_t workspace_bytes, quip_stream_t stream) {
-  return e8prvq3_group_common(planes, qidxs, grid_packed_abs, e81b_i8, ys, ns, count, k, workspace, workspace_bytes,
-                              stream);
-}
-
-// D4 table mode of the matrix-core GEMVs: the first kernel wherever it takes the shape (k <= 28672), else the
-// K-splitting kernel in its D4 table mode (HI's virtual rows at the 70B down_proj width: 2 k = 57344)
-static int d4_group_common(const void* const* planes, const void* const* qidxs, const void* grid_f16,
-                           void* const* ys, const int32_t* ns, int32_t count, int32_t k, void* ws, size_t ws_bytes,
-                           quip_stream_t stream) {
-  if (!planes || !qidxs || !grid_f16 || !ys || !ns) return QUIP_ERR_NULL_POINTER;
-  if (count < 1 || count > QUIP_MAX_GROUP) return QUIP_ERR_BAD_SHAPE;
-  int n32[QUIP_MAX_GROUP];
-  size_t need = 0;
-  for (int i = 0; i < count; ++i) {
-    if (!planes[i] || !qidxs[i] || !ys[i]) return QUIP_ERR_NULL_POINTER;
-    if (!aligned16(planes[i]) || !aligned16(qidxs[i])) return QUIP_ERR_MISALIGNED;
-    if (ns[i] < 1) return QUIP_ERR_BAD_SHAPE;
-    n32[i] = ns[i];
-    need += e8p_gemv_v2_workspace_words(ns[i]) * 4;
-  }
-  if (k < 1 || k % 8 != 0) return QUIP_ERR_BAD_SHAPE;
-  if (ws && !aligned16(ws)) return QUIP_ERR_MISALIGNED;
-  if (ws && ws_bytes < need) ws = nullptr;
-  GemvTune t;
-  t.rep = 64;
-  const int rc = e8p_gemv_mfma_group_launch(planes, qidxs, grid_f16, ys, n32, count, k, t, (hipStream_t)stream);
-  if (rc != QUIP_ERR_UNSUPPORTED) return rc;
-  return e8p_gemv_v2_group_launch(planes, qidxs, grid_f16, ys, ws, n32, count, k, t, (hipStream_t)stream);
+  return gemv_launch(kGemvRVQ3, planes, qidxs, grid_packed_abs, e81b_i8, ys, ns, count, k, workspace, workspace_bytes,
+                     stream);
 }
 
 int quip_d4_gemv_planes(const void* planes, const void* qidxs, const void* grid_f16, void* y, int32_t n,
                         int32_t k, quip_stream_t stream) {
-  return d4_group_common(&planes, &qidxs, grid_f16, &y, &n, 1, k, nullptr, 0, stream);
+  return gemv_launch(kGemvD4, &planes, &qidxs, grid_f16, nullptr, &y, &n, 1, k, nullptr, 0, stream);
 }
 
 int quip_d4_gemv_planes_group(const void* const* planes, const void* const* qidxs, const void* grid_f16,
                               void* const* ys, const int32_t* ns, int32_t count, int32_t k,
                               quip_stream_t stream) {
-  return d4_group_common(planes, qidxs, grid_f16, ys, ns, count, k, nullptr, 0, stream);
+  return gemv_launch(kGemvD4, planes, qidxs, grid_f16, nullptr, ys, ns, count, k, nullptr, 0, stream);
 }
 
 int quip_d4_gemv_planes_v2(const void* planes, const void* qidxs, const void* grid_f16, void* y, int32_t n, int32_t k,
@@ -432,13 +453,13 @@ int quip_d4_gemv_planes_v2(const void* planes, const void* qidxs, const void* gr
   if (workspace && workspace_bytes < e8p_gemv_v2_workspace_words(n) * 4) workspace = nullptr;
   GemvTune t;
   t.rep = 64;
-  return e8p_gemv_v2_launch(planes, qidxs, grid_f16, y, workspace, n, k, t, (hipStream_t)stream);
+  return e8p_gemv_v2_group_launch(&planes, &qidxs, grid_f16, &y, workspace, &n, 1, k, t, (hipStream_t)stream);
 }
 
 int quip_d4_gemv_planes_group_ws(const void* const* planes, const void* const* qidxs, const void* grid_f16,
                                  void* const* ys, const int32_t* ns, int32_t count, int32_t k, void* workspace,
                                  size_t workspace_bytes, quip_stream_t stream) {
-  return d4_group_common(planes, qidxs, grid_f16, ys, ns, count, k, workspace, workspace_bytes, stream);
+  return gemv_launch(kGemvD4, planes, qidxs, grid_f16, nullptr, ys, ns, count, k, workspace, workspace_bytes, stream);
 }
 
 int quip_e8p_gemv_fused(const quip_gemv_fused_in* in, const void* const* qidxs,
@@ -682,55 +703,51 @@ int quip_e8p_gemv_planes(const void* planes, const void* qidxs, const void* grid
   if (n < 0) return QUIP_ERR_BAD_SHAPE;
   if (n == 0) return QUIP_OK;
   if (!aligned16(planes) || !aligned16(qidxs) || !aligned64(grid)) return QUIP_ERR_MISALIGNED;
-  return gemv_group_common(&planes, &qidxs, grid, &y, &n, 1, k, nullptr, 0, stream);
+  return gemv_launch(kGemvE8P, &planes, &qidxs, grid, nullptr, &y, &n, 1, k, nullptr, 0, stream);
+}
+
+// the skinny products (e8p_skinny_gemm.hip): x and the codes 16-byte aligned (E8P12RVQ3B's 3-byte codes: 4), y 4-byte, every
+// table 8-byte; m == 0 is accepted before the alignment is looked at (the caller returns, no launch)
+static int skinny_args_ok(const void* x, const void* qidxs, std::initializer_list<const void*> tables, const void* y,
+                          int32_t m, int32_t n, int32_t k, uintptr_t q_mask = 15u) {
+  if (!x || !qidxs || !y) return QUIP_ERR_NULL_POINTER;
+  for (const void* t : tables)
+    if (!t) return QUIP_ERR_NULL_POINTER;
+  if (m < 0 || n < 1 || k < 8) return QUIP_ERR_BAD_SHAPE;
+  if (m == 0) return QUIP_OK;
+  if (!aligned16(x) || (reinterpret_cast<uintptr_t>(qidxs) & q_mask) || (reinterpret_cast<uintptr_t>(y) & 3u))
+    return QUIP_ERR_MISALIGNED;
+  for (const void* t : tables)
+    if (reinterpret_cast<uintptr_t>(t) & 7u) return QUIP_ERR_MISALIGNED;
+  return QUIP_OK;
 }
 
 int quip_e8p_mm_skinny(const void* x, const void* qidxs, const void* grid, void* y, int32_t m, int32_t n, int32_t k,
                        quip_stream_t stream) {
-  if (!x || !qidxs || !grid || !y) return QUIP_ERR_NULL_POINTER;
-  if (m < 0 || n < 1 || k < 8) return QUIP_ERR_BAD_SHAPE;
-  if (m == 0) return QUIP_OK;
-  if (!aligned16(x) || !aligned16(qidxs) || (reinterpret_cast<uintptr_t>(y) & 3u) || (reinterpret_cast<uintptr_t>(grid) & 7u))
-    return QUIP_ERR_MISALIGNED;
+  if (const int st = skinny_args_ok(x, qidxs, {grid}, y, m, n, k); st != QUIP_OK || m == 0) return st;
   return e8p_skinny_gemm_launch(x, qidxs, grid, y, m, n, k, (hipStream_t)stream);
 }
 
 int quip_e8prvq4_mm_skinny(const void* x, const void* qidxs, const void* grid, float resid_scale, void* y, int32_t m,
                            int32_t n, int32_t k, quip_stream_t stream) {
-  if (!x || !qidxs || !grid || !y) return QUIP_ERR_NULL_POINTER;
-  if (m < 0 || n < 1 || k < 8) return QUIP_ERR_BAD_SHAPE;
-  if (m == 0) return QUIP_OK;
-  if (!aligned16(x) || !aligned16(qidxs) || (reinterpret_cast<uintptr_t>(y) & 3u) || (reinterpret_cast<uintptr_t>(grid) & 7u))
-    return QUIP_ERR_MISALIGNED;
+  if (const int st = skinny_args_ok(x, qidxs, {grid}, y, m, n, k); st != QUIP_OK || m == 0) return st;
   return e8prvq4_skinny_gemm_launch(x, qidxs, grid, resid_scale, y, m, n, k, (hipStream_t)stream);
 }
 
 int quip_e8prvq3_mm_skinny(const void* x, const void* qidxs, const void* grid, const void* e81b_packed, float resid_scale,
                            void* y, int32_t m, int32_t n, int32_t k, quip_stream_t stream) {
-  if (!x || !qidxs || !grid || !e81b_packed || !y) return QUIP_ERR_NULL_POINTER;
-  if (m < 0 || n < 1 || k < 8) return QUIP_ERR_BAD_SHAPE;
-  if (m == 0) return QUIP_OK;
-  if (!aligned16(x) || (reinterpret_cast<uintptr_t>(qidxs) & 3u) || (reinterpret_cast<uintptr_t>(y) & 3u) ||
-      (reinterpret_cast<uintptr_t>(grid) & 7u) || (reinterpret_cast<uintptr_t>(e81b_packed) & 7u))
-    return QUIP_ERR_MISALIGNED;
+  if (const int st = skinny_args_ok(x, qidxs, {grid, e81b_packed}, y, m, n, k, 3u); st != QUIP_OK || m == 0) return st;
   return e8prvq3_skinny_gemm_launch(x, qidxs, grid, e81b_packed, resid_scale, y, m, n, k, (hipStream_t)stream);
 }
 
 int quip_d4_mm_skinny(const void* x, const void* qidxs, const void* grid_f16, void* y, int32_t m, int32_t n, int32_t k,
                       quip_stream_t stream) {
-  if (!x || !qidxs || !grid_f16 || !y) return QUIP_ERR_NULL_POINTER;
-  if (m < 0 || n < 1 || k < 8) return QUIP_ERR_BAD_SHAPE;
-  if (m == 0) return QUIP_OK;
-  if (!aligned16(x) || !aligned16(qidxs) || (reinterpret_cast<uintptr_t>(y) & 3u) || (reinterpret_cast<uintptr_t>(grid_f16) & 7u))
-    return QUIP_ERR_MISALIGNED;
+  if (const int st = skinny_args_ok(x, qidxs, {grid_f16}, y, m, n, k); st != QUIP_OK || m == 0) return st;
   return d4_skinny_gemm_launch(x, qidxs, grid_f16, y, m, n, k, (hipStream_t)stream);
 }
 
 int quip_hi_mm_skinny(const void* x, const void* qidxs, void* y, int32_t m, int32_t n, int32_t k, quip_stream_t stream) {
-  if (!x || !qidxs || !y) return QUIP_ERR_NULL_POINTER;
-  if (m < 0 || n < 1 || k < 8) return QUIP_ERR_BAD_SHAPE;
-  if (m == 0) return QUIP_OK;
-  if (!aligned16(x) || !aligned16(qidxs) || (reinterpret_cast<uintptr_t>(y) & 3u)) return QUIP_ERR_MISALIGNED;
+  if (const int st = skinny_args_ok(x, qidxs, {}, y, m, n, k); st != QUIP_OK || m == 0) return st;
   return hi_skinny_gemm_launch(x, qidxs, y, m, n, k, (hipStream_t)stream);
 }
 
@@ -838,7 +855,7 @@ int quip_e8p_gemv_v2_tuned(const void* planes, const void* qidxs, const void* gr
   GemvTune t;
   t.rep = rep2; t.rows = slots; t.blocks = blocks; t.waves_g = ksplit; t.max_waves = max_waves; t.dbg = dbg;
   t.digits = runlen;
-  return e8p_gemv_v2_launch(planes, qidxs, grid, y, ws, n, k, t, (hipStream_t)stream);
+  return gemv_v2_auto(&planes, &qidxs, grid, &y, ws, &n, 1, k, t, (hipStream_t)stream);
 }
 
 int quip_e8p_gemv_v2_group_tuned(const void* const* planes, const void* const* qidxs, const void* grid,
@@ -852,7 +869,7 @@ int quip_e8p_gemv_v2_group_tuned(const void* const* planes, const void* const* q
   t.digits = runlen;
   int n32[QUIP_MAX_GROUP];
   for (int i = 0; i < count; ++i) n32[i] = ns[i];
-  return e8p_gemv_v2_group_launch(planes, qidxs, grid, ys, ws, n32, count, k, t, (hipStream_t)stream);
+  return gemv_v2_auto(planes, qidxs, grid, ys, ws, n32, count, k, t, (hipStream_t)stream);
 }
 
 size_t quip_e8p_gemv_v2_workspace_bytes(int32_t n) { return e8p_gemv_v2_workspace_words(n) * 4; }

@@ -651,36 +651,13 @@ size_t e8p_gemv_v2_workspace_words(int n) { return (size_t)n * 4 + (size_t)((n +
 int e8p_gemv_v2_group_launch(const void* const* planes, const void* const* qidxs, const void* grid, void* const* ys,
                              void* ws, const int* ns, int count, int k, const GemvTune& tune, hipStream_t stream) {
   if (count < 1 || count > kMaxG) return QUIP_ERR_UNSUPPORTED;
-  // nibble mode (e8p_gemv_v2n.hip): asked for, or -- automatic choice -- for rows whose digit image leaves the byte tables 16
-  // copies only (k > 10240: two-way conflicts on every look-up; the nibble tables are 64 KB and conflict free whatever k is:
-  // 8192 x 28672 -5..9 % on two boxes, level on a third; at k = 8192 both are conflict free and the two kernels trade places from
-  // box to box: profiles/r06_gemv_v2_nibble.txt), and for grouped launches (q / k / v of 8192: 11.5-11.9 against 13.3 us and the
-  // first kernel's 12.4; gate / up 24.6 against 27.5-28.2; at k = 4096 the byte tables win: 8.7 against 9.4 us for 2 x 11008);
-  // QUIP_GEMV_NIB=0 keeps the byte tables
-  {
-    static int nib_mode = -1;
-    if (nib_mode < 0) {
-      const char* e = getenv("QUIP_GEMV_NIB");
-      nib_mode = e ? atoi(e) : 1;
-    }
-    if (tune.rep == 4 || (tune.rep == 0 && !tune.waves_g && nib_mode != 0 && (k > 10240 || (count >= 2 && k >= 8192)))) {
-      GemvTune t = tune;
-      t.rep = 4;
-      const int rc = e8p_gemv_v2n_group_launch(planes, qidxs, grid, ys, ws, ns, count, k, t, stream);
-      if (tune.rep == 4 || (rc != QUIP_ERR_UNSUPPORTED && rc != QUIP_ERR_NULL_POINTER)) return rc;   // (else: the byte tables' candidates)
-    }
-  }
   for (int i = 0; i < count; ++i)
     if (!e8p_gemv_v2_supported(ns[i], k)) return QUIP_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(grid) & 63u) != 0) return QUIP_ERR_MISALIGNED;
+  if (tune.rep == 4) return e8p_gemv_v2n_group_launch(planes, qidxs, grid, ys, ws, ns, count, k, tune, stream);
   if (count == 1) return v2_group_launch<1>(planes, qidxs, grid, ys, ws, ns, k, tune, stream);
   if (count == 2) return v2_group_launch<2>(planes, qidxs, grid, ys, ws, ns, k, tune, stream);
   return v2_group_launch<3>(planes, qidxs, grid, ys, ws, ns, k, tune, stream);
-}
-
-int e8p_gemv_v2_launch(const void* planes, const void* qidxs, const void* grid, void* y, void* ws, int n, int k,
-                       const GemvTune& tune, hipStream_t stream) {
-  return e8p_gemv_v2_group_launch(&planes, &qidxs, grid, &y, ws, &n, 1, k, tune, stream);
 }
 
 }  // namespace quip

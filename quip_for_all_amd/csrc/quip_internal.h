@@ -51,7 +51,7 @@ int e8p_gemv_mfma_launch(const void* planes, const void* qidxs, const void* grid
 // second-generation matrix-core GEMV (e8p_gemv_v2.hip): whole-line loads, K split over workgroups.
 // ws: zeroed int32 workspace of e8p_gemv_v2_workspace_words(n) words (needed when K is split; left zeroed).
 // tune: rep = 32 / 24 / 16 -> (32, 32) / (32, 16) / (16, 16) table copies, rows = load slots per wave,
-// waves_g = K split, digits = segments per run, blocks, max_waves (0: automatic)
+// waves_g = K split, digits = segments per run, blocks, max_waves (0: automatic); rep = 4: nibble mode (below)
 bool e8p_gemv_v2_supported(int n, int k);
 size_t e8p_gemv_v2_workspace_words(int n);
 int e8p_gemv_v2_group_launch(const void* const* planes, const void* const* qidxs, const void* grid, void* const* ys,
@@ -59,8 +59,6 @@ int e8p_gemv_v2_group_launch(const void* const* planes, const void* const* qidxs
 // the same kernel in nibble mode (e8p_gemv_v2n.hip; tune.rep == 4): 4-byte table entries, 64 KB of tables whatever K is
 int e8p_gemv_v2n_group_launch(const void* const* planes, const void* const* qidxs, const void* grid, void* const* ys,
                               void* ws, const int* ns, int count, int k, const GemvTune& tune, hipStream_t stream);
-int e8p_gemv_v2_launch(const void* planes, const void* qidxs, const void* grid, void* y, void* ws, int n, int k,
-                       const GemvTune& tune, hipStream_t stream);
 int shape_probe_launch(const void* qidxs, void* out, int n, int k, const GemvTune& tune, hipStream_t stream);
 int pattern_probe_launch(const void* qidxs, void* out, int n, int k, const GemvTune& tune, hipStream_t stream);
 

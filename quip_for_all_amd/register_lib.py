@@ -3,8 +3,9 @@ register_lib.py:8-192, implemented by the C-ABI library (capi.py) on the
 caller's current HIP stream.  Only a CUDA(=HIP) implementation and a fake
 (meta) implementation are registered -- like the reference there is no CPU
 kernel, and there is deliberately no CPU fallback."""
+import ctypes
 import math
-from typing import Optional
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -170,6 +171,23 @@ def _chk_q(q: Tensor, dtype):
     return q.contiguous()
 
 
+class _Entry:
+    """a C entry point: resolved on the first call (the library loads on first use), then kept; a failure raises"""
+
+    def __init__(self, name):
+        self.name, self.fn = name, None
+
+    def __call__(self, *args):
+        if self.fn is None:
+            self.fn = getattr(capi.lib(), self.name)
+        capi.check(self.fn(*args), self.name)
+
+
+def _args(tables):
+    """the tables' ctypes arguments (the caller keeps `tables` alive over the call)"""
+    return [t.data_ptr() if isinstance(t, Tensor) else t for t in tables]
+
+
 # ---- hadamard ---------------------------------------------------------------------
 _HAD_DTYPES = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}     # QUIP_DTYPE_*
 
@@ -280,64 +298,6 @@ def _vec_ok(t, dev):
     return _ptr(t)
 
 
-def _d4_grid(grid):
-    _need(grid.dtype == torch.float16 and grid.is_contiguous() and tuple(grid.shape) == (256, 4),
-          "D4 grid must be the contiguous fp16 (256, 4) table")
-    return grid
-
-
-def _d4_gemv_planes_cuda(planes, Qidxs, grid):
-    return _d4_gemv_planes_group_cuda([planes], [Qidxs], grid)[0]
-
-
-def _e8prvq3_gemv_planes_group_cuda(planes, Qidxs, grid, e81b_i8):
-    import ctypes
-    count = len(planes)
-    _need(1 <= count <= capi.MAX_GROUP and len(Qidxs) == count, "group of 1..3 problems")
-    _need(Qidxs[0].shape[1] % 3 == 0, "Qidxs: the checkpoint's packed int32 (n, 3 k / 32) codes")
-    k = Qidxs[0].shape[1] * 32 // 3
-    dev = planes[0].device
-    for pl, q in zip(planes, Qidxs):
-        _need(q.dtype == torch.int32 and q.is_contiguous() and q.shape[1] * 32 == 3 * k and q.device == dev,
-              "Qidxs must be the checkpoint's contiguous int32 (n, 3 k / 32) tensors (3-byte codes) with a common k")
-        _need(pl.dtype == torch.uint8 and pl.is_contiguous() and pl.device == dev, "planes must be uint8")
-    _need(e81b_i8.dtype == torch.int8 and tuple(e81b_i8.shape) == (256, 8) and e81b_i8.is_contiguous()
-          and e81b_i8.device == dev, "e81b_i8 must be the contiguous int8 (256, 8) table")
-    g = _grid_i64(grid, planes[0])
-    outs = [_empty((1, q.shape[0]), dtype=torch.float16, device=dev) for q in Qidxs]
-    vp = ctypes.c_void_p * count
-    ns = (ctypes.c_int32 * count)(*[q.shape[0] for q in Qidxs])
-    ws = _gemv_workspace(dev, sum(q.shape[0] for q in Qidxs))
-    with torch.cuda.device(dev):
-        capi.check(capi.lib().quip_e8prvq3_gemv_planes_group_ws(
-            vp(*[p.data_ptr() for p in planes]), vp(*[q.data_ptr() for q in Qidxs]), g.data_ptr(), e81b_i8.data_ptr(),
-            vp(*[o.data_ptr() for o in outs]), ns, count, k, ws.data_ptr(), ws.numel() * 4, _stream(planes[0])),
-            "quip_e8prvq3_gemv_planes_group_ws")
-    return outs
-
-
-def _d4_gemv_planes_group_cuda(planes, Qidxs, grid):
-    import ctypes
-    count = len(planes)
-    _need(1 <= count <= capi.MAX_GROUP and len(Qidxs) == count, "group of 1..3 problems")
-    k = Qidxs[0].shape[1] * 4
-    dev = planes[0].device
-    for pl, q in zip(planes, Qidxs):
-        _need(q.dtype == torch.uint8 and q.is_contiguous() and q.shape[1] * 4 == k and q.device == dev,
-              "Qidxs must be contiguous uint8 (n, k/4) with a common k")
-        _need(pl.dtype == torch.uint8 and pl.is_contiguous() and pl.device == dev, "planes must be uint8")
-    outs = [_empty((1, q.shape[0]), dtype=torch.float16, device=dev) for q in Qidxs]
-    vp = ctypes.c_void_p * count
-    ns = (ctypes.c_int32 * count)(*[q.shape[0] for q in Qidxs])
-    ws = _gemv_workspace(dev, sum(q.shape[0] for q in Qidxs))    # (rows beyond 28672: the K-splitting kernel's partial sums)
-    with torch.cuda.device(dev):
-        capi.check(capi.lib().quip_d4_gemv_planes_group_ws(
-            vp(*[p.data_ptr() for p in planes]), vp(*[q.data_ptr() for q in Qidxs]), _d4_grid(grid).data_ptr(),
-            vp(*[o.data_ptr() for o in outs]), ns, count, k, ws.data_ptr(), ws.numel() * 4, _stream(planes[0])),
-            "quip_d4_gemv_planes_group_ws")
-    return outs
-
-
 def _had_transform_planes_rows_cuda(x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate, resid_scale=0.0):
     xc = _chk_x(x)
     _need(gate is None or (gate.shape == xc.shape and gate.dtype == torch.float16 and gate.is_contiguous()),
@@ -391,14 +351,8 @@ def _e8p_gemv_planes_rows_cuda(planes, Qidxs, grid):
     out = _empty((rows, n), dtype=torch.float16, device=Qidxs.device)
     if per < 1:
         # rows longer than rows mode holds in LDS (k > 28672: E8P12RVQ4B's 2k-wide virtual rows at 70B): one bs=1
-        # launch per row through the dispatcher (the K-splitting kernel) -- the same exact integer sums
-        ws = _gemv_workspace(Qidxs.device, n)
-        with torch.cuda.device(Qidxs.device):
-            for r in range(rows):
-                capi.check(L.quip_e8p_gemv_planes_ws(planes[r].data_ptr(), Qidxs.data_ptr(), g.data_ptr(),
-                                                     out[r].data_ptr(), n, k, ws.data_ptr(), ws.numel() * 4,
-                                                     _stream(out)), "quip_e8p_gemv_planes_ws")
-        return out
+        # launch per row through the stand-alone GEMV (the K-splitting kernel) -- the same exact integer sums
+        return torch.cat([_e8p_gemv_planes_cuda(planes[r], Qidxs, grid) for r in range(rows)]) if rows else out
     with torch.cuda.device(Qidxs.device):
         for r0 in range(0, rows, per):
             m = min(per, rows - r0)
@@ -427,12 +381,12 @@ def _gemv_planes_rows_mode_cuda(planes, Qidxs, grid, grid2, mode):
               "grid2 must be the contiguous int8 (256, 8) E81B table")
     rows = planes.shape[0]
     per = L.quip_gemv_max_rows_mode(n, k, mode)
-    if per < 1 and mode == 40:
-        # virtual rows longer than rows mode holds in LDS (70B down_proj): one bs=1 launch per row (K-splitting kernel)
-        return torch.cat([_e8prvq3_gemv_planes_group_cuda([planes[r]], [Qidxs], grid, grid2)[0] for r in range(rows)])
-    if per < 1 and mode == 64:      # ... the same for the D4 table mode (HI's virtual rows)
-        return torch.cat([_d4_gemv_planes_group_cuda([planes[r]], [Qidxs], grid)[0] for r in range(rows)])
-    _need(per >= 1, "shape not supported by the matrix-core GEMV")
+    if per < 1:
+        # virtual rows longer than rows mode holds in LDS (70B down_proj; HI's virtual rows in the D4 table mode): one bs=1
+        # launch per row (K-splitting kernel)
+        tables = (grid,) if mode == 64 else (grid, grid2)
+        return torch.cat([_gemv(_GEMV_D4 if mode == 64 else _GEMV_RVQ3, [planes[r]], [Qidxs], *tables)[0]
+                          for r in range(rows)])
     out = _empty((rows, n), dtype=torch.float16, device=Qidxs.device)
     with torch.cuda.device(Qidxs.device):
         for r0 in range(0, rows, per):
@@ -611,27 +565,66 @@ def _gemv_workspace(dev, n_total):
     return ws
 
 
-def _e8p_gemv_planes_group_cuda(planes, Qidxs, grid):
-    import ctypes
+# ---- the stand-alone bs=1 GEMV on digit planes, one spec per table mode: (planes, Qidxs, tables) -> outs ------------------
+class _GemvMode(NamedTuple):
+    entry: _Entry             # the group entry point with a workspace
+    qdtype: torch.dtype
+    cols: Tuple[int, int]     # in features per code column, as (numerator, denominator)
+    virtual: int              # the planes hold quip_e8p_planes_bytes(virtual * in features)
+    qmsg: str
+    tables: Callable          # (planes[0], *the op's table arguments) -> the entry point's table arguments
+
+
+def _e81b_i8(e81b_i8, ref):
+    _need(e81b_i8.dtype == torch.int8 and tuple(e81b_i8.shape) == (256, 8) and e81b_i8.is_contiguous()
+          and e81b_i8.device == ref.device, "e81b_i8 must be the contiguous int8 (256, 8) table")
+    return e81b_i8
+
+
+def _d4_grid(grid):
+    _need(grid.dtype == torch.float16 and grid.is_contiguous() and tuple(grid.shape) == (256, 4),
+          "D4 grid must be the contiguous fp16 (256, 4) table")
+    return grid
+
+
+_GEMV_E8P = _GemvMode(_Entry("quip_e8p_gemv_planes_group_ws"), torch.int16, (8, 1), 1,
+                      "Qidxs must be contiguous int16 (n, k/8) with a common k", lambda ref, grid: (_grid_i64(grid, ref),))
+# (HI runs in the D4 table mode through its virtual layout: its uint8 view already counts 2 k weights per row)
+_GEMV_D4 = _GemvMode(_Entry("quip_d4_gemv_planes_group_ws"), torch.uint8, (4, 1), 1,
+                     "Qidxs must be contiguous uint8 (n, k/4) with a common k", lambda ref, grid: (_d4_grid(grid),))
+_GEMV_RVQ3 = _GemvMode(_Entry("quip_e8prvq3_gemv_planes_group_ws"), torch.int32, (32, 3), 2,
+                       "Qidxs must be the checkpoint's contiguous int32 (n, 3 k / 32) tensors (3-byte codes) with a common k",
+                       lambda ref, grid, e81b_i8: (_grid_i64(grid, ref), _e81b_i8(e81b_i8, ref)))
+
+
+def _gemv(mode, planes, Qidxs, *tables):
     count = len(planes)
     _need(1 <= count <= capi.MAX_GROUP and len(Qidxs) == count, "group of 1..3 problems")
-    k = Qidxs[0].shape[1] * 8
+    num, den = mode.cols
+    _need(Qidxs[0].shape[1] * num % den == 0, mode.qmsg)
+    k = Qidxs[0].shape[1] * num // den
     dev = planes[0].device
+    nbytes = capi.lib().quip_e8p_planes_bytes(mode.virtual * k)
     for pl, q in zip(planes, Qidxs):
-        _need(q.dtype == torch.int16 and q.is_contiguous() and q.shape[1] * 8 == k and q.device == dev,
-              "Qidxs must be contiguous int16 (n, k/8) with a common k")
-        _need(pl.dtype == torch.uint8 and pl.is_contiguous() and pl.device == dev, "planes must be uint8")
+        _need(q.dtype == mode.qdtype and q.is_contiguous() and q.shape[1] * num == k * den and q.device == dev, mode.qmsg)
+        _need(pl.dtype == torch.uint8 and pl.is_contiguous() and pl.device == dev and pl.numel() >= nbytes,
+              f"planes must be contiguous uint8 images of at least quip_e8p_planes_bytes({mode.virtual * k}) = {nbytes} bytes")
+    tabs = mode.tables(planes[0], *tables)
     outs = [_empty((1, q.shape[0]), dtype=torch.float16, device=dev) for q in Qidxs]
     vp = ctypes.c_void_p * count
     ns = (ctypes.c_int32 * count)(*[q.shape[0] for q in Qidxs])
-    g = _grid_i64(grid, planes[0])
     ws = _gemv_workspace(dev, sum(q.shape[0] for q in Qidxs))
     with torch.cuda.device(dev):
-        capi.check(capi.lib().quip_e8p_gemv_planes_group_ws(
-            vp(*[p.data_ptr() for p in planes]), vp(*[q.data_ptr() for q in Qidxs]), g.data_ptr(),
-            vp(*[o.data_ptr() for o in outs]), ns, count, k, ws.data_ptr(), ws.numel() * 4, _stream(planes[0])),
-            "quip_e8p_gemv_planes_group_ws")
+        mode.entry(vp(*[p.data_ptr() for p in planes]), vp(*[q.data_ptr() for q in Qidxs]), *_args(tabs),
+                   vp(*[o.data_ptr() for o in outs]), ns, count, k, ws.data_ptr(), ws.numel() * 4, _stream(planes[0]))
     return outs
+
+
+def _e8p_gemv_planes_cuda(planes, Qidxs, grid):
+    Qc = _chk_q(Qidxs, torch.int16)
+    if Qc.shape[0] == 0:         # (the single-matrix entry point takes an empty matrix)
+        return _empty((1, 0), dtype=torch.float16, device=Qidxs.device)
+    return _gemv(_GEMV_E8P, [planes], [Qc], grid)[0]
 
 
 def _e8p_gemv_fused_cuda(x, z, post, residual, rms_weight, rms_eps, z_scale, pre, scale, Qidxs, grid):
@@ -853,167 +846,9 @@ def e8p_mm_batched_supported(m, n, k):
     return m >= 1 and n >= 2 and n % 2 == 0 and k >= 64 and k % 64 == 0
 
 
-def _e8p_mm_batched_cuda(x, Qidxs, grid):
-    g = _grid_i64(grid, x)
-    xc = _chk_x(x)
-    Qc = _chk_q(Qidxs, torch.int16)
-    m, k, n = xc.shape[0], xc.shape[1], Qc.shape[0]
-    _need(Qc.shape[1] * 8 == k, f"e8p_mm_batched: x has {k} columns but Qidxs {tuple(Qidxs.shape)} encodes {Qc.shape[1] * 8}")
-    _need(Qc.device == x.device, "Qidxs and x must be on the same device")
-    _need(e8p_mm_batched_supported(m, n, k), f"e8p_mm_batched: shape ({m}, {n}, {k}) needs k % 64 == 0 and n % 2 == 0")
-    y = _empty((m, n), dtype=torch.float16, device=x.device)
-    if m == 0:
-        return y
-    with torch.cuda.device(x.device):
-        capi.check(capi.lib().quip_e8p_mm_batched(xc.data_ptr(), Qc.data_ptr(), g.data_ptr(), y.data_ptr(), m, n, k,
-                                                  _stream(x)), "quip_e8p_mm_batched")
-    return y
-
-
 def e8p_mm_skinny_supported(m, n, k):
     """(rows beyond 32 run as chunks of 32 in the same launch)"""
     return 1 <= m <= 32 * 65535 and n >= 2 and n % 2 == 0 and k >= 128 and k % 128 == 0
-
-
-def _e8p_mm_skinny_cuda(x, Qidxs, grid):
-    g = _grid_i64(grid, x)
-    xc = _chk_x(x)
-    Qc = _chk_q(Qidxs, torch.int16)
-    m, k, n = xc.shape[0], xc.shape[1], Qc.shape[0]
-    _need(Qc.shape[1] * 8 == k, f"e8p_mm_skinny: x has {k} columns but Qidxs {tuple(Qidxs.shape)} encodes {Qc.shape[1] * 8}")
-    _need(Qc.device == x.device, "Qidxs and x must be on the same device")
-    _need(e8p_mm_skinny_supported(m, n, k), f"e8p_mm_skinny: shape ({m}, {n}, {k}) needs k % 128 == 0, n % 2 == 0")
-    y = _empty((m, n), dtype=torch.float16, device=x.device)
-    with torch.cuda.device(x.device):
-        capi.check(capi.lib().quip_e8p_mm_skinny(xc.data_ptr(), Qc.data_ptr(), g.data_ptr(), y.data_ptr(), m, n, k,
-                                                 _stream(x)), "quip_e8p_mm_skinny")
-    return y
-
-
-def _e8prvq4_mm_skinny_cuda(x, Qidxs, grid, scale):
-    g = _grid_i64(grid, x)
-    xc = _chk_x(x)
-    Qc = _chk_q(Qidxs, torch.int32)
-    m, k, n = xc.shape[0], xc.shape[1], Qc.shape[0]
-    _need(Qc.shape[1] * 8 == k, f"e8prvq4_mm_skinny: x has {k} columns but Qidxs {tuple(Qidxs.shape)} encodes {Qc.shape[1] * 8}")
-    _need(Qc.device == x.device, "Qidxs and x must be on the same device")
-    _need(e8p_mm_skinny_supported(m, n, k), f"e8prvq4_mm_skinny: shape ({m}, {n}, {k}) needs k % 128 == 0, n % 2 == 0")
-    y = _empty((m, n), dtype=torch.float16, device=x.device)
-    with torch.cuda.device(x.device):
-        capi.check(capi.lib().quip_e8prvq4_mm_skinny(xc.data_ptr(), Qc.data_ptr(), g.data_ptr(), float(scale), y.data_ptr(),
-                                                     m, n, k, _stream(x)), "quip_e8prvq4_mm_skinny")
-    return y
-
-
-def _skinny_generic(fn, what, x, Qidxs, qdtype, per_code, extra):
-    xc = _chk_x(x)
-    Qc = _chk_q(Qidxs, qdtype)
-    m, k, n = xc.shape[0], xc.shape[1], Qc.shape[0]
-    _need(Qc.shape[1] * per_code == k, f"{what}: x has {k} columns but Qidxs {tuple(Qidxs.shape)} encodes {Qc.shape[1] * per_code}")
-    _need(Qc.device == x.device, "Qidxs and x must be on the same device")
-    _need(e8p_mm_skinny_supported(m, n, k), f"{what}: shape ({m}, {n}, {k}) needs k % 128 == 0, n % 2 == 0")
-    y = _empty((m, n), dtype=torch.float16, device=x.device)
-    with torch.cuda.device(x.device):
-        capi.check(getattr(capi.lib(), fn)(xc.data_ptr(), Qc.data_ptr(), *extra(), y.data_ptr(), m, n, k, _stream(x)), fn)
-    return y
-
-
-def _e8prvq3_mm_skinny_cuda(x, Qidxs, grid, grid2, scale):
-    g = _grid_i64(grid, x)
-    _need(grid2.dtype == torch.int32 and grid2.numel() == 256, "e81b_grid_packed must be int32[256]")
-    g2 = grid2.contiguous()
-    xc = _chk_x(x)
-    Qc = _chk_q(Qidxs, torch.int32)
-    m, k, n = xc.shape[0], xc.shape[1], Qc.shape[0]
-    _need(Qc.shape[1] * 32 == 3 * k, f"e8prvq3_mm_skinny: x has {k} columns but Qidxs {tuple(Qidxs.shape)} encodes {Qc.shape[1] * 32 // 3}")
-    _need(Qc.device == x.device and g2.device == x.device, "Qidxs, grid2 and x must be on the same device")
-    _need(e8p_mm_skinny_supported(m, n, k), f"e8prvq3_mm_skinny: shape ({m}, {n}, {k}) needs k % 128 == 0, n % 2 == 0")
-    y = _empty((m, n), dtype=torch.float16, device=x.device)
-    with torch.cuda.device(x.device):
-        capi.check(capi.lib().quip_e8prvq3_mm_skinny(xc.data_ptr(), Qc.data_ptr(), g.data_ptr(), g2.data_ptr(), float(scale),
-                                                     y.data_ptr(), m, n, k, _stream(x)), "quip_e8prvq3_mm_skinny")
-    return y
-
-
-def _batched_generic(fn, what, x, Qidxs, qdtype, k_of_cols, extra):
-    """the fused tile kernel in another codebook's mode: x (M, k) fp16, any M >= 0"""
-    xc = _chk_x(x)
-    Qc = _chk_q(Qidxs, qdtype)
-    m, k, n = xc.shape[0], xc.shape[1], Qc.shape[0]
-    _need(k_of_cols(Qc.shape[1]) == k, f"{what}: x has {k} columns but Qidxs {tuple(Qidxs.shape)} encodes {k_of_cols(Qc.shape[1])}")
-    _need(Qc.device == x.device, "Qidxs and x must be on the same device")
-    _need(e8p_mm_batched_supported(max(m, 1), n, k), f"{what}: shape ({m}, {n}, {k}) needs k % 64 == 0 and n % 2 == 0")
-    y = _empty((m, n), dtype=torch.float16, device=x.device)
-    if m == 0:
-        return y
-    with torch.cuda.device(x.device):
-        capi.check(getattr(capi.lib(), fn)(xc.data_ptr(), Qc.data_ptr(), *extra(), y.data_ptr(), m, n, k, _stream(x)), fn)
-    return y
-
-
-def _e8prvq4_mm_batched_cuda(x, Qidxs, grid, scale):
-    g = _grid_i64(grid, x)
-    return _batched_generic("quip_e8prvq4_mm_batched", "e8prvq4_mm_batched", x, Qidxs, torch.int32, lambda c: c * 8,
-                            lambda: (g.data_ptr(), float(scale)))
-
-
-def _e8prvq3_mm_batched_cuda(x, Qidxs, grid, grid2, scale):
-    g = _grid_i64(grid, x)
-    _need(grid2.dtype == torch.int32 and grid2.numel() == 256, "e81b_grid_packed must be int32[256]")
-    g2 = grid2.contiguous()
-    _need(g2.device == x.device, "grid2 and x must be on the same device")
-    return _batched_generic("quip_e8prvq3_mm_batched", "e8prvq3_mm_batched", x, Qidxs, torch.int32, lambda c: c * 32 // 3,
-                            lambda: (g.data_ptr(), g2.data_ptr(), float(scale)))
-
-
-def _d4_mm_batched_cuda(x, Qidxs, grid):
-    g = _d4_grid_f16(grid)
-    return _batched_generic("quip_d4_mm_batched", "d4_mm_batched", x, Qidxs, torch.uint8, lambda c: c * 4, lambda: (g.data_ptr(),))
-
-
-def _hi_mm_batched_cuda(x, Qidxs):
-    return _batched_generic("quip_hi_mm_batched", "hi_mm_batched", x, Qidxs, torch.int32, lambda c: c * 8, lambda: ())
-
-
-def _d4_mm_skinny_cuda(x, Qidxs, grid):
-    g = _d4_grid_f16(grid)
-    return _skinny_generic("quip_d4_mm_skinny", "d4_mm_skinny", x, Qidxs, torch.uint8, 4, lambda: (g.data_ptr(),))
-
-
-def _hi_mm_skinny_cuda(x, Qidxs):
-    return _skinny_generic("quip_hi_mm_skinny", "hi_mm_skinny", x, Qidxs, torch.int32, 8, lambda: ())
-
-
-def _e8p_gemv_planes_cuda(planes, Qidxs, grid):
-    g = _grid_i64(grid, Qidxs)
-    Qc = _chk_q(Qidxs, torch.int16)
-    n, k = Qc.shape[0], Qc.shape[1] * 8
-    L = capi.lib()
-    _need(planes.dtype == torch.uint8 and planes.numel() >= L.quip_e8p_planes_bytes(k), "planes buffer too small")
-    y = _empty((1, n), dtype=torch.float16, device=Qidxs.device)
-    ws = _gemv_workspace(Qidxs.device, n)
-    with torch.cuda.device(Qidxs.device):
-        capi.check(L.quip_e8p_gemv_planes_ws(planes.data_ptr(), Qc.data_ptr(), g.data_ptr(), y.data_ptr(), n, k,
-                                             ws.data_ptr(), ws.numel() * 4, _stream(Qidxs)), "quip_e8p_gemv_planes_ws")
-    return y
-
-
-# ---- mm ops -------------------------------------------------------------------------
-def _mm(fn_name, x, Q, qdtype, k_per_col_num, k_per_col_den, extra):
-    xc = _chk_x(x)
-    Qc = _chk_q(Q, qdtype)
-    k = xc.shape[1]
-    _need(Qc.shape[1] * k_per_col_num == k * k_per_col_den,
-          f"{fn_name}: x has {k} columns but Qidxs {tuple(Q.shape)} encodes {Qc.shape[1] * k_per_col_num // k_per_col_den}")
-    _need(Qc.device == x.device, "Qidxs and x must be on the same device")
-    y = _empty((xc.shape[0], Qc.shape[0]), dtype=x.dtype, device=x.device)
-    if y.numel() == 0:
-        return y
-    with torch.cuda.device(x.device):
-        fn = getattr(capi.lib(), fn_name)
-        capi.check(fn(xc.data_ptr(), Qc.data_ptr(), *extra(), y.data_ptr(), xc.shape[0], Qc.shape[0],
-                      k, _stream(x)), fn_name)
-    return y
 
 
 def _grid_i64(grid: Tensor, x: Tensor):
@@ -1022,14 +857,88 @@ def _grid_i64(grid: Tensor, x: Tensor):
     return grid.contiguous()
 
 
-def _e8p_mm_cuda(x, Qidxs, grid):
-    g = _grid_i64(grid, x)
+def _e81b_packed(grid2: Tensor, x: Tensor):
+    _need(grid2.dtype == torch.int32 and grid2.numel() == 256, "e81b_grid_packed must be int32[256]")
+    _need(grid2.device == x.device, "grid2 and x must be on the same device")
+    return grid2.contiguous()
+
+
+def _d4_grid_f16(grid: Tensor):
+    # the reference kernel reinterprets `grid` as uint64[256], i.e. it silently
+    # requires fp16 (origin_order.cu:794-805, SURVEY a13); cast explicitly here.
+    _need(grid.numel() == 1024, "D4 grid must be (256, 4)")
+    return grid.to(torch.float16).contiguous()
+
+
+# ---- the five codebooks: one description each, one implementation per op family ------------------------------------
+class _Codebook(NamedTuple):
+    qdtype: torch.dtype
+    cols: Tuple[int, int]     # in features per code column, as (numerator, denominator)
+    tables: Callable          # (x, *the op's table arguments) -> the entry point's table arguments (tensors / floats)
+
+
+_CODEBOOKS = {
+    "e8p": _Codebook(torch.int16, (8, 1), lambda x, grid: (_grid_i64(grid, x),)),
+    "e8prvq4": _Codebook(torch.int32, (8, 1), lambda x, grid, scale: (_grid_i64(grid, x), float(scale))),
+    "e8prvq3": _Codebook(torch.int32, (32, 3), lambda x, grid, grid2, scale: (_grid_i64(grid, x), _e81b_packed(grid2, x),
+                                                                              float(scale))),
+    "d4": _Codebook(torch.uint8, (4, 1), lambda x, grid: (_d4_grid_f16(grid),)),
+    "hi": _Codebook(torch.int32, (8, 1), lambda x: ()),
+}
+
+
+def _operands(what, cb, x, Qidxs):
+    """x (M, k) fp16 and the codes of an (n, k) matrix -> (x, Qidxs) contiguous, m, n, k"""
     xc = _chk_x(x)
-    Qc = _chk_q(Qidxs, torch.int16)
+    Qc = _chk_q(Qidxs, cb.qdtype)
+    num, den = cb.cols
     m, k, n = xc.shape[0], xc.shape[1], Qc.shape[0]
-    _need(Qc.shape[1] * 8 == k, f"e8p_mm: x has {k} columns but Qidxs {tuple(Qidxs.shape)} encodes {Qc.shape[1] * 8}")
+    _need(Qc.shape[1] * num == k * den,
+          f"{what}: x has {k} columns but Qidxs {tuple(Qidxs.shape)} encodes {Qc.shape[1] * num // den}")
     _need(Qc.device == x.device, "Qidxs and x must be on the same device")
-    y = _empty((m, n), dtype=x.dtype, device=x.device)
+    return xc, Qc, m, n, k
+
+
+def _product(op, cb, supported=None):
+    """the op `op` (x (M, k) fp16 times the codes -> (M, n) fp16) on the entry point quip_<op>; supported = (shape
+    predicate, what it needs)"""
+    entry = _Entry("quip_" + op)
+
+    def impl(x, Qidxs, *tables):
+        tabs = cb.tables(x, *tables)
+        xc, Qc, m, n, k = _operands(op, cb, x, Qidxs)
+        _need(supported is None or supported[0](m, n, k), f"{op}: shape ({m}, {n}, {k}) needs {supported and supported[1]}")
+        y = _empty((m, n), dtype=torch.float16, device=x.device)
+        if y.numel():
+            with torch.cuda.device(x.device):
+                entry(xc.data_ptr(), Qc.data_ptr(), *_args(tabs), y.data_ptr(), m, n, k, _stream(x))
+        return y
+    return impl
+
+
+_SKINNY = (e8p_mm_skinny_supported, "k % 128 == 0, n % 2 == 0")
+_BATCHED = (lambda m, n, k: e8p_mm_batched_supported(max(m, 1), n, k), "k % 64 == 0 and n % 2 == 0")   # (any M >= 0)
+
+
+def _decompress(name, cb):
+    entry = _Entry(f"quip_decompress_{name}_origorder")
+
+    def impl(Qidxs, *tables):
+        tabs = cb.tables(Qidxs, *tables)
+        Qc = _chk_q(Qidxs, cb.qdtype)
+        k = Qc.shape[1] * cb.cols[0] // cb.cols[1]
+        w = _empty((Qc.shape[0], k), dtype=torch.float16, device=Qidxs.device)
+        with torch.cuda.device(Qidxs.device):
+            entry(Qc.data_ptr(), *_args(tabs), w.data_ptr(), Qc.shape[0], k, _stream(Qidxs))
+        return w
+    return impl
+
+
+def _e8p_mm_cuda(x, Qidxs, grid):
+    """E8P12's product also takes 1 <= M < 32 on the matrix cores, through a workspace for the rows' digit planes"""
+    (g,) = _CODEBOOKS["e8p"].tables(x, grid)
+    xc, Qc, m, n, k = _operands("e8p_mm", _CODEBOOKS["e8p"], x, Qidxs)
+    y = _empty((m, n), dtype=torch.float16, device=x.device)
     if y.numel() == 0:
         return y
     L = capi.lib()
@@ -1041,81 +950,15 @@ def _e8p_mm_cuda(x, Qidxs, grid):
     return y
 
 
-def _e8prvq3_mm_cuda(x, Qidxs, grid, grid2, scale):
-    g = _grid_i64(grid, x)
-    _need(grid2.dtype == torch.int32 and grid2.numel() == 256, "e81b_grid_packed must be int32[256]")
-    g2 = grid2.contiguous()
-    return _mm("quip_e8prvq3_mm_origorder", x, Qidxs, torch.int32, 32, 3,
-               lambda: (g.data_ptr(), g2.data_ptr(), float(scale)))
-
-
-def _e8prvq4_mm_cuda(x, Qidxs, grid, scale):
-    g = _grid_i64(grid, x)
-    return _mm("quip_e8prvq4_mm_origorder", x, Qidxs, torch.int32, 8, 1,
-               lambda: (g.data_ptr(), float(scale)))
-
-
-def _d4_grid_f16(grid: Tensor):
-    # the reference kernel reinterprets `grid` as uint64[256], i.e. it silently
-    # requires fp16 (origin_order.cu:794-805, SURVEY a13); cast explicitly here.
-    _need(grid.numel() == 1024, "D4 grid must be (256, 4)")
-    return grid.to(torch.float16).contiguous()
-
-
-def _d4_mm_cuda(x, Qidxs, grid):
-    g = _d4_grid_f16(grid)
-    return _mm("quip_d4_mm_origorder", x, Qidxs, torch.uint8, 4, 1, lambda: (g.data_ptr(),))
-
-
-def _hi_mm_cuda(x, Qidxs):
-    return _mm("quip_hi_mm_origorder", x, Qidxs, torch.int32, 8, 1, lambda: ())
-
-
-# ---- decompress ops --------------------------------------------------------------------
-def _dec(fn_name, Q, qdtype, k, extra):
-    Qc = _chk_q(Q, qdtype)
-    w = _empty((Qc.shape[0], k), dtype=torch.float16, device=Q.device)
-    with torch.cuda.device(Q.device):
-        fn = getattr(capi.lib(), fn_name)
-        capi.check(fn(Qc.data_ptr(), *extra(), w.data_ptr(), Qc.shape[0], k, _stream(Q)), fn_name)
-    return w
-
-
-def _dec_e8p_cuda(Qidxs, grid):
-    g = _grid_i64(grid, Qidxs)
-    return _dec("quip_decompress_e8p_origorder", Qidxs, torch.int16, Qidxs.shape[1] * 8,
-                lambda: (g.data_ptr(),))
-
-
-def _dec_e8prvq3_cuda(Qidxs, grid, grid2, scale):
-    g = _grid_i64(grid, Qidxs)
-    g2 = grid2.contiguous()
-    _need(g2.dtype == torch.int32 and g2.numel() == 256, "e81b_grid_packed must be int32[256]")
-    return _dec("quip_decompress_e8prvq3_origorder", Qidxs, torch.int32, Qidxs.shape[1] * 32 // 3,
-                lambda: (g.data_ptr(), g2.data_ptr(), float(scale)))
-
-
-def _dec_e8prvq4_cuda(Qidxs, grid, scale):
-    g = _grid_i64(grid, Qidxs)
-    return _dec("quip_decompress_e8prvq4_origorder", Qidxs, torch.int32, Qidxs.shape[1] * 8,
-                lambda: (g.data_ptr(), float(scale)))
-
-
-def _dec_d4_cuda(Qidxs, grid):
-    g = _d4_grid_f16(grid)
-    return _dec("quip_decompress_d4_origorder", Qidxs, torch.uint8, Qidxs.shape[1] * 4,
-                lambda: (g.data_ptr(),))
-
-
-def _dec_hi_cuda(Qidxs):
-    return _dec("quip_decompress_hi_origorder", Qidxs, torch.int32, Qidxs.shape[1] * 8, lambda: ())
-
-
 _IMPLS = {
     "hadamard": _hadamard_cuda,
     "had_transform": _had_transform_cuda,
     "had_transform_planes": _had_transform_planes_cuda,
     "e8p_gemv_planes": _e8p_gemv_planes_cuda,
+    "e8p_gemv_planes_group": lambda planes, Qidxs, grid: _gemv(_GEMV_E8P, planes, Qidxs, grid),
+    "d4_gemv_planes": lambda planes, Qidxs, grid: _gemv(_GEMV_D4, [planes], [Qidxs], grid)[0],
+    "d4_gemv_planes_group": lambda planes, Qidxs, grid: _gemv(_GEMV_D4, planes, Qidxs, grid),
+    "e8prvq3_gemv_planes_group": lambda planes, Qidxs, grid, e81b_i8: _gemv(_GEMV_RVQ3, planes, Qidxs, grid, e81b_i8),
     "rope_attn_decode": _rope_attn_decode_cuda,
     "ffn_engine": _ffn_engine_cuda,
     "block_engine": _block_engine_cuda,
@@ -1124,48 +967,26 @@ _IMPLS = {
     "had_transform_planes_group": _had_transform_planes_group_cuda,
     "had_chain_planes_group": _had_chain_planes_group_cuda,
     "had_transform_group": _had_transform_group_cuda,
-    "e8p_gemv_planes_group": _e8p_gemv_planes_group_cuda,
-    "e8p_mm_batched": _e8p_mm_batched_cuda,
-    "e8prvq4_mm_batched": _e8prvq4_mm_batched_cuda,
-    "e8prvq3_mm_batched": _e8prvq3_mm_batched_cuda,
-    "d4_mm_batched": _d4_mm_batched_cuda,
-    "hi_mm_batched": _hi_mm_batched_cuda,
-    "e8p_mm_skinny": _e8p_mm_skinny_cuda,
-    "e8prvq4_mm_skinny": _e8prvq4_mm_skinny_cuda,
-    "e8prvq3_mm_skinny": _e8prvq3_mm_skinny_cuda,
-    "d4_mm_skinny": _d4_mm_skinny_cuda,
-    "hi_mm_skinny": _hi_mm_skinny_cuda,
     "e8p_mm_planes_rows": _e8p_mm_planes_rows_cuda,
     "had_transform_planes_rows": _had_transform_planes_rows_cuda,
     "e8p_gemv_planes_rows": _e8p_gemv_planes_rows_cuda,
     "e8p_quantize": _e8p_quantize_cuda,
     "argmax_step": _argmax_step_cuda,
     "gemv_planes_rows_mode": _gemv_planes_rows_mode_cuda,
-    "e8prvq3_gemv_planes_group": _e8prvq3_gemv_planes_group_cuda,
-    "d4_gemv_planes": _d4_gemv_planes_cuda,
-    "d4_gemv_planes_group": _d4_gemv_planes_group_cuda,
     "had_transform_fused": _had_transform_fused_cuda,
     "had_transform_planes_fused": _had_transform_planes_fused_cuda,
-    "e8p_mm_origorder": _e8p_mm_cuda,
-    "e8prvq3_mm_origorder": _e8prvq3_mm_cuda,
-    "e8prvq4_mm_origorder": _e8prvq4_mm_cuda,
-    "d4_mm_origorder": _d4_mm_cuda,
-    "hi_mm_origorder": _hi_mm_cuda,
-    "decompress_e8p_origorder": _dec_e8p_cuda,
-    "decompress_e8prvq3_origorder": _dec_e8prvq3_cuda,
-    "decompress_e8prvq4_origorder": _dec_e8prvq4_cuda,
-    "decompress_d4_origorder": _dec_d4_cuda,
-    "decompress_hi_origorder": _dec_hi_cuda,
 }
+for _cb_name, _cb in _CODEBOOKS.items():
+    _IMPLS[f"{_cb_name}_mm_origorder"] = _product(f"{_cb_name}_mm_origorder", _cb)
+    _IMPLS[f"{_cb_name}_mm_skinny"] = _product(f"{_cb_name}_mm_skinny", _cb, _SKINNY)
+    _IMPLS[f"{_cb_name}_mm_batched"] = _product(f"{_cb_name}_mm_batched", _cb, _BATCHED)
+    _IMPLS[f"decompress_{_cb_name}_origorder"] = _decompress(_cb_name, _cb)
+_IMPLS["e8p_mm_origorder"] = _e8p_mm_cuda
 for _name, _fn in _IMPLS.items():
     _lib.impl(_name, _fn, "CUDA")
 
 
 # ---- fake (meta) implementations: shapes only, for torch.compile / export -----------------
-def _fake_mm(x, Qidxs, *a):
-    return x.new_empty((x.shape[0], Qidxs.shape[0]))
-
-
 def _reg_fake(name, fn):
     torch.library.register_fake("quip_lib::" + name, fn, lib=_lib)
 
@@ -1200,11 +1021,6 @@ _reg_fake("had_chain_planes_group", lambda z, z_post, z_residual, z_scale, n, pr
 _reg_fake("had_transform_group", lambda x, out_features, n, K, had, transpose, pre2, post, bias, scale, residual, pre,
           rms_weight, rms_eps, ns=None:
           [t.new_empty((t.shape[0], int(o))) for t, o in zip(x, out_features)])
-_reg_fake("e8prvq3_gemv_planes_group", lambda planes, Qidxs, grid, e81b_i8:
-          [q.new_empty((1, q.shape[0]), dtype=torch.float16) for q in Qidxs])
-_reg_fake("d4_gemv_planes", lambda planes, Qidxs, grid: Qidxs.new_empty((1, Qidxs.shape[0]), dtype=torch.float16))
-_reg_fake("d4_gemv_planes_group", lambda planes, Qidxs, grid:
-          [q.new_empty((1, q.shape[0]), dtype=torch.float16) for q in Qidxs])
 _reg_fake("had_transform_planes_rows", lambda x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate,
           resid_scale=0.0: x.new_empty((x.shape[0], _planes_numel(n, resid_scale)), dtype=torch.uint8))
 _reg_fake("e8p_gemv_planes_rows", lambda planes, Qidxs, grid:
@@ -1215,8 +1031,6 @@ _reg_fake("argmax_step", lambda logits, tok, pos: None)
 _reg_fake("e8p_quantize", lambda X, grid: (torch.empty_like(X), X.new_empty((X.shape[0],), dtype=torch.int64)))
 _reg_fake("e8p_mm_planes_rows", lambda planes, Qidxs, grid:
           Qidxs.new_empty((len(planes), Qidxs.shape[0]), dtype=torch.float16))
-_reg_fake("e8p_gemv_planes_group", lambda planes, Qidxs, grid:
-          [p.new_empty((1, q.shape[0]), dtype=torch.float16) for p, q in zip(planes, Qidxs)])
 _reg_fake("e8p_gemv_fused", lambda x, z, post, residual, rms_weight, rms_eps, z_scale, pre, scale, Qidxs, grid:
           ([z.new_empty((1, z.numel()))] if z is not None else []) +
           [q.new_empty((1, q.shape[0]), dtype=torch.float16) for q in Qidxs])
@@ -1227,24 +1041,12 @@ _reg_fake("block_engine", lambda layers, h_in, pos, cos, sin, grid, workspace, n
 _reg_fake("rope_attn_decode", lambda q, k, v, cos, sin, pos, kcache, vcache, workspace=None, window=0: torch.empty_like(q))
 _reg_fake("rope_attn_decode_z", lambda zs, posts, scales, cos, sin, pos, kcache, vcache, workspace=None, window=0:
           kcache.new_empty((zs[0].numel() // kcache.shape[2], kcache.shape[2])))
-_reg_fake("e8p_mm_skinny", lambda x, Q, g: x.new_empty((x.shape[0], Q.shape[0]), dtype=torch.float16))
-_reg_fake("e8prvq4_mm_skinny", lambda x, Q, g, s: x.new_empty((x.shape[0], Q.shape[0]), dtype=torch.float16))
-_reg_fake("e8prvq3_mm_skinny", lambda x, Q, g, g2, s: x.new_empty((x.shape[0], Q.shape[0]), dtype=torch.float16))
-_reg_fake("d4_mm_skinny", lambda x, Q, g: x.new_empty((x.shape[0], Q.shape[0]), dtype=torch.float16))
-_reg_fake("hi_mm_skinny", lambda x, Q: x.new_empty((x.shape[0], Q.shape[0]), dtype=torch.float16))
-_reg_fake("e8p_mm_batched", lambda x, Q, g: x.new_empty((x.shape[0], Q.shape[0]), dtype=torch.float16))
-_reg_fake("e8prvq4_mm_batched", lambda x, Q, g, s: x.new_empty((x.shape[0], Q.shape[0]), dtype=torch.float16))
-_reg_fake("e8prvq3_mm_batched", lambda x, Q, g, g2, s: x.new_empty((x.shape[0], Q.shape[0]), dtype=torch.float16))
-_reg_fake("d4_mm_batched", lambda x, Q, g: x.new_empty((x.shape[0], Q.shape[0]), dtype=torch.float16))
-_reg_fake("hi_mm_batched", lambda x, Q: x.new_empty((x.shape[0], Q.shape[0]), dtype=torch.float16))
-_reg_fake("e8p_gemv_planes", lambda planes, Q, g: Q.new_empty((1, Q.shape[0]), dtype=torch.float16))
-for _n in ("e8p_mm_origorder", "e8prvq3_mm_origorder", "e8prvq4_mm_origorder", "d4_mm_origorder",
-           "hi_mm_origorder"):
-    _reg_fake(_n, _fake_mm)
-_reg_fake("decompress_e8p_origorder", lambda Q, g: Q.new_empty((Q.shape[0], Q.shape[1] * 8), dtype=torch.float16))
-_reg_fake("decompress_e8prvq3_origorder",
-          lambda Q, g, g2, s: Q.new_empty((Q.shape[0], Q.shape[1] * 32 // 3), dtype=torch.float16))
-_reg_fake("decompress_e8prvq4_origorder",
-          lambda Q, g, s: Q.new_empty((Q.shape[0], Q.shape[1] * 8), dtype=torch.float16))
-_reg_fake("decompress_d4_origorder", lambda Q, g: Q.new_empty((Q.shape[0], Q.shape[1] * 4), dtype=torch.float16))
-_reg_fake("decompress_hi_origorder", lambda Q: Q.new_empty((Q.shape[0], Q.shape[1] * 8), dtype=torch.float16))
+for _n in ("e8p_gemv_planes_group", "d4_gemv_planes_group", "e8prvq3_gemv_planes_group"):
+    _reg_fake(_n, lambda planes, Qidxs, *tables: [q.new_empty((1, q.shape[0]), dtype=torch.float16) for q in Qidxs])
+for _n in ("e8p_gemv_planes", "d4_gemv_planes"):
+    _reg_fake(_n, lambda planes, Q, grid: Q.new_empty((1, Q.shape[0]), dtype=torch.float16))
+for _cb_name, _cb in _CODEBOOKS.items():
+    for _n in ("_mm_origorder", "_mm_skinny", "_mm_batched"):
+        _reg_fake(_cb_name + _n, lambda x, Q, *tables: x.new_empty((x.shape[0], Q.shape[0]), dtype=torch.float16))
+    _reg_fake(f"decompress_{_cb_name}_origorder", lambda Q, *tables, _c=_cb.cols:
+              Q.new_empty((Q.shape[0], Q.shape[1] * _c[0] // _c[1]), dtype=torch.float16))

@@ -89,6 +89,92 @@ def test_argument_validation_without_gpu(libpath):
     assert L.quip_untile_codes(p16, p16 + 1024, 24, 64, None) == -2
     assert L.quip_untile_codes(p16, p16 + 512, 16, 64, None) == -5                       # overlap
     assert L.quip_untile_codes(p16, p16 + 1024, 0, 64, None) == 0
+    # every rejection of the stand-alone bs=1 GEMV (three table modes) and of the skinny products that comes before a
+    # launch: null pointers, counts, the k multiple, misaligned codes / planes / tables / workspace
+    a = (p + 63) & ~63                                   # 64-byte aligned
+    vp = lambda *ps: (ctypes.c_void_p * len(ps))(*ps)    # noqa: E731
+    n1 = (ctypes.c_int32 * 1)(8)
+    n0 = (ctypes.c_int32 * 1)(0)
+    ok, null, bad_count, bad_ns = vp(a), vp(None), 4, n0
+
+    # (planes, qidxs, ys, ns, count, k, ws) -> code, the table arguments given by each mode's own call below
+    def common(call, kmul):
+        assert call(ok, ok, ok, None, 1, kmul * 16, None) == -1                  # ns
+        assert call(None, ok, ok, n1, 1, kmul * 16, None) == -1                  # planes array
+        assert call(ok, None, ok, n1, 1, kmul * 16, None) == -1                  # qidxs array
+        assert call(ok, ok, None, n1, 1, kmul * 16, None) == -1                  # ys array
+        assert call(ok, ok, ok, n1, 0, kmul * 16, None) == -2                    # count
+        assert call(ok, ok, ok, n1, bad_count, kmul * 16, None) == -2
+        assert call(null, ok, ok, n1, 1, kmul * 16, None) == -1                  # planes[0]
+        assert call(ok, null, ok, n1, 1, kmul * 16, None) == -1                  # qidxs[0]
+        assert call(ok, ok, null, n1, 1, kmul * 16, None) == -1                  # ys[0]
+        assert call(vp(a + 2), ok, ok, n1, 1, kmul * 16, None) == -3             # planes[0] misaligned
+        assert call(ok, vp(a + 2), ok, n1, 1, kmul * 16, None) == -3             # qidxs[0] misaligned
+        assert call(ok, ok, ok, bad_ns, 1, kmul * 16, None) == -2                # ns[0] < 1
+        assert call(ok, ok, ok, n1, 1, 0, None) == -2                            # k
+        assert call(ok, ok, ok, n1, 1, kmul * 16 + 8 if kmul > 8 else 12, None) == -2   # k multiple
+        assert call(ok, ok, ok, n1, 1, kmul * 16, a + 2) == -3                   # workspace misaligned
+
+    def e8p(grid):
+        return lambda p, q, y, ns, c, k, ws: L.quip_e8p_gemv_planes_group_ws(p, q, grid, y, ns, c, k, ws, 1 << 20, None)
+    common(e8p(a), 8)
+    assert e8p(None)(ok, ok, ok, n1, 1, 128, None) == -1                         # grid
+    assert e8p(a + 16)(ok, ok, ok, n1, 1, 128, None) == -3                       # grid: 64-byte aligned
+    assert L.quip_e8p_gemv_planes_group(ok, ok, None, ok, n1, 1, 128, None) == -1
+    assert L.quip_e8p_gemv_planes_group(ok, ok, a, ok, n1, 1, 12, None) == -2
+    assert L.quip_e8p_gemv_planes_ws(a, a, a, a, 0, 128, None, 0, None) == 0     # n == 0: ok, no launch
+    assert L.quip_e8p_gemv_planes_ws(a, a, a, a, 8, 12, None, 0, None) == -2
+    assert L.quip_e8p_gemv_planes(a, a, None, a, 8, 128, None) == -1
+    assert L.quip_e8p_gemv_planes(a, a, a, a, -1, 128, None) == -2
+    assert L.quip_e8p_gemv_planes(a, a, a, a, 0, 128, None) == 0
+    assert L.quip_e8p_gemv_planes(a + 2, a, a, a, 8, 128, None) == -3
+    assert L.quip_e8p_gemv_planes(a, a, a + 16, a, 8, 128, None) == -3
+
+    def d4(grid):
+        return lambda p, q, y, ns, c, k, ws: L.quip_d4_gemv_planes_group_ws(p, q, grid, y, ns, c, k, ws, 1 << 20, None)
+    common(d4(a), 8)
+    assert d4(None)(ok, ok, ok, n1, 1, 128, None) == -1
+    assert L.quip_d4_gemv_planes_group(ok, ok, None, ok, n1, 1, 128, None) == -1
+    assert L.quip_d4_gemv_planes_group(ok, ok, a, ok, n1, 1, 12, None) == -2
+    assert L.quip_d4_gemv_planes(a, a, a, a, 8, 12, None) == -2
+
+    def rvq3(grid, e81b):
+        return lambda p, q, y, ns, c, k, ws: L.quip_e8prvq3_gemv_planes_group_ws(p, q, grid, e81b, y, ns, c, k, ws,
+                                                                                 1 << 20, None)
+    common(rvq3(a, a), 32)
+    assert rvq3(None, a)(ok, ok, ok, n1, 1, 128, None) == -1                     # grid
+    assert rvq3(a, None)(ok, ok, ok, n1, 1, 128, None) == -1                     # e81b
+    assert rvq3(a, a + 4)(ok, ok, ok, n1, 1, 128, None) == -3                    # e81b: 8-byte aligned
+    assert rvq3(a, a)(ok, vp(a + 2), ok, n1, 1, 128, None) == -3                 # 3-byte codes: dword aligned
+    assert L.quip_e8prvq3_gemv_planes_group(ok, ok, a, a, ok, n1, 1, 48, None) == -2
+    assert L.quip_e8prvq3_gemv_planes_group(ok, ok, a, None, ok, n1, 1, 128, None) == -1
+
+    # the skinny products: (x, qidxs, y, m, n, k) around each codebook's tables
+    skinny = {
+        "e8p": lambda x, q, y, m, n, k, g=a: L.quip_e8p_mm_skinny(x, q, g, y, m, n, k, None),
+        "e8prvq4": lambda x, q, y, m, n, k, g=a: L.quip_e8prvq4_mm_skinny(x, q, g, 0.5, y, m, n, k, None),
+        "e8prvq3": lambda x, q, y, m, n, k, g=a, g2=a: L.quip_e8prvq3_mm_skinny(x, q, g, g2, 0.5, y, m, n, k, None),
+        "d4": lambda x, q, y, m, n, k, g=a: L.quip_d4_mm_skinny(x, q, g, y, m, n, k, None),
+        "hi": lambda x, q, y, m, n, k: L.quip_hi_mm_skinny(x, q, y, m, n, k, None),
+    }
+    for cb, f in skinny.items():
+        assert f(None, a, a, 2, 8, 128) == -1, cb
+        assert f(a, None, a, 2, 8, 128) == -1, cb
+        assert f(a, a, None, 2, 8, 128) == -1, cb
+        assert f(a, a, a, -1, 8, 128) == -2, cb
+        assert f(a, a, a, 2, 0, 128) == -2, cb
+        assert f(a, a, a, 2, 8, 4) == -2, cb
+        assert f(a + 2, a + 2, a + 2, 0, 8, 128) == 0, cb          # m == 0: ok, no launch (alignment not looked at)
+        assert f(a + 2, a, a, 2, 8, 128) == -3, cb                 # x
+        assert f(a, a + 2, a, 2, 8, 128) == -3, cb                 # qidxs
+        assert f(a, a, a + 2, 2, 8, 128) == -3, cb                 # y: 4-byte aligned
+        if cb != "hi":
+            assert f(a, a, a, 2, 8, 128, g=None) == -1, cb
+            assert f(a, a, a, 2, 8, 128, g=a + 4) == -3, cb         # tables: 8-byte aligned
+    assert skinny["e8prvq3"](a, a, a, 2, 8, 128, g2=None) == -1
+    assert skinny["e8prvq3"](a, a, a, 2, 8, 128, g2=a + 4) == -3
+    for cb in ("e8p", "e8prvq4", "d4"):
+        assert skinny[cb](a, a + 4, a, 2, 8, 128) == -3, cb         # codes: 16-byte aligned (E8P12RVQ3B: 4)
 
 
 def test_ops_registered_and_fail_loudly_on_cpu(libpath):

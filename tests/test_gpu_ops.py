@@ -562,3 +562,41 @@ def test_transform_vector_lengths_are_checked(Q):
     layer = Q.qlinear.QuantLinear(256, 64, cb, bias=False).to(DEV).eval()
     with pytest.raises(RuntimeError):
         layer(torch.zeros(1, 128, dtype=torch.float16, device=DEV))
+
+
+def test_mm_batched_empty_rows_every_codebook(Q):
+    """m == 0: every codebook's fused batched product returns an empty (0, n) tensor (E8P12 included)"""
+    x = torch.zeros(0, 128, dtype=torch.float16, device=DEV)
+    g = torch.zeros(256, dtype=torch.int64, device=DEV)
+    e81b = torch.zeros(256, dtype=torch.int32, device=DEV)
+    d4 = torch.zeros(256, 4, dtype=torch.float16, device=DEV)
+    ops = torch.ops.quip_lib
+    for y in (ops.e8p_mm_batched(x, torch.zeros(64, 16, dtype=torch.int16, device=DEV), g),
+              ops.e8prvq4_mm_batched(x, torch.zeros(64, 16, dtype=torch.int32, device=DEV), g, 0.5),
+              ops.e8prvq3_mm_batched(x, torch.zeros(64, 12, dtype=torch.int32, device=DEV), g, e81b, 0.5),
+              ops.d4_mm_batched(x, torch.zeros(64, 32, dtype=torch.uint8, device=DEV), d4),
+              ops.hi_mm_batched(x, torch.zeros(64, 16, dtype=torch.int32, device=DEV))):
+        assert y.shape == (0, 64) and y.dtype == torch.float16
+
+
+def test_group_gemv_refuses_short_planes(Q):
+    """every stand-alone GEMV op checks its planes against quip_e8p_planes_bytes(k virtual) before the launch
+    (E8P12RVQ3B: 2 k); one byte short is refused"""
+    L = Q.capi.lib()
+    k, n = 4096, 64
+    g = torch.zeros(256, dtype=torch.int64, device=DEV)
+    d4 = torch.zeros(256, 4, dtype=torch.float16, device=DEV)
+    e81b = torch.zeros(256, 8, dtype=torch.int8, device=DEV)
+    q16 = torch.zeros(n, k // 8, dtype=torch.int16, device=DEV)
+    qd4 = torch.zeros(n, k // 4, dtype=torch.uint8, device=DEV)
+    q3 = torch.zeros(n, 3 * k // 32, dtype=torch.int32, device=DEV)
+    ops = torch.ops.quip_lib
+    short = lambda kv: torch.zeros(L.quip_e8p_planes_bytes(kv) - 1, dtype=torch.uint8, device=DEV)   # noqa: E731
+    for call in (lambda: ops.e8p_gemv_planes(short(k), q16, g),
+                 lambda: ops.e8p_gemv_planes_group([short(k)], [q16], g),
+                 lambda: ops.d4_gemv_planes(short(k), qd4, d4),
+                 lambda: ops.d4_gemv_planes_group([short(k), short(k)], [qd4, qd4], d4),
+                 lambda: ops.e8prvq3_gemv_planes_group([short(2 * k)], [q3], g, e81b)):
+        with pytest.raises(ValueError, match="planes"):
+            call()
+    torch.cuda.synchronize()
