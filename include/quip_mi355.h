@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 8
+#define QUIP_ABI_VERSION 9
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -436,6 +436,27 @@ int quip_rope_attn_decode_z_window_f16(const void* const* z, const void* const* 
                                        const float* cos, const float* sin, const int64_t* pos, void* kcache, void* vcache,
                                        void* out, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t max_len,
                                        float scale, int32_t window, void* workspace, quip_stream_t stream);
+
+/* ---- batched decode: `batch` independent sequences, each at its own position, in one launch -------------------
+ *   q / out [batch, heads, head_dim], k / v [batch, kv_heads, head_dim] fp16 (k pre-rope); pos: device int64 [batch]
+ *   kcache / vcache [batch, kv_heads, max_len, head_dim] fp16: sequence b's slice has the bs = 1 layout
+ * Per sequence the arithmetic is quip_rope_attn_decode_window_f16's (same split rule and merge), so sequence b's
+ * output and cache rows are bit identical to that call on sequence b alone.  A position outside [0, max_len) affects
+ * its own sequence only: NaN output row, no cache write.
+ * workspace (optional): quip_rope_attn_batched_workspace_bytes(batch, heads, head_dim) bytes, zeroed once, reused
+ * (partial states per (sequence, head, split), arrival counters per (sequence, head)).  A shorter workspace cannot be
+ * detected here.  batch >= 1, heads % kv_heads == 0 (else QUIP_ERR_BAD_SHAPE); head_dim 64 or 128 (else
+ * QUIP_ERR_UNSUPPORTED). */
+size_t quip_rope_attn_batched_workspace_bytes(int32_t batch, int32_t heads, int32_t head_dim);
+int quip_rope_attn_decode_batched_f16(const void* q, const void* k, const void* v, const float* cos,
+                                      const float* sin, const int64_t* pos, void* kcache, void* vcache,
+                                      void* out, int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                                      int32_t max_len, float scale, int32_t window, void* workspace,
+                                      quip_stream_t stream);
+/* Greedy tail over `batch` rows of n fp16 logits (row-major, [batch, n]): tok[b] = first index of the largest logit of
+ * row b (torch.argmax's tie rule; an all-NaN / all -inf row gives 0), pos[b] += 1 -- one workgroup per row. */
+int quip_argmax_step_batched_f16(const void* logits, int32_t batch, int32_t n, void* tok, void* pos,
+                                 quip_stream_t stream);
 
 /* Which kernel a bs=1 E8P12 GEMV launch of `count` matrices (ns[i] rows, common k) is dispatched to by default, without
  * launching anything: 1 = e8p_gemv_mfma_kernel, 2 = e8p_gemv_v2_kernel (needs the workspace of the *_ws entry points when

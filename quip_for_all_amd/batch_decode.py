@@ -1,0 +1,225 @@
+"""Batched decode: up to `QuantLinear.skinny_max_rows` independent sequences in lockstep, each at its own cache position.
+
+`LlamaDecoder.batched(B)` shares the parent's modules, embeddings, norms, lm_head, window and rotary tables and owns B
+KV caches, B token / position counters, an attention workspace and its own captured step.  One step of B tokens runs,
+per block, the products at M = B rows (whatever `QuantLinear.regime(B)` picks: rows_exact while one rows-mode pass
+carries the rows -- bit identical to bs = 1 per row -- and the single-pass skinny kernel beyond) and ONE attention
+launch for all sequences (quip_lib::rope_attn_decode_batched: per sequence the arithmetic of the bs = 1 launch);
+the greedy tail picks B tokens in one launch (quip_lib::argmax_step_batched).
+
+Slots are independent: `fill_slot(b, prompt)` restarts slot b (its prompt pass writes only slot b's cache) while the
+others keep their state, which is all continuous batching needs from the decoder."""
+import math
+
+import torch
+import torch.nn.functional as F
+
+from . import capi
+from . import register_lib as _R
+from .qlinear import QuantLinear, forward_group
+
+try:
+    # B sequences: q (B, heads, hd), k / v (B, kv_heads, hd), pos (B,), caches (B, kv_heads, max_len, hd)
+    _R._lib.define("rope_attn_decode_batched(Tensor q, Tensor k, Tensor v, Tensor cos, Tensor sin, Tensor pos, "
+                   "Tensor(a!) kcache, Tensor(b!) vcache, Tensor(c!)? workspace, int window=0) -> Tensor")
+    # greedy tail over (B, vocab) logits: tok[b] <- argmax of row b, pos[b] += 1
+    _R._lib.define("argmax_step_batched(Tensor logits, Tensor(a!) tok, Tensor(b!) pos) -> ()")
+except RuntimeError:
+    pass
+
+
+def rope_attn_batched_workspace(batch, heads, head_dim, device):
+    """zeroed scratch for the split (long context) mode of rope_attn_decode_batched; allocate once, reuse"""
+    return torch.zeros(capi.lib().quip_rope_attn_batched_workspace_bytes(batch, heads, head_dim), dtype=torch.uint8,
+                       device=device)
+
+
+def _rope_attn_decode_batched_cuda(q, k, v, cos, sin, pos, kcache, vcache, workspace=None, window=0):
+    need = _R._need
+    for t in (q, k, v, kcache, vcache):
+        need(t.dtype == torch.float16 and t.is_contiguous() and t.is_cuda and t.device == q.device,
+             "rope_attn_decode_batched: fp16 contiguous tensors on one CUDA device")
+    need(cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
+         and cos.device == q.device and sin.device == q.device, "cos / sin must be contiguous float32 on q's device")
+    need(q.dim() == 3 and kcache.dim() == 4, "rope_attn_decode_batched: q (B, heads, hd), caches (B, kv_heads, max_len, hd)")
+    B, heads, hd = q.shape
+    kvh, max_len = kcache.shape[1], kcache.shape[2]
+    need(pos.dtype == torch.int64 and tuple(pos.shape) == (B,) and pos.is_contiguous() and pos.device == q.device,
+         "pos must be a contiguous int64 (B,) tensor on q's device")
+    need(tuple(k.shape) == (B, kvh, hd) and tuple(v.shape) == (B, kvh, hd) and tuple(kcache.shape) == (B, kvh, max_len, hd)
+         and tuple(vcache.shape) == tuple(kcache.shape) and tuple(cos.shape) == (max_len, hd)
+         and tuple(sin.shape) == (max_len, hd), "rope_attn_decode_batched: shape mismatch")
+    if workspace is not None:
+        need(workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == q.device
+             and workspace.numel() >= capi.lib().quip_rope_attn_batched_workspace_bytes(B, heads, hd),
+             "workspace: use rope_attn_batched_workspace(batch, heads, head_dim, device)")
+    out = torch.empty_like(q)
+    with torch.cuda.device(q.device):
+        capi.check(capi.lib().quip_rope_attn_decode_batched_f16(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
+            kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), B, heads, kvh, hd, max_len, 1.0 / math.sqrt(hd),
+            int(window), _R._ptr(workspace), _R._stream(q)), "quip_rope_attn_decode_batched_f16")
+    return out
+
+
+def _argmax_step_batched_cuda(logits, tok, pos):
+    _R._need(logits.dtype == torch.float16 and logits.is_contiguous() and logits.dim() == 2 and logits.is_cuda,
+             "argmax_step_batched: logits must be contiguous float16 (B, n)")
+    B = logits.shape[0]
+    _R._need(all(t.dtype == torch.int64 and tuple(t.shape) == (B,) and t.is_contiguous() and t.device == logits.device
+                 for t in (tok, pos)), "tok / pos: contiguous int64 (B,) on the logits' device")
+    with torch.cuda.device(logits.device):
+        capi.check(capi.lib().quip_argmax_step_batched_f16(logits.data_ptr(), B, logits.shape[1], tok.data_ptr(),
+                                                           pos.data_ptr(), _R._stream(logits)),
+                   "quip_argmax_step_batched_f16")
+
+
+try:
+    _R._lib.impl("rope_attn_decode_batched", _rope_attn_decode_batched_cuda, "CUDA")
+    _R._lib.impl("argmax_step_batched", _argmax_step_batched_cuda, "CUDA")
+    _R._reg_fake("rope_attn_decode_batched",
+                 lambda q, k, v, cos, sin, pos, kcache, vcache, workspace=None, window=0: torch.empty_like(q))
+    _R._reg_fake("argmax_step_batched", lambda logits, tok, pos: None)
+except RuntimeError:
+    pass
+
+
+class BatchDecoder:
+    """B sequences decoded in lockstep on the modules of a LlamaDecoder (see the module docstring).
+
+    tok / pos: (B,) int64 on the device, the current token and position of every slot.  A slot whose position left
+    [0, max_len) gets NaN logits and leaves its cache alone; the other slots are unaffected."""
+
+    def __init__(self, parent, batch, max_len=None):
+        batch = int(batch)
+        if not 1 <= batch <= QuantLinear.skinny_max_rows:
+            raise ValueError(f"batch {batch}: 1 .. QuantLinear.skinny_max_rows = {QuantLinear.skinny_max_rows} sequences")
+        max_len = parent.max_len if max_len is None else int(max_len)
+        if not 1 <= max_len <= parent.max_len:
+            raise ValueError(f"max_len {max_len}: 1 .. the parent decoder's max_len = {parent.max_len}")
+        if getattr(parent, "single_copy", False):
+            raise ValueError("a single_copy decoder keeps only the tiled codes of the bs=1 launch: batched decode would "
+                             "untile every block at every step")
+        s = parent.s
+        if s.head_dim not in (64, 128):
+            raise NotImplementedError(f"head_dim {s.head_dim}: the batched attention launch serves 64 and 128")
+        self.parent, self.batch, self.max_len, self.s, self.dev = parent, batch, max_len, s, parent.dev
+        self.window = parent.window
+        self.cos, self.sin = parent.cos[:max_len], parent.sin[:max_len]
+        self.kcache = torch.zeros(s.layers, batch, s.kv_heads, max_len, s.head_dim, dtype=torch.float16, device=self.dev)
+        self.vcache = torch.zeros_like(self.kcache)
+        self.tok = torch.zeros(batch, dtype=torch.long, device=self.dev)
+        self.pos = torch.zeros(batch, dtype=torch.long, device=self.dev)
+        self.attn_ws = rope_attn_batched_workspace(batch, s.heads, s.head_dim, self.dev)
+        self.graph = None
+        self.sampling = None
+        self.step_logits = None
+
+    def regimes(self):
+        """the product path of every module of a block at M = B (QuantLinear.regime)"""
+        L0 = self.parent.layers[0]
+        return {k: L0[k].regime(self.batch) for k in ("q", "k", "v", "o", "gate", "up", "down")}
+
+    def step(self):
+        """one token for every slot: reads tok / pos, writes the next tokens into tok, advances pos; returns the
+        logits (B, vocab)"""
+        p, s, B = self.parent, self.s, self.batch
+        h = p.embed[self.tok]                                       # (B, hidden)
+        for i, L in enumerate(p.layers):
+            q, k, v = forward_group([L["q"], L["k"], L["v"]], h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
+            a = torch.ops.quip_lib.rope_attn_decode_batched(
+                q.view(B, s.heads, s.head_dim), k.view(B, s.kv_heads, s.head_dim), v.view(B, s.kv_heads, s.head_dim),
+                self.cos, self.sin, self.pos, self.kcache[i], self.vcache[i], self.attn_ws, self.window)
+            h = L["o"].forward_fused(a.reshape(B, s.hidden), residual=h)
+            g, u = forward_group([L["gate"], L["up"]], h, rms_weight=L["ln2"], rms_eps=s.rms_eps)
+            h = L["down"].forward_fused(u, gate=g, residual=h)
+        return self._head(h)
+
+    def _head(self, h):
+        p, s = self.parent, self.s
+        logits = F.rms_norm(h, (s.hidden,), p.final_norm, s.rms_eps) @ p.lm_head.T
+        if self.sampling is None:
+            torch.ops.quip_lib.argmax_step_batched(logits, self.tok, self.pos)
+        else:
+            self.tok.copy_(p.sample(logits, *self.sampling))
+            self.pos.add_(1)
+        return logits
+
+    def set_sampling(self, temperature=None, top_k=None):
+        """greedy (None / 0) or LlamaDecoder's sampler on every row; part of the captured step"""
+        new = None if not temperature else (float(temperature), None if top_k is None else int(top_k))
+        if new != self.sampling:
+            self.sampling, self.graph = new, None
+
+    def reset(self, first_token=1):
+        self.tok.fill_(first_token)
+        self.pos.zero_()
+
+    def capture(self):
+        """warm up and capture one step as a hipGraph (before any prompt is written: the warm-up steps write cache
+        rows 0 and 1 of every slot)"""
+        self.reset()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(2):
+                self.step()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph):
+            self.step_logits = self.step()
+        torch.cuda.synchronize()
+        self.reset()
+
+    @torch.no_grad()
+    def prefill_slot(self, b, tokens):
+        """the parent's batched prompt pass over `tokens`, written into slot b's cache rows 0..P-1; pos[b] = P"""
+        tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
+        if not 0 <= b < self.batch or not 1 <= tokens.numel() <= self.max_len:
+            raise ValueError(f"slot {b} of {self.batch}, {tokens.numel()} prompt tokens (1 .. {self.max_len})")
+        return self.parent.prefill(tokens, kv=(self.kcache[:, b], self.vcache[:, b]), pos=self.pos[b:b + 1])
+
+    @torch.no_grad()
+    def fill_slot(self, b, prompt):
+        """restart slot b on `prompt` (>= 1 ids): all but its last token through prefill_slot, the last one becomes
+        tok[b]; the other slots keep their state"""
+        prompt = torch.as_tensor(prompt, dtype=torch.long, device=self.dev).reshape(-1)
+        if prompt.numel() < 1:
+            raise ValueError("an empty prompt")
+        if prompt.numel() > 1:
+            self.prefill_slot(b, prompt[:-1])
+        else:
+            self.pos[b:b + 1].zero_()
+        self.tok[b:b + 1].copy_(prompt[-1:])
+
+    @torch.no_grad()
+    def decode(self, n_tokens, use_graph=True):
+        """n_tokens steps from the current state -> (B, n_tokens) token ids (device)"""
+        if use_graph and self.graph is None:
+            raise RuntimeError("no captured step: call capture() before any prompt is written")
+        out = torch.empty(self.batch, n_tokens, dtype=torch.long, device=self.dev)
+        for t in range(n_tokens):
+            if use_graph:
+                self.graph.replay()
+            else:
+                self.step_logits = self.step()
+            out[:, t] = self.tok
+        return out
+
+    @torch.no_grad()
+    def generate(self, prompts, n_tokens, use_graph=True, temperature=None, top_k=None):
+        """decode n_tokens for each of the B prompts (1-D ids, ragged lengths >= 1) -> (B, n_tokens) token ids"""
+        prompts = [torch.as_tensor(pr, dtype=torch.long, device=self.dev).reshape(-1) for pr in prompts]
+        if len(prompts) != self.batch:
+            raise ValueError(f"{len(prompts)} prompts for {self.batch} slots")
+        for pr in prompts:
+            if not 1 <= pr.numel() or pr.numel() - 1 + n_tokens > self.max_len:
+                raise ValueError(f"a prompt of {pr.numel()} tokens + {n_tokens} new ones does not fit max_len {self.max_len}")
+        self.set_sampling(temperature, top_k)
+        if use_graph and self.graph is None:
+            self.capture()
+        self.reset()
+        for b, pr in enumerate(prompts):
+            self.fill_slot(b, pr)
+        return self.decode(n_tokens, use_graph)

@@ -645,6 +645,33 @@ int quip_rope_attn_decode_window_f16(const void* q, const void* k, const void* v
                                  max_len, scale, (hipStream_t)stream, workspace, window);
 }
 
+size_t quip_rope_attn_batched_workspace_bytes(int32_t batch, int32_t heads, int32_t head_dim) {
+  return batch > 0 && heads > 0 && head_dim > 0 ? rope_attn_batched_workspace_bytes(batch, heads, head_dim) : 0;
+}
+
+int quip_rope_attn_decode_batched_f16(const void* q, const void* k, const void* v, const float* cos,
+                                      const float* sin, const int64_t* pos, void* kcache, void* vcache,
+                                      void* out, int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                                      int32_t max_len, float scale, int32_t window, void* workspace,
+                                      quip_stream_t stream) {
+  if (!q || !k || !v || !cos || !sin || !pos || !kcache || !vcache || !out) return QUIP_ERR_NULL_POINTER;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kcache) || !aligned16(vcache) ||
+      (reinterpret_cast<uintptr_t>(pos) & 7))
+    return QUIP_ERR_MISALIGNED;
+  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
+  if (window < 0) return QUIP_ERR_BAD_SHAPE;
+  return rope_attn_decode_batched_launch(q, k, v, cos, sin, pos, kcache, vcache, out, batch, heads, kv_heads, head_dim,
+                                         max_len, scale, (hipStream_t)stream, workspace, window);
+}
+
+int quip_argmax_step_batched_f16(const void* logits, int32_t batch, int32_t n, void* tok, void* pos,
+                                 quip_stream_t stream) {
+  if (!logits || !tok || !pos) return QUIP_ERR_NULL_POINTER;
+  if (!aligned16(logits) || (reinterpret_cast<uintptr_t>(tok) & 7) || (reinterpret_cast<uintptr_t>(pos) & 7))
+    return QUIP_ERR_MISALIGNED;
+  return argmax_step_batched_launch(logits, batch, n, tok, pos, (hipStream_t)stream);
+}
+
 int quip_rope_attn_decode_z_supported(int32_t heads, int32_t kv_heads, int32_t head_dim) {
   return rope_attn_decode_z_supported(heads, kv_heads, head_dim) ? 1 : 0;
 }

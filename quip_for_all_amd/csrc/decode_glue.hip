@@ -18,6 +18,11 @@
 // transform launch it replaces), the 8 threads that own this head's 128 values leave them in LDS, and the
 // attention proper continues on the first 256 threads.  Every head repeats the three 4096-point transforms
 // (~0.5 us on otherwise idle CUs) instead of one more dependent launch per block (~5 us).
+//
+// Batched variant (SEQ): B independent sequences in one launch, sequence b = blockIdx.z with its own position pos[b],
+// its own cache slice [b] (the bs=1 layout), its own partial states and arrival counters.  Per sequence the code path
+// is the bs=1 kernel's (same lane groups, key order, split rule and merge), so every sequence's output and cache rows
+// are bit identical to a bs=1 launch on that sequence alone.
 #include "had_device.hip.h"
 #include "quip_device.hip.h"
 #include "quip_internal.h"
@@ -34,19 +39,19 @@ struct AttnZ {
 };
 
 struct AttnArgs {
-  const f16* q;        // [heads, HD]
-  const f16* k;        // [kv_heads, HD]  (pre-rope)
+  const f16* q;        // [heads, HD]            (batched: [B, heads, HD])
+  const f16* k;        // [kv_heads, HD]  (pre-rope; batched: [B, kv_heads, HD])
   const f16* v;        // [kv_heads, HD]
   const float* cos;    // [max_len, HD]
   const float* sin;    // [max_len, HD]
-  const int64_t* pos;  // device scalar: index of the current token
-  f16* kcache;         // [kv_heads, max_len, HD]
+  const int64_t* pos;  // device scalar: index of the current token (batched: [B], one per sequence)
+  f16* kcache;         // [kv_heads, max_len, HD]  (batched: [B, kv_heads, max_len, HD])
   f16* vcache;
-  f16* out;            // [heads, HD]
+  f16* out;            // [heads, HD]            (batched: [B, heads, HD])
   int heads, kv_heads, max_len;
   float scale;
   float* ws;           // split mode: partial (acc[HD], m, l) per (head, split); null: one workgroup per head
-  unsigned* counters;  // split mode: arrivals per head (zero between launches)
+  unsigned* counters;  // split mode: arrivals per head (zero between launches)  (batched: per (sequence, head))
   int window;          // sliding-window attention (Mistral: config.sliding_window): positions (pos - window, pos]; <= 0: [0, pos]
 };
 
@@ -85,15 +90,31 @@ __host__ __device__ constexpr int fht16_barriers(int logl) { return logl <= 8 ? 
 
 // ZIN with LQ == 0: q, k, v of one common width on 3 x 256 threads (run-time length).  LQ > 0 (grouped queries): q of
 // width 2^LQ on the first 2^LQ / 16 threads, k and v of width 2^LKV on the next 2 x 2^LKV / 16 (whole waves each).
-template <int HD, bool ZIN, int LQ = 0, int LKV = 0>
+// SEQ: the batched launch -- blockIdx.z selects the sequence; the pointers move to its tensors before anything is read.
+template <int HD, bool ZIN, int LQ = 0, int LKV = 0, bool SEQ = false>
 __global__ __launch_bounds__(!ZIN ? 256 : (LQ == 0 ? 768 : (1 << LQ) / 16 + 2 * ((1 << LKV) / 16)))
 void rope_attn_decode_kernel(AttnArgs a, AttnZ zz) {
   constexpr int LPK = HD / 8;        // lanes per key
   constexpr int NG = 256 / LPK;      // key groups per workgroup
   constexpr int U = 4;               // keys in flight per group
+  static_assert(!(SEQ && ZIN), "the raw-GEMV-input variants are bs=1 only");
   __shared__ float s_m[NG], s_l[NG];
   __shared__ float s_acc[NG][HD + 4];
   const int tid = threadIdx.x, h = blockIdx.x;
+  if constexpr (SEQ) {
+    const size_t b = blockIdx.z;
+    a.q += b * a.heads * HD;
+    a.k += b * a.kv_heads * HD;
+    a.v += b * a.kv_heads * HD;
+    a.pos += b;
+    a.kcache += b * a.kv_heads * (size_t)a.max_len * HD;
+    a.vcache += b * a.kv_heads * (size_t)a.max_len * HD;
+    a.out += b * a.heads * HD;
+    if (a.ws) {
+      a.ws += b * a.heads * kSplits * (HD + 4);
+      a.counters += b * a.heads;
+    }
+  }
   const int gl = tid % LPK, grp = tid / LPK, d0 = gl * 8;
   const int group = a.heads / a.kv_heads, kvh = h / group;
   // ZIN: the transform inputs do not depend on the position: requested before it is read
@@ -356,6 +377,38 @@ int rope_attn_decode_launch(const void* q, const void* k, const void* v, const f
   return rope_attn_launch_common(a, nullptr, head_dim, max_len, stream, workspace);
 }
 
+// partial states of every (sequence, head, split), then the arrival counters of every (sequence, head): batch 1 is the
+// bs=1 workspace
+size_t rope_attn_batched_workspace_bytes(int batch, int heads, int head_dim) {
+  return (size_t)batch * rope_attn_workspace_bytes(heads, head_dim);
+}
+
+int rope_attn_decode_batched_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                    const int64_t* pos, void* kcache, void* vcache, void* out, int batch, int heads,
+                                    int kv_heads, int head_dim, int max_len, float scale, hipStream_t stream,
+                                    void* workspace, int window) {
+  if (batch < 1 || batch > 65535 || heads < 1 || kv_heads < 1 || heads % kv_heads != 0 || max_len < 1)
+    return QUIP_ERR_BAD_SHAPE;
+  if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
+  AttnArgs a{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
+             cos, sin, pos, reinterpret_cast<f16*>(kcache), reinterpret_cast<f16*>(vcache),
+             reinterpret_cast<f16*>(out), heads, kv_heads, max_len, scale, nullptr, nullptr, window};
+  // the grid rule of rope_attn_launch_common, per sequence
+  const bool split = workspace != nullptr && max_len > kSplitFromPos;
+  if (split) {
+    a.ws = reinterpret_cast<float*>(workspace);
+    a.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) +
+                                             (size_t)batch * heads * kSplits * (head_dim + 4) * sizeof(float));
+  }
+  const dim3 grid(heads, split ? kSplits : 1, batch);
+  const AttnZ none{};
+  if (head_dim == 128)
+    hipLaunchKernelGGL((rope_attn_decode_kernel<128, false, 0, 0, true>), grid, dim3(256), 0, stream, a, none);
+  else
+    hipLaunchKernelGGL((rope_attn_decode_kernel<64, false, 0, 0, true>), grid, dim3(256), 0, stream, a, none);
+  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+}
+
 bool rope_attn_decode_z_supported(int heads, int kv_heads, int head_dim) {
   const int n = heads * head_dim;
   // grouped queries: Llama-2-70B / Llama-3-70B (64 heads, 8 KV heads) and Llama-3-8B / Mistral-7B (32 / 8)
@@ -385,18 +438,24 @@ int rope_attn_decode_z_launch(const void* const* z, const void* const* post, con
 }
 
 // Greedy tail of the decode step (example_generate.py's argmax sampling with temperature 0): next token =
-// first index of the largest logit (torch.argmax's tie rule), stored to tok; pos += 1.  One workgroup: the three
-// framework launches it replaces (reduce, copy, add) cost ~20 us of a 2.5 ms token.
+// first index of the largest logit (torch.argmax's tie rule), stored to tok; pos += 1.  One workgroup per row of
+// (rows, n) logits -- row r sets tok[r] and advances pos[r]; the bs=1 tail is one row: the three framework launches it
+// replaces (reduce, copy, add) cost ~20 us of a 2.5 ms token.  The first index of the maximum does not depend on the
+// order of the scan, so rows whose start is not 16-byte aligned (odd n) take 2-byte loads and give the same token.
 namespace {
 __global__ __launch_bounds__(1024) void argmax_step_kernel(const f16* __restrict__ logits, int n,
                                                            int64_t* __restrict__ tok, int64_t* __restrict__ pos) {
   __shared__ float sv[16];
   __shared__ int si[16];
   const int tid = threadIdx.x;
+  logits += (size_t)blockIdx.x * n;
+  tok += blockIdx.x;
+  pos += blockIdx.x;
+  const bool vec = (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
   float best = -3.0e38f;
   int bi = 0x7fffffff;
   for (int i = tid * 8; i < n; i += 1024 * 8) {
-    if (i + 8 <= n) {
+    if (vec && i + 8 <= n) {
       const uint4 q = *reinterpret_cast<const uint4*>(logits + i);
       const f16* h = reinterpret_cast<const f16*>(&q);
 #pragma unroll
@@ -405,7 +464,7 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(const f16* __restrict
         if (v > best || (v == best && i + j < bi)) { best = v; bi = i + j; }
       }
     } else {
-      for (int j = i; j < n; ++j) {
+      for (int j = i; j < min(n, i + 8); ++j) {
         const float v = (float)logits[j];
         if (v > best || (v == best && j < bi)) { best = v; bi = j; }
       }
@@ -433,6 +492,13 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(const f16* __restrict
 int argmax_step_launch(const void* logits, int n, void* tok, void* pos, hipStream_t stream) {
   if (n < 1) return QUIP_ERR_BAD_SHAPE;
   hipLaunchKernelGGL(argmax_step_kernel, dim3(1), dim3(1024), 0, stream, reinterpret_cast<const f16*>(logits), n,
+                     reinterpret_cast<int64_t*>(tok), reinterpret_cast<int64_t*>(pos));
+  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+}
+
+int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, void* pos, hipStream_t stream) {
+  if (batch < 1 || n < 1) return QUIP_ERR_BAD_SHAPE;
+  hipLaunchKernelGGL(argmax_step_kernel, dim3(batch), dim3(1024), 0, stream, reinterpret_cast<const f16*>(logits), n,
                      reinterpret_cast<int64_t*>(tok), reinterpret_cast<int64_t*>(pos));
   return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
 }

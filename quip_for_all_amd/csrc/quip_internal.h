@@ -176,6 +176,13 @@ int rope_attn_decode_z_launch(const void* const* z, const void* const* post, con
                               int kv_heads, int head_dim, int max_len, float scale, hipStream_t stream,
                               void* workspace, int window = 0);
 int argmax_step_launch(const void* logits, int n, void* tok, void* pos, hipStream_t stream);
+// batched decode (decode_glue.hip): B sequences, each at its own position, in one launch
+size_t rope_attn_batched_workspace_bytes(int batch, int heads, int head_dim);
+int rope_attn_decode_batched_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                    const int64_t* pos, void* kcache, void* vcache, void* out, int batch, int heads,
+                                    int kv_heads, int head_dim, int max_len, float scale, hipStream_t stream,
+                                    void* workspace, int window);
+int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, void* pos, hipStream_t stream);
 // persistent decode engine, stage 1 (decode_engine.hip): GEMV[gate, up] -> output transforms -> SiLU product ->
 // input transform of down -> GEMV[down] of one decoder block in one launch
 struct FfnEngineArgs {

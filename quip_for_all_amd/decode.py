@@ -645,16 +645,25 @@ class LlamaDecoder:
                 return logits
             self.tok.copy_(logits.argmax(-1))
         else:
-            temperature, top_k = self.sampling
-            lg = logits.float() / max(temperature, 1e-5)
-            if top_k is not None:
-                v, _ = torch.topk(lg, min(top_k, lg.size(-1)))
-                lg = torch.where(lg < v[..., -1:], -float("inf"), lg)
-            probs = torch.softmax(lg, dim=-1)
-            q = torch.empty_like(probs).exponential_(1)
-            self.tok.copy_(torch.argmax(probs / q, dim=-1))
+            self.tok.copy_(self.sample(logits, *self.sampling))
         self.pos.add_(1)
         return logits
+
+    @staticmethod
+    def sample(logits, temperature, top_k):
+        """one token per row of `logits` (rows, vocab): the sampler of set_sampling"""
+        lg = logits.float() / max(temperature, 1e-5)
+        if top_k is not None:
+            v, _ = torch.topk(lg, min(top_k, lg.size(-1)))
+            lg = torch.where(lg < v[..., -1:], -float("inf"), lg)
+        probs = torch.softmax(lg, dim=-1)
+        q = torch.empty_like(probs).exponential_(1)
+        return torch.argmax(probs / q, dim=-1)
+
+    def batched(self, batch, max_len=None):
+        """a decoder of `batch` independent sequences on this decoder's modules (batch_decode.BatchDecoder)"""
+        from .batch_decode import BatchDecoder
+        return BatchDecoder(self, batch, max_len)
 
     prefill_graph_cache_size = 8      # captured prompt lengths kept (each graph owns a memory pool)
 
@@ -686,15 +695,18 @@ class LlamaDecoder:
         g.replay()
         return logits
 
-    def prefill(self, tokens):
+    def prefill(self, tokens, kv=None, pos=None):
         """Batched prompt pass (the reference demo's prefill, example_generate.py:36-47): all `tokens` (1-D ids) go
         through every block at once -- QuantLinear on (P, hidden) rows (M >= 32: skinny chunks or decompress + dense GEMM, fewer
         rows: the skinny paths), rotary embedding for positions 0..P-1, causal attention, K / V written to rows 0..P-1
-        of the static cache -- and the position counter is left at P.  Returns the logits of the last token (1, vocab)."""
+        of the static cache -- and the position counter is left at P.  Returns the logits of the last token (1, vocab).
+        `kv` = (keys, values): per-layer (kv_heads, >= P, head_dim) tensors to write instead of this decoder's cache, and
+        `pos`: the counter to leave at P instead of self.pos (BatchDecoder.prefill_slot: one slot of a batched cache)."""
         s = self.s
         tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
         P = tokens.numel()
         assert 1 <= P <= self.max_len
+        kcache, vcache = (self.kcache, self.vcache) if kv is None else kv
         h = self.embed[tokens]                                          # (P, hidden)
         cos, sin = self.cos[:P], self.sin[:P]                           # (P, head_dim)
         for i, L in enumerate(self.layers):
@@ -703,8 +715,8 @@ class LlamaDecoder:
             q = self._rope(q.view(P, s.heads, s.head_dim).transpose(0, 1), cos, sin)          # (heads, P, hd)
             k = self._rope(k.view(P, s.kv_heads, s.head_dim).transpose(0, 1), cos, sin)
             v = v.view(P, s.kv_heads, s.head_dim).transpose(0, 1)
-            self.kcache[i][:, :P].copy_(k)
-            self.vcache[i][:, :P].copy_(v)
+            kcache[i][:, :P].copy_(k)
+            vcache[i][:, :P].copy_(v)
             if self.window and P > self.window:     # causal band: key t for query p iff p - window < t <= p
                 band = (self.arange[:P, None] >= self.arange[None, :P]) & (self.arange[:P, None] - self.arange[None, :P] < self.window)
                 a = F.scaled_dot_product_attention(q[None], k[None], v[None], attn_mask=band,
@@ -716,7 +728,7 @@ class LlamaDecoder:
             g, u = forward_group([L["gate"], L["up"]], h, rms_weight=L["ln2"], rms_eps=s.rms_eps)
             h = L["down"].forward_fused(u, gate=g, residual=h)
             self._rm_exit(L)
-        self.pos.fill_(P)
+        (self.pos if pos is None else pos).fill_(P)
         return F.rms_norm(h[-1:], (s.hidden,), self.final_norm, s.rms_eps) @ self.lm_head.T
 
     def reset(self, first_token=1):
