@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 9
+#define QUIP_ABI_VERSION 10
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -547,6 +547,25 @@ int quip_block_engine_supported(int32_t hidden, int32_t heads, int32_t kv_heads,
 size_t quip_block_engine_workspace_bytes(void);
 size_t quip_block_engine_layer_bytes(void);
 int quip_block_engine(const quip_block_engine_args* args, quip_stream_t stream);
+/* A WHOLE greedy token in the same launch (shapes 0 and 2; shape 1: QUIP_ERR_UNSUPPORTED): the launch reads the token id and
+ * fetches its embedding row itself (args->h_in is ignored and may be NULL, a token outside [0, vocab) reads row 0), runs the
+ * blocks, and behind the last one applies the final RMSNorm (x = fp16(h * rsqrt(mean(h^2) + rms_eps) * final_norm), one rounding),
+ * multiplies lm_head (fp32 sums, rounded once to fp16), picks the arg-max of the logits as stored (first index on ties, NaN
+ * never wins, nothing found = token 0) and stores it into *tok and *pos + 1 into *pos: the next launch needs nothing in
+ * between.  args->h_out may be NULL.  Workgroup w multiplies the rows [w q + min(w, r), + q (+ 1 for w < r)), vocab = 256 q + r.
+ * A launch that gives up (workspace word 1, as above) writes NaN into every logit, token 0 and *pos + 1.
+ * args->n_layers <= 146 as before: the tail's hand-off is the 1023rd and last value of the launch's hop counter. */
+typedef struct quip_token_tail_args {
+  void* tok;                 /* int64 device scalar: the current token in, the next token out */
+  void* pos;                 /* int64 device scalar, the same address as args->pos: advanced by 1 */
+  const void* embed;         /* fp16 [vocab, 4096] */
+  const void* final_norm;    /* fp16 [4096] */
+  const void* lm_head;       /* fp16 [vocab, 4096], row major */
+  void* logits;              /* fp16 [vocab] */
+  void* xnorm;               /* NULL, or fp16 [4096]: the normalised hidden state (debug output) */
+  int32_t vocab;             /* 256 <= vocab < 256 * 65535 */
+} quip_token_tail_args;
+int quip_block_engine_token(const quip_block_engine_args* args, const quip_token_tail_args* tail, quip_stream_t stream);
 /* shape 1 (grouped-query attention, hidden 8192; csrc/decode_block_gqa.hip): the same call with args->shape = 1, h_in / h_out
  * fp16 [8192], kcache / vcache fp16 [kv_heads, max_len, 128], its own workspace size, and descriptors of the same 256-byte
  * layout whose static vectors are stored the way the launch reads them:

@@ -54,6 +54,7 @@ SIGNATURES = {
     "quip_block_engine_workspace_bytes": [],
     "quip_block_engine_layer_bytes": [],
     "quip_block_engine": [_P, _P],
+    "quip_block_engine_token": [_P, _P, _P],
     "quip_debug_occupy": [_I32, _I32, _c.c_int64, _P, _P],
     "quip_block_engine_gqa_supported": [_I32, _I32, _I32, _I32, _I32, _I32],
     "quip_block_engine_gqa_workspace_bytes": [],
@@ -134,6 +135,12 @@ class BlockEngineArgs(_c.Structure):
                 ("grid_packed_abs", _P), ("workspace", _P), ("dbg", _P), ("n_layers", _I32), ("max_len", _I32),
                 ("dbg_layer", _I32), ("rms_eps", _F), ("attn_scale", _F), ("codebook", _I32), ("resid_scale", _F),
                 ("shape", _I32), ("grid2", _P)]
+
+
+class TokenTailArgs(_c.Structure):
+    """mirror of quip_token_tail_args (include/quip_mi355.h)"""
+    _fields_ = [("tok", _P), ("pos", _P), ("embed", _P), ("final_norm", _P), ("lm_head", _P), ("logits", _P),
+                ("xnorm", _P), ("vocab", _I32)]
 
 
 class HadFusion(_c.Structure):

@@ -552,6 +552,33 @@ int quip_block_engine(const quip_block_engine_args* in, quip_stream_t stream) {
   return block_engine_launch(a, (hipStream_t)stream);
 }
 
+int quip_block_engine_token(const quip_block_engine_args* in, const quip_token_tail_args* t, quip_stream_t stream) {
+  if (!in || !t) return QUIP_ERR_NULL_POINTER;
+  if (!in->layers || !in->pos || !in->cos || !in->sin || !in->grid_packed_abs || !in->workspace || !t->tok || !t->pos ||
+      !t->embed || !t->final_norm || !t->lm_head || !t->logits)
+    return QUIP_ERR_NULL_POINTER;
+  if (!aligned16(in->layers) || !aligned16(in->workspace) || (in->h_out && !aligned16(in->h_out)) ||
+      (reinterpret_cast<uintptr_t>(in->grid_packed_abs) & 63u) != 0 || !aligned16(t->embed) || !aligned16(t->lm_head) ||
+      !aligned16(t->logits) || !aligned16(t->final_norm) || (t->xnorm && !aligned16(t->xnorm)) ||
+      (reinterpret_cast<uintptr_t>(t->tok) & 7u) != 0 || (reinterpret_cast<uintptr_t>(t->pos) & 7u) != 0)
+    return QUIP_ERR_MISALIGNED;
+  if (in->n_layers < 1 || in->max_len < 1 || t->vocab < 256 || t->vocab >= 256 * 65535) return QUIP_ERR_BAD_SHAPE;
+  if (t->pos != in->pos) return QUIP_ERR_BAD_SHAPE;              // ONE position counter: read at the top, advanced at the end
+  if (in->shape != 0 && in->shape != 2) return QUIP_ERR_UNSUPPORTED;
+  BlockEngineArgs a;
+  a.layers = in->layers; a.h_in = nullptr; a.h_out = in->h_out; a.pos = in->pos; a.cos = in->cos; a.sin = in->sin;
+  a.grid = in->grid_packed_abs; a.workspace = in->workspace; a.dbg = in->dbg;
+  a.n_layers = in->n_layers; a.max_len = in->max_len; a.dbg_layer = in->dbg_layer;
+  a.rms_eps = in->rms_eps; a.attn_scale = in->attn_scale; a.codebook = in->codebook; a.resid_scale = in->resid_scale;
+  a.grid2 = in->grid2;
+  if (in->codebook == 4 && (!in->grid2 || (reinterpret_cast<uintptr_t>(in->grid2) & 7u) != 0))
+    return in->grid2 ? QUIP_ERR_MISALIGNED : QUIP_ERR_NULL_POINTER;
+  a.tok = t->tok; a.embed = t->embed; a.final_norm = t->final_norm; a.lm_head = t->lm_head; a.logits = t->logits;
+  a.xnorm = t->xnorm; a.vocab = t->vocab;
+  if (in->shape == 2) return block_engine_g8_launch(a, (hipStream_t)stream);
+  return block_engine_launch(a, (hipStream_t)stream);
+}
+
 namespace {
 // tiled[rb][c][q][n] = bytes [64 c + 16 q, +16) of row 16 rb + n: one 16-byte piece per thread, destination order
 __global__ void tile_codes_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, long long pieces, int row_u4) {

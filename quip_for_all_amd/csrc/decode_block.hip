@@ -16,6 +16,9 @@
 //     kernels, so the same bits); the 11008-wide MLP edge is the distributed two-hop computation of decode_engine.hip;
 //   * attention runs on the workgroup that owns the first 16 rows of its head (the other seven wait for the result); from 128
 //     positions on all eight take every eighth position each and merge their partial softmax states through one more hand-off.
+//   * with the tail arguments present (BlockArgs::tail) the launch is a whole greedy token: it loads the embedding row of the
+//     token id itself and, behind the last block, runs token_tail.hip.h -- final RMSNorm on the hidden state every workgroup
+//     already holds, lm_head rows split over the 256 workgroups, arg-max through one more hand-off, next token and position.
 // Codebooks: E8P12 (32 copies of the abs table, 16 of the sign table), D4 (the one-table mode of e8p_gemv_core.hip.h) and
 // E8P12RVQ4B (virtual rows of twice the width against x' = [s x_g | x_g]: twice the digits and items, eight of the nine slots).
 // Row ownership: q / k / v / o / down rows [16 w, 16 w + 16); gate / up rows k * 256 + w, k = 0..42 (column w of the
@@ -28,6 +31,7 @@
 #include "e8p_gemv_core.hip.h"
 #include "engine_sync.hip.h"
 #include "fht_wg512x.hip.h"
+#include "token_tail.hip.h"
 
 #ifndef QUIP_INO_EXACT
 #define QUIP_INO_EXACT 0
@@ -122,6 +126,8 @@ struct BlockArgs {
   float rms_eps, attn_scale;
   float resid_scale;       // E8P12RVQ4B / RVQ3B: the fp16 residual scale (as float)
   const void* grid2;       // E8P12RVQ3B: the E81B residual table, 256 x 8 int8 (4 r); else unused
+  tail::Args tail;         // lm_head != nullptr: the launch is a whole token (token_tail.hip.h): h_in is the embedding row of *tail.tok,
+                           // and behind the last block come the final norm, the logits, the next token and position + 1
 };
 
 constexpr int kWaves = 8, kThreads = 512;
@@ -463,9 +469,15 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
   // thread's h[tid + 512 k], k < 8, as four fp16 pairs (k = 2 j | 2 j + 1)
   uint32_t hreg[4];
   uint32_t hraw[8];
+  const bool whole_token = a.tail.lm_head != nullptr;      // (workgroup-uniform, the same in every workgroup)
+  const f16* h_in = a.h_in;
+  if (whole_token) {
+    const long long tk = *a.tail.tok;                     // (a token outside the table: row 0, what the arg-max answers when it found nothing)
+    h_in = a.tail.embed + (size_t)(tk >= 0 && tk < (long long)a.tail.vocab ? tk : 0) * HID;
+  }
 #pragma unroll
   for (int k = 0; k < 8; ++k)
-    asm volatile("global_load_ushort %0, %1, off" : "=v"(hraw[k]) : "v"(reinterpret_cast<const uint16_t*>(a.h_in) + tid + 512 * k) : "memory");
+    asm volatile("global_load_ushort %0, %1, off" : "=v"(hraw[k]) : "v"(reinterpret_cast<const uint16_t*>(h_in) + tid + 512 * k) : "memory");
   {
     const BlockLayer& L0 = a.layers[0];
     if constexpr (RVQ) ISSUE_RVQ_QKV(L0); else if constexpr (G8) { ISSUE8_QKV(L0, 0); ISSUE8_QKV(L0, 1); } else { ISSUE(L0, 0); ISSUE(L0, 1); ISSUE(L0, 2); }
@@ -2052,6 +2064,15 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
     esync::drain();
     own_slots(SLOTS(M_QKV));
   }
+  // ---- the token's tail: final norm, lm_head, arg-max (token_tail.hip.h) --------------------------------------------------
+  // The tables, the slots and the decode state are dead here.  The arg-max granules take the first 256 places of z_q: its
+  // last readers were this launch's last q products, and the tag is one more hop of this launch's counter.
+  if (whole_token) {
+    static_assert(B::kArea % 16 == 0 && B::kAreaBytes >= tail::kLdsBytes, "the tail's x and reduction slots in the transient area");
+    const bool tst = a.dbg != nullptr && (a.dbg_layer & 0xffff) == a.n_layers;     // stamps: dbg_layer = n_layers reuses the slots
+    ++hop;
+    tail::run(a.tail, hreg, smem + B::kArea, ctl, zbufs, ebase | hop, w, a.rms_eps, pos64, tst ? a.dbg + w * 32 : nullptr, dbg_rt);
+  }
   // ---- h_out -----------------------------------------------------------------------------------------------------------
   if (w == 0) {
     // A launch in which a wait gave up (ctl[1] != 0) has no result: h_out is all NaN then -- whoever consumes it sees that
@@ -2063,10 +2084,12 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
     esync::own(e);
     esync::own(fp);
     const bool failed = __builtin_amdgcn_readfirstlane((int)e) != 0;
+    if (a.h_out) {                                     // (a whole-token launch may do without)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      reinterpret_cast<uint16_t*>(a.h_out)[tid + 512 * (2 * j)] = failed ? (uint16_t)0x7e00 : (uint16_t)(hreg[j] & 0xffffu);
-      reinterpret_cast<uint16_t*>(a.h_out)[tid + 512 * (2 * j + 1)] = failed ? (uint16_t)0x7e00 : (uint16_t)(hreg[j] >> 16);
+      for (int j = 0; j < 4; ++j) {
+        reinterpret_cast<uint16_t*>(a.h_out)[tid + 512 * (2 * j)] = failed ? (uint16_t)0x7e00 : (uint16_t)(hreg[j] & 0xffffu);
+        reinterpret_cast<uint16_t*>(a.h_out)[tid + 512 * (2 * j + 1)] = failed ? (uint16_t)0x7e00 : (uint16_t)(hreg[j] >> 16);
+      }
     }
     if (tid == 0) {
       if (failed && fp == 0u) esync::st_word(ctl + 2, (uint32_t)pos + 1u);
@@ -2091,6 +2114,21 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
 #undef ISSUE_RVQ_DOWN_G2
 #undef ISSUE_RVQ_UP_A_G
 #undef ISSUE_RVQ_DOWN
+}
+
+// the whole-token arguments of a launch (all null / 0: blocks only, as before)
+tail::Args tail_args(const BlockEngineArgs& in) {
+  tail::Args t;
+  if (!in.lm_head) return t;
+  t.tok = reinterpret_cast<int64_t*>(in.tok);
+  t.pos = reinterpret_cast<int64_t*>(const_cast<void*>(in.pos));
+  t.embed = reinterpret_cast<const f16*>(in.embed);
+  t.norm_w = reinterpret_cast<const f16*>(in.final_norm);
+  t.lm_head = reinterpret_cast<const f16*>(in.lm_head);
+  t.logits = reinterpret_cast<f16*>(in.logits);
+  t.xnorm = reinterpret_cast<f16*>(in.xnorm);
+  t.vocab = in.vocab;
+  return t;
 }
 
 }  // namespace
@@ -2119,6 +2157,7 @@ int block_engine_g8_launch(const BlockEngineArgs& in, hipStream_t stream) {
   a.n_layers = in.n_layers; a.max_len = in.max_len; a.dbg_layer = in.dbg_layer;
   a.rms_eps = in.rms_eps; a.attn_scale = in.attn_scale; a.resid_scale = 0.f;
   a.grid2 = nullptr;
+  a.tail = tail_args(in);
   // QUIP_ENG_REP=24: the byte tables of round 5 (32 / 16 copies) instead of the nibble mode, for A/B
   static const bool rep24 = getenv("QUIP_ENG_REP") && atoi(getenv("QUIP_ENG_REP")) == 24;
   auto go = [&](auto kern, int lds, DynLdsCache& configured, ResidencyCache& resident) -> int {
@@ -2155,6 +2194,7 @@ int block_engine_launch(const BlockEngineArgs& in, hipStream_t stream) {
   a.n_layers = in.n_layers; a.max_len = in.max_len; a.dbg_layer = in.dbg_layer;
   a.rms_eps = in.rms_eps; a.attn_scale = in.attn_scale; a.resid_scale = 0.f;
   a.grid2 = in.grid2;
+  a.tail = tail_args(in);
   // codebook 0: E8P12 (32 copies of the abs table, 16 of the sign table), 1: D4 (one table of 256 x 4 bytes, a private copy per lane)
   auto go = [&](auto kern, int lds, DynLdsCache& configured, ResidencyCache& resident) -> int {
     if (ensure_dyn_lds(configured, reinterpret_cast<const void*>(kern), lds) != QUIP_OK) return QUIP_ERR_LAUNCH;

@@ -222,6 +222,15 @@ struct BlockEngineArgs {
   int codebook = 0;                  // 0: E8P12 (grid = grid_packed_abs), 1: D4 (grid = the fp16 (256, 4) table), 2: E8P12RVQ4B, 3: HI (grid = the byte table), 4: E8P12RVQ3B
   float resid_scale = 0.f;           // codebooks 2, 4: the fp16 residual scale
   const void* grid2 = nullptr;       // codebook 4 (E8P12RVQ3B): int8 (256, 8) E81B table
+  // the whole token in the launch (token_tail.hip.h; shapes 0 and 2).  lm_head == nullptr: blocks only, h_in -> h_out.  Else
+  // h_in is row *tok of embed, and the launch writes logits, the arg-max into *tok and *pos + 1 into *pos (h_out may be null)
+  void* tok = nullptr;               // int64 device scalar
+  const void* embed = nullptr;       // fp16 [vocab, hidden]
+  const void* final_norm = nullptr;  // fp16 [hidden]
+  const void* lm_head = nullptr;     // fp16 [vocab, hidden]
+  void* logits = nullptr;            // fp16 [vocab]
+  void* xnorm = nullptr;             // optional: fp16 [hidden], the normalised hidden state (debug)
+  int vocab = 0;
 };
 bool block_engine_supported(int hidden, int heads, int kv_heads, int head_dim, int n_ffn, int K);
 size_t block_engine_workspace_bytes();

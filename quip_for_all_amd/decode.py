@@ -17,6 +17,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn.functional as F
 
+from . import token_tail as _token_tail  # noqa: F401  (defines quip_lib::block_engine_token)
 from .codebook import codebook_id
 from .qlinear import (QuantLinear, chain_planes, chain_supported, ffn_engine, ffn_engine_ok, forward_group,
                       fused_in_supported, gemv_chain, gemv_fused, gemv_group_unfused, gemv_unfused, out_transform_group)
@@ -293,6 +294,7 @@ class LlamaDecoder:
         # all blocks of a token as ONE persistent launch (csrc/decode_block.hip); QUIP_BLOCK_ENGINE=0 keeps the stage-wise step
         # (E8P12; D4 through the same kernel's one-table mode; E8P12RVQ4B, E8P12RVQ3B and HI as rows of twice the virtual width)
         self.block_eng = False
+        self.token_tail = os.environ.get("QUIP_TOKEN_TAIL", "1") != "0"     # the token's tail inside that launch (step())
         d4 = all(getattr(m.codebook, "id", None) in ("D4", "E8P12RVQ4B", "HI", "E8P12RVQ3B") for m in L0.values() if isinstance(m, QuantLinear))
         gqa_shape = self.fused_prologue and self.chain and s.kv_heads != s.heads and s.hidden in (8192, 4096)   # (csrc/decode_block_gqa.hip; decode_block_g8.hip)
         if ((self.ffn_eng or gqa_shape or (d4 and self.fused_prologue and self.chain and os.environ.get("QUIP_FFN_ENGINE", "1") != "0"))
@@ -551,6 +553,18 @@ class LlamaDecoder:
         """one token: reads self.tok / self.pos, writes the greedy next token into self.tok and
         advances self.pos (all on the device)"""
         s = self.s
+        if self._token_tail_on():
+            # the whole token in ONE launch: embedding row, blocks, final norm, lm_head, arg-max, position (csrc/token_tail.hip.h)
+            lg = self.__dict__.get("_tail_logits")
+            if lg is None or lg.shape[1] != self.lm_head.shape[0] or lg.device != self.lm_head.device:
+                lg = self._tail_logits = torch.empty(1, self.lm_head.shape[0], dtype=torch.float16, device=self.lm_head.device)
+            torch.ops.quip_lib.block_engine_token(self.eng_layers, self.tok, self.pos, self.embed, self.final_norm, self.lm_head,
+                                                  lg, self.cos, self.sin, self.eng_grid, self.eng_ws, len(self.layers),
+                                                  self.max_len, s.rms_eps, 1.0 / math.sqrt(s.head_dim), None, -1,
+                                                  self.eng_codebook, self.eng_resid_scale, self.eng_shape,
+                                                  getattr(self, "eng_grid2", None),
+                                                  *((self.kcache, self.vcache) if torch.is_tensor(self.kcache) else (None, None)))
+            return lg
         h = self.embed[self.tok]                                   # (1, hidden)
         cos = sin = mask = None
         if not self.fused_attention:
@@ -579,6 +593,18 @@ class LlamaDecoder:
             h = L["down"].forward_fused(u, gate=g, residual=h)
             self._rm_exit(L)
         return self._head(h)
+
+    def _token_tail_on(self):
+        """greedy decoding on the 4096-wide persistent launch: the tail of the token rides on it.  QUIP_TOKEN_TAIL=0 (read
+        when the runtime state is built; `token_tail` afterwards, with `graph = None`) keeps the separate launches."""
+        if not (getattr(self, "block_eng", False) and getattr(self, "token_tail", True)
+                and getattr(self, "sampling", None) is None and getattr(self, "eng_shape", 0) in (0, 2)):
+            return False
+        lm, em = self.lm_head, self.embed
+        return (lm.is_cuda and lm.dtype == torch.float16 and lm.is_contiguous() and lm.dim() == 2 and lm.shape[1] == 4096
+                and 256 <= lm.shape[0] < 256 * 65535 and em.dtype == torch.float16 and em.is_contiguous()
+                and em.shape == lm.shape and em.device == lm.device and self.final_norm.dtype == torch.float16
+                and self.final_norm.is_contiguous() and len(self.layers) <= 146)
 
     def _step_fused(self, h, cos, sin, mask):
         """8 launches per block: the GEMV launches of q/k/v, o and gate/up compute their own input

@@ -235,6 +235,10 @@ class _FastDecode:
                     dec.graph = None
                 set_inputs()
                 logits = dec.step()
+        if logits is dec.__dict__.get("_tail_logits"):
+            # the whole-token launch writes ONE preallocated row (decode.py): callers of this wrapper keep what they get
+            # (generate(output_scores=True), the compiled operator's result), so they get a tensor of their own
+            logits = logits.clone()
         return logits
 
     def _dynamic_decoder(self, dev):

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Phase clocks of one block inside the persistent token launch (csrc/decode_block.hip, BSTAMP), Llama-2-7B shape.
-usage: python tools/block_stamps.py [layers] [dbg_layer] [pos] [g8]      (g8: the Llama-3-8B shape, decode_block_g8.hip)"""
+usage: python tools/block_stamps.py [layers] [dbg_layer] [pos] [g8]      (g8: the Llama-3-8B shape, decode_block_g8.hip)
+       python tools/block_stamps.py [layers] tail [pos] [g8]           the token's tail behind the last block (csrc/token_tail.hip.h:
+                                                                       dbg_layer = layers reuses the slots; the device-wide 100 MHz clock)"""
 import math
 import os
 import sys
@@ -12,7 +14,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from quip_for_all_amd import decode as D  # noqa: E402
 
 layers = int(sys.argv[1]) if len(sys.argv) > 1 else 32
-dl = int(sys.argv[2]) if len(sys.argv) > 2 else layers // 2
+tail = len(sys.argv) > 2 and sys.argv[2] == "tail"
+dl = layers if tail else (int(sys.argv[2]) if len(sys.argv) > 2 else layers // 2)
 pos0 = int(sys.argv[3]) if len(sys.argv) > 3 else 100
 g8 = len(sys.argv) > 4 and sys.argv[4] == "g8"
 shape = (D.LlamaShape(hidden=4096, ffn=14336, layers=layers, heads=32, kv_heads=8, vocab=32000) if g8 else
@@ -23,6 +26,33 @@ dec.reset(7)
 dec.pos.fill_(pos0)
 h = dec.embed[dec.tok].reshape(-1)
 dbg = torch.zeros(256 * 32, dtype=torch.int64, device="cuda:0")
+if tail:
+    # stamps of the whole-token launch: 0 tail entered, 1 x in registers (final norm), 2 rows streamed, 3 granule published,
+    # 4 (workgroup 0) token and position stored
+    logits = torch.empty(1, shape.vocab, dtype=torch.float16, device="cuda:0")
+    runs = []
+    for it in range(8):
+        dbg.zero_()
+        dec.tok.fill_(7)
+        dec.pos.fill_(pos0)
+        torch.ops.quip_lib.block_engine_token(dec.eng_layers, dec.tok, dec.pos, dec.embed, dec.final_norm, dec.lm_head, logits,
+                                              dec.cos, dec.sin, dec.eng_grid, dec.eng_ws, layers, dec.max_len, shape.rms_eps,
+                                              1.0 / math.sqrt(128), dbg, dl | 0x10000, 0, 0.0, dec.eng_shape)
+        torch.cuda.synchronize()
+        if it >= 2:
+            runs.append(dbg.cpu().numpy().reshape(256, 32)[:, :5].astype(np.float64) / 100.0)      # us
+    T = np.stack(runs)                          # (runs, 256, 5)
+    t0 = T[:, :, 0].min(axis=1, keepdims=True)
+    print(f"status {dec.engine_status()}; the token's tail behind block {layers - 1}, us (median over {len(runs)} launches; 100 MHz device clock):")
+    print(f"  workgroups enter the tail over            {np.median(T[:, :, 0].max(axis=1) - t0[:, 0]):7.2f}")
+    print(f"  final norm, x in registers (per wg, mean) {np.median((T[:, :, 1] - T[:, :, 0]).mean(axis=1)):7.2f}")
+    print(f"  lm_head rows (per wg, mean | slowest)     {np.median((T[:, :, 2] - T[:, :, 1]).mean(axis=1)):7.2f} | {np.median((T[:, :, 2] - T[:, :, 1]).max(axis=1)):7.2f}")
+    print(f"  first entry -> last workgroup streamed    {np.median(T[:, :, 2].max(axis=1) - t0[:, 0]):7.2f}   ({shape.vocab * 8192 / 1e6:.0f} MB: "
+          f"{shape.vocab * 8192 / 1e6 / np.median(T[:, :, 2].max(axis=1) - T[:, :, 1].min(axis=1)):.2f} TB/s over the stream's span)")
+    print(f"  arg-max of the workgroup + granule (mean) {np.median((T[:, :, 3] - T[:, :, 2]).mean(axis=1)):7.2f}")
+    print(f"  last granule -> token stored (wg 0)       {np.median(T[:, 0, 4] - T[:, :, 3].max(axis=1)):7.2f}")
+    print(f"  first entry -> token stored               {np.median(T[:, 0, 4] - t0[:, 0]):7.2f}")
+    sys.exit(0)
 names = ["(top)", "z_d gathered", "edge: out(down) + next block's in(q,k,v)", "next block's gemv q,k,v + publish", "head: z_qkv gathered", "head: out(q,k,v)",
          "attention + publish a", "a gathered", "in(o)", "gemv o + publish", "z_o gathered", "edge: out(o) + in(gate,up)",
          "gemv gate,up", "kmix + publish (mlp hop 1)", "row owner", "rows gathered", "kmix_in + planes", "gemv down + publish"]
