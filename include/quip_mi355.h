@@ -245,10 +245,16 @@ typedef struct quip_had_problem {
   const void* gate;
   int32_t in_features, out_features;
   float scale, rms_eps;
-  /* chain (optional; K == 1 and in_features == n): the input row is the finished output of the
-   * PRODUCER module, computed first from its raw GEMV output z:
-   *   x = z_post_scale (.) (z_scale * H_n z) + z_residual    (qlinear.py:108-114 of the producer)
-   * rounded to fp16 and also stored to h_out (by the first problem of the group).  x is ignored. */
+  /* chain (optional; in_features == n): the input row is the finished output of the PRODUCER
+   * module, computed first from its raw GEMV output z:
+   *   x = z_post_scale (.) (z_scale * (z_had (x) H_L) z) + z_residual    (qlinear.py:108-114 of the producer)
+   * rounded to fp16 and also stored to h_out (by the first problem of the group).  x is ignored.
+   * K == 1 (z_had unused, H_n): both group launches, 256 <= n <= 16384.  K > 1: the planes group only, with
+   * K in {3, 5, 7}, 512 <= L = n / K <= 4096, n <= 16384 (5120 = 5 x 1024, 3584 = 7 x 512, ...), every problem of
+   * the launch a chain, no gate / pre_scale2, h_out must not alias z either (QUIP_ERR_BAD_SHAPE); the producer's
+   * K x K factor has the launch's K.  The tall shapes
+   * (L <= 256: 5120 = 20 x 256, 11008 = 43 x 256) answer QUIP_ERR_UNSUPPORTED.  Either way the results are bit
+   * identical to quip_had_transform_group_f16 on z followed by the plain planes launch on h_out. */
   const void* z;             /* fp16 [rows, n] or NULL */
   const void* z_post_scale;  /* fp16 [n] */
   const void* z_residual;    /* fp16 [rows, n] or NULL */
@@ -270,6 +276,9 @@ typedef struct quip_had_problem {
    * instead of the launch's n, so that output transforms of different widths (q_proj next to the narrower k / v of
    * a grouped-query model) share one launch; no rms_weight in such a group.  0: the launch's n. */
   int32_t n;
+  /* chain with K > 1: the producer's (K, K) fp16 factor (had_right, applied as stored, not transposed); required
+   * then (QUIP_ERR_NULL_POINTER), ignored when z is NULL or K == 1. */
+  const void* z_had;
 } quip_had_problem;
 int quip_had_transform_group_f16(const quip_had_problem* problems, int32_t count, int64_t rows,
                                  int32_t n, int32_t K, int32_t transpose, quip_stream_t stream);

@@ -63,6 +63,8 @@ struct HadArgs {
   const f16* z_post;    // [n]
   const f16* z_res;     // [rows, n] or null
   f16* h_out;           // [rows, n]
+  const f16* z_had;     // chain with K > 1: the producer's (K, K) factor (had_right, applied as stored)
+  int chain_off;        // chain with K > 1: floats from buf to the LDS images [z | h | z_had]
   float z_scale;
   int pp;               // floats between the two halves of the ping-pong shuffle buffer (0: single buffer)
   float rvq_scale;      // != 0: planes of the E8P12RVQ4B virtual vector (see the PLANES epilogue)
@@ -168,6 +170,12 @@ __device__ __forceinline__ void raw_math16(const HadArgs& a, int idx0, const Raw
   }
 }
 
+// a requested 16-byte piece stays PACKED in its four registers up to this point: the compiler otherwise converts a
+// piece to fp32 where it lands and carries twice the registers across whatever lies between request and use
+// (an optimisation barrier only, results do not depend on it; whether it is still needed is the compiler's business:
+// checked with the clang of ROCm 7.2 through -Rpass-analysis=kernel-resource-usage, profiles/chain_k_bench.txt)
+__device__ __forceinline__ void keep_piece(uint4& q) { asm volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w)); }
+
 // One workgroup transforms E = R * L elements (R rows kp of the (K, L) view), 16 per thread.
 //   wide (TALL == false): R = 1, thread owns 16 consecutive columns, K-mix by looping over k with
 //                         16-byte loads (K == 1, or long rows: 28672 = 7 x 4096);
@@ -176,8 +184,14 @@ __device__ __forceinline__ void raw_math16(const HadArgs& a, int idx0, const Raw
 //                         tile sits in LDS and is read as broadcasts.
 // KONE: instantiation for K == 1 only (no K-mix code: far fewer registers, so that many token rows
 // of a prefill batch are resident per CU)
-template <bool PLANES, bool TALL, int MAXT, bool KONE = false>
+// CLOGL != 0: the chain of a wide K > 1 decode launch with L = 2^CLOGL (a.z set on every problem): every workgroup first
+// rebuilds the whole input row from the producer's raw GEMV output, h = fp16(z_post (.) (z_scale * (z_had (x) H_L) z) +
+// z_res), as an fp16 image in LDS -- the arithmetic of the fp16 launch it replaces, operation for operation -- and then
+// runs the K > 1 input code on that image instead of on x.  (One instantiation per length: with the run-time dispatch of
+// had::fht16 the addresses of every length stay in registers next to the vectors requested up front, and it spills.)
+template <bool PLANES, bool TALL, int MAXT, bool KONE = false, int CLOGL = 0>
 __global__ __launch_bounds__(MAXT) void had_fast_kernel(HadGroup grp) {
+  constexpr bool CHAINK = CLOGL != 0;
   HadArgs a = grp.p[blockIdx.z];
   if constexpr (PLANES) a.planes += (size_t)blockIdx.y * ((size_t)3 * a.Kp + 16);   // one plane image per token row
   extern __shared__ __attribute__((aligned(16))) float buf[];
@@ -206,7 +220,7 @@ __global__ __launch_bounds__(MAXT) void had_fast_kernel(HadGroup grp) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) v[r] = 0.f;
   if constexpr (!TALL) {
-    if ((KONE || K == 1) && a.z) {
+    if (!CHAINK && (KONE || K == 1) && a.z) {
       // producer's output transform + residual first (host guarantees vec, in_features == n == L)
       const f16* zr = a.z + row * a.n;
       float tp[16], tr[16];
@@ -252,8 +266,139 @@ __global__ __launch_bounds__(MAXT) void had_fast_kernel(HadGroup grp) {
       }
       __syncthreads();   // the shuffle buffer is reused by the transform below
       HSTAMP(9);
-    } else if (KONE || K == 1) {
+    } else if (!CHAINK && (KONE || K == 1)) {
       in_vals16(a, xr, gr, kp * L + j0, v, ss_x);
+    } else if constexpr (CHAINK) {
+      // host guarantees: rows of 16-byte vectors, in_features == n, no gate / pre2, TG = min(K, 4) groups of L / 16
+      // threads, K <= 2 TG.  Thread (tgrp, tt) meets the same rows twice: as row kq = tgrp + i TG of the producer's
+      // transform and as term k = tgrp + i TG of this module's K-mix, i = 0, 1, always at columns [j0, j0 + 16).
+      const int TG = a.tgroups;
+      a.gate = nullptr;
+      a.pre2 = nullptr;
+      f16* zs = reinterpret_cast<f16*>(buf + a.chain_off);   // z as loaded, [K][L]
+      f16* hl = zs + a.n;                                    // h, [K][L]
+      float* hz = reinterpret_cast<float*>(hl + a.n);        // z_had, [K][K]
+      const f16* zr = a.z + row * a.n;
+      const f16* zres = a.z_res ? a.z_res + row * a.n : nullptr;
+      // everything the launch reads is requested here: one memory round trip
+      uint4 zq[4];                                           // n / 8 pieces over nt = TG L / 16 threads: 2 K / TG <= 4 each
+#pragma unroll
+      for (int i = 0; i < 4; ++i) zq[i] = ldp(zr + min((tid + i * nt) * 8, a.n - 8));
+      const float hzq = (float)a.z_had[min(tid, K * K - 1)];
+      Raw16 raw[2];
+      uint4 tpq[2][2], trq[2][2];
+      float hq[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int k = min(tgrp + i * TG, K - 1);
+        hq[i] = (float)(a.transpose ? a.had[k * K + kp] : a.had[kp * K + k]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int c = k * L + j0 + 8 * h;
+          tpq[i][h] = ldp(a.z_post + c);
+          if (zres) trq[i][h] = ldp(zres + c);
+          if (a.rms_w) raw[i].d[1][h] = ldp(a.rms_w + c);
+          if (a.pre) raw[i].d[3][h] = ldp(a.pre + c);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if ((tid + i * nt) * 8 < a.n) *reinterpret_cast<uint4*>(zs + (tid + i * nt) * 8) = zq[i];
+      if (tid < K * K) hz[tid] = hzq;
+      __syncthreads();
+      // (a) the producer's rows kq = tgrp, tgrp + TG: K-mix in the association of the fp16 launch (per thread group g the
+      //     fma chain over k = g, g + TG, ..; the partial sums added in the order 0 + 1 + 2 + 3), transform on the
+      //     group's own shuffle buffer, out_elem; the workgroup that owns row kq of problem 0 also stores it to h_out
+      for (int rd = 0; rd * TG < K; ++rd) {
+        const int kq = tgrp + rd * TG;
+        const bool ract = kq < K;
+        float w[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) w[r] = 0.f;
+        if (ract) {
+          for (int g = 0; g < TG; ++g) {
+            float p[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) p[r] = 0.f;
+            for (int k = g; k < K; k += TG) {
+              const float hh = hz[kq * K + k];
+              float e[16];
+              ld8(zs + k * L + j0, e);
+              ld8(zs + k * L + j0 + 8, e + 8);
+#pragma unroll
+              for (int r = 0; r < 16; ++r) p[r] = __builtin_fmaf(hh, e[r], p[r]);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) w[r] = g == 0 ? p[r] : had::fadd(w[r], p[r]);
+          }
+        }
+        had::fht16_fixed<CLOGL, true>(w, buf + tgrp * 2 * a.pp, a.pp, tt, ract);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          keep_piece(tpq[0][h]);
+          keep_piece(tpq[1][h]);
+          if (zres) { keep_piece(trq[0][h]); keep_piece(trq[1][h]); }
+        }
+        if (ract) {
+          float tp[16], tr[16];
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            had::unpack8(rd ? tpq[1][h] : tpq[0][h], tp + 8 * h);
+            if (zres) had::unpack8(rd ? trq[1][h] : trq[0][h], tr + 8 * h);
+          }
+          f16 o[16];
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            o[r] = had::out_elem(w[r], a.z_scale, true, tp[r], false, 0.f, zres != nullptr, zres ? tr[r] : 0.f);
+          uint4* dl = reinterpret_cast<uint4*>(hl + kq * L + j0);
+          dl[0] = *reinterpret_cast<uint4*>(&o[0]);
+          dl[1] = *reinterpret_cast<uint4*>(&o[8]);
+          if (blockIdx.z == 0 && kq == kp) {
+            uint4* dst = reinterpret_cast<uint4*>(a.h_out + row * a.n + kq * L + j0);
+            dst[0] = *reinterpret_cast<uint4*>(&o[0]);
+            dst[1] = *reinterpret_cast<uint4*>(&o[8]);
+          }
+        }
+      }
+      __syncthreads();   // h is complete; the shuffle buffers are free for the partial sums and the transform below
+      // (b) this module's K-mix, the k loop of the plain launch with x read from the image
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if (a.rms_w) keep_piece(raw[i].d[1][h]);
+          if (a.pre) keep_piece(raw[i].d[3][h]);
+        }
+        const int k = tgrp + i * TG;
+        if (k < K) {
+          const int idx0 = k * L + j0;
+          raw[i].d[0][0] = *reinterpret_cast<const uint4*>(hl + idx0);
+          raw[i].d[0][1] = *reinterpret_cast<const uint4*>(hl + idx0 + 8);
+          float e[16];
+          float sx = 0.f;
+          raw_math16(a, idx0, raw[i], e, sx);
+          ss_x += sx;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            ss_in = __builtin_fmaf(e[r], e[r], ss_in);
+            v[r] = __builtin_fmaf(hq[i], e[r], v[r]);
+          }
+        }
+      }
+      if (TG > 1) {   // combine the groups' partial sums in a fixed order: 0 + 1 + 2 + 3
+        float* part = buf + a.part_off;
+        if (tgrp > 0) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) part[((tgrp - 1) * 16 + r) * nta + tt] = v[r];
+        }
+        __syncthreads();
+        if (act) {
+          for (int o = 1; o < TG; ++o) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) v[r] = had::fadd(v[r], part[((o - 1) * 16 + r) * nta + tt]);
+          }
+        }
+      }
     } else if constexpr (!KONE) {
       constexpr int U = MAXT <= 256 ? 2 : 1;       // k values per memory round trip
       const int TG = a.tgroups;
@@ -388,7 +533,8 @@ __global__ __launch_bounds__(MAXT) void had_fast_kernel(HadGroup grp) {
 
   HSTAMP(4);
   // (2) length-L transform: 4 index bits per pass in registers, LDS re-shuffle in between
-  had::fht16(v, buf, tt, logL, act, a.pp);
+  if constexpr (CHAINK) had::fht16_fixed<CLOGL, true>(v, buf, a.pp, tt, act);
+  else had::fht16(v, buf, tt, logL, act, a.pp);
   HSTAMP(5);
   const bool live = act && kp < K;                // rows past K in the last tall workgroup
 
@@ -1151,6 +1297,23 @@ int launch(HadGroup& g, int count, int64_t rows, hipStream_t stream) {
         const int part = 2 * had::buf_floats(L);
         const int lds2 = (part + (tg - 1) * 16 * (L / 16)) * 4;
         for (int i = 0; i < count; ++i) { g.p[i].tgroups = tg; g.p[i].part_off = part; g.p[i].pp = had::buf_floats(L); }
+        if (g.p[0].z) {
+          // chain: a ping-pong shuffle buffer per thread group -- the partial sums reuse the buffers of groups 1..
+          // afterwards -- then the fp16 images of z and h and the producer's factor.  What the kernel's CLOGL branch
+          // relies on, from fill(): K in {3, 5, 7} and 512 <= L <= 4096, hence tg = min(K, 4) here (L / 16 * 4 <= 1024),
+          // K <= 2 tg (two rounds of rows / k terms per thread group), K * K <= 49 <= 64 floats of z_had and <= 96 =
+          // the fewest threads of a launch (tg L / 16 at K = 3, L = 512), and n / 8 <= 4 threads pieces of z
+          if (!(K == 3 || K == 5 || K == 7) || L < 512 || tg != (K < 4 ? K : 4)) return QUIP_ERR_UNSUPPORTED;
+          const int chain = tg * part;
+          const int lds3 = chain * 4 + 2 * n * 2 + 64 * 4;
+          for (int i = 0; i < count; ++i) g.p[i].chain_off = chain;
+          static DynLdsCache c3[4];
+          const int threads = (L / 16) * tg, logL = g.p[0].logL;
+          return logL == 9 ? launch_one(had_fast_kernel<true, false, 512, false, 9>, c3[0], g, grid, threads, lds3, stream)
+               : logL == 10 ? launch_one(had_fast_kernel<true, false, 512, false, 10>, c3[1], g, grid, threads, lds3, stream)
+               : logL == 11 ? launch_one(had_fast_kernel<true, false, 512, false, 11>, c3[2], g, grid, threads, lds3, stream)
+                            : launch_one(had_fast_kernel<true, false, 768, false, 12>, c3[3], g, grid, threads, lds3, stream);
+        }
         static DynLdsCache c2[2];
         return planes ? launch_one(had_fast_kernel<true, false, 1024>, c2[0], g, grid, (L / 16) * tg, lds2, stream)
                       : launch_one(had_fast_kernel<false, false, 1024>, c2[1], g, grid, (L / 16) * tg, lds2, stream);
@@ -1244,12 +1407,21 @@ int fill(HadArgs& a, const HadProblem& pr, bool planes, int n, int K, int transp
   a.z_scale = pr.z_scale;
   a.tgroups = 1;
   a.part_off = 0;
-  if (pr.z) {   // chain: plain power-of-two width, blocked kernel, vector access
-    if (K != 1 || pr.in_features != n || a.L < 256 || a.L > 16384) return QUIP_ERR_UNSUPPORTED;
-    if (!pr.z_post || !pr.h_out) return QUIP_ERR_NULL_POINTER;
+  a.z_had = reinterpret_cast<const f16*>(pr.z_had);
+  a.chain_off = 0;
+  if (pr.z) {   // chain: blocked kernel, vector access
+    // K == 1: plain power-of-two width; K > 1: the wide single-row planes launch with K = 3, 5, 7 thread-group
+    // rounds (512 <= L <= 4096, n <= 16384) -- the tall shapes (L <= 256, K-mix on the matrix cores) have no chain
+    if (pr.in_features != n) return QUIP_ERR_UNSUPPORTED;
+    if (K == 1 ? (a.L < 256 || a.L > 16384)
+               : (!(K == 3 || K == 5 || K == 7) || a.L < 512 || a.L > 4096 || n > 16384 || !planes || pr.gate || pr.pre2))
+      return QUIP_ERR_UNSUPPORTED;
+    if (!pr.z_post || !pr.h_out || (K > 1 && !pr.z_had)) return QUIP_ERR_NULL_POINTER;
     if (pr.h_out == pr.z_residual) return QUIP_ERR_BAD_SHAPE;
-    const uintptr_t al = reinterpret_cast<uintptr_t>(pr.z) | reinterpret_cast<uintptr_t>(pr.z_post) |
-                         reinterpret_cast<uintptr_t>(pr.z_residual) | reinterpret_cast<uintptr_t>(pr.h_out);
+    if (K > 1 && pr.h_out == pr.z) return QUIP_ERR_BAD_SHAPE;   // every workgroup rereads all of z while rows of h_out are stored
+    uintptr_t al = reinterpret_cast<uintptr_t>(pr.z) | reinterpret_cast<uintptr_t>(pr.z_post) |
+                   reinterpret_cast<uintptr_t>(pr.z_residual) | reinterpret_cast<uintptr_t>(pr.h_out);
+    if (K > 1) al |= reinterpret_cast<uintptr_t>(pr.pre) | reinterpret_cast<uintptr_t>(pr.rms_weight);   // its k loop is the vector one
     if (al & 15) return QUIP_ERR_MISALIGNED;
   }
   a.in_features = pr.in_features; a.out_features = planes ? n : pr.out_features; a.n = n; a.K = K;
@@ -1281,6 +1453,11 @@ int had_transform_group_launch(const HadProblem* problems, int count, bool plane
     if (planes && (reinterpret_cast<uintptr_t>(problems[i].out) & 15) != 0) return QUIP_ERR_MISALIGNED;
   }
   if (planes && (g.p[0].L < 4 || n % 16 != 0)) return QUIP_ERR_BAD_SHAPE;
+  if (K > 1) {   // the K > 1 chain is one instantiation for the whole launch: one token row, every problem a chain
+    bool any = false, all = true;
+    for (int i = 0; i < count; ++i) { any = any || problems[i].z; all = all && problems[i].z; }
+    if (any && (!all || rows != 1)) return QUIP_ERR_UNSUPPORTED;
+  }
   if (rows <= 0) return QUIP_OK;
   // grid.y carries the token rows (<= 65535 per launch): longer batches go out in slices
   constexpr int64_t kMaxRows = 65535;

@@ -95,7 +95,8 @@ struct HadProblem {
   const void* gate = nullptr;
   int in_features = 0, out_features = 0;
   float scale = 1.f, rms_eps = 1e-5f;
-  // chain (K == 1, in_features == n): x := z_post (.) (z_scale * H_n z) + z_residual, also stored to h_out
+  // chain (in_features == n; K == 1, or the wide K = 3, 5, 7 planes launch with z_had): x := z_post (.) (z_scale *
+  // (z_had (x) H_L) z) + z_residual, also stored to h_out
   const void* z = nullptr;
   const void* z_post = nullptr;
   const void* z_residual = nullptr;
@@ -104,6 +105,7 @@ struct HadProblem {
   float resid_scale = 0.f;   // planes only: != 0 -> planes of the E8P12RVQ4B virtual vector [s * x_g | x_g] (2n digits)
   int planes_layout = 0;     // planes only: 0 plain (or RVQ4 when resid_scale != 0), 2 = HI virtual vector (2n digits)
   int n = 0;                 // fp16, K == 1: this problem's own width (0: the launch's n)
+  const void* z_had = nullptr;   // chain, K > 1: the producer's (K, K) fp16 had_right (its K is the launch's K)
 };
 int had_transform_group_launch(const HadProblem* problems, int count, bool planes, int64_t rows, int n, int K,
                                int transpose, hipStream_t stream);

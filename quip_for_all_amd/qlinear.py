@@ -454,18 +454,41 @@ def gemv_unfused(layer, x, gate=None, rms_weight=None, rms_eps=1e-5):
     return layer.codebook.mm_planes(planes, layer.Qidxs)
 
 
+def _chain_shape(n, K):
+    """widths the chain launch takes: a power of two (K == 1), or K = 3, 5, 7 times a power of two 512..4096 (5120 = 5 x
+    1024, 3584 = 7 x 512: the wide single-row launch; tall factorisations such as 20 x 256 have no chain).  The same table
+    as fill() in csrc/hadamard.hip (`if (pr.z)`); tests/test_chain_k_host.py sweeps both and holds them together."""
+    if K == 1:
+        return _pow2(n) and 256 <= n <= 16384
+    L = n // K
+    return K in (3, 5, 7) and n == K * L and _pow2(L) and 512 <= L <= 4096 and n <= 16384
+
+
 def chain_supported(layers, prev):
     """can `gemv_chain` fold `prev`'s output side into the input transforms of `layers`?"""
     l0 = layers[0]
     cb = l0.codebook
-    n = l0.q_in_features
-    return (hasattr(cb, "planes_group_supported") and 1 <= len(layers) <= 3 and _pow2(n) and 256 <= n <= 16384
-            and all(type(l.codebook) is type(cb) and not l.training and l.K_left == 1 and l.SU is not None
-                    and l.in_features == l.q_in_features == n
+    n, K = l0.q_in_features, l0.K_left
+    return (hasattr(cb, "planes_group_supported") and 1 <= len(layers) <= 3 and _chain_shape(n, K)
+            and all(type(l.codebook) is type(cb) and not l.training and l.K_left == K and l.SU is not None
+                    and l.in_features == l.q_in_features == n and (K == 1 or l.had_left is not None)
                     and cb.planes_supported(l.q_out_features, n) for l in layers)
             and cb.planes_group_supported([l.q_out_features for l in layers], n)
-            and prev.K_right == 1 and prev.out_features == prev.q_out_features == n
+            and prev.K_right == K and prev.out_features == prev.q_out_features == n
+            and (K == 1 or prev.had_right is not None)
             and prev.bias is None and not prev.per_channel and prev.SV is not None)
+
+
+def _chain_launch(layers, prev, z, residual, rms_weight, rms_eps):
+    l0 = layers[0]
+    n, K = l0.q_in_features, l0.K_left
+    L = n // K
+    return torch.ops.quip_lib.had_chain_planes_group(
+        z.reshape(1, n), prev._vec(prev.SV), None if residual is None else residual.reshape(1, n),
+        1.0 / math.sqrt(prev.q_out_features // prev.K_right), n, [l._vec(l.SU) for l in layers],
+        [l.wscale_float / math.sqrt(L) for l in layers], None if rms_weight is None else l0._vec(rms_weight), rms_eps,
+        getattr(l0.codebook, "planes_resid_scale", 0.0), K, prev._had("had_right") if K > 1 else None,
+        [l._had("had_left") for l in layers] if K > 1 else None)
 
 
 def gemv_chain(layers, prev, z, residual=None, rms_weight=None, rms_eps=1e-5):
@@ -473,13 +496,7 @@ def gemv_chain(layers, prev, z, residual=None, rms_weight=None, rms_eps=1e-5):
     finishes the producer `prev` (output transform of its raw GEMV output `z`, + `residual`) and
     then runs its own input transform (RMSNorm, SU, Hadamard -> digit planes); (2) the grouped
     GEMV.  Returns (h, [z_i]) like gemv_fused."""
-    l0 = layers[0]
-    n = l0.q_in_features
-    res = torch.ops.quip_lib.had_chain_planes_group(
-        z.reshape(1, n), prev._vec(prev.SV), None if residual is None else residual.reshape(1, n),
-        1.0 / math.sqrt(prev.q_out_features // prev.K_right), n, [l._vec(l.SU) for l in layers],
-        [l.wscale_float / math.sqrt(n) for l in layers], None if rms_weight is None else l0._vec(rms_weight), rms_eps,
-        getattr(l0.codebook, "planes_resid_scale", 0.0))
+    res = _chain_launch(layers, prev, z, residual, rms_weight, rms_eps)
     h, planes = res[0], list(res[1:])
     return h, _gemv_planes_grouped(layers, planes)
 
@@ -533,11 +550,5 @@ def ffn_engine(gate, up, down, planes, workspace, dbg=None):
 
 def chain_planes(layers, prev, z, residual=None, rms_weight=None, rms_eps=1e-5):
     """the Hadamard chain launch of `gemv_chain` alone: (h, [planes_i])"""
-    l0 = layers[0]
-    n = l0.q_in_features
-    res = torch.ops.quip_lib.had_chain_planes_group(
-        z.reshape(1, n), prev._vec(prev.SV), None if residual is None else residual.reshape(1, n),
-        1.0 / math.sqrt(prev.q_out_features // prev.K_right), n, [l._vec(l.SU) for l in layers],
-        [l.wscale_float / math.sqrt(n) for l in layers], None if rms_weight is None else l0._vec(rms_weight), rms_eps,
-        getattr(l0.codebook, "planes_resid_scale", 0.0))
+    res = _chain_launch(layers, prev, z, residual, rms_weight, rms_eps)
     return res[0], list(res[1:])

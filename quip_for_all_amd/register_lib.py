@@ -81,7 +81,8 @@ _SCHEMAS = {
     # chain: output side of the producer module (z, its SV, residual) + input transforms of 1..3 consumers;
     # returns [h] + planes
     "had_chain_planes_group": "(Tensor z, Tensor z_post, Tensor? z_residual, float z_scale, int n, Tensor[] pre, "
-                              "float[] scale, Tensor? rms_weight, float rms_eps, float resid_scale=0.0) -> Tensor[]",
+                              "float[] scale, Tensor? rms_weight, float rms_eps, float resid_scale=0.0, int K=1, "
+                              "Tensor? z_had=None, Tensor?[]? had=None) -> Tensor[]",
     "had_transform_group": "(Tensor[] x, int[] out_features, int n, int K, Tensor?[] had, bool transpose, "
                            "Tensor?[] pre2, Tensor?[] post, Tensor?[] bias, float[] scale, Tensor?[] residual, "
                            "Tensor?[] pre, Tensor? rms_weight, float rms_eps, int[]? ns=None) -> Tensor[]",
@@ -442,26 +443,35 @@ def _had_transform_planes_group_cuda(x, n, K, had, transpose, pre, scale, rms_we
     return outs
 
 
-def _had_chain_planes_group_cuda(z, z_post, z_residual, z_scale, n, pre, scale, rms_weight, rms_eps, resid_scale=0.0):
+def _had_chain_planes_group_cuda(z, z_post, z_residual, z_scale, n, pre, scale, rms_weight, rms_eps, resid_scale=0.0,
+                                 K=1, z_had=None, had=None):
+    """K > 1 (n = K * L): z_had is the producer's (K, K) had_right, had[i] consumer i's had_left (applied transposed);
+    z_scale and scale then carry 1 / sqrt(L)"""
     zc = _chk_x(z)
     count = len(pre)
     _need(zc.shape == (1, n), "had_chain_planes_group is the bs=1 path: z must be (1, n)")
     _need(1 <= count <= capi.MAX_GROUP and len(scale) == count, "group of 1..3 problems")
     _need(z_residual is None or tuple(z_residual.shape) == (1, n), "residual shape")
+    had = list(had) if had is not None else [None] * count
+    _need(len(had) == count, "had: one factor per problem")
+    _need(K == 1 or z_had is not None, f"had_chain_planes_group: K = {K} needs the producer's (K, K) factor")
     for i in range(count):
-        _chk_lens("had_chain_planes_group", n, n, n, 1, None, pre[i], post=z_post, rms_weight=rms_weight)
+        _chk_lens("had_chain_planes_group", n, n, n, K, had[i], pre[i], post=z_post, rms_weight=rms_weight)
+    _chk_lens("had_chain_planes_group (producer)", n, n, n, K, z_had if K > 1 else None)
     L = capi.lib()
     nbytes = L.quip_e8p_planes_bytes(2 * n if resid_scale != 0.0 else n)
     outs = [_empty(nbytes, dtype=torch.uint8, device=z.device) for _ in range(count)]
     h = _empty((1, n), dtype=torch.float16, device=z.device)
     arr = (capi.HadProblem * count)()
     for i in range(count):
-        arr[i] = capi.HadProblem(None, outs[i].data_ptr(), None, _vec_ok(pre[i], z.device), None, None, None, None,
+        arr[i] = capi.HadProblem(None, outs[i].data_ptr(), _vec_ok(had[i], z.device) if K > 1 else None,
+                                 _vec_ok(pre[i], z.device), None, None, None, None,
                                  _vec_ok(rms_weight, z.device), None, n, n, float(scale[i]), float(rms_eps),
                                  zc.data_ptr(), _vec_ok(z_post, z.device), _vec_ok(z_residual, z.device),
-                                 h.data_ptr(), float(z_scale), *_layout(resid_scale))
+                                 h.data_ptr(), float(z_scale), *_layout(resid_scale), 0,
+                                 _vec_ok(z_had, z.device) if K > 1 else None)
     with torch.cuda.device(z.device):
-        capi.check(L.quip_had_transform_planes_group(arr, count, n, 1, 1, _stream(z)),
+        capi.check(L.quip_had_transform_planes_group(arr, count, n, int(K), 1, _stream(z)),
                    "quip_had_transform_planes_group (chain)")
     return [h] + outs
 
@@ -1016,8 +1026,8 @@ _reg_fake("had_transform_planes_fused", lambda x, n, K, had, transpose, pre, sca
 _reg_fake("had_transform_planes_group", lambda x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate,
           resid_scale=0.0: [x.new_empty((_planes_numel(n, resid_scale),), dtype=torch.uint8) for _ in pre])
 _reg_fake("had_chain_planes_group", lambda z, z_post, z_residual, z_scale, n, pre, scale, rms_weight, rms_eps,
-          resid_scale=0.0: [z.new_empty((1, n))] + [z.new_empty((_planes_numel(n, resid_scale),), dtype=torch.uint8)
-                                                     for _ in pre])
+          resid_scale=0.0, K=1, z_had=None, had=None:
+          [z.new_empty((1, n))] + [z.new_empty((_planes_numel(n, resid_scale),), dtype=torch.uint8) for _ in pre])
 _reg_fake("had_transform_group", lambda x, out_features, n, K, had, transpose, pre2, post, bias, scale, residual, pre,
           rms_weight, rms_eps, ns=None:
           [t.new_empty((t.shape[0], int(o))) for t, o in zip(x, out_features)])
