@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 10
+#define QUIP_ABI_VERSION 11
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -462,6 +462,25 @@ int quip_rope_attn_decode_batched_f16(const void* q, const void* k, const void* 
                                       void* out, int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim,
                                       int32_t max_len, float scale, int32_t window, void* workspace,
                                       quip_stream_t stream);
+/* ---- prompt-side attention: a chunk of `rows` tokens appended behind a live cache, one launch ---------------------
+ * Row i of the chunk is at position p = *pos + i (pos: device int64 scalar, read by the launch -- a captured call
+ * serves every start position).  Its k row, rotated, and its v row are written to cache row p; out[i] is the softmax
+ * attention of the rotated q[i] over keys max(0, p + 1 - window) .. p (window == 0: 0 .. p): cache rows below *pos and
+ * the chunk's own rows.
+ *   q / out [rows, heads, head_dim], k / v [rows, kv_heads, head_dim] fp16, token major (k pre-rope)
+ *   cos / sin [max_len, head_dim] fp32; kcache / vcache [kv_heads, max_len, head_dim] fp16
+ * Arithmetic: q and k rotated as quip_rope_attn_decode_f16 does and rounded to fp16 -- the cached K rows are bit
+ * identical to what that call writes for the same k at the same position, V rows are copies; scores, the scale
+ * applied to them, running max and sum in fp32; probabilities rounded to fp16 for the product with V; fp32
+ * accumulation; one rounding of the output.  A row's result depends on its own q and on cache rows <= its position
+ * only: one call on `rows` tokens and any split of them into consecutive calls give bit-identical outputs and caches.
+ * *pos < 0 or *pos + rows > max_len: nothing is written to the caches and every out row is NaN.
+ * rows >= 1, max_len >= 1, heads % kv_heads == 0, window >= 0 (else QUIP_ERR_BAD_SHAPE); head_dim 64 or 128 (else
+ * QUIP_ERR_UNSUPPORTED); all tensors 16-byte aligned, pos 8-byte (else QUIP_ERR_MISALIGNED). */
+int quip_rope_attn_chunk_f16(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                             const int64_t* pos, void* kcache, void* vcache, void* out, int32_t rows, int32_t heads,
+                             int32_t kv_heads, int32_t head_dim, int32_t max_len, float scale, int32_t window,
+                             quip_stream_t stream);
 /* Greedy tail over `batch` rows of n fp16 logits (row-major, [batch, n]): tok[b] = first index of the largest logit of
  * row b (torch.argmax's tie rule; an all-NaN / all -inf row gives 0), pos[b] += 1 -- one workgroup per row. */
 int quip_argmax_step_batched_f16(const void* logits, int32_t batch, int32_t n, void* tok, void* pos,

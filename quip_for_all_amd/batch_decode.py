@@ -7,8 +7,9 @@ carries the rows -- bit identical to bs = 1 per row -- and the single-pass skinn
 launch for all sequences (quip_lib::rope_attn_decode_batched: per sequence the arithmetic of the bs = 1 launch);
 the greedy tail picks B tokens in one launch (quip_lib::argmax_step_batched).
 
-Slots are independent: `fill_slot(b, prompt)` restarts slot b (its prompt pass writes only slot b's cache) while the
-others keep their state, which is all continuous batching needs from the decoder."""
+Slots are independent: `fill_slot(b, prompt)` restarts slot b (its prompt pass writes only slot b's cache) and
+`extend_slot(b, tokens)` appends to it while the others keep their state, which is all continuous batching needs from
+the decoder."""
 import math
 
 import torch
@@ -179,6 +180,15 @@ class BatchDecoder:
         if not 0 <= b < self.batch or not 1 <= tokens.numel() <= self.max_len:
             raise ValueError(f"slot {b} of {self.batch}, {tokens.numel()} prompt tokens (1 .. {self.max_len})")
         return self.parent.prefill(tokens, kv=(self.kcache[:, b], self.vcache[:, b]), pos=self.pos[b:b + 1])
+
+    @torch.no_grad()
+    def extend_slot(self, b, tokens, chunk=512):
+        """the parent's extend() on slot b: `tokens` (>= 1 ids) appended behind pos[b] in slot b's cache, pos[b] advanced
+        on the device; the other slots keep their state.  Returns the last token's logits (1, vocab)."""
+        tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
+        if not 0 <= b < self.batch or tokens.numel() < 1:
+            raise ValueError(f"slot {b} of {self.batch}, {tokens.numel()} tokens to append (>= 1)")
+        return self.parent.extend(tokens, chunk=chunk, kv=(self.kcache[:, b], self.vcache[:, b]), pos=self.pos[b:b + 1])
 
     @torch.no_grad()
     def fill_slot(self, b, prompt):

@@ -185,6 +185,10 @@ int rope_attn_decode_batched_launch(const void* q, const void* k, const void* v,
                                     int kv_heads, int head_dim, int max_len, float scale, hipStream_t stream,
                                     void* workspace, int window);
 int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, void* pos, hipStream_t stream);
+// chunk_attn.hip.h (in decode_glue.hip): rows queries at positions [*pos, *pos + rows) against cache rows [0, *pos + rows)
+int rope_attn_chunk_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                           const int64_t* pos, void* kcache, void* vcache, void* out, int rows, int heads, int kv_heads,
+                           int head_dim, int max_len, float scale, int window, hipStream_t stream);
 // persistent decode engine, stage 1 (decode_engine.hip): GEMV[gate, up] -> output transforms -> SiLU product ->
 // input transform of down -> GEMV[down] of one decoder block in one launch
 struct FfnEngineArgs {

@@ -17,6 +17,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn.functional as F
 
+from . import chunk_attn as _chunk_attn  # noqa: F401  (defines quip_lib::rope_attn_chunk)
 from . import token_tail as _token_tail  # noqa: F401  (defines quip_lib::block_engine_token)
 from .codebook import codebook_id
 from .qlinear import (QuantLinear, chain_planes, chain_supported, ffn_engine, ffn_engine_ok, forward_group,
@@ -757,6 +758,81 @@ class LlamaDecoder:
         (self.pos if pos is None else pos).fill_(P)
         return F.rms_norm(h[-1:], (s.hidden,), self.final_norm, s.rms_eps) @ self.lm_head.T
 
+    @torch.no_grad()
+    def extend(self, tokens, chunk=512, kv=None, pos=None):
+        """Append `tokens` (1-D ids, >= 1) behind the current position: the prompt pass for a cache that already holds a
+        conversation (a second turn, a prompt too long for one pass, a slot of a batched cache).  The tokens run in chunks
+        of at most `chunk` rows -- bounded activations whatever the prompt length -- and per block and chunk the
+        attention is ONE launch (quip_lib::rope_attn_chunk: rotary embedding, cache append, causal attention of the
+        chunk's rows at positions [pos, pos + rows) over cache rows [0, pos + rows), sliding window included).  The
+        position is read by that launch and advanced on the device by each chunk's length: nothing here reads it on the
+        host, so the pass can be captured once and replayed at any position (extend_graph).  Tokens that do not fit
+        (position + rows > max_len) write nothing and give NaN logits -- the launch's range rule is the guard.
+        Returns the logits of the last token (1, vocab).  `kv` / `pos`: as in prefill()."""
+        s = self.s
+        tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
+        P, chunk = tokens.numel(), int(chunk)
+        if P < 1:
+            raise ValueError("extend: an empty token list")
+        if chunk < 1:
+            raise ValueError(f"extend: chunk {chunk} < 1")
+        if s.head_dim not in (64, 128):
+            raise NotImplementedError(f"head_dim {s.head_dim}: the chunk attention launch serves 64 and 128")
+        kcache, vcache = (self.kcache, self.vcache) if kv is None else kv
+        pos = self.pos if pos is None else pos
+        h = None
+        for c0 in range(0, P, chunk):
+            n = min(chunk, P - c0)
+            h = self.embed[tokens[c0:c0 + n]]                           # (n, hidden)
+            for i, L in enumerate(self.layers):
+                self._rm_enter(L)
+                try:
+                    q, k, v = forward_group([L["q"], L["k"], L["v"]], h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
+                    kc, vc = kcache[i], vcache[i]
+                    a = torch.ops.quip_lib.rope_attn_chunk(
+                        q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim), v.view(n, s.kv_heads, s.head_dim),
+                        self.cos[:kc.shape[1]], self.sin[:kc.shape[1]], pos, kc, vc, self.window)
+                    h = L["o"].forward_fused(a.reshape(n, s.hidden), residual=h)
+                    g, u = forward_group([L["gate"], L["up"]], h, rms_weight=L["ln2"], rms_eps=s.rms_eps)
+                    h = L["down"].forward_fused(u, gate=g, residual=h)
+                finally:
+                    self._rm_exit(L)
+            pos.add_(n)
+        return F.rms_norm(h[-1:], (s.hidden,), self.final_norm, s.rms_eps) @ self.lm_head.T
+
+    @torch.no_grad()
+    def extend_graph(self, tokens):
+        """extend() replayed from a hipGraph captured per token COUNT, with prefill_graph's cache-size rule.  The launches
+        read the position on the device, so one captured graph serves every start position."""
+        tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
+        P = tokens.numel()
+        if P < 1:
+            raise ValueError("extend_graph: an empty token list")
+        cache = self.__dict__.setdefault("_extend_graphs", {})
+        if P not in cache and len(cache) >= self.prefill_graph_cache_size:
+            cache.pop(next(iter(cache)))
+        if P not in cache:
+            static_tok = tokens.clone()
+            pos0 = self.pos.clone()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side), torch.no_grad():
+                # warm-up (attribute setup, allocator) on the tokens of this very call: it appends the rows the replay
+                # below writes again, bit for bit; the counter goes back to where it was
+                self.extend(static_tok)
+                self.pos.copy_(pos0)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.no_grad(), torch.cuda.graph(g):
+                logits = self.extend(static_tok)
+            torch.cuda.synchronize()
+            cache[P] = (g, static_tok, logits)
+        g, static_tok, logits = cache[P]
+        static_tok.copy_(tokens)
+        g.replay()
+        return logits
+
     def reset(self, first_token=1):
         if getattr(self, "block_eng", False) and getattr(self, "_eng_sig", None) != self._engine_signature():
             # a module's tensors were replaced or edited since the descriptors were baked: rebuild them (and the captured step)
@@ -787,14 +863,35 @@ class LlamaDecoder:
 
     @torch.no_grad()
     def generate(self, n_tokens, first_token=1, use_graph=True, prompt=None, temperature=None, top_k=None,
-                 batched_prefill=True, prefill_graph=False):
+                 batched_prefill=True, prefill_graph=False, append=False):
         """decode n_tokens (greedy, or sampled when a temperature is given: set_sampling); returns the
         token ids (device tensor).  `prompt` (1-D token ids): all but its last token go through ONE batched
         pass (`prefill`; batched_prefill=False feeds them token by token through the captured step instead, teacher
-        forced), then decoding continues from the last prompt token; prompt length + n_tokens <= max_len + 1."""
+        forced), then decoding continues from the last prompt token; prompt length + n_tokens <= max_len + 1.
+        append=True (the next turn of a conversation; needs a `prompt`): nothing is reset -- the token the previous call
+        left picked but not yet cached, then prompt[:-1], go through extend() behind what the cache holds, prompt[-1]
+        becomes the current token and decoding continues.  Lengths are checked against the host-side count of the tokens
+        the previous calls fed.  A step that is not captured yet runs eagerly in such a call (capturing warms up on cache
+        rows 0 and 1, which the conversation still attends to)."""
         if prompt is not None:
             prompt = torch.as_tensor(prompt, dtype=torch.long, device=self.dev).reshape(-1)
-            first_token = int(prompt[0])
+            first_token = int(prompt[0]) if not append else first_token
+        if append:
+            fed = getattr(self, "_fed", None)
+            if fed is None:
+                raise RuntimeError("generate(append=True): no earlier generate() call on this decoder to continue")
+            if prompt is None or prompt.numel() < 1:
+                raise ValueError("generate(append=True) needs a prompt of at least one token")
+            if fed + prompt.numel() + n_tokens > self.max_len:
+                raise ValueError(f"{fed} cached tokens + {prompt.numel()} prompt tokens + {n_tokens} new ones do not fit "
+                                 f"max_len {self.max_len}")
+            self.set_sampling(temperature, top_k)
+            use_graph = bool(use_graph) and self.graph is not None
+            out = torch.empty(n_tokens, dtype=torch.long, device=self.dev)
+            self.extend(torch.cat([self.tok.reshape(1), prompt[:-1]]))
+            self.tok.copy_(prompt[-1:].view_as(self.tok))
+            n_prompt, pos0 = 0, fed + prompt.numel()
+            return self._decode_loop(out, n_tokens, n_prompt, pos0, prompt, first_token, use_graph, True)
         n_prompt = 0 if prompt is None else prompt.numel() - 1
         assert n_prompt + n_tokens <= self.max_len
         self.set_sampling(temperature, top_k)
@@ -810,6 +907,13 @@ class LlamaDecoder:
             self.tok.copy_(prompt[-1:].view_as(self.tok))
             n_prompt = 0
         pos0 = prompt.numel() - 1 if (batched_prefill and prompt is not None and prompt.numel() > 1) else 0
+        return self._decode_loop(out, n_tokens, n_prompt, pos0, prompt, first_token, use_graph,
+                                 batched_prefill and prompt is not None and prompt.numel() > 1)
+
+    def _decode_loop(self, out, n_tokens, n_prompt, pos0, prompt, first_token, use_graph, tok_from_prompt):
+        """the token loop of generate(): n_prompt teacher-forced steps, n_tokens decoded ones, from position pos0 with the
+        current token in self.tok (tok_from_prompt: that token is prompt[-1]), and the recovery from a persistent launch
+        that gave up; leaves the host-side count of fed tokens for generate(append=True)"""
 
         replay = [bool(use_graph)]
 
@@ -850,10 +954,11 @@ class LlamaDecoder:
                 replay[0] = False
             self.pos.fill_(pos0 + t_from)
             if t_from == 0:
-                self.tok.fill_(first_token if not (batched_prefill and prompt is not None and prompt.numel() > 1) else int(prompt[-1]))
+                self.tok.fill_(first_token if not tok_from_prompt else int(prompt[-1]))
             elif t_from <= n_prompt:
                 self.tok.copy_(prompt[t_from:t_from + 1].view_as(self.tok))
             else:
                 self.tok.copy_(out[t_from - 1 - n_prompt].view_as(self.tok))
             run(t_from)
+        self._fed = pos0 + n_prompt + n_tokens
         return out
