@@ -11,13 +11,15 @@ Slots are independent: `fill_slot(b, prompt)` restarts slot b (its prompt pass w
 `extend_slot(b, tokens)` appends to it while the others keep their state, which is all continuous batching needs from
 the decoder."""
 import math
+from functools import partial
 
 import torch
 import torch.nn.functional as F
 
 from . import capi
 from . import register_lib as _R
-from .qlinear import QuantLinear, forward_group
+from .decode import PROJECTIONS, capture_graph
+from .qlinear import QuantLinear
 
 try:
     # B sequences: q (B, heads, hd), k / v (B, kv_heads, hd), pos (B,), caches (B, kv_heads, max_len, hd)
@@ -98,7 +100,7 @@ class BatchDecoder:
         max_len = parent.max_len if max_len is None else int(max_len)
         if not 1 <= max_len <= parent.max_len:
             raise ValueError(f"max_len {max_len}: 1 .. the parent decoder's max_len = {parent.max_len}")
-        if getattr(parent, "single_copy", False):
+        if parent.single_copy:
             raise ValueError("a single_copy decoder keeps only the tiled codes of the bs=1 launch: batched decode would "
                              "untile every block at every step")
         s = parent.s
@@ -119,21 +121,20 @@ class BatchDecoder:
     def regimes(self):
         """the product path of every module of a block at M = B (QuantLinear.regime)"""
         L0 = self.parent.layers[0]
-        return {k: L0[k].regime(self.batch) for k in ("q", "k", "v", "o", "gate", "up", "down")}
+        return {k: L0[k].regime(self.batch) for k in PROJECTIONS}
 
     def step(self):
         """one token for every slot: reads tok / pos, writes the next tokens into tok, advances pos; returns the
         logits (B, vocab)"""
         p, s, B = self.parent, self.s, self.batch
         h = p.embed[self.tok]                                       # (B, hidden)
-        for i, L in enumerate(p.layers):
-            q, k, v = forward_group([L["q"], L["k"], L["v"]], h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
-            a = torch.ops.quip_lib.rope_attn_decode_batched(
+
+        def attend(i, q, k, v):
+            return torch.ops.quip_lib.rope_attn_decode_batched(
                 q.view(B, s.heads, s.head_dim), k.view(B, s.kv_heads, s.head_dim), v.view(B, s.kv_heads, s.head_dim),
-                self.cos, self.sin, self.pos, self.kcache[i], self.vcache[i], self.attn_ws, self.window)
-            h = L["o"].forward_fused(a.reshape(B, s.hidden), residual=h)
-            g, u = forward_group([L["gate"], L["up"]], h, rms_weight=L["ln2"], rms_eps=s.rms_eps)
-            h = L["down"].forward_fused(u, gate=g, residual=h)
+                self.cos, self.sin, self.pos, self.kcache[i], self.vcache[i], self.attn_ws, self.window).reshape(B, s.hidden)
+        for i, L in enumerate(p.layers):
+            h = p._block(L, h, partial(attend, i))
         return self._head(h)
 
     def _head(self, h):
@@ -160,17 +161,7 @@ class BatchDecoder:
         """warm up and capture one step as a hipGraph (before any prompt is written: the warm-up steps write cache
         rows 0 and 1 of every slot)"""
         self.reset()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(2):
-                self.step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.step_logits = self.step()
-        torch.cuda.synchronize()
+        self.graph, self.step_logits = capture_graph(lambda: (self.step(), self.step()), self.step)
         self.reset()
 
     @torch.no_grad()

@@ -12,16 +12,25 @@ Only the linear layers are the QuIP# hot path; embeddings, norms, RoPE, attentio
 cache and the fp16 lm_head use stock torch ops (they are what remains once the GEMVs are
 fast: SURVEY.md 8f rank 1)."""
 import math
+import os
+import warnings
+from contextlib import contextmanager
 from dataclasses import dataclass
+from functools import partial
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
 from . import chunk_attn as _chunk_attn  # noqa: F401  (defines quip_lib::rope_attn_chunk)
+from . import register_lib as _R
 from . import token_tail as _token_tail  # noqa: F401  (defines quip_lib::block_engine_token)
 from .codebook import codebook_id
-from .qlinear import (QuantLinear, chain_planes, chain_supported, ffn_engine, ffn_engine_ok, forward_group,
+from .qlinear import (QuantLinear, _engine_had3, chain_planes, chain_supported, ffn_engine, ffn_engine_ok, forward_group,
                       fused_in_supported, gemv_chain, gemv_fused, gemv_group_unfused, gemv_unfused, out_transform_group)
+
+PROJECTIONS = ("q", "k", "v", "o", "gate", "up", "down")      # the seven QuantLinear modules of a decoder block
+_ENGINE_CODEBOOK = {"E8P12": 0, "D4": 1, "E8P12RVQ4B": 2, "HI": 3, "E8P12RVQ3B": 4}     # the persistent launch's table modes
 
 
 @dataclass
@@ -112,6 +121,84 @@ def qidxs_nbytes(m):
     return m.Qidxs.numel() * m.Qidxs.element_size() if m.Qidxs is not None else m._qidxs_tiled.numel()
 
 
+# ---- what the persistent block launch reads of one decoder block (LlamaDecoder._init_block_engine) -----------------------------
+def _f16(t):
+    return t.detach().to(torch.float16).contiguous()
+
+
+def _strided(t, per_thread):
+    """a vector in the strided layout of the launch's 512-thread transforms: p[per_thread t + k] = v[t + 512 k]"""
+    return _f16(t).reshape(per_thread, 512).t().contiguous().reshape(-1)
+
+
+def _engine_vectors(L, per_thread):
+    """(SU x 7, SV x 7, [ln1, ln2]) of block L.  The vectors the launch multiplies inside a strided transform -- ln, SU of
+    q k v gate up, SV of o and down -- are pre-permuted: 16 elements per thread on the 8192-wide shape, 8 on the 4096-wide ones"""
+    su = [_f16(L[k].SU) if k in ("o", "down") else _strided(L[k].SU, per_thread) for k in PROJECTIONS]
+    sv = [_strided(L[k].SV, per_thread) if k in ("o", "down") else _f16(L[k].SV) for k in PROJECTIONS]
+    return su, sv, [_strided(L["ln1"], per_thread), _strided(L["ln2"], per_thread)]
+
+
+def _had3_mix(L, dev):
+    """shape 1: the K x K factors of gate, up (right) and down (left, transposed) as fp32 rows of 8"""
+    K = L["gate"].K_right
+    mix = torch.zeros(3, K, 8, dtype=torch.float32, device=dev)
+    mix[0, :, :K] = L["gate"].had_right.detach().float()
+    mix[1, :, :K] = L["up"].had_right.detach().float()
+    mix[2, :, :K] = L["down"].had_left.detach().float().t()
+    return mix.contiguous()
+
+
+def _had3_k56(L, dev):
+    """shape 2 (Llama-3-8B / Mistral-7B, n_ffn = 14336 = 56 x 256):
+    (R_7 (x) H_2048) / sqrt 2048 on the (7, 2048) view = ((R_7 (x) H_8) (x) H_256) / (sqrt 8 sqrt 256) on the (56, 256) view:
+    the launch's K = 56 factors are R_7 (x) H_8 (entries +-R_7: exact in fp16); it folds the 1 / sqrt 8 into its scales
+    (decode_block.hip: kMixScale; the descriptor's scale of down is wscale / sqrt 2048 already)"""
+    h8 = torch.tensor([[1.0 - 2.0 * (bin(i & j).count("1") & 1) for j in range(8)] for i in range(8)], device=dev)
+    k56 = lambda r: torch.kron(r.detach().float(), h8)      # noqa: E731
+    had3 = torch.zeros(2 * 3136 + 64 * 72, dtype=torch.float16, device=dev)      # (down's: rows of 72: bank spread)
+    had3[:3136] = k56(L["gate"].had_right).to(torch.float16).reshape(-1)
+    had3[3136:6272] = k56(L["up"].had_right).to(torch.float16).reshape(-1)
+    hdT = torch.zeros(64, 72, dtype=torch.float16, device=dev)
+    hdT[:56, :56] = k56(L["down"].had_left).to(torch.float16).T
+    had3[6272:] = hdT.reshape(-1)
+    return had3
+
+
+def _tiled_codes(mods, single_copy):
+    """shape 1 streams a re-tiled copy of the codes (decode_block_gqa.hip: full-line requests): one more copy of the weights in
+    HBM, made once per model; the checkpoint's tensors stay what the stage-wise step and prefill read -- unless `single_copy`:
+    then the tiled copy replaces the module's `Qidxs` (its shape and dtype are kept for LlamaDecoder._row_major).  A tiled copy
+    that exists is the truth and is used as it is: `Qidxs` may be None, or scratch lent by _row_major.  So the codes of a
+    single-copy module cannot be replaced after the build (load_state_dict into `Qidxs`): the tiled copy would stay."""
+    wq = []
+    for m in mods:
+        t = getattr(m, "_qidxs_tiled", None)
+        if t is None:
+            t = tile_codes(m.Qidxs)
+            if single_copy:
+                m._qidxs_meta = (tuple(m.Qidxs.shape), m.Qidxs.dtype)
+                m._qidxs_tiled, m.Qidxs = t, None
+        wq.append(t)
+    return wq
+
+
+def capture_graph(warmup, body):
+    """warmup() on a side stream (kernel attribute setup, allocator), then body() captured as a hipGraph, synchronised after
+    each -> (graph, what body() returned: the static outputs, valid after every replay)"""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side), torch.no_grad():
+        warmup()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.no_grad(), torch.cuda.graph(graph):
+        out = body()
+    torch.cuda.synchronize()
+    return graph, out
+
+
 class LlamaDecoder:
     """Random-init Llama with QuantLinear projections, static KV cache, bs=1.
 
@@ -124,10 +211,9 @@ class LlamaDecoder:
 
     def __init__(self, shape: LlamaShape = LLAMA2_7B, codebook="E8P12", max_len=256, device="cuda", seed=0,
                  device_init=False, window=0, single_copy=None, **cb_kwargs):
-        import os
-        self.single_copy = bool(int(os.environ.get("QUIP_SINGLE_COPY", "0"))) if single_copy is None else bool(single_copy)
+        if single_copy is None:
+            single_copy = bool(int(os.environ.get("QUIP_SINGLE_COPY", "0")))
         self.s, self.dev, self.max_len = shape, torch.device(device), max_len
-        self.window = int(window) if 0 < int(window) < max_len else 0     # sliding-window attention (HF config.sliding_window)
         g = torch.Generator().manual_seed(seed)
         gq = torch.Generator(device=self.dev).manual_seed(seed) if device_init else g
         s = shape
@@ -148,7 +234,8 @@ class LlamaDecoder:
                 ln1=vec(s.hidden), ln2=vec(s.hidden),
                 q=ql(s.hidden, s.hidden), k=ql(s.hidden, kv), v=ql(s.hidden, kv), o=ql(s.hidden, s.hidden),
                 gate=ql(s.hidden, s.ffn), up=ql(s.hidden, s.ffn), down=ql(s.ffn, s.hidden)))
-        self._init_runtime()
+        # (sliding-window attention, HF config.sliding_window: a window that covers the whole cache is full attention)
+        self._init_runtime(window=int(window) if 0 < int(window) < max_len else 0, single_copy=single_copy)
 
     # architectures whose decoder block is Llama's: RMSNorm (weight only) -> q / k / v (+ bias) -> rotary -> softmax attention
     # -> o -> residual -> RMSNorm -> SiLU-gated MLP -> residual, embeddings and residuals unscaled
@@ -194,7 +281,7 @@ class LlamaDecoder:
         prf = getattr(cfg, "partial_rotary_factor", prf)
         if prf not in (None, 1, 1.0):
             raise NotImplementedError(f"partial rotary embeddings (factor {prf}) are not supported")
-        self.window = 0
+        window = 0
         # (HF's Llama modelling code never reads `sliding_window`: on such a config the attribute changes nothing there,
         #  so it changes nothing here)
         if (getattr(cfg, "sliding_window", None) and getattr(cfg, "use_sliding_window", True)
@@ -212,10 +299,10 @@ class LlamaDecoder:
             # a window that is never shorter than the context is full attention (Mistral-7B: 4096 on a 4096 cache); a
             # shorter one bounds the attention walk from below -- the cache stays linear (row t = position t)
             if types[0] == "sliding_attention" and max_len > int(cfg.sliding_window):
-                self.window = int(cfg.sliding_window)
+                window = int(cfg.sliding_window)
         # rotary frequencies and attention scaling as the model computes them (llama3 / linear / yarn scaling change
         # inv_freq at every position; taking only rope_theta from the config would silently give other logits)
-        self._inv_freq, self._att_scale = None, 1.0
+        inv_freq, att_scale = None, 1.0
         rot = getattr(model.model, "rotary_emb", None)
         if rot is not None and hasattr(rot, "inv_freq"):
             rope_type = getattr(rot, "rope_type", None) or (rp.get("rope_type", "default") if isinstance(rp, dict) else "default")
@@ -224,12 +311,11 @@ class LlamaDecoder:
             inv = rot.inv_freq.detach().to(torch.float32).cpu()
             if inv.numel() != head_dim // 2:
                 raise NotImplementedError(f"rotary_emb.inv_freq has {inv.numel()} entries for head_dim {head_dim}")
-            self._inv_freq, self._att_scale = inv, float(getattr(rot, "attention_scaling", 1.0) or 1.0)
+            inv_freq, att_scale = inv, float(getattr(rot, "attention_scaling", 1.0) or 1.0)
         self.s = LlamaShape(hidden=cfg.hidden_size, ffn=cfg.intermediate_size, layers=cfg.num_hidden_layers,
                             heads=heads, kv_heads=getattr(cfg, "num_key_value_heads", heads) or heads,
                             vocab=cfg.vocab_size, rms_eps=cfg.rms_norm_eps, rope_theta=float(rope))
         self.dev, self.max_len = dev, max_len
-        self._external_kv = kv_cache
         h16 = lambda t: t.detach().to(device=dev, dtype=torch.float16).contiguous()  # noqa: E731
         self.embed = h16(model.model.embed_tokens.weight)
         self.lm_head = h16(model.lm_head.weight)
@@ -244,36 +330,46 @@ class LlamaDecoder:
                 mod.to(dev).eval()
             self.layers.append(dict(ln1=h16(blk.input_layernorm.weight), ln2=h16(blk.post_attention_layernorm.weight),
                                     **mods))
-        self._init_runtime()
+        self._init_runtime(window=window, kv_cache=kv_cache, inv_freq=inv_freq, att_scale=att_scale, single_copy=False)
         return self
 
-    def _init_runtime(self):
+    def _init_runtime(self, window=None, kv_cache=None, inv_freq=None, att_scale=1.0, single_copy=False):
+        """Everything but the model (s, dev, max_len, embed, lm_head, final_norm, layers: the constructors' part).  Receives
+        what differs between the constructors: the attention window, `kv_cache` = (keys, values) to use instead of an own
+        cache, the rotary frequencies (None: from rope_theta) with their attention scaling, and single_copy.  EVERY attribute
+        the class reads is assigned here.  Called again without arguments -- after max_len was changed: the prompt-pass
+        benchmark -- it keeps `window` and `single_copy` as the attributes stand now and the other three as they were given."""
+        if window is None:
+            window, single_copy = self.window, self.single_copy
+            kv_cache, inv_freq, att_scale = self._init_args
+        self._init_args = (kv_cache, inv_freq, att_scale)
         s, max_len = self.s, self.max_len
-        ext = getattr(self, "_external_kv", None)
-        if ext is not None:
-            self.kcache, self.vcache = self._check_kv(*ext)
+        self.single_copy = bool(single_copy)
+        self.window = int(window)            # sliding-window attention: keys (pos - window, pos]; 0 = all
+        if kv_cache is not None:
+            self.kcache, self.vcache = self._check_kv(*kv_cache)
         else:
             self.kcache = torch.zeros(s.layers, s.kv_heads, max_len, s.head_dim, dtype=torch.float16, device=self.dev)
             self.vcache = torch.zeros_like(self.kcache)
-        inv = getattr(self, "_inv_freq", None)
-        if inv is None:
-            inv = 1.0 / (s.rope_theta ** (torch.arange(0, s.head_dim, 2, dtype=torch.float32) / s.head_dim))
-        att = float(getattr(self, "_att_scale", 1.0))
-        ang = torch.arange(max_len, dtype=torch.float32)[:, None] * inv[None, :]
-        self.cos = (torch.cat([ang.cos(), ang.cos()], -1) * att).to(self.dev)     # (max_len, head_dim) fp32
-        self.sin = (torch.cat([ang.sin(), ang.sin()], -1) * att).to(self.dev)
+        if inv_freq is None:
+            inv_freq = 1.0 / (s.rope_theta ** (torch.arange(0, s.head_dim, 2, dtype=torch.float32) / s.head_dim))
+        ang = torch.arange(max_len, dtype=torch.float32)[:, None] * inv_freq[None, :]
+        self.cos = (torch.cat([ang.cos(), ang.cos()], -1) * float(att_scale)).to(self.dev)     # (max_len, head_dim) fp32
+        self.sin = (torch.cat([ang.sin(), ang.sin()], -1) * float(att_scale)).to(self.dev)
         self.arange = torch.arange(max_len, device=self.dev)
         # static step I/O (graph capture): current token id, its position, next token id
         self.tok = torch.zeros(1, dtype=torch.long, device=self.dev)
         self.pos = torch.zeros(1, dtype=torch.long, device=self.dev)
-        self.graph = None
+        self.graph = None                   # the captured step and its static logits (capture())
+        self.step_logits = None
         self.sampling = None
+        self._fed = None                    # host-side count of the tokens generate() fed (generate(append=True))
+        self._tail_logits = None            # the whole-token launch's one logits row (step())
+        self._prefill_graphs, self._extend_graphs = {}, {}      # length -> (graph, logits, static tokens)
+        self._rm_scratch = {}               # projection name -> row-major scratch (_row_major)
         self.fused_attention = s.head_dim in (64, 128)
-        self.window = int(getattr(self, "window", 0) or 0)    # sliding-window attention: keys (pos - window, pos]; 0 = all
-        from .register_lib import rope_attn_workspace
-        self.attn_ws = rope_attn_workspace(s.heads, s.head_dim, self.dev) if self.fused_attention else None
+        self.attn_ws = _R.rope_attn_workspace(s.heads, s.head_dim, self.dev) if self.fused_attention else None
         L0 = self.layers[0]
-        import os
         qkv0, gu0 = [L0["q"], L0["k"], L0["v"]], [L0["gate"], L0["up"]]
         planes_ok = all(hasattr(m.codebook, "mm_planes") and m.codebook.planes_supported(m.q_out_features, m.q_in_features)
                         for m in L0.values() if isinstance(m, QuantLinear))
@@ -288,13 +384,14 @@ class LlamaDecoder:
         # (csrc/decode_engine.hip); QUIP_FFN_ENGINE=0 keeps the four stage-wise launches
         self.ffn_eng = (self.fused_prologue and self.chain and os.environ.get("QUIP_FFN_ENGINE", "1") != "0"
                         and all(ffn_engine_ok(L["gate"], L["up"], L["down"]) for L in self.layers))
-        self.ffn_ws = None
-        if self.ffn_eng:
-            from .register_lib import ffn_engine_workspace
-            self.ffn_ws = ffn_engine_workspace(s.ffn, L0["gate"].K_right, self.dev)
+        self.ffn_ws = _R.ffn_engine_workspace(s.ffn, L0["gate"].K_right, self.dev) if self.ffn_eng else None
         # all blocks of a token as ONE persistent launch (csrc/decode_block.hip); QUIP_BLOCK_ENGINE=0 keeps the stage-wise step
-        # (E8P12; D4 through the same kernel's one-table mode; E8P12RVQ4B, E8P12RVQ3B and HI as rows of twice the virtual width)
+        # (E8P12; D4 through the same kernel's one-table mode; E8P12RVQ4B, E8P12RVQ3B and HI as rows of twice the virtual width).
+        # What _init_block_engine fills in when every block qualifies:
         self.block_eng = False
+        self.eng_layers = self.eng_grid = self.eng_grid2 = self.eng_ws = None
+        self.eng_codebook, self.eng_resid_scale, self.eng_shape = 0, 0.0, 0
+        self._eng_keep = self._eng_sig = self._kv_ptr_host = None
         self.token_tail = os.environ.get("QUIP_TOKEN_TAIL", "1") != "0"     # the token's tail inside that launch (step())
         d4 = all(getattr(m.codebook, "id", None) in ("D4", "E8P12RVQ4B", "HI", "E8P12RVQ3B") for m in L0.values() if isinstance(m, QuantLinear))
         gqa_shape = self.fused_prologue and self.chain and s.kv_heads != s.heads and s.hidden in (8192, 4096)   # (csrc/decode_block_gqa.hip; decode_block_g8.hip)
@@ -303,162 +400,97 @@ class LlamaDecoder:
             self._init_block_engine()
         # q / k / v output transforms inside the attention launch (multi-head attention with a power-of-two hidden <= 4096,
         # or 64 / 32 heads on 8 KV heads -- Llama-2-70B, Llama-3, Mistral-7B; plain SV output side)
-        from .register_lib import rope_attn_decode_z_supported
         self.attn_z = (self.fused_prologue and self.fused_attention and os.environ.get("QUIP_ATTN_Z", "1") != "0"
-                       and rope_attn_decode_z_supported(s.heads, s.kv_heads, s.head_dim)
+                       and _R.rope_attn_decode_z_supported(s.heads, s.kv_heads, s.head_dim)
                        and all(l.K_right == 1 and not l.per_channel and l.bias is None and l.SV is not None
                                and l.q_out_features == l.out_features == (s.heads if i == 0 else s.kv_heads) * s.head_dim
                                for i, l in enumerate(qkv0)))
 
     def _init_block_engine(self):
         """descriptors + workspace of the persistent block launch, when every block qualifies"""
-        import numpy as np
-        from .qlinear import _engine_had3
-        from .register_lib import block_engine_supported, block_engine_workspace
-        s = self.s
-        L0 = self.layers[0]
-        names = ("q", "k", "v", "o", "gate", "up", "down")
-
+        s, L0 = self.s, self.layers[0]
         cbid = getattr(L0["q"].codebook, "id", None)
-        if cbid not in ("E8P12", "D4", "E8P12RVQ4B", "HI", "E8P12RVQ3B"):
+        if cbid not in _ENGINE_CODEBOOK:
             return
 
         def plain(m, n_in, n_out):
             return (getattr(m.codebook, "id", None) == cbid and not m.per_channel and m.bias is None and not m.training
                     and m.SU is not None and m.SV is not None and m.in_features == m.q_in_features == n_in
                     and m.out_features == m.q_out_features == n_out)
-        from .register_lib import block_engine_gqa_supported
         with torch.cuda.device(self.dev):           # (the support queries ask the CURRENT device for its CU count)
-            return self._init_block_engine_on_device(L0, names, cbid, plain, block_engine_supported, block_engine_gqa_supported,
-                                                     block_engine_workspace, _engine_had3)
+            dims = (s.hidden, s.heads, s.kv_heads, s.head_dim, s.ffn, L0["gate"].K_right)
+            gqa = _R.block_engine_gqa_supported(*dims) and cbid == "E8P12"        # shape 1: the 8192-wide launch
+            # shape 2: Llama-3-8B / Mistral-7B -- the shape-0 launch compiled for 32 / 8 heads and n_ffn = 14336 = 56 x 256
+            g8 = (not gqa and cbid == "E8P12" and os.environ.get("QUIP_BLOCK_ENGINE_G8", "1") != "0" and not self.window
+                  and _R.block_engine_g8_supported(*dims))
+            ok = ((gqa or g8 or _R.block_engine_supported(*dims))
+                  and len(self.layers) <= 146)      # (the launch's hand-off counter: 7 per block in 10 bits)
+            kvw = s.kv_heads * s.head_dim
+            for L in self.layers:
+                ok = ok and all(plain(L[k], s.hidden, s.hidden) and L[k].K_left == 1 and L[k].K_right == 1 for k in "qo")
+                ok = ok and all(plain(L[k], s.hidden, kvw) and L[k].K_left == 1 and L[k].K_right == 1 for k in "kv")
+                ok = ok and all(plain(L[k], s.hidden, s.ffn) and L[k].K_left == 1 for k in ("gate", "up"))
+                ok = ok and plain(L["down"], s.ffn, s.hidden) and L["down"].K_right == 1
+            if not ok:
+                return
+            keep, rec = [], np.zeros((len(self.layers), 32), dtype=np.uint64)
+            # (a rebuild -- reset() after the modules were edited: the previous descriptors' tensors, for shape 1 a whole tiled
+            #  copy of the codes, go BEFORE the new ones are made, not after: no third copy of the weights in between)
+            self._eng_keep = None
+            self.eng_layers = None
+            for i, L in enumerate(self.layers):
+                mods = [L[k] for k in PROJECTIONS]
+                su, sv, ln = _engine_vectors(L, 16 if gqa else 8)
+                had3 = _had3_mix(L, self.dev) if gqa else (_had3_k56(L, self.dev) if g8
+                                                           else _engine_had3(L["gate"], L["up"], L["down"]))
+                wq = _tiled_codes(mods, self.single_copy) if gqa else [m.Qidxs for m in mods]
+                keep += su + sv + ln + [had3] + (wq if gqa else [])
+                ptrs = ([t.data_ptr() for t in wq] + [t.data_ptr() for t in ln] + [t.data_ptr() for t in su]
+                        + [t.data_ptr() for t in sv] + [had3.data_ptr(), self.kcache[i].data_ptr(), self.vcache[i].data_ptr()])
+                rec[i, :26] = np.array(ptrs, dtype=np.uint64)
+                sc = [m.wscale_float / math.sqrt(m.q_in_features // m.K_left) for m in mods]
+                rec[i, 26:].view(np.float32)[:7] = np.array(sc, dtype=np.float32)
+            self._eng_keep = keep
+            self.eng_layers = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(self.dev)
+            self.eng_shape = 1 if gqa else (2 if g8 else 0)
+            self.eng_ws = _R.block_engine_workspace(self.dev, self.eng_shape)
+            self.eng_codebook = _ENGINE_CODEBOOK[cbid]
+            cb0 = L0["q"].codebook
+            self.eng_grid = cb0.grid if cbid == "D4" else (cb0._virtual_grid(self.dev) if cbid == "HI" else cb0.grid_packed_abs)
+            self.eng_resid_scale = float(getattr(cb0, "planes_resid_scale", 0.0)) if cbid in ("E8P12RVQ4B", "E8P12RVQ3B") else 0.0
+            self.eng_grid2 = cb0._e81b_i8(self.dev) if cbid == "E8P12RVQ3B" else None      # int8 (256, 8): 4 x the E81B entries
+            self._eng_sig = self._engine_signature()
+            self._kv_ptr_host = torch.empty(len(self.layers), 2, dtype=torch.int64).pin_memory()      # (bind_kv's staging buffer)
+            self.block_eng = True
 
     def _engine_signature(self):
         """(data_ptr, version) of every tensor the engine descriptors were built from: a load_state_dict / .to() / in-place
-        edit of a module after the descriptors were baked shows up here (reset() rebuilds them then)"""
+        edit of a module after the descriptors were baked shows up here (reset() rebuilds them then).  Of the codes it is the
+        tiled copy where a module has one: its `Qidxs` is None then, or scratch on loan (_row_major)"""
         sig = []
         for L in self.layers:
-            for k in ("q", "k", "v", "o", "gate", "up", "down"):
+            for k in PROJECTIONS:
                 m = L[k]
-                for t in (m.Qidxs if m.Qidxs is not None else getattr(m, "_qidxs_tiled", None), m.SU, m.SV, m.had_left, m.had_right):
+                tiled = getattr(m, "_qidxs_tiled", None)
+                for t in (tiled if tiled is not None else m.Qidxs, m.SU, m.SV, m.had_left, m.had_right):
                     if t is not None:
                         sig.append((t.data_ptr(), t._version))
                 sig.append(float(m.wscale_float))
             sig += [(L["ln1"].data_ptr(), L["ln1"]._version), (L["ln2"].data_ptr(), L["ln2"]._version)]
         return tuple(sig)
 
-    def _init_block_engine_on_device(self, L0, names, cbid, plain, block_engine_supported, block_engine_gqa_supported,
-                                     block_engine_workspace, _engine_had3):
-        import numpy as np
-        s = self.s
-        gqa = block_engine_gqa_supported(s.hidden, s.heads, s.kv_heads, s.head_dim, s.ffn, L0["gate"].K_right) and cbid == "E8P12"
-        import os
-        from .register_lib import block_engine_g8_supported
-        # shape 2 (round 5): Llama-3-8B / Mistral-7B -- the shape-0 launch compiled for 32 / 8 heads and n_ffn = 14336 = 56 x 256
-        g8 = (not gqa and cbid == "E8P12" and os.environ.get("QUIP_BLOCK_ENGINE_G8", "1") != "0" and not self.window
-              and block_engine_g8_supported(s.hidden, s.heads, s.kv_heads, s.head_dim, s.ffn, L0["gate"].K_right))
-        ok = ((gqa or g8 or block_engine_supported(s.hidden, s.heads, s.kv_heads, s.head_dim, s.ffn, L0["gate"].K_right))
-              and len(self.layers) <= 146)      # (the launch's hand-off counter: 7 per block in 10 bits)
-        kvw = s.kv_heads * s.head_dim
-        for L in self.layers:
-            ok = ok and all(plain(L[k], s.hidden, s.hidden) and L[k].K_left == 1 and L[k].K_right == 1 for k in "qo")
-            ok = ok and all(plain(L[k], s.hidden, kvw) and L[k].K_left == 1 and L[k].K_right == 1 for k in "kv")
-            ok = ok and all(plain(L[k], s.hidden, s.ffn) and L[k].K_left == 1 for k in ("gate", "up"))
-            ok = ok and plain(L["down"], s.ffn, s.hidden) and L["down"].K_right == 1
-        if not ok:
-            return
-        keep, rec = [], np.zeros((len(self.layers), 32), dtype=np.uint64)
-        # (a rebuild -- reset() after the modules were edited: the previous descriptors' tensors, for shape 1 a whole tiled copy of
-        #  the codes, go BEFORE the new ones are made, not after: no third copy of the weights in between.  ADVICE r5)
-        self._eng_keep = None
-        self.eng_layers = None
-        for i, L in enumerate(self.layers):
-            mods = [L[k] for k in names]
-            vec = lambda t: t.detach().to(torch.float16).contiguous()     # noqa: E731
-            # shape 1 reads the vectors it multiplies in the strided layout of its 512-thread transforms pre-permuted:
-            # p[16 t + k] = v[t + 512 k]
-            perm = lambda t: vec(t).reshape(16, 512).t().contiguous().reshape(-1)     # noqa: E731
-            if gqa:
-                su = [perm(m.SU) if k in ("q", "k", "v", "gate", "up") else vec(m.SU) for k, m in zip(names, mods)]
-                sv = [perm(m.SV) if k in ("o", "down") else vec(m.SV) for k, m in zip(names, mods)]
-                ln = [perm(L["ln1"]), perm(L["ln2"])]
-                K = L["gate"].K_right
-                mix = torch.zeros(3, K, 8, dtype=torch.float32, device=self.dev)
-                mix[0, :, :K] = L["gate"].had_right.detach().float()
-                mix[1, :, :K] = L["up"].had_right.detach().float()
-                mix[2, :, :K] = L["down"].had_left.detach().float().t()
-                had3 = mix.contiguous()
-            else:
-                # shape 0 (round 5): the 4096-wide edges work in the strided layout too (8 elements per thread):
-                # p[8 t + k] = v[t + 512 k] for the vectors they multiply -- ln, SU of q k v gate up, SV of o and down
-                perm8 = lambda t: vec(t).reshape(8, 512).t().contiguous().reshape(-1)     # noqa: E731
-                su = [perm8(m.SU) if k in ("q", "k", "v", "gate", "up") else vec(m.SU) for k, m in zip(names, mods)]
-                sv = [perm8(m.SV) if k in ("o", "down") else vec(m.SV) for k, m in zip(names, mods)]
-                ln = [perm8(L["ln1"]), perm8(L["ln2"])]
-                if g8:
-                    # (R_7 (x) H_2048) / sqrt 2048 on the (7, 2048) view = ((R_7 (x) H_8) (x) H_256) / (sqrt 8 sqrt 256) on the
-                    # (56, 256) view: the launch's K = 56 factors are R_7 (x) H_8 (entries +-R_7: exact in fp16); it folds the
-                    # 1 / sqrt 8 into its scales (decode_block.hip: kMixScale; sc[6] below is wscale / sqrt 2048 already)
-                    h8 = torch.tensor([[1.0 - 2.0 * (bin(i & j).count("1") & 1) for j in range(8)] for i in range(8)], device=self.dev)
-                    k56 = lambda r: torch.kron(r.detach().float(), h8)      # noqa: E731
-                    had3 = torch.zeros(2 * 3136 + 64 * 72, dtype=torch.float16, device=self.dev)      # (down's: rows of 72: bank spread)
-                    had3[:3136] = k56(L["gate"].had_right).to(torch.float16).reshape(-1)
-                    had3[3136:6272] = k56(L["up"].had_right).to(torch.float16).reshape(-1)
-                    hdT = torch.zeros(64, 72, dtype=torch.float16, device=self.dev)
-                    hdT[:56, :56] = k56(L["down"].had_left).to(torch.float16).T
-                    had3[6272:] = hdT.reshape(-1)
-                else:
-                    had3 = _engine_had3(L["gate"], L["up"], L["down"])
-            keep += su + sv + ln + [had3]
-            if gqa:
-                # shape 1 streams a re-tiled copy of the codes (decode_block_gqa.hip: full-line requests): one more copy of the
-                # weights in HBM, made once per model; the checkpoint's tensors stay what the stage-wise step and prefill read
-                wq = []
-                for m in mods:
-                    t = getattr(m, "_qidxs_tiled", None)          # (a rebuild in single-copy mode: the tiled copy is all there is)
-                    if m.Qidxs is not None:
-                        t = tile_codes(m.Qidxs)
-                    if getattr(self, "single_copy", False):
-                        if m.Qidxs is not None:
-                            m._qidxs_meta = (tuple(m.Qidxs.shape), m.Qidxs.dtype)
-                        m._qidxs_tiled = t
-                        m.Qidxs = None
-                    wq.append(t)
-                keep += wq
-            else:
-                wq = [m.Qidxs for m in mods]
-            ptrs = ([t.data_ptr() for t in wq] + [t.data_ptr() for t in ln] + [t.data_ptr() for t in su]
-                    + [t.data_ptr() for t in sv] + [had3.data_ptr(), self.kcache[i].data_ptr(), self.vcache[i].data_ptr()])
-            rec[i, :26] = np.array(ptrs, dtype=np.uint64)
-            sc = [m.wscale_float / math.sqrt(m.q_in_features // m.K_left) for m in mods]
-            rec[i, 26:].view(np.float32)[:7] = np.array(sc, dtype=np.float32)
-        self._eng_keep = keep
-        self.eng_layers = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(self.dev)
-        self.eng_shape = 1 if gqa else (2 if g8 else 0)
-        self.eng_ws = block_engine_workspace(self.dev, self.eng_shape)
-        self.eng_codebook = {"E8P12": 0, "D4": 1, "E8P12RVQ4B": 2, "HI": 3, "E8P12RVQ3B": 4}[cbid]
-        cb0 = L0["q"].codebook
-        self.eng_grid = cb0.grid if cbid == "D4" else (cb0._virtual_grid(self.dev) if cbid == "HI" else cb0.grid_packed_abs)
-        self.eng_resid_scale = (float(getattr(L0["q"].codebook, "planes_resid_scale", 0.0))
-                                if cbid in ("E8P12RVQ4B", "E8P12RVQ3B") else 0.0)
-        self.eng_grid2 = cb0._e81b_i8(self.dev) if cbid == "E8P12RVQ3B" else None      # int8 (256, 8): 4 x the E81B entries
-        self._eng_sig = self._engine_signature()
-        self._kv_ptr_host = torch.empty(len(self.layers), 2, dtype=torch.int64).pin_memory()      # (bind_kv's staging buffer)
-        self.block_eng = True
-
     def engine_status(self):
         """0, or the code of a wait that gave up inside a persistent launch (synchronises)"""
-        from .register_lib import ffn_engine_status
-        for ws in (getattr(self, "eng_ws", None), getattr(self, "ffn_ws", None)):
-            if ws is not None and ffn_engine_status(ws) != 0:
-                return ffn_engine_status(ws)
+        for ws in (self.eng_ws, self.ffn_ws):
+            if ws is not None and _R.ffn_engine_status(ws) != 0:
+                return _R.ffn_engine_status(ws)
         return 0
 
     def engine_fail_position(self):
         """position of the first token a persistent block launch did not compute (workspace word 2 - 1), or None"""
-        ws = getattr(self, "eng_ws", None)
-        if ws is None:
+        if self.eng_ws is None:
             return None
-        v = int(ws[8:12].view(torch.int32).item())
+        v = int(self.eng_ws[8:12].view(torch.int32).item())
         return v - 1 if v > 0 else None
 
     def _check_kv(self, keys, values):
@@ -477,12 +509,10 @@ class LlamaDecoder:
         block launch's descriptors hold the row pointers (words 24, 25 of a 256-byte descriptor) and are patched in place;
         a captured step is dropped (its launches hold the old pointers)"""
         self.kcache, self.vcache = self._check_kv(keys, values)
-        if getattr(self, "block_eng", False):
+        if self.block_eng:
             # through a pinned staging buffer that lives as long as the decoder: the copy is legal inside a stream capture
             # (a re-recording torch.compile graph meets a new cache object there) and replays read the same host memory
-            host = getattr(self, "_kv_ptr_host", None)
-            if host is None:
-                host = self._kv_ptr_host = torch.empty(len(self.layers), 2, dtype=torch.int64).pin_memory()
+            host = self._kv_ptr_host
             for i, (k, v) in enumerate(zip(self.kcache, self.vcache)):
                 host[i, 0], host[i, 1] = k.data_ptr(), v.data_ptr()
             rec = self.eng_layers.view(torch.int64).view(len(self.layers), 32)
@@ -491,42 +521,62 @@ class LlamaDecoder:
 
     def engine_reset(self):
         """after a launch that gave up: workspaces back to their allocation state (generation 0, no granules, no code)"""
-        for ws in (getattr(self, "eng_ws", None), getattr(self, "ffn_ws", None)):
+        for ws in (self.eng_ws, self.ffn_ws):
             if ws is not None:
                 ws.zero_()
 
-    # ---- single-copy mode: a block's matrices in the checkpoint's layout, for the operators that read it ------------------------
-    def _rm_enter(self, L):
-        """the seven modules of block L get their row-major `Qidxs` back (in scratch buffers shared by all blocks, filled by
-        untile_codes on the current stream) until _rm_exit; a no-op unless the modules hold tiled copies only"""
-        if not getattr(self, "single_copy", False):
-            return
-        scr = self.__dict__.setdefault("_rm_scratch", {})
-        for k in ("q", "k", "v", "o", "gate", "up", "down"):
-            m = L[k]
-            if m.Qidxs is None and getattr(m, "_qidxs_tiled", None) is not None:
-                shape, dtype = m._qidxs_meta
-                buf = scr.get(k)
-                if buf is None or tuple(buf.shape) != shape or buf.dtype != dtype:
-                    buf = scr[k] = torch.empty(shape, dtype=dtype, device=self.dev)
-                untile_codes(m._qidxs_tiled, shape[0], buf.numel() * buf.element_size() // shape[0], buf)
-                m.Qidxs = buf
-                m._qidxs_borrowed = True
+    def _engine_recover(self):
+        """The one answer to a persistent launch that gave up.  Such a launch -- its workgroups were not all resident: something
+        else on the device -- ends on a hand-off instead of hanging, leaves a code in its workspace, answers NaN and remembers
+        the position of the first token it did not compute.  Reads the status (synchronises), zeroes the workspaces and, unless
+        the code only says that the workspace wanted zeroing (its launch counter was about to wrap), warns, switches both
+        persistent launches off and drops the captured step.  Returns (code, that position or None); code 0: nothing
+        happened, anything else: the caller repeats what it ran, on the path this decoder is on now."""
+        if not (self.block_eng or self.ffn_eng):
+            return 0, None
+        st = self.engine_status()
+        if not st:
+            return 0, None
+        fail = self.engine_fail_position()
+        self.engine_reset()
+        if st != 0xE000:
+            warnings.warn("persistent decode launch gave up on a hand-off (code 0x%x): the device was shared with other "
+                          "work; decoding continues on the stage-wise step" % st)
+            self.block_eng = self.ffn_eng = False
+            self.graph = None
+        return st, fail
 
-    def _rm_exit(self, L):
-        if not getattr(self, "single_copy", False):
+    # ---- single-copy mode: a block's matrices in the checkpoint's layout, for the operators that read it ------------------------
+    @contextmanager
+    def _row_major(self, L):
+        """inside the `with`, the seven modules of block L have their row-major `Qidxs` back (in scratch buffers shared by all
+        blocks, filled by untile_codes on the current stream); handed back on the way out, whatever happens inside.  Does
+        nothing unless the modules hold tiled copies only."""
+        if not self.single_copy:
+            yield
             return
-        for k in ("q", "k", "v", "o", "gate", "up", "down"):
-            m = L[k]
-            if getattr(m, "_qidxs_borrowed", False):
+        lent = []
+        try:
+            for k in PROJECTIONS:
+                m = L[k]
+                if m.Qidxs is None and getattr(m, "_qidxs_tiled", None) is not None:
+                    shape, dtype = m._qidxs_meta
+                    buf = self._rm_scratch.get(k)
+                    if buf is None or tuple(buf.shape) != shape or buf.dtype != dtype:
+                        buf = self._rm_scratch[k] = torch.empty(shape, dtype=dtype, device=self.dev)
+                    untile_codes(m._qidxs_tiled, shape[0], buf.numel() * buf.element_size() // shape[0], buf)
+                    m.Qidxs = buf
+                    lent.append(m)
+            yield
+        finally:
+            for m in lent:
                 m.Qidxs = None
-                m._qidxs_borrowed = False
 
     # ---- model bytes the decode step has to stream (roofline denominator, SURVEY 8d) -----------
     def algorithmic_bytes_per_token(self):
         b = 0
         for L in self.layers:
-            for k in ("q", "k", "v", "o", "gate", "up", "down"):
+            for k in PROJECTIONS:
                 m = L[k]
                 b += qidxs_nbytes(m) + 2 * (m.in_features + m.out_features)
         return b + self.lm_head.numel() * 2
@@ -550,21 +600,37 @@ class LlamaDecoder:
         return F.scaled_dot_product_attention(q, self.kcache[i][None], self.vcache[i][None], attn_mask=mask,
                                               enable_gqa=(s.kv_heads != s.heads))
 
+    def _block(self, L, h, attend):
+        """one decoder block on the rows of `h`, stage by stage; `attend(q, k, v)` -> the attention output, (rows, hidden):
+        the decode step, the prompt passes and BatchDecoder.step differ in nothing else"""
+        s = self.s
+        with self._row_major(L):
+            # q / k / v (and gate / up below): one launch per stage for the whole group; RMSNorm rides on
+            # the input-side Hadamard launch
+            q, k, v = forward_group([L["q"], L["k"], L["v"]], h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
+            # residual adds ride on the output-side Hadamard launch, SiLU(gate)*up on down's input side
+            h = L["o"].forward_fused(attend(q, k, v), residual=h)
+            g, u = forward_group([L["gate"], L["up"]], h, rms_weight=L["ln2"], rms_eps=s.rms_eps)
+            return L["down"].forward_fused(u, gate=g, residual=h)
+
+    def _engine_args(self):
+        """the arguments quip_lib::block_engine and quip_lib::block_engine_token share: everything behind their own I/O"""
+        s = self.s
+        return (self.cos, self.sin, self.eng_grid, self.eng_ws, len(self.layers), self.max_len, s.rms_eps,
+                1.0 / math.sqrt(s.head_dim), None, -1, self.eng_codebook, self.eng_resid_scale, self.eng_shape, self.eng_grid2,
+                *((self.kcache, self.vcache) if torch.is_tensor(self.kcache) else (None, None)))
+
     def step(self):
         """one token: reads self.tok / self.pos, writes the greedy next token into self.tok and
         advances self.pos (all on the device)"""
         s = self.s
         if self._token_tail_on():
             # the whole token in ONE launch: embedding row, blocks, final norm, lm_head, arg-max, position (csrc/token_tail.hip.h)
-            lg = self.__dict__.get("_tail_logits")
+            lg = self._tail_logits
             if lg is None or lg.shape[1] != self.lm_head.shape[0] or lg.device != self.lm_head.device:
                 lg = self._tail_logits = torch.empty(1, self.lm_head.shape[0], dtype=torch.float16, device=self.lm_head.device)
             torch.ops.quip_lib.block_engine_token(self.eng_layers, self.tok, self.pos, self.embed, self.final_norm, self.lm_head,
-                                                  lg, self.cos, self.sin, self.eng_grid, self.eng_ws, len(self.layers),
-                                                  self.max_len, s.rms_eps, 1.0 / math.sqrt(s.head_dim), None, -1,
-                                                  self.eng_codebook, self.eng_resid_scale, self.eng_shape,
-                                                  getattr(self, "eng_grid2", None),
-                                                  *((self.kcache, self.vcache) if torch.is_tensor(self.kcache) else (None, None)))
+                                                  lg, *self._engine_args())
             return lg
         h = self.embed[self.tok]                                   # (1, hidden)
         cos = sin = mask = None
@@ -573,33 +639,22 @@ class LlamaDecoder:
             mask = (self.arange[None, None, None, :] <= self.pos)      # (1,1,1,max_len) keys <= current
             if self.window:
                 mask = mask & (self.arange[None, None, None, :] > self.pos - self.window)
-        if getattr(self, "block_eng", False):
-            h = torch.ops.quip_lib.block_engine(self.eng_layers, h.reshape(-1), self.pos, self.cos, self.sin,
-                                                self.eng_grid, self.eng_ws, len(self.layers), self.max_len, s.rms_eps,
-                                                1.0 / math.sqrt(s.head_dim), None, -1, self.eng_codebook, self.eng_resid_scale,
-                                                getattr(self, "eng_shape", 0), getattr(self, "eng_grid2", None),
-                                                *((self.kcache, self.vcache) if torch.is_tensor(self.kcache) else (None, None)))
+        if self.block_eng:
+            h = torch.ops.quip_lib.block_engine(self.eng_layers, h.reshape(-1), self.pos, *self._engine_args())
             return self._head(h.reshape(1, -1))
         if self.fused_prologue:
             return self._step_fused(h, cos, sin, mask)
+
+        def attend(i, q, k, v):
+            return self._attention(i, q, k, v, cos, sin, mask).reshape(1, s.hidden)
         for i, L in enumerate(self.layers):
-            self._rm_enter(L)
-            # q / k / v (and gate / up below): one launch per stage for the whole group; RMSNorm rides on
-            # the input-side Hadamard launch
-            q, k, v = forward_group([L["q"], L["k"], L["v"]], h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
-            a = self._attention(i, q, k, v, cos, sin, mask)
-            # residual adds ride on the output-side Hadamard launch, SiLU(gate)*up on down's input side
-            h = L["o"].forward_fused(a.reshape(1, s.hidden), residual=h)
-            g, u = forward_group([L["gate"], L["up"]], h, rms_weight=L["ln2"], rms_eps=s.rms_eps)
-            h = L["down"].forward_fused(u, gate=g, residual=h)
-            self._rm_exit(L)
+            h = self._block(L, h, partial(attend, i))
         return self._head(h)
 
     def _token_tail_on(self):
         """greedy decoding on the 4096-wide persistent launch: the tail of the token rides on it.  QUIP_TOKEN_TAIL=0 (read
         when the runtime state is built; `token_tail` afterwards, with `graph = None`) keeps the separate launches."""
-        if not (getattr(self, "block_eng", False) and getattr(self, "token_tail", True)
-                and getattr(self, "sampling", None) is None and getattr(self, "eng_shape", 0) in (0, 2)):
+        if not (self.block_eng and self.token_tail and self.sampling is None and self.eng_shape in (0, 2)):
             return False
         lm, em = self.lm_head, self.embed
         return (lm.is_cuda and lm.dtype == torch.float16 and lm.is_contiguous() and lm.dim() == 2 and lm.shape[1] == 4096
@@ -614,36 +669,35 @@ class LlamaDecoder:
         s = self.s
         zd = prev_down = None
         for i, L in enumerate(self.layers):
-            self._rm_enter(L)
-            qkv = [L["q"], L["k"], L["v"]]
-            if zd is None and self.qkv_fused:
-                _, zs = gemv_fused(qkv, x=h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
-            elif zd is None:
-                zs = gemv_group_unfused(qkv, h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
-            else:   # finishes the previous block: h += down(...)
-                h, zs = self._zx(qkv, prev_down, zd, h, L["ln1"])
-            if self.attn_z:
-                # the K = 1 output transforms of q / k / v in the attention launch's prologue: 9 launches per block
-                a = torch.ops.quip_lib.rope_attn_decode_z(
-                    list(zs), [l._vec(l.SV) for l in qkv], [1.0 / math.sqrt(l.q_out_features) for l in qkv],
-                    self.cos, self.sin, self.pos, self.kcache[i], self.vcache[i], self.attn_ws, self.window)
-            else:
-                q, k, v = out_transform_group(qkv, zs)
-                a = self._attention(i, q, k, v, cos, sin, mask)
-            if self.o_fused:
-                _, (zo,) = gemv_fused([L["o"]], x=a.reshape(1, s.hidden))
-            else:
-                zo = gemv_unfused(L["o"], a.reshape(1, s.hidden))
-            if self.ffn_eng:
-                h, planes = chain_planes([L["gate"], L["up"]], L["o"], zo, residual=h, rms_weight=L["ln2"],
-                                         rms_eps=s.rms_eps)
-                zd = ffn_engine(L["gate"], L["up"], L["down"], planes, self.ffn_ws)
-            else:
-                h, zgu = self._zx([L["gate"], L["up"]], L["o"], zo, h, L["ln2"])
-                g, u = out_transform_group([L["gate"], L["up"]], zgu)
-                zd = gemv_unfused(L["down"], u, gate=g)
-            prev_down = L["down"]
-            self._rm_exit(L)
+            with self._row_major(L):
+                qkv = [L["q"], L["k"], L["v"]]
+                if zd is None and self.qkv_fused:
+                    _, zs = gemv_fused(qkv, x=h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
+                elif zd is None:
+                    zs = gemv_group_unfused(qkv, h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
+                else:   # finishes the previous block: h += down(...)
+                    h, zs = self._zx(qkv, prev_down, zd, h, L["ln1"])
+                if self.attn_z:
+                    # the K = 1 output transforms of q / k / v in the attention launch's prologue: 9 launches per block
+                    a = torch.ops.quip_lib.rope_attn_decode_z(
+                        list(zs), [l._vec(l.SV) for l in qkv], [1.0 / math.sqrt(l.q_out_features) for l in qkv],
+                        self.cos, self.sin, self.pos, self.kcache[i], self.vcache[i], self.attn_ws, self.window)
+                else:
+                    q, k, v = out_transform_group(qkv, zs)
+                    a = self._attention(i, q, k, v, cos, sin, mask)
+                if self.o_fused:
+                    _, (zo,) = gemv_fused([L["o"]], x=a.reshape(1, s.hidden))
+                else:
+                    zo = gemv_unfused(L["o"], a.reshape(1, s.hidden))
+                if self.ffn_eng:
+                    h, planes = chain_planes([L["gate"], L["up"]], L["o"], zo, residual=h, rms_weight=L["ln2"],
+                                             rms_eps=s.rms_eps)
+                    zd = ffn_engine(L["gate"], L["up"], L["down"], planes, self.ffn_ws)
+                else:
+                    h, zgu = self._zx([L["gate"], L["up"]], L["o"], zo, h, L["ln2"])
+                    g, u = out_transform_group([L["gate"], L["up"]], zgu)
+                    zd = gemv_unfused(L["down"], u, gate=g)
+                prev_down = L["down"]
         (h,) = out_transform_group([prev_down], [zd], residual=[h])
         return self._head(h)
 
@@ -660,13 +714,13 @@ class LlamaDecoder:
         (example_generate.py:9-26: logits / T, optional top-k cut, softmax, exponential-race arg-max --
         no host synchronisation).  The choice is part of the captured step: changing it re-captures."""
         new = None if not temperature else (float(temperature), None if top_k is None else int(top_k))
-        if new != getattr(self, "sampling", None):
+        if new != self.sampling:
             self.sampling, self.graph = new, None
 
     def _head(self, h):
         s = self.s
         logits = F.rms_norm(h, (s.hidden,), self.final_norm, s.rms_eps) @ self.lm_head.T
-        if getattr(self, "sampling", None) is None:
+        if self.sampling is None:
             if logits.dtype == torch.float16 and logits.is_cuda:
                 torch.ops.quip_lib.argmax_step(logits, self.tok, self.pos)      # tok <- argmax, pos += 1: one launch
                 return logits
@@ -694,33 +748,27 @@ class LlamaDecoder:
 
     prefill_graph_cache_size = 8      # captured prompt lengths kept (each graph owns a memory pool)
 
+    def _replay_per_length(self, cache, tokens, warmup, run):
+        """run(tokens) replayed from the graph `cache` holds for this token count; a count met for the first time is captured
+        (after warmup(tokens); both get a static copy of the tokens), the oldest one leaving at prefill_graph_cache_size"""
+        P = tokens.numel()
+        if P not in cache:
+            if len(cache) >= self.prefill_graph_cache_size:
+                cache.pop(next(iter(cache)))              # oldest captured length out (a graph keeps its own memory pool)
+            static_tok = tokens.clone()
+            cache[P] = (*capture_graph(lambda: warmup(static_tok), lambda: run(static_tok)), static_tok)
+        g, logits, static_tok = cache[P]
+        static_tok.copy_(tokens)
+        g.replay()
+        return logits
+
     @torch.no_grad()
     def prefill_graph(self, tokens):
         """prefill() replayed from a hipGraph captured per prompt LENGTH (first call of a length captures: a serving
         loop would bucket its prompt lengths).  Short prompts are bound by the ~600 eager launches of the pass, not by
         the GPU: 33..256 tokens 18.7 -> 4..8 ms on the 32-layer 7B model (tools/ttft_bench.py --graph)."""
         tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
-        P = tokens.numel()
-        cache = self.__dict__.setdefault("_prefill_graphs", {})
-        if P not in cache and len(cache) >= self.prefill_graph_cache_size:
-            cache.pop(next(iter(cache)))              # oldest captured length out (a graph keeps its own memory pool)
-        if P not in cache:
-            static_tok = tokens.clone()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad():
-                self.prefill(static_tok)                      # warm-up (attribute setup, allocator)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.no_grad(), torch.cuda.graph(g):
-                logits = self.prefill(static_tok)
-            torch.cuda.synchronize()
-            cache[P] = (g, static_tok, logits)
-        g, static_tok, logits = cache[P]
-        static_tok.copy_(tokens)
-        g.replay()
-        return logits
+        return self._replay_per_length(self._prefill_graphs, tokens, self.prefill, self.prefill)
 
     def prefill(self, tokens, kv=None, pos=None):
         """Batched prompt pass (the reference demo's prefill, example_generate.py:36-47): all `tokens` (1-D ids) go
@@ -736,9 +784,8 @@ class LlamaDecoder:
         kcache, vcache = (self.kcache, self.vcache) if kv is None else kv
         h = self.embed[tokens]                                          # (P, hidden)
         cos, sin = self.cos[:P], self.sin[:P]                           # (P, head_dim)
-        for i, L in enumerate(self.layers):
-            self._rm_enter(L)
-            q, k, v = forward_group([L["q"], L["k"], L["v"]], h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
+
+        def attend(i, q, k, v):
             q = self._rope(q.view(P, s.heads, s.head_dim).transpose(0, 1), cos, sin)          # (heads, P, hd)
             k = self._rope(k.view(P, s.kv_heads, s.head_dim).transpose(0, 1), cos, sin)
             v = v.view(P, s.kv_heads, s.head_dim).transpose(0, 1)
@@ -751,10 +798,9 @@ class LlamaDecoder:
             else:
                 a = F.scaled_dot_product_attention(q[None], k[None], v[None], is_causal=True,
                                                    enable_gqa=(s.kv_heads != s.heads))[0]     # (heads, P, hd)
-            h = L["o"].forward_fused(a.transpose(0, 1).reshape(P, s.hidden), residual=h)
-            g, u = forward_group([L["gate"], L["up"]], h, rms_weight=L["ln2"], rms_eps=s.rms_eps)
-            h = L["down"].forward_fused(u, gate=g, residual=h)
-            self._rm_exit(L)
+            return a.transpose(0, 1).reshape(P, s.hidden)
+        for i, L in enumerate(self.layers):
+            h = self._block(L, h, partial(attend, i))
         (self.pos if pos is None else pos).fill_(P)
         return F.rms_norm(h[-1:], (s.hidden,), self.final_norm, s.rms_eps) @ self.lm_head.T
 
@@ -780,23 +826,18 @@ class LlamaDecoder:
             raise NotImplementedError(f"head_dim {s.head_dim}: the chunk attention launch serves 64 and 128")
         kcache, vcache = (self.kcache, self.vcache) if kv is None else kv
         pos = self.pos if pos is None else pos
+
+        def attend(i, q, k, v):
+            n, kc, vc = q.shape[0], kcache[i], vcache[i]
+            return torch.ops.quip_lib.rope_attn_chunk(
+                q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim), v.view(n, s.kv_heads, s.head_dim),
+                self.cos[:kc.shape[1]], self.sin[:kc.shape[1]], pos, kc, vc, self.window).reshape(n, s.hidden)
         h = None
         for c0 in range(0, P, chunk):
             n = min(chunk, P - c0)
             h = self.embed[tokens[c0:c0 + n]]                           # (n, hidden)
             for i, L in enumerate(self.layers):
-                self._rm_enter(L)
-                try:
-                    q, k, v = forward_group([L["q"], L["k"], L["v"]], h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
-                    kc, vc = kcache[i], vcache[i]
-                    a = torch.ops.quip_lib.rope_attn_chunk(
-                        q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim), v.view(n, s.kv_heads, s.head_dim),
-                        self.cos[:kc.shape[1]], self.sin[:kc.shape[1]], pos, kc, vc, self.window)
-                    h = L["o"].forward_fused(a.reshape(n, s.hidden), residual=h)
-                    g, u = forward_group([L["gate"], L["up"]], h, rms_weight=L["ln2"], rms_eps=s.rms_eps)
-                    h = L["down"].forward_fused(u, gate=g, residual=h)
-                finally:
-                    self._rm_exit(L)
+                h = self._block(L, h, partial(attend, i))
             pos.add_(n)
         return F.rms_norm(h[-1:], (s.hidden,), self.final_norm, s.rms_eps) @ self.lm_head.T
 
@@ -805,36 +846,19 @@ class LlamaDecoder:
         """extend() replayed from a hipGraph captured per token COUNT, with prefill_graph's cache-size rule.  The launches
         read the position on the device, so one captured graph serves every start position."""
         tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
-        P = tokens.numel()
-        if P < 1:
+        if tokens.numel() < 1:
             raise ValueError("extend_graph: an empty token list")
-        cache = self.__dict__.setdefault("_extend_graphs", {})
-        if P not in cache and len(cache) >= self.prefill_graph_cache_size:
-            cache.pop(next(iter(cache)))
-        if P not in cache:
-            static_tok = tokens.clone()
+
+        def warmup(static_tok):
+            # on the tokens of this very call: it appends the rows the replay writes again, bit for bit; the counter goes
+            # back to where it was
             pos0 = self.pos.clone()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad():
-                # warm-up (attribute setup, allocator) on the tokens of this very call: it appends the rows the replay
-                # below writes again, bit for bit; the counter goes back to where it was
-                self.extend(static_tok)
-                self.pos.copy_(pos0)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.no_grad(), torch.cuda.graph(g):
-                logits = self.extend(static_tok)
-            torch.cuda.synchronize()
-            cache[P] = (g, static_tok, logits)
-        g, static_tok, logits = cache[P]
-        static_tok.copy_(tokens)
-        g.replay()
-        return logits
+            self.extend(static_tok)
+            self.pos.copy_(pos0)
+        return self._replay_per_length(self._extend_graphs, tokens, warmup, self.extend)
 
     def reset(self, first_token=1):
-        if getattr(self, "block_eng", False) and getattr(self, "_eng_sig", None) != self._engine_signature():
+        if self.block_eng and self._eng_sig != self._engine_signature():
             # a module's tensors were replaced or edited since the descriptors were baked: rebuild them (and the captured step)
             for L in self.layers:
                 if hasattr(L["down"], "_eng_had3"):
@@ -846,19 +870,10 @@ class LlamaDecoder:
         self.pos.zero_()
 
     def capture(self):
-        """warm up (kernel attribute setup, allocator) and capture one step as a hipGraph"""
+        """warm up (kernel attribute setup, allocator: two steps) and capture one step as a hipGraph; step_logits is the
+        static output of the captured step (valid after each replay)"""
         self.reset()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(2):
-                self.step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.step_logits = self.step()      # static output of the captured step (valid after each replay)
-        torch.cuda.synchronize()
+        self.graph, self.step_logits = capture_graph(lambda: (self.step(), self.step()), self.step)
         self.reset()
 
     @torch.no_grad()
@@ -877,7 +892,7 @@ class LlamaDecoder:
             prompt = torch.as_tensor(prompt, dtype=torch.long, device=self.dev).reshape(-1)
             first_token = int(prompt[0]) if not append else first_token
         if append:
-            fed = getattr(self, "_fed", None)
+            fed = self._fed
             if fed is None:
                 raise RuntimeError("generate(append=True): no earlier generate() call on this decoder to continue")
             if prompt is None or prompt.numel() < 1:
@@ -928,24 +943,13 @@ class LlamaDecoder:
                 else:
                     out[t - n_prompt] = self.tok.reshape(-1)[0]
         run(0)
-        # A persistent launch whose workgroups were not all resident (something else on the device) gives up on a hand-off
-        # instead of hanging, leaves a code, answers NaN, and remembers the position of the first token it did not compute:
-        # that token and everything behind it is decoded again -- on the stage-wise step, unless the code only says that the
-        # workspace wants zeroing (0xE000: its launch counter is about to wrap).  Cache rows of earlier positions are results.
+        # A persistent launch that gave up (_engine_recover) remembers the position of the first token it did not compute:
+        # that token and everything behind it is decoded again -- on the stage-wise step, unless the code only said that the
+        # workspace wanted zeroing (0xE000).  Cache rows of earlier positions are results.
         for _ in range(3):
-            if not (getattr(self, "block_eng", False) or getattr(self, "ffn_eng", False)):
-                break
-            st = self.engine_status()
+            st, fail = self._engine_recover()
             if not st:
                 break
-            fail = self.engine_fail_position()
-            self.engine_reset()
-            if st != 0xE000:
-                import warnings
-                warnings.warn("persistent decode launch gave up on a hand-off (code 0x%x): the device was shared with other "
-                              "work; this decoder continues on the stage-wise step" % st)
-                self.block_eng = self.ffn_eng = False
-                self.graph = None
             t_from = 0 if fail is None else max(0, fail - pos0)
             if use_graph and self.graph is None:
                 # The rest of THIS call runs eagerly: capture() warms up with two steps at positions 0 and 1, which would

@@ -115,6 +115,7 @@ class _FastDecode:
         self.disabled = None         # the reason LlamaDecoder refused this model, once known
         self.fast_steps = 0
         self.fast_prefills = 0
+        self._static_checked = None  # weakref of the static cache object whose padding was looked at
         import weakref
         _FastDecode._next_handle = getattr(_FastDecode, "_next_handle", 0) + 1
         self.handle = _FastDecode._next_handle
@@ -220,22 +221,13 @@ class _FastDecode:
     def _step_checked(self, dec, set_inputs):
         """one decoder step; when the call is not being captured into a graph, the persistent launch's status word is read
         back (one small synchronising copy per token -- HF's generate loop synchronises per token anyway) and a launch that
-        gave up on a hand-off (a shared device: NaN logits, decode.py) is answered by the same step on the stage-wise path"""
+        gave up on a hand-off (a shared device: NaN logits; LlamaDecoder._engine_recover) is answered by the same step again"""
         set_inputs()
         logits = dec.step()
-        if (getattr(dec, "block_eng", False) or getattr(dec, "ffn_eng", False)) and not torch.cuda.is_current_stream_capturing():
-            st = dec.engine_status()
-            if st:
-                dec.engine_reset()
-                if st != 0xE000:        # (0xE000: the workspace's launch counter was about to wrap -- zeroed, same path again)
-                    import warnings
-                    warnings.warn("persistent decode launch gave up on a hand-off (code 0x%x): the device was shared with "
-                                  "other work; fast decode continues on the stage-wise step" % st)
-                    dec.block_eng = dec.ffn_eng = False
-                    dec.graph = None
-                set_inputs()
-                logits = dec.step()
-        if logits is dec.__dict__.get("_tail_logits"):
+        if not torch.cuda.is_current_stream_capturing() and dec._engine_recover()[0]:
+            set_inputs()
+            logits = dec.step()
+        if logits is dec._tail_logits:
             # the whole-token launch writes ONE preallocated row (decode.py): callers of this wrapper keep what they get
             # (generate(output_scores=True), the compiled operator's result), so they get a tensor of their own
             logits = logits.clone()
@@ -336,7 +328,7 @@ class _FastDecode:
         # zero): a cache that is reset and used again with a padded prompt goes to the stock forward
         if getattr(cache, "_quip_padded", None) is True:
             return None
-        seen = getattr(self, "_static_checked", None)
+        seen = self._static_checked
         if seen is None or seen() is not cache:                      # a cache object seen for the first time
             import weakref
             if not self._unpadded(attention_mask, position_ids, layers[0].cumulative_length):

@@ -13,6 +13,8 @@ import time
 
 import torch
 
+from .decode import capture_graph
+
 
 class HFStaticDecoder:
     def __init__(self, model, max_cache_len=2048):
@@ -23,7 +25,7 @@ class HFStaticDecoder:
         self.cache = StaticCache(config=model.config, max_cache_len=max_cache_len)
         self.tok = torch.zeros(1, 1, dtype=torch.long, device=self.dev)
         self.pos = torch.zeros(1, dtype=torch.long, device=self.dev)
-        self.graph = None
+        self.graph = self._next = self._compiled = None
 
     def _forward(self, ids, cache_position):
         return self.model(ids, past_key_values=self.cache, cache_position=cache_position, use_cache=True, return_dict=False)[0]
@@ -45,17 +47,8 @@ class HFStaticDecoder:
 
     def capture(self):
         """the single-token step as a hipGraph on static token / position tensors"""
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            for _ in range(2):
-                self.decode_one_token(self.tok, self.pos)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph):
-            self._next = self.decode_one_token(self.tok, self.pos)
-        torch.cuda.synchronize()
+        one = lambda: self.decode_one_token(self.tok, self.pos)     # noqa: E731
+        self.graph, self._next = capture_graph(lambda: (one(), one()), one)
 
     def compile(self, fullgraph=True):
         """the reference's own call: torch.compile(decode_one_tokens, mode="reduce-overhead", fullgraph=True)
@@ -71,7 +64,7 @@ class HFStaticDecoder:
         if mode == "graph" and self.graph is None:
             self.prefill(prompt_ids)                   # (the warm-up steps need an initialised cache)
             self.capture()
-        if mode == "compile" and getattr(self, "_compiled", None) is None:
+        if mode == "compile" and self._compiled is None:
             self.compile()
         out = torch.empty(max_new_tokens, dtype=torch.long, device=self.dev)
         out[0] = self.prefill(prompt_ids).reshape(-1)[0]

@@ -134,7 +134,7 @@ def test_op_fake_on_meta_tensors():
 
 def _stub(head_dim=64):
     from quip_for_all_amd.decode import LlamaShape
-    return types.SimpleNamespace(max_len=64, dev=torch.device("cpu"), window=0,
+    return types.SimpleNamespace(max_len=64, dev=torch.device("cpu"), window=0, _fed=None,
                                  s=LlamaShape(hidden=4 * head_dim, ffn=688, layers=2, heads=4, kv_heads=2, vocab=512))
 
 

@@ -240,6 +240,25 @@ def test_single_copy_mode_keeps_one_copy_of_the_codes_and_still_serves_prompts_a
     assert torch.equal(pa, pb)
     assert torch.equal(one.kcache[0][:, :6], two.kcache[0][:, :6])
     assert all(L[k].Qidxs is None for L in one.layers for k in ("q", "k", "v", "o", "gate", "up", "down"))      # (handed back)
+    # 3b. a prompt pass that fails mid-block (a host exception in block 1, while its matrices are on loan) hands them back too:
+    #     the next reset() sees the descriptors' signature unchanged, re-tiles nothing, and the launch still decodes the model
+    def failing(*a, **kw):
+        raise RuntimeError("host failure inside block 1")
+    m_o = one.layers[1]["o"]
+    m_o.forward_fused = failing
+    try:
+        with pytest.raises(RuntimeError, match="host failure inside block 1"), torch.no_grad():
+            one.prefill(prompt)
+    finally:
+        del m_o.forward_fused                      # (the instance attribute that shadowed the method)
+    assert all(L[k].Qidxs is None for L in one.layers for k in ("q", "k", "v", "o", "gate", "up", "down"))
+    tiled = [L[k]._qidxs_tiled.data_ptr() for L in one.layers for k in ("q", "k", "v", "o", "gate", "up", "down")]
+    one.reset(first_token=7)
+    two.reset(first_token=7)
+    assert [L[k]._qidxs_tiled.data_ptr() for L in one.layers for k in ("q", "k", "v", "o", "gate", "up", "down")] == tiled
+    with torch.no_grad():
+        la, lb = one.step().clone(), two.step().clone()
+    assert torch.equal(la, lb) and one.engine_status() == 0
     # 4. the stage-wise fallback step
     for dec in decs:
         dec.block_eng = False

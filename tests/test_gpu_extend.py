@@ -135,7 +135,7 @@ def test_windowed_extend_matches_prefill_band_path():
 
 def test_extend_graph_serves_every_start_position():
     dec = _fresh("SMALL")
-    dec.__dict__.pop("_extend_graphs", None)
+    dec._extend_graphs.clear()
     first, second, history = _tokens(dec, 8, 21), _tokens(dec, 8, 22), _tokens(dec, 37, 23)
     le = dec.extend(first).clone()
     ke, ve = dec.kcache.clone(), dec.vcache.clone()

@@ -76,6 +76,12 @@ def test_fast_decoder_from_loaded_hf_model(tmp_path):
     qz.save(model, str(tmp_path))
     q = load_quantized_model(str(tmp_path), device_map={"": "cuda:0"})
     dec = LlamaDecoder.from_hf(q, max_len=64)
+    # both constructors end in one initialiser: the same attributes exist straight after construction, nothing is left to a
+    # getattr default (the same shape as _tiny_config(): hidden 256, ffn 688, 2 blocks, 4 / 2 heads, vocab 320)
+    from quip_for_all_amd.decode import LlamaShape
+    own = LlamaDecoder(LlamaShape(hidden=256, ffn=688, layers=2, heads=4, kv_heads=2, vocab=320), "E8P12", max_len=64, device="cuda:0")
+    assert set(vars(dec)) == set(vars(own)), set(vars(dec)) ^ set(vars(own))
+    del own
     toks = dec.generate(12, first_token=5, use_graph=True)
     eager = dec.generate(12, first_token=5, use_graph=False)
     assert torch.equal(toks, eager)
