@@ -101,6 +101,7 @@ _INTERNAL = {
     "quip_e8p_gemv_v2_tuned": [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P],
     "quip_e8p_gemv_v2_group_tuned": [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P],
     "quip_e8p_gemv_v2_workspace_bytes": [_I32],
+    "quip_e8p_gemv_v2_plan": [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "quip_e8p_gemv_tuned": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P],
 }
 
@@ -180,6 +181,19 @@ def check_symbols():
     if missing:
         raise QuipNativeError(f"libquip_mi355.so lacks symbols: {missing}")
     return sorted(SIGNATURES) + ["quip_strerror"]
+
+
+GEMV_V2_PLAN_FIELDS = ("rc", "rep", "slots", "ksplit", "nrb", "spw", "rpb0", "rpb1", "rpb2", "runlen", "rpr_inv", "threads",
+                       "lds")
+
+
+def gemv_v2_plan(ns, k, rep=0, slots=0, blocks=0, ksplit=0, max_waves=0, runlen=0, grid2=False, ws=True):
+    """The launch plan of the K-splitting GEMV for these tuning arguments (rep 4: nibble mode) as a list in the order of
+    GEMV_V2_PLAN_FIELDS.  Host arithmetic only: nothing is launched, no GPU is needed."""
+    n = (_I32 * max(len(ns), 1))(*ns)
+    out = (_I32 * len(GEMV_V2_PLAN_FIELDS))()
+    lib().quip_e8p_gemv_v2_plan(n, len(ns), k, rep, slots, blocks, ksplit, max_waves, runlen, int(bool(grid2)), int(bool(ws)), out)
+    return list(out)
 
 
 def check(code, what):

@@ -5,7 +5,7 @@
 
 #include <initializer_list>
 
-#include "quip_internal.h"
+#include "launch.hip.h"
 
 namespace quip {
 
@@ -56,7 +56,11 @@ int ensure_dyn_lds(DynLdsCache& cache, const void* kernel, int lds) {
   return QUIP_OK;
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
 static inline bool aligned64(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 63u) == 0; }
 
 static int mm_common(CodebookId cb, const void* x, const void* q, const CodebookArgs& a, void* y,
@@ -96,16 +100,12 @@ struct GemvPlan {
 
 // QUIP_GEMV_V2 = 0 / 1 forces the first / the K-splitting kernel for E8P12; QUIP_GEMV_NIB = 0 keeps the byte tables.
 // Both are read once per process.
-int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
 int gemv_v2_env() {
-  static const int v = [] { return env_int("QUIP_GEMV_V2", -1); }();
+  static const int v = env_int("QUIP_GEMV_V2", -1);
   return v;
 }
 bool gemv_nibble_env() {
-  static const bool v = [] { return env_int("QUIP_GEMV_NIB", 1) != 0; }();
+  static const bool v = env_int("QUIP_GEMV_NIB", 1) != 0;
   return v;
 }
 
@@ -236,10 +236,7 @@ __global__ void occupy_kernel(long long ticks, unsigned* sink) {
 
 int quip_debug_occupy(int32_t nwg, int32_t lds_bytes, int64_t ticks, void* sink, quip_stream_t stream) {
   if (nwg < 1 || nwg > 4096 || lds_bytes < 0 || lds_bytes > 160 * 1024 || ticks < 0 || !sink) return QUIP_ERR_BAD_SHAPE;
-  static quip::DynLdsCache configured;
-  if (quip::ensure_dyn_lds(configured, reinterpret_cast<const void*>(occupy_kernel), lds_bytes) != QUIP_OK) return QUIP_ERR_LAUNCH;
-  hipLaunchKernelGGL(occupy_kernel, dim3(nwg), dim3(64), lds_bytes, (hipStream_t)stream, (long long)ticks, reinterpret_cast<unsigned*>(sink));
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return launch<occupy_kernel>(dim3(nwg), dim3(64), lds_bytes, (hipStream_t)stream, (long long)ticks, reinterpret_cast<unsigned*>(sink));
 }
 
 int quip_hadamard_f16(const void* x, void* y, int64_t rows, int32_t n, float scale,
@@ -531,6 +528,25 @@ int quip_block_engine_supported(int32_t hidden, int32_t heads, int32_t kv_heads,
 size_t quip_block_engine_workspace_bytes(void) { return block_engine_workspace_bytes(); }
 size_t quip_block_engine_layer_bytes(void) { return block_engine_layer_bytes(); }
 
+namespace {
+// the public arguments (and, for a whole-token launch, its tail `t`: h_in is then the embedding row of *t->tok) as
+// BlockEngineArgs; codebook 4 needs its second table, 8-byte aligned
+int block_engine_args_of(const quip_block_engine_args* in, const quip_token_tail_args* t, BlockEngineArgs& a) {
+  a.layers = in->layers; a.h_in = t ? nullptr : in->h_in; a.h_out = in->h_out; a.pos = in->pos; a.cos = in->cos; a.sin = in->sin;
+  a.grid = in->grid_packed_abs; a.workspace = in->workspace; a.dbg = in->dbg;
+  a.n_layers = in->n_layers; a.max_len = in->max_len; a.dbg_layer = in->dbg_layer;
+  a.rms_eps = in->rms_eps; a.attn_scale = in->attn_scale; a.codebook = in->codebook; a.resid_scale = in->resid_scale;
+  a.grid2 = in->grid2;
+  if (in->codebook == 4 && (!in->grid2 || (reinterpret_cast<uintptr_t>(in->grid2) & 7u) != 0))
+    return in->grid2 ? QUIP_ERR_MISALIGNED : QUIP_ERR_NULL_POINTER;
+  if (t) {
+    a.tok = t->tok; a.embed = t->embed; a.final_norm = t->final_norm; a.lm_head = t->lm_head; a.logits = t->logits;
+    a.xnorm = t->xnorm; a.vocab = t->vocab;
+  }
+  return QUIP_OK;
+}
+}  // namespace
+
 int quip_block_engine(const quip_block_engine_args* in, quip_stream_t stream) {
   if (!in) return QUIP_ERR_NULL_POINTER;
   if (!in->layers || !in->h_in || !in->h_out || !in->pos || !in->cos || !in->sin || !in->grid_packed_abs || !in->workspace)
@@ -540,13 +556,7 @@ int quip_block_engine(const quip_block_engine_args* in, quip_stream_t stream) {
     return QUIP_ERR_MISALIGNED;
   if (in->n_layers < 1 || in->max_len < 1) return QUIP_ERR_BAD_SHAPE;
   BlockEngineArgs a;
-  a.layers = in->layers; a.h_in = in->h_in; a.h_out = in->h_out; a.pos = in->pos; a.cos = in->cos; a.sin = in->sin;
-  a.grid = in->grid_packed_abs; a.workspace = in->workspace; a.dbg = in->dbg;
-  a.n_layers = in->n_layers; a.max_len = in->max_len; a.dbg_layer = in->dbg_layer;
-  a.rms_eps = in->rms_eps; a.attn_scale = in->attn_scale; a.codebook = in->codebook; a.resid_scale = in->resid_scale;
-  a.grid2 = in->grid2;
-  if (in->codebook == 4 && (!in->grid2 || (reinterpret_cast<uintptr_t>(in->grid2) & 7u) != 0))
-    return in->grid2 ? QUIP_ERR_MISALIGNED : QUIP_ERR_NULL_POINTER;
+  if (const int rc = block_engine_args_of(in, nullptr, a); rc != QUIP_OK) return rc;
   if (in->shape == 1) return block_engine_gqa_launch(a, (hipStream_t)stream);
   if (in->shape == 2) return block_engine_g8_launch(a, (hipStream_t)stream);
   if (in->shape != 0) return QUIP_ERR_UNSUPPORTED;
@@ -567,15 +577,7 @@ int quip_block_engine_token(const quip_block_engine_args* in, const quip_token_t
   if (t->pos != in->pos) return QUIP_ERR_BAD_SHAPE;              // ONE position counter: read at the top, advanced at the end
   if (in->shape != 0 && in->shape != 2) return QUIP_ERR_UNSUPPORTED;
   BlockEngineArgs a;
-  a.layers = in->layers; a.h_in = nullptr; a.h_out = in->h_out; a.pos = in->pos; a.cos = in->cos; a.sin = in->sin;
-  a.grid = in->grid_packed_abs; a.workspace = in->workspace; a.dbg = in->dbg;
-  a.n_layers = in->n_layers; a.max_len = in->max_len; a.dbg_layer = in->dbg_layer;
-  a.rms_eps = in->rms_eps; a.attn_scale = in->attn_scale; a.codebook = in->codebook; a.resid_scale = in->resid_scale;
-  a.grid2 = in->grid2;
-  if (in->codebook == 4 && (!in->grid2 || (reinterpret_cast<uintptr_t>(in->grid2) & 7u) != 0))
-    return in->grid2 ? QUIP_ERR_MISALIGNED : QUIP_ERR_NULL_POINTER;
-  a.tok = t->tok; a.embed = t->embed; a.final_norm = t->final_norm; a.lm_head = t->lm_head; a.logits = t->logits;
-  a.xnorm = t->xnorm; a.vocab = t->vocab;
+  if (const int rc = block_engine_args_of(in, t, a); rc != QUIP_OK) return rc;
   if (in->shape == 2) return block_engine_g8_launch(a, (hipStream_t)stream);
   return block_engine_launch(a, (hipStream_t)stream);
 }
@@ -603,39 +605,34 @@ __global__ void untile_codes_kernel(const uint4* __restrict__ src, uint4* __rest
   const int c = (int)(cc - rb * pieces_per_row);
   dst[(rb * 16 + n) * row_u4 + c * 4 + q] = src[i];
 }
+
+// src -> dst through tile_codes_kernel or its inverse, one 16-byte piece per thread
+int retile_codes(bool inverse, const void* src, void* dst, int64_t rows, int64_t row_bytes, quip_stream_t stream) {
+  if (!src || !dst) return QUIP_ERR_NULL_POINTER;
+  if (rows < 0 || row_bytes <= 0 || rows % 16 != 0 || row_bytes % 64 != 0 || row_bytes > (1 << 24)) return QUIP_ERR_BAD_SHAPE;
+  if (rows == 0) return QUIP_OK;
+  if (!aligned16(src) || !aligned16(dst)) return QUIP_ERR_MISALIGNED;
+  {
+    // not in place, and no partial overlap either (ADVICE r5): the kernel gathers from the source while it scatters
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
+    const uintptr_t bytes = (uintptr_t)rows * (uintptr_t)row_bytes;
+    if (s0 < d0 + bytes && d0 < s0 + bytes) return QUIP_ERR_UNSUPPORTED;
+  }
+  const long long pieces = rows * (row_bytes / 16);
+  const dim3 grid((unsigned)((pieces + 255) / 256)), block(256);
+  const uint4* s = reinterpret_cast<const uint4*>(src);
+  uint4* d = reinterpret_cast<uint4*>(dst);
+  return inverse ? launch<untile_codes_kernel>(grid, block, 0, (hipStream_t)stream, s, d, pieces, (int)(row_bytes / 16))
+                 : launch<tile_codes_kernel>(grid, block, 0, (hipStream_t)stream, s, d, pieces, (int)(row_bytes / 16));
+}
 }  // namespace
 
 int quip_tile_codes(const void* qidxs, void* tiled, int64_t rows, int64_t row_bytes, quip_stream_t stream) {
-  if (!qidxs || !tiled) return QUIP_ERR_NULL_POINTER;
-  if (rows < 0 || row_bytes <= 0 || rows % 16 != 0 || row_bytes % 64 != 0 || row_bytes > (1 << 24)) return QUIP_ERR_BAD_SHAPE;
-  if (rows == 0) return QUIP_OK;
-  if (!aligned16(qidxs) || !aligned16(tiled)) return QUIP_ERR_MISALIGNED;
-  {
-    // not in place, and no partial overlap either (ADVICE r5): the kernel gathers from the source while it scatters
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(qidxs), d0 = reinterpret_cast<uintptr_t>(tiled);
-    const uintptr_t bytes = (uintptr_t)rows * (uintptr_t)row_bytes;
-    if (s0 < d0 + bytes && d0 < s0 + bytes) return QUIP_ERR_UNSUPPORTED;
-  }
-  const long long pieces = rows * (row_bytes / 16);
-  hipLaunchKernelGGL(tile_codes_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     reinterpret_cast<const uint4*>(qidxs), reinterpret_cast<uint4*>(tiled), pieces, (int)(row_bytes / 16));
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return retile_codes(false, qidxs, tiled, rows, row_bytes, stream);
 }
 
 int quip_untile_codes(const void* tiled, void* qidxs, int64_t rows, int64_t row_bytes, quip_stream_t stream) {
-  if (!qidxs || !tiled) return QUIP_ERR_NULL_POINTER;
-  if (rows < 0 || row_bytes <= 0 || rows % 16 != 0 || row_bytes % 64 != 0 || row_bytes > (1 << 24)) return QUIP_ERR_BAD_SHAPE;
-  if (rows == 0) return QUIP_OK;
-  if (!aligned16(qidxs) || !aligned16(tiled)) return QUIP_ERR_MISALIGNED;
-  {
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(tiled), d0 = reinterpret_cast<uintptr_t>(qidxs);
-    const uintptr_t bytes = (uintptr_t)rows * (uintptr_t)row_bytes;
-    if (s0 < d0 + bytes && d0 < s0 + bytes) return QUIP_ERR_UNSUPPORTED;
-  }
-  const long long pieces = rows * (row_bytes / 16);
-  hipLaunchKernelGGL(untile_codes_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     reinterpret_cast<const uint4*>(tiled), reinterpret_cast<uint4*>(qidxs), pieces, (int)(row_bytes / 16));
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return retile_codes(true, tiled, qidxs, rows, row_bytes, stream);
 }
 
 int quip_block_engine_gqa_supported(int32_t hidden, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t n_ffn, int32_t K) {

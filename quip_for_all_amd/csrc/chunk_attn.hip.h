@@ -263,11 +263,9 @@ int rope_attn_chunk_launch(const void* q, const void* k, const void* v, const fl
   for (int t0 = 0; t0 < tiles; t0 += kChunkMaxTilesY) {
     a.tile0 = t0;
     const dim3 grid(heads, min(kChunkMaxTilesY, tiles - t0));
-    if (head_dim == 128)
-      hipLaunchKernelGGL(rope_attn_chunk_kernel<128>, grid, dim3(kChunkThreads), 0, stream, a);
-    else
-      hipLaunchKernelGGL(rope_attn_chunk_kernel<64>, grid, dim3(kChunkThreads), 0, stream, a);
-    if (hipGetLastError() != hipSuccess) return QUIP_ERR_LAUNCH;
+    const int rc = head_dim == 128 ? launch<rope_attn_chunk_kernel<128>>(grid, dim3(kChunkThreads), 0, stream, a)
+                                   : launch<rope_attn_chunk_kernel<64>>(grid, dim3(kChunkThreads), 0, stream, a);
+    if (rc != QUIP_OK) return rc;
   }
   return QUIP_OK;
 }

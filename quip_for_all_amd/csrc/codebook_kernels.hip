@@ -4,7 +4,7 @@
 //     (origin_order.cu:388-555 with BLayout_{D4,HI,E8,E8RVQ3,E8RVQ4}, :143-385)
 // One decode functor per codebook yields 8 fp16 weights (16 B) of a packed row.
 #include "quip_device.hip.h"
-#include "quip_internal.h"
+#include "launch.hip.h"
 
 namespace quip {
 
@@ -143,10 +143,8 @@ static int launch_mm(const Dec& dec, const void* x, const void* q, void* y, int 
                      hipStream_t s) {
   const int waves = 4;
   dim3 grid((n + waves - 1) / waves), block(64 * waves);
-  hipLaunchKernelGGL((generic_mm_kernel<Dec, 8>), grid, block, Dec::kLds, s,
-                     reinterpret_cast<const f16*>(x), reinterpret_cast<const uint8_t*>(q), dec,
-                     reinterpret_cast<f16*>(y), m, n, k);
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return launch<generic_mm_kernel<Dec, 8>>(grid, block, Dec::kLds, s, reinterpret_cast<const f16*>(x),
+                                           reinterpret_cast<const uint8_t*>(q), dec, reinterpret_cast<f16*>(y), m, n, k);
 }
 
 template <class Dec>
@@ -156,9 +154,8 @@ static int launch_dec(const Dec& dec, const void* q, void* w, int64_t rows, int 
   const int64_t cap = (int64_t)device_cu_count() * 16;
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((decompress_kernel<Dec>), dim3((unsigned)blocks), dim3(256), Dec::kLds, s,
-                     reinterpret_cast<const uint8_t*>(q), dec, reinterpret_cast<uint4*>(w), rows, k);
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return launch<decompress_kernel<Dec>>(dim3((unsigned)blocks), dim3(256), Dec::kLds, s,
+                                        reinterpret_cast<const uint8_t*>(q), dec, reinterpret_cast<uint4*>(w), rows, k);
 }
 
 int generic_mm_launch(CodebookId cb, const void* x, const void* q, const CodebookArgs& a, void* y,

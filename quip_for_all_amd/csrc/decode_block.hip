@@ -32,6 +32,7 @@
 #include "engine_sync.hip.h"
 #include "fht_wg512x.hip.h"
 #include "token_tail.hip.h"
+#include "block_engine_host.hip.h"
 
 #ifndef QUIP_INO_EXACT
 #define QUIP_INO_EXACT 0
@@ -2145,31 +2146,11 @@ bool block_engine_g8_supported(int hidden, int heads, int kv_heads, int head_dim
 int block_engine_g8_launch(const BlockEngineArgs& in, hipStream_t stream) {
   if (in.n_layers < 1 || in.n_layers > 146) return QUIP_ERR_BAD_SHAPE;     // up to 7 hand-offs per block, 10-bit counter
   if (in.codebook != 0) return QUIP_ERR_UNSUPPORTED;
-  BlockArgs a;
-  a.layers = reinterpret_cast<const BlockLayer*>(in.layers);
-  a.h_in = reinterpret_cast<const f16*>(in.h_in);
-  a.h_out = reinterpret_cast<f16*>(in.h_out);
-  a.pos = reinterpret_cast<const int64_t*>(in.pos);
-  a.cos = in.cos; a.sin = in.sin;
-  a.grid = reinterpret_cast<const uint64_t*>(in.grid);
-  a.ws = reinterpret_cast<char*>(in.workspace);
-  a.dbg = reinterpret_cast<uint64_t*>(in.dbg);
-  a.n_layers = in.n_layers; a.max_len = in.max_len; a.dbg_layer = in.dbg_layer;
-  a.rms_eps = in.rms_eps; a.attn_scale = in.attn_scale; a.resid_scale = 0.f;
-  a.grid2 = nullptr;
+  BlockArgs a = block_args_of<BlockArgs, BlockLayer>(in);   // (resid_scale 0, no grid2)
   a.tail = tail_args(in);
   // QUIP_ENG_REP=24: the byte tables of round 5 (32 / 16 copies) instead of the nibble mode, for A/B
-  static const bool rep24 = getenv("QUIP_ENG_REP") && atoi(getenv("QUIP_ENG_REP")) == 24;
-  auto go = [&](auto kern, int lds, DynLdsCache& configured, ResidencyCache& resident) -> int {
-    if (ensure_dyn_lds(configured, reinterpret_cast<const void*>(kern), lds) != QUIP_OK) return QUIP_ERR_LAUNCH;
-    if (!persistent_grid_fits(resident, reinterpret_cast<const void*>(kern), kThreads, lds, NWG)) return QUIP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(kern, dim3(NWG), dim3(kThreads), lds, stream, a);
-    return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
-  };
-  static DynLdsCache c24, c4;
-  static ResidencyCache r24, r4;
-  if (rep24) return go(decode_block_kernel<24>, BLds<24>::kBytes, c24, r24);
-  return go(decode_block_kernel<4>, BLds<4>::kBytes, c4, r4);
+  if (eng_rep_env() == 24) return launch_persistent<decode_block_kernel<24>>(NWG, kThreads, BLds<24>::kBytes, stream, a);
+  return launch_persistent<decode_block_kernel<4>>(NWG, kThreads, BLds<4>::kBytes, stream, a);
 }
 #else
 size_t block_engine_workspace_bytes() { return kWsBytes; }
@@ -2182,45 +2163,24 @@ bool block_engine_supported(int hidden, int heads, int kv_heads, int head_dim, i
 
 int block_engine_launch(const BlockEngineArgs& in, hipStream_t stream) {
   if (in.n_layers < 1 || in.n_layers > 146) return QUIP_ERR_BAD_SHAPE;     // up to 7 hand-offs per block, 10-bit counter
-  BlockArgs a;
-  a.layers = reinterpret_cast<const BlockLayer*>(in.layers);
-  a.h_in = reinterpret_cast<const f16*>(in.h_in);
-  a.h_out = reinterpret_cast<f16*>(in.h_out);
-  a.pos = reinterpret_cast<const int64_t*>(in.pos);
-  a.cos = in.cos; a.sin = in.sin;
-  a.grid = reinterpret_cast<const uint64_t*>(in.grid);
-  a.ws = reinterpret_cast<char*>(in.workspace);
-  a.dbg = reinterpret_cast<uint64_t*>(in.dbg);
-  a.n_layers = in.n_layers; a.max_len = in.max_len; a.dbg_layer = in.dbg_layer;
-  a.rms_eps = in.rms_eps; a.attn_scale = in.attn_scale; a.resid_scale = 0.f;
+  BlockArgs a = block_args_of<BlockArgs, BlockLayer>(in);
   a.grid2 = in.grid2;
   a.tail = tail_args(in);
   // codebook 0: E8P12 (32 copies of the abs table, 16 of the sign table), 1: D4 (one table of 256 x 4 bytes, a private copy per lane)
-  auto go = [&](auto kern, int lds, DynLdsCache& configured, ResidencyCache& resident) -> int {
-    if (ensure_dyn_lds(configured, reinterpret_cast<const void*>(kern), lds) != QUIP_OK) return QUIP_ERR_LAUNCH;
-    if (!persistent_grid_fits(resident, reinterpret_cast<const void*>(kern), kThreads, lds, NWG)) return QUIP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(kern, dim3(NWG), dim3(kThreads), lds, stream, a);
-    return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
-  };
-  static DynLdsCache c16, c64;
-  static DynLdsCache crvq, chi, crvq3;
-  static ResidencyCache r16, r24, r64, rrvq, rhi, rrvq3;
+  auto go = [&](auto kern, int lds) -> int { return launch_persistent<decltype(kern)::value>(NWG, kThreads, lds, stream, a); };
   if (in.codebook == 4) {
     if (!in.grid2) return QUIP_ERR_NULL_POINTER;
     a.resid_scale = in.resid_scale;
-    return go(decode_block_kernel<12, true>, BLds<12, true>::kBytes, crvq3, rrvq3);
+    return go(kernel_c<decode_block_kernel<12, true>>, BLds<12, true>::kBytes);
   }
-  if (in.codebook == 3) return go(decode_block_kernel<64, true, true>, BLds<64, true>::kBytes, chi, rhi);
-  if (in.codebook == 2) { a.resid_scale = in.resid_scale; return go(decode_block_kernel<16, true>, BLds<16, true>::kBytes, crvq, rrvq); }
-  if (in.codebook == 1) return go(decode_block_kernel<64>, BLds<64>::kBytes, c64, r64);
+  if (in.codebook == 3) return go(kernel_c<decode_block_kernel<64, true, true>>, BLds<64, true>::kBytes);
+  if (in.codebook == 2) { a.resid_scale = in.resid_scale; return go(kernel_c<decode_block_kernel<16, true>>, BLds<16, true>::kBytes); }
+  if (in.codebook == 1) return go(kernel_c<decode_block_kernel<64>>, BLds<64>::kBytes);
   if (in.codebook != 0) return QUIP_ERR_UNSUPPORTED;
   // A/B: QUIP_ENG_REP=16: byte tables, two-way conflicts on both; 24: byte tables, 32 / 16 copies (round 5); default: nibble mode
-  static const int eng_rep = getenv("QUIP_ENG_REP") ? atoi(getenv("QUIP_ENG_REP")) : 4;
-  static DynLdsCache c24, c4;
-  static ResidencyCache r4;
-  if (eng_rep == 16) return go(decode_block_kernel<16>, BLds<16>::kBytes, c16, r16);
-  if (eng_rep == 24) return go(decode_block_kernel<24>, BLds<24>::kBytes, c24, r24);
-  return go(decode_block_kernel<4>, BLds<4>::kBytes, c4, r4);
+  if (eng_rep_env() == 16) return go(kernel_c<decode_block_kernel<16>>, BLds<16>::kBytes);
+  if (eng_rep_env() == 24) return go(kernel_c<decode_block_kernel<24>>, BLds<24>::kBytes);
+  return go(kernel_c<decode_block_kernel<4>>, BLds<4>::kBytes);
 }
 
 #endif

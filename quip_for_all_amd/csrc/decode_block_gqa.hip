@@ -28,6 +28,7 @@
 #include "e8p_gemv_core.hip.h"
 #include "engine_sync.hip.h"
 #include "fht_wg512x.hip.h"
+#include "block_engine_host.hip.h"
 #include <utility>
 
 // table mode (e8p_gemv_core.hip.h: Lds<REP>): 4 = NIBBLE MODE (round 6, the shipped one): 4-byte entries, 32 conflict-free copies
@@ -1732,25 +1733,9 @@ bool block_engine_gqa_supported(int hidden, int heads, int kv_heads, int head_di
 int block_engine_gqa_launch(const BlockEngineArgs& in, hipStream_t stream) {
   if (in.n_layers < 1 || in.n_layers > 146) return QUIP_ERR_BAD_SHAPE;     // 7 hand-offs per block, 10-bit counter
   if (in.codebook != 0) return QUIP_ERR_UNSUPPORTED;
-  GArgs a;
-  a.layers = reinterpret_cast<const GLayer*>(in.layers);
-  a.h_in = reinterpret_cast<const f16*>(in.h_in);
-  a.h_out = reinterpret_cast<f16*>(in.h_out);
-  a.pos = reinterpret_cast<const int64_t*>(in.pos);
-  a.cos = in.cos; a.sin = in.sin;
-  a.grid = reinterpret_cast<const uint64_t*>(in.grid);
-  a.ws = reinterpret_cast<char*>(in.workspace);
-  a.dbg = reinterpret_cast<uint64_t*>(in.dbg);
-  a.n_layers = in.n_layers; a.max_len = in.max_len; a.dbg_layer = in.dbg_layer;
-  a.rms_eps = in.rms_eps; a.attn_scale = in.attn_scale;
-  static DynLdsCache cache;
-  if (ensure_dyn_lds(cache, reinterpret_cast<const void*>(decode_block_gqa_kernel), GLds::kBytes) != QUIP_OK) return QUIP_ERR_LAUNCH;
-  static ResidencyCache resident;
-  if (!persistent_grid_fits(resident, reinterpret_cast<const void*>(decode_block_gqa_kernel), kThreads, GLds::kBytes, NWG))
-    return QUIP_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(decode_block_gqa_kernel, dim3(NWG), dim3(kThreads), GLds::kBytes, stream, a);
-  if (hipGetLastError() != hipSuccess) return QUIP_ERR_LAUNCH;
-  return in.dbg_layer == -2 ? QUIP_NO_RESULT : QUIP_OK;      // (measurement mode: h_out holds no hidden state)
+  const GArgs a = block_args_of<GArgs, GLayer>(in);
+  const int rc = launch_persistent<decode_block_gqa_kernel>(NWG, kThreads, GLds::kBytes, stream, a);
+  return rc == QUIP_OK && in.dbg_layer == -2 ? QUIP_NO_RESULT : rc;      // (measurement mode: h_out holds no hidden state)
 }
 
 }  // namespace quip

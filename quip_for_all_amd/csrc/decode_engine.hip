@@ -36,7 +36,7 @@
 // every spin is bounded (engine_sync.hip.h) and a launch that gives up leaves a code in ctl[1].
 #include "e8p_gemv_core.hip.h"
 #include "engine_sync.hip.h"
-#include <cstdlib>
+#include "block_engine_host.hip.h"
 
 namespace quip {
 
@@ -570,16 +570,10 @@ __global__ __launch_bounds__(kEngThreads) void ffn_engine_kernel(FfnArgs a) {
 template <int REP, int K, int LOGL, int NGU, int ND>
 int launch_ffn(const FfnArgs& a, hipStream_t stream) {
   using E = EngLds<REP, K, LOGL>;
-  auto kern = ffn_engine_kernel<REP, K, LOGL, NGU, ND, 2>;
   const int kp_in = (a.hidden + 511) & ~511;
   const int lds = E::bytes(kp_in);
   if (lds > 160 * 1024) return QUIP_ERR_UNSUPPORTED;
-  static DynLdsCache configured;
-  if (ensure_dyn_lds(configured, reinterpret_cast<const void*>(kern), lds) != QUIP_OK) return QUIP_ERR_LAUNCH;
-  static ResidencyCache resident;
-  if (!persistent_grid_fits(resident, reinterpret_cast<const void*>(kern), kEngThreads, lds, E::L)) return QUIP_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(kern, dim3(E::L), dim3(kEngThreads), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return launch_persistent<ffn_engine_kernel<REP, K, LOGL, NGU, ND, 2>>(E::L, kEngThreads, lds, stream, a);
 }
 
 // the (K, log2 L, hidden) combinations with an instantiation
@@ -634,8 +628,7 @@ int ffn_engine_launch(const FfnEngineArgs& in, hipStream_t stream) {
   a.frow = a.inbox + (size_t)in.K * 2 * L;
   a.dbg = reinterpret_cast<uint64_t*>(in.dbg);
   a.out_scale = in.out_scale; a.in_scale = in.in_scale; a.hidden = in.hidden;
-  static const int rep16 = [] { const char* e = getenv("QUIP_ENG_REP"); return e && atoi(e) == 16; }();
-  if (s.K == 43 && s.logL == 8 && rep16) return launch_ffn<16, 43, 8, 6, 3>(a, stream);
+  if (s.K == 43 && s.logL == 8 && eng_rep_env() == 16) return launch_ffn<16, 43, 8, 6, 3>(a, stream);
   if (s.K == 43 && s.logL == 8) return launch_ffn<24, 43, 8, 6, 3>(a, stream);
   if (s.K == 11 && s.logL == 8) return launch_ffn<24, 11, 8, 1, 1>(a, stream);
   if (s.K == 43 && s.logL == 7) return launch_ffn<24, 43, 7, 3, 2>(a, stream);

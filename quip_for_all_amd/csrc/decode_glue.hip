@@ -25,7 +25,7 @@
 // are bit identical to a bs=1 launch on that sequence alone.
 #include "had_device.hip.h"
 #include "quip_device.hip.h"
-#include "quip_internal.h"
+#include "launch.hip.h"
 
 namespace quip {
 namespace {
@@ -342,29 +342,19 @@ static int rope_attn_launch_common(AttnArgs a, const AttnZ* zz, int head_dim, in
     const int nq = a.heads * head_dim, nkv = a.kv_heads * head_dim;
     const size_t lds = ((size_t)had::buf_floats(nq) + 2 * (size_t)had::buf_floats(nkv)) * sizeof(float);
     if (head_dim == 128 && nq == 8192 && nkv == 1024)
-      hipLaunchKernelGGL((rope_attn_decode_kernel<128, true, 13, 10>), grid, dim3(512 + 128), lds, stream, a, *zz);
-    else if (head_dim == 128 && nq == 4096 && nkv == 1024)
-      hipLaunchKernelGGL((rope_attn_decode_kernel<128, true, 12, 10>), grid, dim3(256 + 128), lds, stream, a, *zz);
-    else
-      return QUIP_ERR_UNSUPPORTED;
+      return launch<rope_attn_decode_kernel<128, true, 13, 10>>(grid, dim3(512 + 128), (int)lds, stream, a, *zz);
+    if (head_dim == 128 && nq == 4096 && nkv == 1024)
+      return launch<rope_attn_decode_kernel<128, true, 12, 10>>(grid, dim3(256 + 128), (int)lds, stream, a, *zz);
   } else if (zz) {
     const size_t lds = 3 * (size_t)had::buf_floats(zz->n) * sizeof(float);
-    if (head_dim == 128)
-      hipLaunchKernelGGL((rope_attn_decode_kernel<128, true>), grid, dim3(768), lds, stream, a, *zz);
-    else if (head_dim == 64)
-      hipLaunchKernelGGL((rope_attn_decode_kernel<64, true>), grid, dim3(768), lds, stream, a, *zz);
-    else
-      return QUIP_ERR_UNSUPPORTED;
+    if (head_dim == 128) return launch<rope_attn_decode_kernel<128, true>>(grid, dim3(768), (int)lds, stream, a, *zz);
+    if (head_dim == 64) return launch<rope_attn_decode_kernel<64, true>>(grid, dim3(768), (int)lds, stream, a, *zz);
   } else {
     const AttnZ none{};
-    if (head_dim == 128)
-      hipLaunchKernelGGL((rope_attn_decode_kernel<128, false>), grid, dim3(256), 0, stream, a, none);
-    else if (head_dim == 64)
-      hipLaunchKernelGGL((rope_attn_decode_kernel<64, false>), grid, dim3(256), 0, stream, a, none);
-    else
-      return QUIP_ERR_UNSUPPORTED;
+    if (head_dim == 128) return launch<rope_attn_decode_kernel<128, false>>(grid, dim3(256), 0, stream, a, none);
+    if (head_dim == 64) return launch<rope_attn_decode_kernel<64, false>>(grid, dim3(256), 0, stream, a, none);
   }
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return QUIP_ERR_UNSUPPORTED;
 }
 
 int rope_attn_decode_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
@@ -402,11 +392,8 @@ int rope_attn_decode_batched_launch(const void* q, const void* k, const void* v,
   }
   const dim3 grid(heads, split ? kSplits : 1, batch);
   const AttnZ none{};
-  if (head_dim == 128)
-    hipLaunchKernelGGL((rope_attn_decode_kernel<128, false, 0, 0, true>), grid, dim3(256), 0, stream, a, none);
-  else
-    hipLaunchKernelGGL((rope_attn_decode_kernel<64, false, 0, 0, true>), grid, dim3(256), 0, stream, a, none);
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  if (head_dim == 128) return launch<rope_attn_decode_kernel<128, false, 0, 0, true>>(grid, dim3(256), 0, stream, a, none);
+  return launch<rope_attn_decode_kernel<64, false, 0, 0, true>>(grid, dim3(256), 0, stream, a, none);
 }
 
 bool rope_attn_decode_z_supported(int heads, int kv_heads, int head_dim) {
@@ -491,16 +478,14 @@ __global__ __launch_bounds__(1024) void argmax_step_kernel(const f16* __restrict
 
 int argmax_step_launch(const void* logits, int n, void* tok, void* pos, hipStream_t stream) {
   if (n < 1) return QUIP_ERR_BAD_SHAPE;
-  hipLaunchKernelGGL(argmax_step_kernel, dim3(1), dim3(1024), 0, stream, reinterpret_cast<const f16*>(logits), n,
-                     reinterpret_cast<int64_t*>(tok), reinterpret_cast<int64_t*>(pos));
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return launch<argmax_step_kernel>(dim3(1), dim3(1024), 0, stream, reinterpret_cast<const f16*>(logits), n,
+                                    reinterpret_cast<int64_t*>(tok), reinterpret_cast<int64_t*>(pos));
 }
 
 int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, void* pos, hipStream_t stream) {
   if (batch < 1 || n < 1) return QUIP_ERR_BAD_SHAPE;
-  hipLaunchKernelGGL(argmax_step_kernel, dim3(batch), dim3(1024), 0, stream, reinterpret_cast<const f16*>(logits), n,
-                     reinterpret_cast<int64_t*>(tok), reinterpret_cast<int64_t*>(pos));
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return launch<argmax_step_kernel>(dim3(batch), dim3(1024), 0, stream, reinterpret_cast<const f16*>(logits), n,
+                                    reinterpret_cast<int64_t*>(tok), reinterpret_cast<int64_t*>(pos));
 }
 
 }  // namespace quip

@@ -7,6 +7,7 @@
 // mode 4 = nibble (round 6), 16 / 24 / 32 = the byte tables with 16 / 16, 32 / 16, 32 / 32 copies.
 // tests/test_gpu_exhaustive_codes.py::test_decode_core_of_every_table_mode_decodes_every_code.
 #include "e8p_gemv_core.hip.h"
+#include "launch.hip.h"
 
 namespace quip {
 namespace {
@@ -85,11 +86,8 @@ template <int REP>
 int probe_launch(const void* grid, const void* codes, void* out, hipStream_t stream) {
   using T = Lds<REP>;
   const int lds = T::kNib ? kNibTableBytes : T::kT3;
-  static DynLdsCache cache;
-  if (ensure_dyn_lds(cache, reinterpret_cast<const void*>(decode_probe_kernel<REP>), lds) != QUIP_OK) return QUIP_ERR_LAUNCH;
-  hipLaunchKernelGGL(decode_probe_kernel<REP>, dim3(8), dim3(512), lds, stream, reinterpret_cast<const uint64_t*>(grid),
-                     reinterpret_cast<const uint4*>(codes), reinterpret_cast<int8_t*>(out));
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return launch<decode_probe_kernel<REP>>(dim3(8), dim3(512), lds, stream, reinterpret_cast<const uint64_t*>(grid),
+                                          reinterpret_cast<const uint4*>(codes), reinterpret_cast<int8_t*>(out));
 }
 
 }  // namespace

@@ -36,7 +36,7 @@
 // overlaps the first HBM round trip of the weight loads issued before it).
 // REP = 1 keeps compact 2 KiB tables for launches too small to amortise the fill.
 #include "quip_device.hip.h"
-#include "quip_internal.h"
+#include "launch.hip.h"
 
 namespace quip {
 
@@ -407,14 +407,10 @@ template <int REP, int ROWS, int NDIG, int MAXT, int XMODE>
 int launch_variant(const void* xsrc, const int* sh, const void* qidxs, const void* grid, void* y,
                    int n, int k, int J, int G, int rpb, int nblocks, uint64_t* dbg,
                    hipStream_t stream) {
-  auto kern = e8p_gemv_i8_kernel<REP, ROWS, NDIG, MAXT, XMODE>;
   const int lds = XMODE ? Lds<REP>::bytes(k) : Lds<REP>::kEnd;
-  static DynLdsCache configured;   // per instantiation, per device
-  if (ensure_dyn_lds(configured, reinterpret_cast<const void*>(kern), lds) != QUIP_OK) return QUIP_ERR_LAUNCH;
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64 * G * J), lds, stream,
-                     reinterpret_cast<const uint4*>(qidxs), xsrc, sh, reinterpret_cast<f16*>(y),
-                     reinterpret_cast<const uint64_t*>(grid), n, k, J, G, rpb, dbg);
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return launch<e8p_gemv_i8_kernel<REP, ROWS, NDIG, MAXT, XMODE>>(
+      dim3(nblocks), dim3(64 * G * J), lds, stream, reinterpret_cast<const uint4*>(qidxs), xsrc, sh,
+      reinterpret_cast<f16*>(y), reinterpret_cast<const uint64_t*>(grid), n, k, J, G, rpb, dbg);
 }
 
 // Streaming-read probe: same grid / load pattern as the GEMV (rotating nt loads of
@@ -476,15 +472,13 @@ int stream_probe_launch(const void* qidxs, void* out, int n, int k, const GemvTu
   nblocks = (n + rpb - 1) / rpb;
   const int rows = tune.rows ? tune.rows : 2;
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64 * G * J), 0, stream,
-                       reinterpret_cast<const uint4*>(qidxs), reinterpret_cast<uint32_t*>(out), n,
-                       slices, J, G, rpb);
-    return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+    return launch<decltype(kern)::value>(dim3(nblocks), dim3(64 * G * J), 0, stream, reinterpret_cast<const uint4*>(qidxs),
+                                         reinterpret_cast<uint32_t*>(out), n, slices, J, G, rpb);
   };
-  if (rows == 1) return go(stream_probe_kernel<1>);
-  if (rows == 2) return go(stream_probe_kernel<2>);
-  if (rows == 4) return go(stream_probe_kernel<4>);
-  return go(stream_probe_kernel<8>);
+  if (rows == 1) return go(kernel_c<stream_probe_kernel<1>>);
+  if (rows == 2) return go(kernel_c<stream_probe_kernel<2>>);
+  if (rows == 4) return go(kernel_c<stream_probe_kernel<4>>);
+  return go(kernel_c<stream_probe_kernel<8>>);
 }
 
 bool e8p_gemv_i8_supported(int n, int k) {
@@ -499,9 +493,8 @@ int x_to_planes_launch(const void* x, void* planes, int k, hipStream_t stream) {
   if (k < 64 || k % 64 != 0) return QUIP_ERR_BAD_SHAPE;
   int* sh = reinterpret_cast<int*>(reinterpret_cast<char*>(planes) + (size_t)3 * k);
   const int threads = k >= 8192 ? 1024 : (k >= 2048 ? 256 : 64);
-  hipLaunchKernelGGL(x_to_planes_kernel, dim3(1), dim3(threads), 0, stream,
-                     reinterpret_cast<const f16*>(x), reinterpret_cast<uint2*>(planes), sh, k);
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return launch<x_to_planes_kernel>(dim3(1), dim3(threads), 0, stream, reinterpret_cast<const f16*>(x),
+                                    reinterpret_cast<uint2*>(planes), sh, k);
 }
 
 // xmode 0: `xsrc` = planes buffer (3*k bytes of digits followed by the int shift);

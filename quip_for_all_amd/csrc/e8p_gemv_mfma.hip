@@ -40,6 +40,7 @@
 // LDS: T1/T2 with REP = 32 copies (ds_read_b64 conflict free, 128 KiB), x planes
 // (3 x 8 KiB), int32 accumulators [rows][4].
 #include "e8p_gemv_core.hip.h"
+#include "launch.hip.h"
 
 namespace quip {
 
@@ -564,16 +565,12 @@ __global__ __launch_bounds__(MAXT) void e8p_gemv_mfma_kernel(
 }
 
 template <int REP, int SLOTS, int MAXT, int G, bool ONESHOT = false, bool FUSED = false, bool ROWS = false>
-int launch(const GemvGroup<G>& gp, const void* grid, int k, int kp, int nblocks, int threads, uint64_t* dbg,
-           hipStream_t stream, const FusedIn* fin = nullptr, int mrows = 1) {
-  auto kern = e8p_gemv_mfma_kernel<REP, SLOTS, MAXT, G, ONESHOT, FUSED, ROWS>;
+int launch_variant(const GemvGroup<G>& gp, const void* grid, int k, int kp, int nblocks, int threads, uint64_t* dbg,
+                   hipStream_t stream, const FusedIn* fin = nullptr, int mrows = 1) {
   const int lds = FUSED ? Lds<REP>::bytes_fused(kp, G) : Lds<REP>::bytes(kp, ROWS ? mrows : G);
   const FusedIn fi = fin ? *fin : FusedIn{};
-  static DynLdsCache configured;   // per instantiation, per device
-  if (ensure_dyn_lds(configured, reinterpret_cast<const void*>(kern), lds) != QUIP_OK) return QUIP_ERR_LAUNCH;
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(threads), lds, stream, gp, fi,
-                     reinterpret_cast<const uint64_t*>(grid), k, kp, dbg, mrows);
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return launch<e8p_gemv_mfma_kernel<REP, SLOTS, MAXT, G, ONESHOT, FUSED, ROWS>>(
+      dim3(nblocks), dim3(threads), lds, stream, gp, fi, reinterpret_cast<const uint64_t*>(grid), k, kp, dbg, mrows);
 }
 
 // Streaming probe with the matrix-core kernel's access pattern (item = 16 rows x LINES x 128 B,
@@ -692,15 +689,14 @@ int shape_probe_launch(const void* qidxs, void* out, int n, int k, const GemvTun
   nblocks = (n + rpb - 1) / rpb;
   const int waves = tune.max_waves > 0 ? tune.max_waves : 8;
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64 * waves), 0, stream, reinterpret_cast<const uint4*>(qidxs),
-                       reinterpret_cast<uint32_t*>(out), n, k, rpb);
-    return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+    return launch<decltype(kern)::value>(dim3(nblocks), dim3(64 * waves), 0, stream, reinterpret_cast<const uint4*>(qidxs),
+                                         reinterpret_cast<uint32_t*>(out), n, k, rpb);
   };
-  if (tune.rows == 1) return go(shape_probe_kernel<1>);
-  if (tune.rows == 4) return go(shape_probe_kernel<4>);
-  if (tune.rows == 8) return go(shape_probe_kernel<8>);
-  if (tune.rows == 2) return go(shape_probe_kernel<2>);
-  return go(shape_probe_kernel<16>);
+  if (tune.rows == 1) return go(kernel_c<shape_probe_kernel<1>>);
+  if (tune.rows == 4) return go(kernel_c<shape_probe_kernel<4>>);
+  if (tune.rows == 8) return go(kernel_c<shape_probe_kernel<8>>);
+  if (tune.rows == 2) return go(kernel_c<shape_probe_kernel<2>>);
+  return go(kernel_c<shape_probe_kernel<16>>);
 }
 
 namespace {
@@ -775,9 +771,8 @@ int x_to_planes_linear_launch(const void* x, void* planes, int k, hipStream_t st
   const int kp = kp_of(k);
   int* sh = reinterpret_cast<int*>(reinterpret_cast<char*>(planes) + (size_t)3 * kp);
   const int threads = k >= 8192 ? 1024 : (k >= 2048 ? 256 : 64);
-  hipLaunchKernelGGL(x_to_planes_linear_kernel, dim3(rows), dim3(threads), 0, stream,
-                     reinterpret_cast<const f16*>(x), reinterpret_cast<uint8_t*>(planes), sh, k, kp);
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return launch<x_to_planes_linear_kernel>(dim3(rows), dim3(threads), 0, stream, reinterpret_cast<const f16*>(x),
+                                           reinterpret_cast<uint8_t*>(planes), sh, k, kp);
 }
 
 int pattern_probe_launch(const void* qidxs, void* out, int n, int k, const GemvTune& tune, hipStream_t stream) {
@@ -789,13 +784,12 @@ int pattern_probe_launch(const void* qidxs, void* out, int n, int k, const GemvT
   int waves = tune.max_waves > 0 ? tune.max_waves : 16;
   const int lines = tune.rows ? tune.rows : 1;
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64 * waves), 0, stream, reinterpret_cast<const uint4*>(qidxs),
-                       reinterpret_cast<uint32_t*>(out), n, k, rpb);
-    return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+    return launch<decltype(kern)::value>(dim3(nblocks), dim3(64 * waves), 0, stream, reinterpret_cast<const uint4*>(qidxs),
+                                         reinterpret_cast<uint32_t*>(out), n, k, rpb);
   };
-  if (lines == 1) return go(pattern_probe_kernel<1>);
-  if (lines == 2) return go(pattern_probe_kernel<2>);
-  return go(pattern_probe_kernel<4>);
+  if (lines == 1) return go(kernel_c<pattern_probe_kernel<1>>);
+  if (lines == 2) return go(kernel_c<pattern_probe_kernel<2>>);
+  return go(kernel_c<pattern_probe_kernel<4>>);
 }
 
 // one-shot regime: all items of a wave in flight at once (SLOTS = items per wave, rounded up)
@@ -805,7 +799,7 @@ static int launch_oneshot(const GemvGroup<G>& gp, const void* grid, int k, int k
   // 9..16 waves: the 128-VGPR budget of a 1024-thread workgroup holds up to 4 slot register sets
 #define QUIP_ONE_BIG(R, S)                                                          \
   if (threads > 512 && rep == R && items_per_wave <= S)                             \
-    return launch<R, S, 1024, G, true>(gp, grid, k, kp, nblocks, threads, dbg, stream);
+    return launch_variant<R, S, 1024, G, true>(gp, grid, k, kp, nblocks, threads, dbg, stream);
   QUIP_ONE_BIG(32, 1) QUIP_ONE_BIG(32, 2) QUIP_ONE_BIG(32, 3) QUIP_ONE_BIG(32, 4)
   QUIP_ONE_BIG(24, 1) QUIP_ONE_BIG(24, 2) QUIP_ONE_BIG(24, 3) QUIP_ONE_BIG(24, 4)
   QUIP_ONE_BIG(16, 1) QUIP_ONE_BIG(16, 2) QUIP_ONE_BIG(16, 3) QUIP_ONE_BIG(16, 4)
@@ -815,7 +809,7 @@ static int launch_oneshot(const GemvGroup<G>& gp, const void* grid, int k, int k
   if (threads > 512) return QUIP_ERR_UNSUPPORTED;
 #define QUIP_ONE(R, S)                                                              \
   if (rep == R && items_per_wave <= S)                                              \
-    return launch<R, S, 512, G, true>(gp, grid, k, kp, nblocks, threads, dbg, stream);
+    return launch_variant<R, S, 512, G, true>(gp, grid, k, kp, nblocks, threads, dbg, stream);
   QUIP_ONE(32, 1) QUIP_ONE(32, 2) QUIP_ONE(32, 3) QUIP_ONE(32, 4) QUIP_ONE(32, 6) QUIP_ONE(32, 8)
   QUIP_ONE(24, 1) QUIP_ONE(24, 2) QUIP_ONE(24, 3) QUIP_ONE(24, 4) QUIP_ONE(24, 6) QUIP_ONE(24, 8)
   QUIP_ONE(16, 1) QUIP_ONE(16, 2) QUIP_ONE(16, 3) QUIP_ONE(16, 4) QUIP_ONE(16, 6) QUIP_ONE(16, 8)
@@ -871,10 +865,10 @@ int e8p_gemv_mfma_launch(const void* planes, const void* qidxs, const void* grid
     return launch_oneshot<1>(gp, grid, k, kp, nblocks, threads, rep, items_per_wave, dbg, stream);
 #define QUIP_CASE(R, S)                                                                        \
   if (rep == R && slots == S && threads <= 512)                                                \
-    return launch<R, S, 512, 1>(gp, grid, k, kp, nblocks, threads, dbg, stream);
+    return launch_variant<R, S, 512, 1>(gp, grid, k, kp, nblocks, threads, dbg, stream);
 #define QUIP_CASE_BIG(R, S)                                                                    \
   if (rep == R && slots == S && threads > 512)                                                 \
-    return launch<R, S, 1024, 1>(gp, grid, k, kp, nblocks, threads, dbg, stream);
+    return launch_variant<R, S, 1024, 1>(gp, grid, k, kp, nblocks, threads, dbg, stream);
   QUIP_CASE(32, 1) QUIP_CASE(32, 2) QUIP_CASE(32, 3) QUIP_CASE(32, 4) QUIP_CASE(32, 6) QUIP_CASE(32, 8)
   QUIP_CASE(24, 1) QUIP_CASE(24, 2) QUIP_CASE(24, 3) QUIP_CASE(24, 4)
   QUIP_CASE(16, 1) QUIP_CASE(16, 2) QUIP_CASE(16, 3) QUIP_CASE(16, 4) QUIP_CASE(16, 6) QUIP_CASE(16, 8)
@@ -929,7 +923,7 @@ int e8p_gemv_mfma_rows_launch(const void* planes, const void* qidxs, const void*
                   {reinterpret_cast<f16*>(y)}, {n}, {rpb}, {0}, tune.grid2};
 #define QUIP_ROWS(R, S, T, ONE)                                                                   \
   if (rep == R && (T == 1024) == (threads > 512) && (ONE ? ipw <= S : true))                      \
-    return launch<R, S, T, 1, ONE, false, true>(gp, grid, k, kp, nblocks, threads, dbg, stream, nullptr, mrows);
+    return launch_variant<R, S, T, 1, ONE, false, true>(gp, grid, k, kp, nblocks, threads, dbg, stream, nullptr, mrows);
   if ((threads <= 512 && ipw <= 8) || (threads > 512 && ipw <= 4)) {
 #define QUIP_ROWS_ONE(R)                                                                                          \
     QUIP_ROWS(R, 1, 512, true) QUIP_ROWS(R, 2, 512, true) QUIP_ROWS(R, 3, 512, true) QUIP_ROWS(R, 4, 512, true)   \
@@ -1017,8 +1011,8 @@ static int group_launch(const void* const* planes, const void* const* qidxs, con
     return launch_oneshot<G>(gp, grid, k, kp, nblocks, threads, rep, (items + waves - 1) / waves, dbg, stream);
 #define QUIP_CASE(R, S)                                                                        \
   if (rep == R && slots == S)                                                                  \
-    return threads > 512 ? launch<R, S, 1024, G>(gp, grid, k, kp, nblocks, threads, dbg, stream) \
-                         : launch<R, S, 512, G>(gp, grid, k, kp, nblocks, threads, dbg, stream);
+    return threads > 512 ? launch_variant<R, S, 1024, G>(gp, grid, k, kp, nblocks, threads, dbg, stream) \
+                         : launch_variant<R, S, 512, G>(gp, grid, k, kp, nblocks, threads, dbg, stream);
   QUIP_CASE(32, 1) QUIP_CASE(32, 2) QUIP_CASE(24, 1) QUIP_CASE(24, 2) QUIP_CASE(16, 1) QUIP_CASE(16, 2)
   QUIP_CASE(64, 1) QUIP_CASE(64, 2) QUIP_CASE(40, 1) QUIP_CASE(40, 2) QUIP_CASE(20, 1) QUIP_CASE(20, 2)
 #undef QUIP_CASE
@@ -1080,10 +1074,10 @@ static int fused_launch(const GemvFusedIn& in, const void* const* qidxs, const v
   const int ipw = (items + waves - 1) / waves;
   uint64_t* dbg = reinterpret_cast<uint64_t*>(tune.dbg);
 #define QUIP_ONE(S)                                                                                   \
-  if (ipw <= S) return launch<16, S, 512, G, true, true>(gp, grid, k, kp, nblocks, threads, dbg, stream, &fi);
+  if (ipw <= S) return launch_variant<16, S, 512, G, true, true>(gp, grid, k, kp, nblocks, threads, dbg, stream, &fi);
   QUIP_ONE(1) QUIP_ONE(2) QUIP_ONE(3) QUIP_ONE(4) QUIP_ONE(6) QUIP_ONE(8)
 #undef QUIP_ONE
-  return launch<16, 2, 512, G, false, true>(gp, grid, k, kp, nblocks, threads, dbg, stream, &fi);
+  return launch_variant<16, 2, 512, G, false, true>(gp, grid, k, kp, nblocks, threads, dbg, stream, &fi);
 }
 
 int e8p_gemv_mfma_fused_launch(const GemvFusedIn& in, const void* const* qidxs, const void* grid,

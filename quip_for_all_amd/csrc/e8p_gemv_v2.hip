@@ -29,11 +29,11 @@
 //  * Up to three problems of the same K per launch (q/k/v, gate/up): tables, launch and drain paid once.
 //  * SLOTS load instructions (1 KiB each) per wave are in flight from the first instructions of the kernel,
 //    so the table build runs in the shadow of the first HBM burst.
-#include <cstdlib>
 #include <type_traits>
 
 #include "quip_device.hip.h"
-#include "quip_internal.h"
+#include "e8p_gemv_v2_plan.hip.h"
+#include "launch.hip.h"
 
 namespace quip {
 
@@ -515,62 +515,34 @@ __global__ __launch_bounds__(1024) void e8p_gemv_v2_kernel(V2Args a) {
 #undef V2_STAMP
 }
 
-template <int REP1, int REP2, int SLOTS, int G, bool RVQ3 = false>
-int v2_launch(const V2Args& a, int nrb, int threads, int lds, hipStream_t stream) {
-  auto kern = e8p_gemv_v2_kernel<REP1, REP2, SLOTS, G, RVQ3>;
-  static DynLdsCache configured;   // per instantiation, per device
-  if (ensure_dyn_lds(configured, reinterpret_cast<const void*>(kern), lds) != QUIP_OK) return QUIP_ERR_LAUNCH;
-  hipLaunchKernelGGL(kern, dim3(a.ksplit, nrb), dim3(threads), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
-}
-
 // rep code: 32 = (32, 32) copies, 24 = (32, 16), 16 = (16, 16); 40 = E8P12RVQ3B: (32, 16) + T3 x 16
 static int lds_x(int rep) {
   if (rep == 40) return V2Lds<32, 16, true>::kX;
   return rep == 32 ? V2Lds<32, 32>::kX : (rep == 24 ? V2Lds<32, 16>::kX : V2Lds<16, 16>::kX);
 }
 
-template <int G>
-int v2_group_launch(const void* const* planes, const void* const* qidxs, const void* grid, void* const* ys,
-                    void* ws, const int* ns, int k, const GemvTune& tune, hipStream_t stream) {
+GemvV2Plan v2_plan(const int* ns, int G, int k, const GemvTune& tune, bool have_ws) {
+  GemvV2Plan pl;
   const int ncu = device_cu_count();
   const int segs = (k + 1023) >> 10;
-  const int slots = tune.rows > 0 ? tune.rows : 2;
+  pl.slots = tune.rows > 0 ? tune.rows : 2;
   // Candidates (table replication, K split).  K is split only when the digit images of the whole rows do not fit
   // even beside the smallest tables, because combining partial sums across workgroups costs two more memory round
   // trips at the end of the launch; among forced splits (full tables) the one with the fewest units per
   // workgroup wins.
-  int rep = 0, ksplit = 0, nrb = 0, spw = 0, rpb[kMaxG] = {0, 0, 0}, best = 0;
+  int rep = 0, spw = 0, best = 0;
+  V2RowSplit split;
   auto consider = [&](int rp, int ks) -> bool {
-    int nrb_c = (tune.blocks > 0 ? tune.blocks : ncu) / ks;
-    if (nrb_c < 1) nrb_c = 1;
-    int rp_c[kMaxG] = {0, 0, 0}, rows = 0, quads = 0, need = 1;
-    for (;;) {   // accumulator rows must fit: more row blocks until they do
-      rows = 0; quads = 0; need = 1;
-      for (int p = 0; p < G; ++p) {
-        int v = (ns[p] + nrb_c - 1) / nrb_c;
-        v = (v + 3) & ~3;
-        rp_c[p] = v;
-        rows += v;
-        quads += v >> 2;
-        const int nb = (ns[p] + v - 1) / v;
-        need = nb > need ? nb : need;
-      }
-      if (rows <= 1024) break;
-      nrb_c *= 2;
-    }
+    const V2RowSplit c = v2_row_split(ns, G, (tune.blocks > 0 ? tune.blocks : ncu) / ks, 4);
     const int spw_c = (segs + ks - 1) / ks;
-    const int room = (V2Lds<16, 16>::kTotal - lds_x(rp) - rows * 16 - 16) / kSegBytes;
+    const int room = (V2Lds<16, 16>::kTotal - lds_x(rp) - c.rows * 16 - 16) / kSegBytes;
     if (G * spw_c > room || spw_c * 64 > (G == 1 ? 2 : 1) * 1024) return false;      // (1 or 2 k16 indices per thread)
-    const int cost = quads * spw_c;
-    if (!ksplit || cost < best) {
-      ksplit = ks; nrb = need; spw = spw_c; best = cost; rep = rp;
-      for (int p = 0; p < G; ++p) rpb[p] = rp_c[p];
-    }
+    const int cost = c.units * spw_c;
+    if (!spw || cost < best) { split = c; spw = spw_c; best = cost; rep = rp; }
     return true;
   };
   if (tune.rep == 40) {            // E8P12RVQ3B: one table configuration
-    if (G != 1 || !tune.grid2) return QUIP_ERR_UNSUPPORTED;
+    if (G != 1 || !tune.grid2) return pl;
     for (int ks = 1; ks <= segs; ++ks)
       if (consider(40, ks)) break;
   } else if ((tune.rep && tune.rep != 64) || tune.waves_g) {
@@ -579,66 +551,45 @@ int v2_group_launch(const void* const* planes, const void* const* qidxs, const v
       if (consider(rp, ks)) break;
   } else {
     const int reps[3] = {32, 24, 16};
-    for (int ri = 0; ri < 3 && !ksplit; ++ri) consider(reps[ri], 1);
-    if (!ksplit)
+    for (int ri = 0; ri < 3 && !spw; ++ri) consider(reps[ri], 1);
+    if (!spw)
       for (int ks = 2, tried = 0; ks <= segs && tried < 4; ++ks) tried += consider(32, ks) ? 1 : 0;
   }
-  if (!ksplit) return QUIP_ERR_UNSUPPORTED;
-  ksplit = (segs + spw - 1) / spw;
-  if (ksplit > 1 && !ws) return QUIP_ERR_NULL_POINTER;
+  if (!spw || !v2_plan_split(pl, rep, segs, spw, split, have_ws)) return pl;
+  v2_plan_waves(pl, G, split.units, tune, 64, 3);
+  pl.lds = lds_x(rep) + G * spw * kSegBytes + split.rows * 16 + 16;
+  const bool have_kernel = rep == 40 || ((rep == 32 || rep == 24 || rep == 16) && pl.slots >= 1 && pl.slots <= 4);
+  pl.rc = have_kernel ? QUIP_OK : QUIP_ERR_UNSUPPORTED;
+  return pl;
+}
+
+template <int G>
+int v2_group_launch(const void* const* planes, const void* const* qidxs, const void* grid, void* const* ys,
+                    void* ws, const int* ns, int k, const GemvTune& tune, hipStream_t stream) {
+  const GemvV2Plan pl = v2_plan(ns, G, k, tune, ws != nullptr);
+  if (pl.rc != QUIP_OK) return pl.rc;
   V2Args a;
-  size_t ws_off = 0;
-  int quads = 0, rows = 0;
-  for (int p = 0; p < kMaxG; ++p) {
-    const int pp = p < G ? p : 0;
-    a.W[p] = reinterpret_cast<const uint4*>(qidxs[pp]);
-    a.planes[p] = reinterpret_cast<const uint8_t*>(planes[pp]);
-    a.y[p] = reinterpret_cast<f16*>(ys[pp]);
-    a.N[p] = ns[pp];
-    a.rpb[p] = rpb[pp];
-    a.ws[p] = ws ? reinterpret_cast<int*>(ws) + ws_off : nullptr;
-    if (p < G) {
-      ws_off += (size_t)ns[p] * 4;                 // accumulators back to back; the counters follow the last one
-      quads += rpb[p] >> 2;
-      rows += rpb[p];
-    }
-  }
-  // row blocks <= max_p ceil(n_p / 4) <= the counter words e8p_gemv_v2_workspace_words() reserves in total
-  a.cnt = ws ? reinterpret_cast<int*>(ws) + ws_off : nullptr;
-  a.grid = reinterpret_cast<const uint64_t*>(grid);
+  v2_fill_args(a, pl, G, planes, qidxs, grid, ys, ws, ns, k, (k + 1023) >> 10, tune.dbg);
   a.grid2 = reinterpret_cast<const uint64_t*>(tune.grid2);
-  a.K = k;
-  a.kp_src = (k + 511) & ~511;
-  a.segs = segs; a.spw = spw; a.ksplit = ksplit;
-  a.dbg = reinterpret_cast<uint64_t*>(tune.dbg);
   a.d4 = tune.rep == 64 ? 1 : 0;      // (the first kernel's mode number for its D4 table)
-  // 16 waves for long streams; 12 when a workgroup has few units (8192^2: 64 units, 7.2 vs 7.9 us with 16)
-  int waves = tune.max_waves > 0 ? tune.max_waves : (quads * spw >= 128 ? 16 : 12);
-  if (waves < 8) waves = 8;     // the table build uses waves 0..7
-  if (waves > 16) waves = 16;
-  while (waves < 16 && spw * 64 > (G == 1 ? 2 : 1) * waves * 64) ++waves;   // k16 indices per thread
-  // run length: the longest (fewest LDS flushes, longest contiguous reads) that still leaves about three runs per wave (measured)
-  int runlen = tune.digits > 0 ? tune.digits : spw;
-  if (tune.digits <= 0)
-    while (runlen > slots && quads * ((spw + runlen - 1) / runlen) < 3 * waves) runlen = (runlen + 1) / 2;
-  if (runlen > spw) runlen = spw;
-  if (runlen < 1) runlen = 1;
-  a.runlen = runlen;
-  {
-    const int rpr = (spw + runlen - 1) / runlen;
-    a.rpr_inv = (rpr << 24) | (((1 << 20) / rpr + 1) & 0xffffff);
-  }
-  const int threads = waves * 64;
-  const int lds = lds_x(rep) + G * spw * kSegBytes + rows * 16 + 16;
+  const dim3 grd(pl.ksplit, pl.nrb), block(pl.threads);
   if constexpr (G == 1)
-    if (rep == 40) return v2_launch<32, 16, 2, 1, true>(a, nrb, threads, lds, stream);
+    if (pl.rep == 40) return launch<e8p_gemv_v2_kernel<32, 16, 2, 1, true>>(grd, block, pl.lds, stream, a);
 #define QUIP_V2(R1, R2, RR, S) \
-  if (rep == RR && slots == S) return v2_launch<R1, R2, S, G>(a, nrb, threads, lds, stream);
+  if (pl.rep == RR && pl.slots == S) return launch<e8p_gemv_v2_kernel<R1, R2, S, G>>(grd, block, pl.lds, stream, a);
   QUIP_V2(32, 32, 32, 1) QUIP_V2(32, 32, 32, 2) QUIP_V2(32, 32, 32, 3) QUIP_V2(32, 32, 32, 4)
   QUIP_V2(32, 16, 24, 1) QUIP_V2(32, 16, 24, 2) QUIP_V2(32, 16, 24, 3) QUIP_V2(32, 16, 24, 4)
   QUIP_V2(16, 16, 16, 1) QUIP_V2(16, 16, 16, 2) QUIP_V2(16, 16, 16, 3) QUIP_V2(16, 16, 16, 4)
 #undef QUIP_V2
   return QUIP_ERR_UNSUPPORTED;
+}
+
+// the shared validation of both table modes, above the mode choice (e8p_gemv_v2n.hip repeats none of it)
+int v2_check(const int* ns, int count, int k) {
+  if (count < 1 || count > kMaxG) return QUIP_ERR_UNSUPPORTED;
+  for (int i = 0; i < count; ++i)
+    if (!e8p_gemv_v2_supported(ns[i], k)) return QUIP_ERR_UNSUPPORTED;
+  return QUIP_OK;
 }
 
 }  // namespace
@@ -650,9 +601,7 @@ size_t e8p_gemv_v2_workspace_words(int n) { return (size_t)n * 4 + (size_t)((n +
 
 int e8p_gemv_v2_group_launch(const void* const* planes, const void* const* qidxs, const void* grid, void* const* ys,
                              void* ws, const int* ns, int count, int k, const GemvTune& tune, hipStream_t stream) {
-  if (count < 1 || count > kMaxG) return QUIP_ERR_UNSUPPORTED;
-  for (int i = 0; i < count; ++i)
-    if (!e8p_gemv_v2_supported(ns[i], k)) return QUIP_ERR_UNSUPPORTED;
+  if (const int rc = v2_check(ns, count, k); rc != QUIP_OK) return rc;
   if ((reinterpret_cast<uintptr_t>(grid) & 63u) != 0) return QUIP_ERR_MISALIGNED;
   if (tune.rep == 4) return e8p_gemv_v2n_group_launch(planes, qidxs, grid, ys, ws, ns, count, k, tune, stream);
   if (count == 1) return v2_group_launch<1>(planes, qidxs, grid, ys, ws, ns, k, tune, stream);
@@ -661,3 +610,21 @@ int e8p_gemv_v2_group_launch(const void* const* planes, const void* const* qidxs
 }
 
 }  // namespace quip
+
+// the plan e8p_gemv_v2_group_launch would launch (rep 4: nibble mode) as 13 ints, see GemvV2Plan; launches nothing
+extern "C" int quip_e8p_gemv_v2_plan(const int32_t* ns, int32_t count, int32_t k, int32_t rep, int32_t slots, int32_t blocks,
+                                     int32_t ksplit, int32_t max_waves, int32_t runlen, int32_t have_grid2, int32_t have_ws,
+                                     int32_t* out) {
+  using namespace quip;
+  if (!ns || !out) return QUIP_ERR_NULL_POINTER;
+  GemvTune t;
+  t.rep = rep; t.rows = slots; t.blocks = blocks; t.waves_g = ksplit; t.max_waves = max_waves; t.digits = runlen;
+  t.grid2 = have_grid2 ? out : nullptr;   // (only its presence counts)
+  GemvV2Plan pl;
+  pl.rc = v2_check(ns, count, k);
+  if (pl.rc == QUIP_OK) pl = rep == 4 ? e8p_gemv_v2n_plan(ns, count, k, t, have_ws != 0) : v2_plan(ns, count, k, t, have_ws != 0);
+  const int v[13] = {pl.rc, pl.rep, pl.slots, pl.ksplit, pl.nrb, pl.spw, pl.rpb[0], pl.rpb[1], pl.rpb[2],
+                     pl.runlen, pl.rpr_inv, pl.threads, pl.lds};
+  for (int i = 0; i < 13; ++i) out[i] = v[i];
+  return pl.rc;
+}

@@ -21,6 +21,8 @@
 #include <type_traits>
 
 #include "e8p_gemv_core.hip.h"
+#include "e8p_gemv_v2_plan.hip.h"
+#include "launch.hip.h"
 
 namespace quip {
 
@@ -417,87 +419,39 @@ __global__ __launch_bounds__(1024) void e8p_gemv_v2n_kernel(V2nArgs a) {
 #undef V2_STAMP
 }
 
-template <int SLOTS, int G>
-int v2n_launch(const V2nArgs& a, int nrb, int threads, int lds, hipStream_t stream) {
-  auto kern = e8p_gemv_v2n_kernel<SLOTS, G>;
-  static DynLdsCache configured;   // per instantiation, per device
-  if (ensure_dyn_lds(configured, reinterpret_cast<const void*>(kern), lds) != QUIP_OK) return QUIP_ERR_LAUNCH;
-  hipLaunchKernelGGL(kern, dim3(a.ksplit, nrb), dim3(threads), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+GemvV2Plan v2n_plan(const int* ns, int G, int k, const GemvTune& tune, bool have_ws) {
+  GemvV2Plan pl;
+  const int ncu = device_cu_count();
+  const int segs = (k + 511) >> 9;
+  pl.slots = tune.rows > 0 ? tune.rows : 2;      // (measured, 58.7 MB shapes: 2 < 3 < 4 < 6 < 8 slots)
+  // the smallest K split whose digit images fit beside the tables (combining partial sums across workgroups costs two more
+  // memory round trips at the end of the launch)
+  int spw = 0;
+  V2RowSplit split;
+  for (int ks = tune.waves_g > 0 ? tune.waves_g : 1; ks <= segs && !spw; ++ks) {
+    const V2RowSplit c = v2_row_split(ns, G, (tune.blocks > 0 ? tune.blocks : ncu) / ks, 8);
+    const int spw_c = (segs + ks - 1) / ks;
+    const int room = (160 * 1024 - kTablesN - c.rows * 16 - 16 * kMaxGN - 16) / kSegBytesN;
+    if (G * spw_c > room || spw_c * 32 > (G == 1 ? 2 : 1) * 1024) continue;      // (1 or 2 k16 indices per thread)
+    split = c; spw = spw_c;
+  }
+  if (!spw || !v2_plan_split(pl, 4, segs, spw, split, have_ws)) return pl;
+  // run length: about two runs per wave (measured: 28672 x 8192 4 = 8 segments, 8192 x 28672 7-8 > 4 > 2)
+  v2_plan_waves(pl, G, split.units, tune, 32, 2);
+  pl.lds = kTablesN + G * spw * kSegBytesN + split.rows * 16 + 16 * G + 16;
+  pl.rc = pl.slots >= 2 && pl.slots <= 4 ? QUIP_OK : QUIP_ERR_UNSUPPORTED;
+  return pl;
 }
 
 template <int G>
 int v2n_group_launch(const void* const* planes, const void* const* qidxs, const void* grid, void* const* ys,
                      void* ws, const int* ns, int k, const GemvTune& tune, hipStream_t stream) {
-  const int ncu = device_cu_count();
-  const int segs = (k + 511) >> 9;
-  const int slots = tune.rows > 0 ? tune.rows : 2;      // (measured, 58.7 MB shapes: 2 < 3 < 4 < 6 < 8 slots)
-  // the smallest K split whose digit images fit beside the tables (combining partial sums across workgroups costs two more
-  // memory round trips at the end of the launch)
-  int ksplit = 0, nrb = 0, spw = 0, rpb[kMaxGN] = {0, 0, 0}, rows = 0, octets = 0;
-  for (int ks = tune.waves_g > 0 ? tune.waves_g : 1; ks <= segs && !ksplit; ++ks) {
-    int nrb_c = (tune.blocks > 0 ? tune.blocks : ncu) / ks;
-    if (nrb_c < 1) nrb_c = 1;
-    int rp_c[kMaxGN] = {0, 0, 0}, need = 1;
-    for (;;) {   // accumulator rows must fit: more row blocks until they do
-      rows = 0; octets = 0; need = 1;
-      for (int p = 0; p < G; ++p) {
-        int v = (ns[p] + nrb_c - 1) / nrb_c;
-        v = (v + 7) & ~7;
-        rp_c[p] = v;
-        rows += v;
-        octets += v >> 3;
-        const int nb = (ns[p] + v - 1) / v;
-        need = nb > need ? nb : need;
-      }
-      if (rows <= 1024) break;
-      nrb_c *= 2;
-    }
-    const int spw_c = (segs + ks - 1) / ks;
-    const int room = (160 * 1024 - kTablesN - rows * 16 - 16 * kMaxGN - 16) / kSegBytesN;
-    if (G * spw_c > room || spw_c * 32 > (G == 1 ? 2 : 1) * 1024) continue;      // (1 or 2 k16 indices per thread)
-    ksplit = ks; nrb = need; spw = spw_c;
-    for (int p = 0; p < G; ++p) rpb[p] = rp_c[p];
-  }
-  if (!ksplit) return QUIP_ERR_UNSUPPORTED;
-  ksplit = (segs + spw - 1) / spw;
-  if (ksplit > 1 && !ws) return QUIP_ERR_NULL_POINTER;
+  const GemvV2Plan pl = v2n_plan(ns, G, k, tune, ws != nullptr);
+  if (pl.rc != QUIP_OK) return pl.rc;
   V2nArgs a;
-  size_t ws_off = 0;
-  for (int p = 0; p < kMaxGN; ++p) {
-    const int pp = p < G ? p : 0;
-    a.W[p] = reinterpret_cast<const uint4*>(qidxs[pp]);
-    a.planes[p] = reinterpret_cast<const uint8_t*>(planes[pp]);
-    a.y[p] = reinterpret_cast<f16*>(ys[pp]);
-    a.N[p] = ns[pp];
-    a.rpb[p] = rpb[pp];
-    a.ws[p] = ws ? reinterpret_cast<int*>(ws) + ws_off : nullptr;
-    if (p < G) ws_off += (size_t)ns[p] * 4;        // accumulators back to back; the counters follow the last one
-  }
-  a.cnt = ws ? reinterpret_cast<int*>(ws) + ws_off : nullptr;
-  a.grid = reinterpret_cast<const uint64_t*>(grid);
-  a.K = k;
-  a.kp_src = (k + 511) & ~511;
-  a.segs = segs; a.spw = spw; a.ksplit = ksplit;
-  a.dbg = reinterpret_cast<uint64_t*>(tune.dbg);
-  int waves = tune.max_waves > 0 ? tune.max_waves : (octets * spw >= 128 ? 16 : 12);
-  if (waves < 8) waves = 8;     // the table build uses waves 0..7
-  if (waves > 16) waves = 16;
-  while (waves < 16 && spw * 32 > (G == 1 ? 2 : 1) * waves * 64) ++waves;   // k16 indices per thread
-  // run length: the longest that still leaves about two runs per wave (measured: 28672 x 8192 4 = 8 segments, 8192 x 28672 7-8 > 4 > 2)
-  int runlen = tune.digits > 0 ? tune.digits : spw;
-  if (tune.digits <= 0)
-    while (runlen > slots && octets * ((spw + runlen - 1) / runlen) < 2 * waves) runlen = (runlen + 1) / 2;
-  if (runlen > spw) runlen = spw;
-  if (runlen < 1) runlen = 1;
-  a.runlen = runlen;
-  {
-    const int rpr = (spw + runlen - 1) / runlen;
-    a.rpr_inv = (rpr << 24) | (((1 << 20) / rpr + 1) & 0xffffff);
-  }
-  const int threads = waves * 64;
-  const int lds = kTablesN + G * spw * kSegBytesN + rows * 16 + 16 * G + 16;
-#define QUIP_V2N(S) if (slots == S) return v2n_launch<S, G>(a, nrb, threads, lds, stream);
+  v2_fill_args(a, pl, G, planes, qidxs, grid, ys, ws, ns, k, (k + 511) >> 9, tune.dbg);
+  const dim3 grd(pl.ksplit, pl.nrb), block(pl.threads);
+#define QUIP_V2N(S) if (pl.slots == S) return launch<e8p_gemv_v2n_kernel<S, G>>(grd, block, pl.lds, stream, a);
   QUIP_V2N(2) QUIP_V2N(3) QUIP_V2N(4)
 #undef QUIP_V2N
   return QUIP_ERR_UNSUPPORTED;
@@ -505,12 +459,13 @@ int v2n_group_launch(const void* const* planes, const void* const* qidxs, const 
 
 }  // namespace
 
+GemvV2Plan e8p_gemv_v2n_plan(const int* ns, int count, int k, const GemvTune& tune, bool have_ws) {
+  return v2n_plan(ns, count, k, tune, have_ws);
+}
+
+// reached through e8p_gemv_v2_group_launch only, which has checked count, the shapes and the alignment of `grid`
 int e8p_gemv_v2n_group_launch(const void* const* planes, const void* const* qidxs, const void* grid, void* const* ys,
                               void* ws, const int* ns, int count, int k, const GemvTune& tune, hipStream_t stream) {
-  if (count < 1 || count > kMaxGN) return QUIP_ERR_UNSUPPORTED;
-  for (int i = 0; i < count; ++i)
-    if (!e8p_gemv_v2_supported(ns[i], k)) return QUIP_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(grid) & 63u) != 0) return QUIP_ERR_MISALIGNED;
   if (count == 1) return v2n_group_launch<1>(planes, qidxs, grid, ys, ws, ns, k, tune, stream);
   if (count == 2) return v2n_group_launch<2>(planes, qidxs, grid, ys, ws, ns, k, tune, stream);
   return v2n_group_launch<3>(planes, qidxs, grid, ys, ws, ns, k, tune, stream);

@@ -45,7 +45,7 @@
 #include <type_traits>
 
 #include "quip_device.hip.h"
-#include "quip_internal.h"
+#include "launch.hip.h"
 
 namespace quip {
 
@@ -532,9 +532,9 @@ static int prefill_launch_mode(int mode, const void* x, const void* qidxs, const
   const int NT = (n + kBN - 1) / kBN;
   // 128-row tiles while 256-row tiles would leave CUs without a workgroup (the K loop of a workgroup takes the same
   // time whatever the tile height: a second half-filled round costs less than idle CUs)
-  static const int force = getenv("QUIP_PREFILL_TILE") ? atoi(getenv("QUIP_PREFILL_TILE")) : 0;   // 128 / 256: experiments
+  static const int force = env_int("QUIP_PREFILL_TILE", 0);   // 128 / 256: experiments
   // wave layout (see the kernel): 0 = eight waves of 256 x 32, 1 = 2 x 4 waves of 128 x 64, 2 = four waves of 256 x 64
-  static const int layout = getenv("QUIP_PREFILL_LAYOUT") ? atoi(getenv("QUIP_PREFILL_LAYOUT")) : 0;   // measured: 0 is the fastest
+  static const int layout = env_int("QUIP_PREFILL_LAYOUT", 0);   // measured: 0 is the fastest
   // (E8P12RVQ3B: a third table; E8P12RVQ4B: four table entries per fragment in flight, the 256-row tile's 128
   //  accumulator registers would leave it 9 registers short -- 128-row tiles always)
   const bool half = (mode == 4 || mode == 1) ? true : force ? force == 128 : (m + kBM - 1) / kBM * NT < device_cu_count();
@@ -542,22 +542,19 @@ static int prefill_launch_mode(int mode, const void* x, const void* qidxs, const
   const int MT = (int)((m + bm - 1) / bm);
   const int64_t blocks = MT >= 8 ? (int64_t)((MT + 7) / 8) * NT * 8 : (int64_t)MT * NT;
   if (blocks > 0x7fffffff) return QUIP_ERR_UNSUPPORTED;
-  auto go = [&](auto kern, DynLdsCache& configured, int threads) -> int {
-    const int lds = lds_bytes(bm, mode);
-    if (ensure_dyn_lds(configured, reinterpret_cast<const void*>(kern), lds) != QUIP_OK) return QUIP_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), lds, stream, reinterpret_cast<const f16*>(x),
-                       reinterpret_cast<const uint8_t*>(qidxs), reinterpret_cast<const uint64_t*>(grid),
-                       reinterpret_cast<f16*>(y), (int)m, n, k, MT, NT, resid_scale, reinterpret_cast<const uint32_t*>(grid2));
-    return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  auto go = [&](auto kern, int threads) -> int {
+    return launch<decltype(kern)::value>(dim3((unsigned)blocks), dim3(threads), lds_bytes(bm, mode), stream,
+                                         reinterpret_cast<const f16*>(x), reinterpret_cast<const uint8_t*>(qidxs),
+                                         reinterpret_cast<const uint64_t*>(grid), reinterpret_cast<f16*>(y), (int)m, n, k, MT,
+                                         NT, resid_scale, reinterpret_cast<const uint32_t*>(grid2));
   };
-  static DynLdsCache c[13];   // per instantiation, per device
-  if (mode == 1) return go(e8p_prefill_gemm_kernel<4, 1, 1, 8, 1>, c[6], 512);
-  if (mode == 2) return half ? go(e8p_prefill_gemm_kernel<4, 1, 1, 8, 2>, c[8], 512) : go(e8p_prefill_gemm_kernel<8, 1, 1, 8, 2>, c[9], 512);
-  if (mode == 3) return half ? go(e8p_prefill_gemm_kernel<4, 1, 1, 8, 3>, c[10], 512) : go(e8p_prefill_gemm_kernel<8, 1, 1, 8, 3>, c[11], 512);
-  if (mode == 4) return go(e8p_prefill_gemm_kernel<4, 1, 1, 8, 4>, c[12], 512);
-  if (layout == 2) return half ? go(e8p_prefill_gemm_kernel<4, 2, 1, 4>, c[0], 256) : go(e8p_prefill_gemm_kernel<8, 2, 1, 4>, c[1], 256);
-  if (layout == 1) return half ? go(e8p_prefill_gemm_kernel<2, 2, 2, 4>, c[2], 512) : go(e8p_prefill_gemm_kernel<4, 2, 2, 4>, c[3], 512);
-  return half ? go(e8p_prefill_gemm_kernel<4, 1, 1, 8>, c[4], 512) : go(e8p_prefill_gemm_kernel<8, 1, 1, 8>, c[5], 512);
+  if (mode == 1) return go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8, 1>>, 512);
+  if (mode == 2) return half ? go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8, 2>>, 512) : go(kernel_c<e8p_prefill_gemm_kernel<8, 1, 1, 8, 2>>, 512);
+  if (mode == 3) return half ? go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8, 3>>, 512) : go(kernel_c<e8p_prefill_gemm_kernel<8, 1, 1, 8, 3>>, 512);
+  if (mode == 4) return go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8, 4>>, 512);
+  if (layout == 2) return half ? go(kernel_c<e8p_prefill_gemm_kernel<4, 2, 1, 4>>, 256) : go(kernel_c<e8p_prefill_gemm_kernel<8, 2, 1, 4>>, 256);
+  if (layout == 1) return half ? go(kernel_c<e8p_prefill_gemm_kernel<2, 2, 2, 4>>, 512) : go(kernel_c<e8p_prefill_gemm_kernel<4, 2, 2, 4>>, 512);
+  return half ? go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8>>, 512) : go(kernel_c<e8p_prefill_gemm_kernel<8, 1, 1, 8>>, 512);
 }
 
 int e8p_prefill_gemm_launch(const void* x, const void* qidxs, const void* grid, void* y, int64_t m, int n, int k,

@@ -51,7 +51,7 @@
 // MODE 3 = HI (hi.py:41-50; origin_order.cu:1028-1051): eight nibbles per 8 weights -- the data movement of MODE 1 --,
 // w = nibble - 7.5 through the 0x4c00 | n << 6 = 16 + n identity and one packed subtraction; no table.
 #include "quip_device.hip.h"
-#include "quip_internal.h"
+#include "launch.hip.h"
 #include <type_traits>
 
 namespace quip {
@@ -517,33 +517,30 @@ static int skinny_launch_mode(int mode, const void* x, const void* qidxs, const 
   // (a function of n alone: the K slicing fixes the order of the fp32 sums, and a row's result must not depend on
   //  how many rows the launch has)
   const bool one = (n + 63) / 64 < 2 * device_cu_count() / 3;
-  auto go = [&](auto kern, int cols, int slot) -> int {
-    static DynLdsCache configured[20];   // per instantiation, per device
-    if (ensure_dyn_lds(configured[slot], reinterpret_cast<const void*>(kern), kSLds) != QUIP_OK) return QUIP_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((n + cols - 1) / cols, (m + 31) / 32), dim3(1024), kSLds, stream,
-                       reinterpret_cast<const f16*>(x),
-                       reinterpret_cast<const uint16_t*>(qidxs), reinterpret_cast<const uint64_t*>(grid),
-                       reinterpret_cast<f16*>(y), m, n, k, resid_scale, reinterpret_cast<const uint32_t*>(grid2));
-    return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  auto go = [&](auto kern, int cols) -> int {
+    return launch<decltype(kern)::value>(dim3((n + cols - 1) / cols, (m + 31) / 32), dim3(1024), kSLds, stream,
+                                         reinterpret_cast<const f16*>(x), reinterpret_cast<const uint16_t*>(qidxs),
+                                         reinterpret_cast<const uint64_t*>(grid), reinterpret_cast<f16*>(y), m, n, k,
+                                         resid_scale, reinterpret_cast<const uint32_t*>(grid2));
   };
   if (mode == 1) {
-    if (m <= 16) return one ? go(e8p_skinny_gemm_kernel<1, 16, 1>, 32, 4) : go(e8p_skinny_gemm_kernel<2, 16, 1>, 64, 5);
-    return one ? go(e8p_skinny_gemm_kernel<1, 32, 1>, 32, 6) : go(e8p_skinny_gemm_kernel<2, 32, 1>, 64, 7);
+    if (m <= 16) return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 16, 1>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 16, 1>>, 64);
+    return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 32, 1>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 32, 1>>, 64);
   }
   if (mode == 2) {
-    if (m <= 16) return one ? go(e8p_skinny_gemm_kernel<1, 16, 2>, 32, 8) : go(e8p_skinny_gemm_kernel<2, 16, 2>, 64, 9);
-    return one ? go(e8p_skinny_gemm_kernel<1, 32, 2>, 32, 10) : go(e8p_skinny_gemm_kernel<2, 32, 2>, 64, 11);
+    if (m <= 16) return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 16, 2>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 16, 2>>, 64);
+    return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 32, 2>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 32, 2>>, 64);
   }
   if (mode == 4) {
-    if (m <= 16) return one ? go(e8p_skinny_gemm_kernel<1, 16, 4>, 32, 16) : go(e8p_skinny_gemm_kernel<2, 16, 4>, 64, 17);
-    return one ? go(e8p_skinny_gemm_kernel<1, 32, 4>, 32, 18) : go(e8p_skinny_gemm_kernel<2, 32, 4>, 64, 19);
+    if (m <= 16) return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 16, 4>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 16, 4>>, 64);
+    return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 32, 4>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 32, 4>>, 64);
   }
   if (mode == 3) {
-    if (m <= 16) return one ? go(e8p_skinny_gemm_kernel<1, 16, 3>, 32, 12) : go(e8p_skinny_gemm_kernel<2, 16, 3>, 64, 13);
-    return one ? go(e8p_skinny_gemm_kernel<1, 32, 3>, 32, 14) : go(e8p_skinny_gemm_kernel<2, 32, 3>, 64, 15);
+    if (m <= 16) return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 16, 3>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 16, 3>>, 64);
+    return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 32, 3>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 32, 3>>, 64);
   }
-  if (m <= 16) return one ? go(e8p_skinny_gemm_kernel<1, 16>, 32, 0) : go(e8p_skinny_gemm_kernel<2, 16>, 64, 1);
-  return one ? go(e8p_skinny_gemm_kernel<1, 32>, 32, 2) : go(e8p_skinny_gemm_kernel<2, 32>, 64, 3);
+  if (m <= 16) return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 16>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 16>>, 64);
+  return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 32>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 32>>, 64);
 }
 
 int e8p_skinny_gemm_launch(const void* x, const void* qidxs, const void* grid, void* y, int m, int n, int k,

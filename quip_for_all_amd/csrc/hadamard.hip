@@ -27,7 +27,7 @@
 // compute alone: K == 1: the exact max |v| of the transformed row; K > 1: |v_i| <= ||v||_2 =
 // scale * sqrt(L) * ||H||_2 * ||input||_2 with H ~ orthogonal.
 #include "had_device.hip.h"
-#include "quip_internal.h"
+#include "launch.hip.h"
 
 namespace quip {
 
@@ -1193,18 +1193,8 @@ __global__ __launch_bounds__(256) void had_small_kernel(HadGroup grp) {
   }
 }
 
-template <typename Kern>
-int launch_one(Kern kern, DynLdsCache& configured, const HadGroup& g, dim3 grid, int threads, int lds,
-               hipStream_t stream) {
-  if (ensure_dyn_lds(configured, reinterpret_cast<const void*>(kern), lds) != QUIP_OK) return QUIP_ERR_LAUNCH;
-  hipLaunchKernelGGL(kern, grid, dim3(threads), lds, stream, g);
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // `count` problems of the same (n, K, L) and kind (planes / fp16) in one launch (grid.z)
-int launch(HadGroup& g, int count, int64_t rows, hipStream_t stream) {
+int launch_group(HadGroup& g, int count, int64_t rows, hipStream_t stream) {
   const int L = g.p[0].L, K = g.p[0].K, n = g.p[0].n;
   const bool planes = g.p[0].planes != nullptr;
   for (int i = 0; i < count; ++i) {
@@ -1214,7 +1204,6 @@ int launch(HadGroup& g, int count, int64_t rows, hipStream_t stream) {
     a.vec_out = (a.out_features % 8 == 0) && aligned16(a.y) && aligned16(a.post) && aligned16(a.bias) &&
                 aligned16(a.residual);
   }
-  static DynLdsCache cfg[8];   // per kernel instantiation, per device
   if (K > 1 && L >= 64 && L <= 256) {   // tall: 256 threads, R = 4096 / L rows per workgroup
     const int R = 4096 / L;
     // [shuffle buffer | H tile | x rows | second half of the ping-pong buffer]
@@ -1233,7 +1222,6 @@ int launch(HadGroup& g, int count, int64_t rows, hipStream_t stream) {
       }
       ok = ok && !(in_side && out_side);
       if (ok) {
-        static DynLdsCache cfgb[8];
         const int BR = (K + 3) & ~3;
         const int KP = K <= 48 ? 48 : 176;
         const bool pair = K > 48;   // two rows in flight in ONE workgroup per CU (they share the 62 KB of H); else two workgroups
@@ -1241,17 +1229,13 @@ int launch(HadGroup& g, int count, int64_t rows, hipStream_t stream) {
         const int threads = pair ? 512 : 256;
         const int64_t want = (pair ? 1 : 2) * (int64_t)device_cu_count(), units = pair ? (rows + 1) / 2 : rows;
         const dim3 grid((unsigned)(units < want ? units : want), 1, count);
-        auto go = [&](auto kern, DynLdsCache& cache) {
-          if (ensure_dyn_lds(cache, reinterpret_cast<const void*>(kern), lds) != QUIP_OK) return (int)QUIP_ERR_LAUNCH;
-          hipLaunchKernelGGL(kern, grid, dim3(threads), lds, stream, g, (int)rows);
-          return hipGetLastError() == hipSuccess ? (int)QUIP_OK : (int)QUIP_ERR_LAUNCH;
-        };
+        auto go = [&](auto kern) { return launch<decltype(kern)::value>(grid, dim3(threads), lds, stream, g, (int)rows); };
         const int logL = g.p[0].logL;
-        if (K > 48) return in_side ? go(had_tall_batch_kernel<6, 0, 11, true>, cfgb[6]) : go(had_tall_batch_kernel<6, 1, 11, true>, cfgb[7]);
-        if (!in_side) return logL == 8 ? go(had_tall_batch_kernel<8, 1, 3, false>, cfgb[0]) : logL == 7 ? go(had_tall_batch_kernel<7, 1, 3, false>, cfgb[1])
-                                                                                                  : go(had_tall_batch_kernel<6, 1, 3, false>, cfgb[2]);
-        return logL == 8 ? go(had_tall_batch_kernel<8, 0, 3, false>, cfgb[3]) : logL == 7 ? go(had_tall_batch_kernel<7, 0, 3, false>, cfgb[4])
-                                                                                    : go(had_tall_batch_kernel<6, 0, 3, false>, cfgb[5]);
+        if (K > 48) return in_side ? go(kernel_c<had_tall_batch_kernel<6, 0, 11, true>>) : go(kernel_c<had_tall_batch_kernel<6, 1, 11, true>>);
+        if (!in_side) return logL == 8 ? go(kernel_c<had_tall_batch_kernel<8, 1, 3, false>>) : logL == 7 ? go(kernel_c<had_tall_batch_kernel<7, 1, 3, false>>)
+                                                                                                  : go(kernel_c<had_tall_batch_kernel<6, 1, 3, false>>);
+        return logL == 8 ? go(kernel_c<had_tall_batch_kernel<8, 0, 3, false>>) : logL == 7 ? go(kernel_c<had_tall_batch_kernel<7, 0, 3, false>>)
+                                                                                    : go(kernel_c<had_tall_batch_kernel<6, 0, 3, false>>);
       }
     }
     const int pp = had::buf_floats(4096) + ((K + 3) & ~3) * R + K * (L + 8);
@@ -1259,8 +1243,8 @@ int launch(HadGroup& g, int count, int64_t rows, hipStream_t stream) {
     for (int i = 0; i < count; ++i) g.p[i].pp = batch ? 0 : pp;
     const dim3 grid((K + R - 1) / R, (unsigned)rows, count);
     const int threads = batch ? 512 : 1024;
-    return planes ? launch_one(had_fast_kernel<true, true, 1024>, cfg[0], g, grid, threads, lds, stream)
-                  : launch_one(had_fast_kernel<false, true, 1024>, cfg[1], g, grid, threads, lds, stream);
+    return planes ? launch<had_fast_kernel<true, true, 1024>>(grid, dim3(threads), lds, stream, g)
+                  : launch<had_fast_kernel<false, true, 1024>>(grid, dim3(threads), lds, stream, g);
   }
   const dim3 grid(K, (unsigned)rows, count);
   bool mixed = false;
@@ -1278,9 +1262,8 @@ int launch(HadGroup& g, int count, int64_t rows, hipStream_t stream) {
       g.p[i].pp = batch ? 0 : had::buf_floats(g.p[i].L);
     }
     const int lds = (batch ? 1 : 2) * had::buf_floats(Lmax) * 4;
-    static DynLdsCache cm[2];
-    return Lmax <= 4096 ? launch_one(had_fast_kernel<false, false, 256, true>, cm[0], g, grid, Lmax / 16, lds, stream)
-                        : launch_one(had_fast_kernel<false, false, 1024>, cm[1], g, grid, Lmax / 16, lds, stream);
+    return Lmax <= 4096 ? launch<had_fast_kernel<false, false, 256, true>>(grid, dim3(Lmax / 16), lds, stream, g)
+                        : launch<had_fast_kernel<false, false, 1024>>(grid, dim3(Lmax / 16), lds, stream, g);
   }
   if (L >= 256 && L <= 16384) {
     // ping-pong shuffle buffer for the latency-bound decode launches; batches (prefill) take the single
@@ -1307,16 +1290,14 @@ int launch(HadGroup& g, int count, int64_t rows, hipStream_t stream) {
           const int chain = tg * part;
           const int lds3 = chain * 4 + 2 * n * 2 + 64 * 4;
           for (int i = 0; i < count; ++i) g.p[i].chain_off = chain;
-          static DynLdsCache c3[4];
           const int threads = (L / 16) * tg, logL = g.p[0].logL;
-          return logL == 9 ? launch_one(had_fast_kernel<true, false, 512, false, 9>, c3[0], g, grid, threads, lds3, stream)
-               : logL == 10 ? launch_one(had_fast_kernel<true, false, 512, false, 10>, c3[1], g, grid, threads, lds3, stream)
-               : logL == 11 ? launch_one(had_fast_kernel<true, false, 512, false, 11>, c3[2], g, grid, threads, lds3, stream)
-                            : launch_one(had_fast_kernel<true, false, 768, false, 12>, c3[3], g, grid, threads, lds3, stream);
+          return logL == 9 ? launch<had_fast_kernel<true, false, 512, false, 9>>(grid, dim3(threads), lds3, stream, g)
+               : logL == 10 ? launch<had_fast_kernel<true, false, 512, false, 10>>(grid, dim3(threads), lds3, stream, g)
+               : logL == 11 ? launch<had_fast_kernel<true, false, 512, false, 11>>(grid, dim3(threads), lds3, stream, g)
+                            : launch<had_fast_kernel<true, false, 768, false, 12>>(grid, dim3(threads), lds3, stream, g);
         }
-        static DynLdsCache c2[2];
-        return planes ? launch_one(had_fast_kernel<true, false, 1024>, c2[0], g, grid, (L / 16) * tg, lds2, stream)
-                      : launch_one(had_fast_kernel<false, false, 1024>, c2[1], g, grid, (L / 16) * tg, lds2, stream);
+        return planes ? launch<had_fast_kernel<true, false, 1024>>(grid, dim3((L / 16) * tg), lds2, stream, g)
+                      : launch<had_fast_kernel<false, false, 1024>>(grid, dim3((L / 16) * tg), lds2, stream, g);
       }
     }
     if ((K == 3 || K == 5 || K == 7) && !planes && rows > 8 && L >= 512 && L <= 4096) {   // batches, small odd K
@@ -1327,13 +1308,10 @@ int launch(HadGroup& g, int count, int64_t rows, hipStream_t stream) {
         const int lds1 = had::buf_floats(L) * 4;
         const dim3 grid1(1, (unsigned)rows, count);
         const int logL = g.p[0].logL;
-        auto go = [&](auto kern) {
-          hipLaunchKernelGGL(kern, grid1, dim3(L / 16), lds1, stream, g);
-          return hipGetLastError() == hipSuccess ? (int)QUIP_OK : (int)QUIP_ERR_LAUNCH;
-        };
+        auto go = [&](auto kern) { return launch<decltype(kern)::value>(grid1, dim3(L / 16), lds1, stream, g); };
 #define QUIP_WIDE_BATCH(KK)                                                                               \
-        return logL == 12 ? go(had_wide_batch_kernel<12, KK>) : logL == 11 ? go(had_wide_batch_kernel<11, KK>) \
-             : logL == 10 ? go(had_wide_batch_kernel<10, KK>) : go(had_wide_batch_kernel<9, KK>)
+        return logL == 12 ? go(kernel_c<had_wide_batch_kernel<12, KK>>) : logL == 11 ? go(kernel_c<had_wide_batch_kernel<11, KK>>) \
+             : logL == 10 ? go(kernel_c<had_wide_batch_kernel<10, KK>>) : go(kernel_c<had_wide_batch_kernel<9, KK>>)
         if (K == 3) { QUIP_WIDE_BATCH(3); }
         if (K == 5) { QUIP_WIDE_BATCH(5); }
         QUIP_WIDE_BATCH(7);
@@ -1346,32 +1324,30 @@ int launch(HadGroup& g, int count, int64_t rows, hipStream_t stream) {
         ok = ok && g.p[i].vec && g.p[i].vec_out && !g.p[i].rms_w && !g.p[i].z && g.p[i].out_features % 8 == 0;
       if (ok) {
         const int lds1 = had::buf_floats(L) * 4;
-        if (L == 8192) hipLaunchKernelGGL(had_kone_batch_kernel<13>, grid, dim3(L / 16), lds1, stream, g);
-        else if (L == 4096) hipLaunchKernelGGL(had_kone_batch_kernel<12>, grid, dim3(L / 16), lds1, stream, g);
-        else if (L == 2048) hipLaunchKernelGGL(had_kone_batch_kernel<11>, grid, dim3(L / 16), lds1, stream, g);
-        else hipLaunchKernelGGL(had_kone_batch_kernel<10>, grid, dim3(L / 16), lds1, stream, g);
-        return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+        const dim3 block(L / 16);
+        return L == 8192 ? launch<had_kone_batch_kernel<13>>(grid, block, lds1, stream, g)
+             : L == 4096 ? launch<had_kone_batch_kernel<12>>(grid, block, lds1, stream, g)
+             : L == 2048 ? launch<had_kone_batch_kernel<11>>(grid, block, lds1, stream, g)
+                         : launch<had_kone_batch_kernel<10>>(grid, block, lds1, stream, g);
       }
     }
     if (L <= 4096 && K == 1) {
-      static DynLdsCache c1[2];
-      return planes ? launch_one(had_fast_kernel<true, false, 256, true>, c1[0], g, grid, L / 16, lds, stream)
-                    : launch_one(had_fast_kernel<false, false, 256, true>, c1[1], g, grid, L / 16, lds, stream);
+      return planes ? launch<had_fast_kernel<true, false, 256, true>>(grid, dim3(L / 16), lds, stream, g)
+                    : launch<had_fast_kernel<false, false, 256, true>>(grid, dim3(L / 16), lds, stream, g);
     }
     if (L == 8192 && K == 1) {   // Llama-2-70B's hidden size: the K == 1 instantiation (no K-mix code) on 512 threads
-      static DynLdsCache c8[2];
-      return planes ? launch_one(had_fast_kernel<true, false, 512, true>, c8[0], g, grid, L / 16, lds, stream)
-                    : launch_one(had_fast_kernel<false, false, 512, true>, c8[1], g, grid, L / 16, lds, stream);
+      return planes ? launch<had_fast_kernel<true, false, 512, true>>(grid, dim3(L / 16), lds, stream, g)
+                    : launch<had_fast_kernel<false, false, 512, true>>(grid, dim3(L / 16), lds, stream, g);
     }
     if (L <= 4096)
-      return planes ? launch_one(had_fast_kernel<true, false, 256>, cfg[2], g, grid, L / 16, lds, stream)
-                    : launch_one(had_fast_kernel<false, false, 256>, cfg[3], g, grid, L / 16, lds, stream);
-    return planes ? launch_one(had_fast_kernel<true, false, 1024>, cfg[6], g, grid, L / 16, lds, stream)
-                  : launch_one(had_fast_kernel<false, false, 1024>, cfg[7], g, grid, L / 16, lds, stream);
+      return planes ? launch<had_fast_kernel<true, false, 256>>(grid, dim3(L / 16), lds, stream, g)
+                    : launch<had_fast_kernel<false, false, 256>>(grid, dim3(L / 16), lds, stream, g);
+    return planes ? launch<had_fast_kernel<true, false, 1024>>(grid, dim3(L / 16), lds, stream, g)
+                  : launch<had_fast_kernel<false, false, 1024>>(grid, dim3(L / 16), lds, stream, g);
   }
   const int threads = L >= 512 ? 256 : 64;
-  return planes ? launch_one(had_small_kernel<true>, cfg[4], g, grid, threads, L * 4, stream)
-                : launch_one(had_small_kernel<false>, cfg[5], g, grid, threads, L * 4, stream);
+  return planes ? launch<had_small_kernel<true>>(grid, dim3(threads), L * 4, stream, g)
+                : launch<had_small_kernel<false>>(grid, dim3(threads), L * 4, stream, g);
 }
 
 int check_shape(int in_features, int out_features, int n, int K, const void* had, int& L, int& logL) {
@@ -1473,7 +1449,7 @@ int had_transform_group_launch(const HadProblem* problems, int count, bool plane
       if (a.residual) a.residual += r0 * a.out_features;
       if (a.z) { a.z += r0 * a.n; a.h_out += r0 * a.n; if (a.z_res) a.z_res += r0 * a.n; }
     }
-    const int rc = launch(part, count, nr, stream);
+    const int rc = launch_group(part, count, nr, stream);
     if (rc != QUIP_OK) return rc;
   }
   return QUIP_OK;

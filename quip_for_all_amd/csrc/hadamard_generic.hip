@@ -8,7 +8,7 @@
 #include <hip/hip_bf16.h>
 
 #include "quip_device.hip.h"
-#include "quip_internal.h"
+#include "launch.hip.h"
 
 namespace quip {
 
@@ -64,15 +64,14 @@ int launch_generic(const void* x, void* y, int64_t rows, int n, float scale, hip
   while ((1 << logn) < n) ++logn;
   const int threads = n >= 2048 ? 1024 : (n >= 128 ? n / 2 : 64);
   const int lds = n * 4;
-  auto kern = hadamard_generic_kernel<T>;
-  static DynLdsCache configured;   // per instantiation, per device
-  if (ensure_dyn_lds(configured, reinterpret_cast<const void*>(kern), lds) != QUIP_OK) return QUIP_ERR_LAUNCH;
   for (int64_t r0 = 0; r0 < rows; r0 += 1 << 30) {   // grid.x limit
     const int64_t m = rows - r0 < (1 << 30) ? rows - r0 : (1 << 30);
-    hipLaunchKernelGGL(kern, dim3((unsigned)m), dim3(threads), lds, stream, reinterpret_cast<const T*>(x) + r0 * n,
-                       reinterpret_cast<T*>(y) + r0 * n, n, logn, scale);
+    const int rc = launch<hadamard_generic_kernel<T>>(dim3((unsigned)m), dim3(threads), lds, stream,
+                                                      reinterpret_cast<const T*>(x) + r0 * n,
+                                                      reinterpret_cast<T*>(y) + r0 * n, n, logn, scale);
+    if (rc != QUIP_OK) return rc;
   }
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  return QUIP_OK;
 }
 
 }  // namespace

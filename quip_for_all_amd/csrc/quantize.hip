@@ -24,7 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "quip_device.hip.h"
-#include "quip_internal.h"
+#include "launch.hip.h"
 
 namespace quip {
 
@@ -168,15 +168,13 @@ int e8p_quantize_launch(const void* x, int64_t nvec, const void* grid_packed_abs
   const int lanes = nvec < 65536 ? 8 : 1;
   const int64_t blocks = (nvec * lanes + threads - 1) / threads;
   if (blocks > 0x7fffffff) return QUIP_ERR_BAD_SHAPE;
-  if (lanes == 8)
-    hipLaunchKernelGGL(e8p_quantize_kernel<8>, dim3((unsigned)blocks), dim3(threads), 0, stream,
-                       reinterpret_cast<const float*>(x), nvec, reinterpret_cast<const uint64_t*>(grid_packed_abs),
-                       reinterpret_cast<float*>(vals), reinterpret_cast<int64_t*>(idx));
-  else
-    hipLaunchKernelGGL(e8p_quantize_kernel<1>, dim3((unsigned)blocks), dim3(threads), 0, stream,
-                       reinterpret_cast<const float*>(x), nvec, reinterpret_cast<const uint64_t*>(grid_packed_abs),
-                       reinterpret_cast<float*>(vals), reinterpret_cast<int64_t*>(idx));
-  return hipGetLastError() == hipSuccess ? QUIP_OK : QUIP_ERR_LAUNCH;
+  const dim3 grid((unsigned)blocks), block(threads);
+  const float* xf = reinterpret_cast<const float*>(x);
+  const uint64_t* tab = reinterpret_cast<const uint64_t*>(grid_packed_abs);
+  float* v = reinterpret_cast<float*>(vals);
+  int64_t* ix = reinterpret_cast<int64_t*>(idx);
+  return lanes == 8 ? launch<e8p_quantize_kernel<8>>(grid, block, 0, stream, xf, nvec, tab, v, ix)
+                    : launch<e8p_quantize_kernel<1>>(grid, block, 0, stream, xf, nvec, tab, v, ix);
 }
 
 }  // namespace quip

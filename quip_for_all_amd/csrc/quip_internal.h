@@ -10,16 +10,20 @@ namespace quip {
 int device_cu_count();
 // Persistent launches (decode_engine.hip, decode_block*.hip) spin across workgroups: every one of the `nwg` workgroups has to be
 // resident at once.  True when the current device has at least nwg CUs (no fall-back value: a failed query says no) and the
-// occupancy query admits the grid for this kernel / block size / dynamic LDS.  Cached per kernel and device by the caller.
+// occupancy query admits the grid for this kernel / block size / dynamic LDS.  Cached per kernel and device (launch.hip.h).
 struct ResidencyCache { signed char ok[16] = {}; };      // 0 unknown, 1 fits, -1 does not
 bool persistent_grid_fits(ResidencyCache& cache, const void* kernel, int threads, int lds, int nwg);
 int device_cu_count_strict();                            // 0 when the query fails
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel: one static DynLdsCache per kernel
-// instantiation (at its launch site) remembers the largest size configured on each device of the process, so a
+// hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel: the one DynLdsCache per kernel
+// instantiation (launch.hip.h) remembers the largest size configured on each device of the process, so a
 // process that drives several GPUs configures the kernel on each of them.  (Benign race: the attribute is idempotent.)
 struct DynLdsCache { int bytes[16] = {}; };
 int ensure_dyn_lds(DynLdsCache& cache, const void* kernel, int lds);   // QUIP_OK / QUIP_ERR_LAUNCH
+
+// Environment switches are integers, read once per process: static const int v = env_int("QUIP_X", dflt) at the point of use.
+int env_int(const char* name, int dflt);
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // Tuning knobs of the E8P decode GEMV (0 = pick automatically).  Exposed through
 // quip_e8p_gemv_tuned() for the micro-benchmark only; the ABI entry points use auto.
@@ -278,6 +282,12 @@ extern "C" int quip_e8p_gemv_v2_group_tuned(const void* const* planes, const voi
                                             int32_t rep, int32_t slots, int32_t blocks, int32_t ksplit,
                                             int32_t max_waves, int32_t runlen, void* dbg, quip_stream_t stream);
 extern "C" size_t quip_e8p_gemv_v2_workspace_bytes(int32_t n);
+// the plan e8p_gemv_v2_group_launch makes for these tuning arguments (rep 4: nibble mode), without a launch: out[13] = rc, rep, slots,
+// ksplit, nrb, spw, rpb[3], runlen, rpr_inv, threads, lds (e8p_gemv_v2_plan.hip.h); have_grid2 / have_ws: the E81B table /
+// a workspace would be passed.  Pure host arithmetic: the same answer with and without a GPU of 256 CUs
+extern "C" int quip_e8p_gemv_v2_plan(const int32_t* ns, int32_t count, int32_t k, int32_t rep, int32_t slots,
+                                     int32_t blocks, int32_t ksplit, int32_t max_waves, int32_t runlen,
+                                     int32_t have_grid2, int32_t have_ws, int32_t* out);
 // kernel 2 in quip_e8p_gemv_tuned = streaming-read probe (y is a 4-byte scratch)
 // lane-ordered digit planes for the VALU integer GEMV (kernel 0); planes: 3*k + 16 bytes
 extern "C" int quip_e8p_x_to_planes_laneorder(const void* x, void* planes, int32_t k, quip_stream_t stream);
