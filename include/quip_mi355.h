@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 11
+#define QUIP_ABI_VERSION 12
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -481,6 +481,27 @@ int quip_rope_attn_chunk_f16(const void* q, const void* k, const void* v, const 
                              const int64_t* pos, void* kcache, void* vcache, void* out, int32_t rows, int32_t heads,
                              int32_t kv_heads, int32_t head_dim, int32_t max_len, float scale, int32_t window,
                              quip_stream_t stream);
+/* ---- the same for a RAGGED batch of chunks: several slots of a batched cache continued in one launch ---------------
+ * The `rows` rows of q / k / v / out are nseg segments of consecutive rows; segment s has seg_rows[s] rows and continues
+ * slot seg_slot[s] of the batched cache at position pos[seg_slot[s]] (pos: `batch` device int64 counters, read by the
+ * launch).  seg_slot / seg_rows are HOST arrays of nseg entries, copied into the kernel arguments by this call.
+ *   q / out [rows, heads, head_dim], k / v [rows, kv_heads, head_dim] fp16, token major (k pre-rope)
+ *   cos / sin [max_len, head_dim] fp32; kcache / vcache [batch, kv_heads, max_len, head_dim] fp16; pos [batch] int64
+ * Segment s's out rows and the cache rows of its slot are bit identical to quip_rope_attn_chunk_f16 on that segment
+ * alone (its q / k / v / out rows, pos + seg_slot[s], the slot's cache slice), whatever the other segments are and in
+ * whatever order they come; slots that are not named are not touched.  The range rule is per segment:
+ * pos[slot] < 0 or pos[slot] + seg_rows[s] > max_len appends nothing to that slot and makes that segment's out rows
+ * NaN, the other segments are unaffected.
+ * nseg in 1 .. QUIP_RAGGED_MAX_SEGMENTS, every seg_rows[s] >= 1 with sum == rows, every slot in [0, batch) and named
+ * once, max_len >= 1, heads % kv_heads == 0, window >= 0 (else QUIP_ERR_BAD_SHAPE); head_dim 64 or 128, at most 65535
+ * query tiles (sum of ceil(seg_rows[s] / 64)) (else QUIP_ERR_UNSUPPORTED); all tensors 16-byte aligned, pos 8-byte
+ * (else QUIP_ERR_MISALIGNED). */
+#define QUIP_RAGGED_MAX_SEGMENTS 32
+int quip_rope_attn_ragged_f16(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                              const int64_t* pos, void* kcache, void* vcache, void* out, int32_t rows, int32_t heads,
+                              int32_t kv_heads, int32_t head_dim, int32_t max_len, int32_t batch,
+                              const int32_t* seg_slot, const int32_t* seg_rows, int32_t nseg, float scale,
+                              int32_t window, quip_stream_t stream);
 /* Greedy tail over `batch` rows of n fp16 logits (row-major, [batch, n]): tok[b] = first index of the largest logit of
  * row b (torch.argmax's tie rule; an all-NaN / all -inf row gives 0), pos[b] += 1 -- one workgroup per row. */
 int quip_argmax_step_batched_f16(const void* logits, int32_t batch, int32_t n, void* tok, void* pos,

@@ -9,7 +9,9 @@ the greedy tail picks B tokens in one launch (quip_lib::argmax_step_batched).
 
 Slots are independent: `fill_slot(b, prompt)` restarts slot b (its prompt pass writes only slot b's cache) and
 `extend_slot(b, tokens)` appends to it while the others keep their state, which is all continuous batching needs from
-the decoder."""
+the decoder.  `fill_slots` / `extend_slots` do the same for SEVERAL slots in one ragged prompt pass: the rows of all
+prompts go through every block together and attention is one quip_lib::rope_attn_ragged launch per block
+(csrc/ragged_attn.hip.h), so B short prompts cost ceil(sum of lengths / chunk) passes instead of B."""
 import math
 from functools import partial
 
@@ -17,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from . import capi
+from . import ragged_attn as _ragged_attn
 from . import register_lib as _R
 from .decode import PROJECTIONS, capture_graph
 from .qlinear import QuantLinear
@@ -85,6 +88,48 @@ try:
     _R._reg_fake("argmax_step_batched", lambda logits, tok, pos: None)
 except RuntimeError:
     pass
+
+
+def plan_ragged_passes(lengths, chunk, max_segments=_ragged_attn.MAX_SEGMENTS):
+    """Split segments of `lengths[s]` tokens into prompt passes of at most `chunk` rows and `max_segments` segments:
+    -> [[(segment, start, rows), ...], ...].  Segments are taken in order; one that does not fit the pass's remaining
+    budget is split there and continues in the next pass.  So a segment appears at most once per pass, its pieces are
+    consecutive and in order, every token is covered exactly once and no pass is empty.  Pure host arithmetic."""
+    chunk, max_segments = int(chunk), int(max_segments)
+    if chunk < 1 or max_segments < 1:
+        raise ValueError(f"plan_ragged_passes: chunk {chunk}, max_segments {max_segments} (both >= 1)")
+    passes, cur, room = [], [], chunk
+    for s, n in enumerate(lengths):
+        start, n = 0, int(n)
+        while start < n:
+            if room == 0 or len(cur) == max_segments:
+                passes.append(cur)
+                cur, room = [], chunk
+            rows = min(n - start, room)
+            cur.append((s, start, rows))
+            start, room = start + rows, room - rows
+    if cur:
+        passes.append(cur)
+    return passes
+
+
+def _check_ragged(dec, slots, token_lists, what):
+    """what extend_slots / fill_slots refuse, before anything is written -> (slots, 1-D id tensors on the device)"""
+    slots = [int(b) for b in slots]
+    token_lists = list(token_lists)
+    if len(slots) != len(token_lists):
+        raise ValueError(f"{what}: {len(slots)} slots for {len(token_lists)} token lists (length mismatch)")
+    if len(set(slots)) != len(slots):
+        raise ValueError(f"{what}: a duplicate slot in {slots} (one launch continues a slot once)")
+    for b in slots:
+        if not 0 <= b < dec.batch:
+            raise ValueError(f"{what}: slot {b} of {dec.batch} is out of range")
+    toks = [torch.as_tensor(t, dtype=torch.long, device=dec.dev).reshape(-1) for t in token_lists]
+    if any(t.numel() < 1 for t in toks):
+        raise ValueError(f"{what}: an empty token list")
+    if dec.s.head_dim not in (64, 128):
+        raise NotImplementedError(f"head_dim {dec.s.head_dim}: the ragged attention launch serves 64 and 128")
+    return slots, toks
 
 
 class BatchDecoder:
@@ -182,6 +227,57 @@ class BatchDecoder:
         return self.parent.extend(tokens, chunk=chunk, kv=(self.kcache[:, b], self.vcache[:, b]), pos=self.pos[b:b + 1])
 
     @torch.no_grad()
+    def extend_slots(self, slots, token_lists, chunk=512):
+        """extend_slot for several slots in one ragged prompt pass: token_lists[j] (>= 1 ids) is appended behind
+        pos[slots[j]] in that slot's cache (distinct slots), the positions advance on the device, slots that are not
+        named keep cache, tok and pos bit for bit.  The rows of all lists run through every block together, in passes
+        of at most `chunk` rows (plan_ragged_passes); per block and pass the attention is ONE launch
+        (quip_lib::rope_attn_ragged: per segment the bits of rope_attn_chunk).  Nothing reads pos on the host.  Tokens
+        that do not fit a slot's max_len append nothing and give that slot NaN logits (the launch's range rule, per
+        segment).  Returns the last-token logits of every list, (len(slots), vocab), in the order of `slots`."""
+        chunk = int(chunk)
+        slots, toks = _check_ragged(self, slots, token_lists, "extend_slots")
+        if chunk < 1:
+            raise ValueError(f"extend_slots: chunk {chunk} < 1")
+        p, s = self.parent, self.s
+        last = [None] * len(slots)
+        for pieces in plan_ragged_passes([t.numel() for t in toks], chunk):
+            seg_slot, seg_rows = [slots[j] for j, _, _ in pieces], [r for _, _, r in pieces]
+            n = sum(seg_rows)
+
+            def attend(i, q, k, v):
+                return torch.ops.quip_lib.rope_attn_ragged(
+                    q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim), v.view(n, s.kv_heads, s.head_dim),
+                    self.cos, self.sin, self.pos, seg_slot, seg_rows, self.kcache[i], self.vcache[i],
+                    self.window).reshape(n, s.hidden)
+            h = p.embed[torch.cat([toks[j][a:a + r] for j, a, r in pieces])]      # (n, hidden)
+            for i, L in enumerate(p.layers):
+                h = p._block(L, h, partial(attend, i))
+            self.pos.index_add_(0, torch.tensor(seg_slot, dtype=torch.long, device=self.dev),
+                                torch.tensor(seg_rows, dtype=torch.long, device=self.dev))
+            row = 0
+            for j, a, r in pieces:
+                row += r
+                if a + r == toks[j].numel():
+                    last[j] = h[row - 1]
+        return F.rms_norm(torch.stack(last), (s.hidden,), p.final_norm, s.rms_eps) @ p.lm_head.T
+
+    @torch.no_grad()
+    def fill_slots(self, slots, prompts):
+        """fill_slot for several slots at once: every named slot restarts on its prompt (>= 1 ids) -- pos zeroed on the
+        device, all but the last token of every prompt through ONE extend_slots call (one-token prompts contribute no
+        segment), the last token becomes tok[slot]; the other slots keep their state"""
+        slots, prompts = _check_ragged(self, slots, prompts, "fill_slots")
+        if not slots:
+            return
+        idx = torch.tensor(slots, dtype=torch.long, device=self.dev)
+        self.pos.index_fill_(0, idx, 0)
+        longer = [j for j, pr in enumerate(prompts) if pr.numel() > 1]
+        if longer:
+            self.extend_slots([slots[j] for j in longer], [prompts[j][:-1] for j in longer])
+        self.tok.index_copy_(0, idx, torch.stack([pr[-1] for pr in prompts]))
+
+    @torch.no_grad()
     def fill_slot(self, b, prompt):
         """restart slot b on `prompt` (>= 1 ids): all but its last token through prefill_slot, the last one becomes
         tok[b]; the other slots keep their state"""
@@ -209,8 +305,10 @@ class BatchDecoder:
         return out
 
     @torch.no_grad()
-    def generate(self, prompts, n_tokens, use_graph=True, temperature=None, top_k=None):
-        """decode n_tokens for each of the B prompts (1-D ids, ragged lengths >= 1) -> (B, n_tokens) token ids"""
+    def generate(self, prompts, n_tokens, use_graph=True, temperature=None, top_k=None, ragged=False):
+        """decode n_tokens for each of the B prompts (1-D ids, ragged lengths >= 1) -> (B, n_tokens) token ids.
+        ragged: fill all slots with one fill_slots call (the ragged prompt pass on the chunk-attention route: equivalent
+        to the slot-by-slot passes, not bit equal) instead of one fill_slot per prompt"""
         prompts = [torch.as_tensor(pr, dtype=torch.long, device=self.dev).reshape(-1) for pr in prompts]
         if len(prompts) != self.batch:
             raise ValueError(f"{len(prompts)} prompts for {self.batch} slots")
@@ -221,6 +319,9 @@ class BatchDecoder:
         if use_graph and self.graph is None:
             self.capture()
         self.reset()
-        for b, pr in enumerate(prompts):
-            self.fill_slot(b, pr)
+        if ragged:
+            self.fill_slots(range(self.batch), prompts)
+        else:
+            for b, pr in enumerate(prompts):
+                self.fill_slot(b, pr)
         return self.decode(n_tokens, use_graph)

@@ -701,6 +701,20 @@ int quip_rope_attn_chunk_f16(const void* q, const void* k, const void* v, const 
                                 scale, window, (hipStream_t)stream);
 }
 
+int quip_rope_attn_ragged_f16(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                              const int64_t* pos, void* kcache, void* vcache, void* out, int32_t rows, int32_t heads,
+                              int32_t kv_heads, int32_t head_dim, int32_t max_len, int32_t batch,
+                              const int32_t* seg_slot, const int32_t* seg_rows, int32_t nseg, float scale,
+                              int32_t window, quip_stream_t stream) {
+  if (!q || !k || !v || !cos || !sin || !pos || !kcache || !vcache || !out || !seg_slot || !seg_rows)
+    return QUIP_ERR_NULL_POINTER;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kcache) || !aligned16(vcache) || !aligned16(out) ||
+      !aligned16(cos) || !aligned16(sin) || (reinterpret_cast<uintptr_t>(pos) & 7))
+    return QUIP_ERR_MISALIGNED;
+  return rope_attn_ragged_launch(q, k, v, cos, sin, pos, kcache, vcache, out, rows, heads, kv_heads, head_dim, max_len,
+                                 batch, seg_slot, seg_rows, nseg, scale, window, (hipStream_t)stream);
+}
+
 int quip_argmax_step_batched_f16(const void* logits, int32_t batch, int32_t n, void* tok, void* pos,
                                  quip_stream_t stream) {
   if (!logits || !tok || !pos) return QUIP_ERR_NULL_POINTER;

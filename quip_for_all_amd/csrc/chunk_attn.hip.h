@@ -70,8 +70,11 @@ __device__ __forceinline__ cf16x4 lds_read_tr16(const unsigned char* p) {
   return __builtin_bit_cast(cf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_ptr)(uintptr_t)p));
 }
 
+// One (64-row query tile, head) of a chunk: the whole body of the launch.  `tile` is the query tile inside the chunk
+// `a` describes (wave uniform).  Shared, inlined, by rope_attn_chunk_kernel and the ragged launch (ragged_attn.hip.h),
+// which points `a` at one segment of its rows first.
 template <int HD>
-__global__ __launch_bounds__(kChunkThreads) void rope_attn_chunk_kernel(ChunkArgs a) {
+__device__ __forceinline__ void chunk_tile_body(const ChunkArgs& a, const int tile) {
   constexpr int NCH = HD / 8;                       // 16-byte chunks per row
   constexpr int KROW = HD * 2, VROW = HD * 2 + 64;  // bytes per K / V row in LDS
   constexpr int NIT = kChunkTile * NCH / kChunkThreads;
@@ -79,7 +82,7 @@ __global__ __launch_bounds__(kChunkThreads) void rope_attn_chunk_kernel(ChunkArg
   __shared__ __attribute__((aligned(16))) unsigned char s_k[kChunkTile * KROW];
   __shared__ __attribute__((aligned(16))) unsigned char s_v[kChunkTile * VROW];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h = blockIdx.x, i0 = (a.tile0 + (int)blockIdx.y) * kChunkTile;
+  const int h = blockIdx.x, i0 = tile * kChunkTile;
   const int nrow = min(kChunkTile, a.rows - i0);
   const int group = a.heads / a.kv_heads, kvh = h / group;
   const long long pos64 = *a.pos;
@@ -244,6 +247,11 @@ __global__ __launch_bounds__(kChunkThreads) void rope_attn_chunk_kernel(ChunkArg
         *reinterpret_cast<uint2*>(orow + 32 * db + 8 * gq + 4 * hh) = w;
       }
   }
+}
+
+template <int HD>
+__global__ __launch_bounds__(kChunkThreads) void rope_attn_chunk_kernel(ChunkArgs a) {
+  chunk_tile_body<HD>(a, a.tile0 + (int)blockIdx.y);
 }
 
 }  // namespace

@@ -492,3 +492,4 @@ int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, 
 
 // the prompt-side launch: rope + cache append + causal attention for a chunk of rows (uses rope8 above)
 #include "chunk_attn.hip.h"
+#include "ragged_attn.hip.h"

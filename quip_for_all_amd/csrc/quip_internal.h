@@ -193,6 +193,12 @@ int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, 
 int rope_attn_chunk_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
                            const int64_t* pos, void* kcache, void* vcache, void* out, int rows, int heads, int kv_heads,
                            int head_dim, int max_len, float scale, int window, hipStream_t stream);
+// ragged_attn.hip.h (in decode_glue.hip): the same for nseg segments of the rows, segment s continuing slot seg_slot[s] of a
+// batched cache at pos[seg_slot[s]]; seg_slot / seg_rows are host arrays
+int rope_attn_ragged_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                            const int64_t* pos, void* kcache, void* vcache, void* out, int rows, int heads, int kv_heads,
+                            int head_dim, int max_len, int batch, const int32_t* seg_slot, const int32_t* seg_rows,
+                            int nseg, float scale, int window, hipStream_t stream);
 // persistent decode engine, stage 1 (decode_engine.hip): GEMV[gate, up] -> output transforms -> SiLU product ->
 // input transform of down -> GEMV[down] of one decoder block in one launch
 struct FfnEngineArgs {

@@ -1,0 +1,94 @@
+// The chunk attention launch (chunk_attn.hip.h, included just before this file by decode_glue.hip) for a RAGGED batch of
+// chunks: S segments of consecutive rows of token-major q / k / v / out, segment s = seg_rows[s] rows that continue
+// slot seg_slot[s] of a batched cache (B, kv_heads, max_len, HD) at the position the launch reads from pos[seg_slot[s]]
+// (pos: the (B,) device counters of the batched decoder).  Per segment: rotary embedding, append to that slot's cache,
+// causal (and windowed) attention over that slot's rows [0, pos + rows) -- chunk_tile_body, the code of
+// rope_attn_chunk_kernel, unchanged.
+//
+// Grid (heads, sum_s ceil(seg_rows[s] / 64)): one workgroup per (64-row query tile of ONE segment, head); query tiles
+// are per segment and never span two sequences.  The segment table (slot, first row, rows; <= kRaggedMaxSegments
+// entries) travels by value in the kernel arguments: no device table, no host read of pos.  A workgroup finds its
+// segment by scanning the cumulative tile counts (wave uniform, <= 32 steps, scalar loads from the argument segment),
+// moves q / k / v / out to the segment's first row, kcache / vcache to the slot's slice and pos to the slot's entry,
+// and runs the tile code.
+//
+// The two rules of chunk_attn.hip.h across segments:
+//   (1) No workgroup reads a cache row another workgroup of the launch writes: within a segment by the chunk launch's
+//       argument; across segments because the slots of one launch are DISTINCT (the host check refuses a slot named
+//       twice), so two segments never touch the same cache slice.
+//   (2) A row's result depends on its own q and on its slot's cache rows <= its position only.  Hence the oracle:
+//       segment s's out rows and cache rows are bit identical to rope_attn_chunk run on that segment alone against
+//       that slot's cache slice -- whatever the other segments are and in whatever order they come.
+// Range rule, per segment: pos[slot] < 0 or pos[slot] + seg_rows[s] > max_len -> nothing is appended to that slot and
+// that segment's out rows are NaN; every other segment is unaffected.
+#pragma once
+
+namespace quip {
+namespace {
+
+constexpr int kRaggedMaxSegments = QUIP_RAGGED_MAX_SEGMENTS;
+
+struct RaggedArgs {
+  ChunkArgs c;     // q / k / v / out at row 0 of the pass, kcache / vcache at slot 0, pos at entry 0; rows / tile0 unused
+  int nseg;
+  int slot[kRaggedMaxSegments], row0[kRaggedMaxSegments], rows[kRaggedMaxSegments];
+};
+
+template <int HD>
+__global__ __launch_bounds__(kChunkThreads) void rope_attn_ragged_kernel(RaggedArgs ra) {
+  // the segment of query tile blockIdx.y: the host made gridDim.y the total tile count, so the scan ends inside the table
+  int s = 0, t0 = 0;
+  for (; s < ra.nseg - 1; ++s) {
+    const int n = (ra.rows[s] + kChunkTile - 1) / kChunkTile;
+    if ((int)blockIdx.y < t0 + n) break;
+    t0 += n;
+  }
+  const int slot = ra.slot[s];
+  const size_t r0 = (size_t)ra.row0[s], slice = (size_t)slot * ra.c.kv_heads * ra.c.max_len * HD;
+  ChunkArgs a = ra.c;
+  a.q += r0 * a.heads * HD;
+  a.out += r0 * a.heads * HD;
+  a.k += r0 * a.kv_heads * HD;
+  a.v += r0 * a.kv_heads * HD;
+  a.kcache += slice;
+  a.vcache += slice;
+  a.pos += slot;
+  a.rows = ra.rows[s];
+  chunk_tile_body<HD>(a, (int)blockIdx.y - t0);
+}
+
+}  // namespace
+
+int rope_attn_ragged_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                            const int64_t* pos, void* kcache, void* vcache, void* out, int rows, int heads, int kv_heads,
+                            int head_dim, int max_len, int batch, const int32_t* seg_slot, const int32_t* seg_rows,
+                            int nseg, float scale, int window, hipStream_t stream) {
+  if (nseg < 1 || nseg > kRaggedMaxSegments || rows < 1 || max_len < 1 || batch < 1 || heads < 1 || kv_heads < 1 ||
+      heads % kv_heads != 0 || window < 0)
+    return QUIP_ERR_BAD_SHAPE;
+  RaggedArgs ra{};
+  long long total = 0, tiles = 0;
+  for (int s = 0; s < nseg; ++s) {
+    if (seg_rows[s] < 1 || seg_slot[s] < 0 || seg_slot[s] >= batch) return QUIP_ERR_BAD_SHAPE;
+    for (int t = 0; t < s; ++t)
+      if (seg_slot[t] == seg_slot[s]) return QUIP_ERR_BAD_SHAPE;     // rule (1) needs distinct slots
+    if (total + seg_rows[s] > rows) return QUIP_ERR_BAD_SHAPE;
+    ra.slot[s] = seg_slot[s];
+    ra.row0[s] = (int)total;
+    ra.rows[s] = seg_rows[s];
+    total += seg_rows[s];
+    tiles += (seg_rows[s] - 1) / kChunkTile + 1;
+  }
+  if (total != rows) return QUIP_ERR_BAD_SHAPE;
+  if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
+  if (tiles > kChunkMaxTilesY) return QUIP_ERR_UNSUPPORTED;           // callers chunk their passes
+  ra.c = ChunkArgs{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
+                   cos, sin, pos, reinterpret_cast<f16*>(kcache), reinterpret_cast<f16*>(vcache),
+                   reinterpret_cast<f16*>(out), 0, 0, heads, kv_heads, max_len, window, scale};
+  ra.nseg = nseg;
+  const dim3 grid(heads, (unsigned)tiles);
+  return head_dim == 128 ? launch<rope_attn_ragged_kernel<128>>(grid, dim3(kChunkThreads), 0, stream, ra)
+                         : launch<rope_attn_ragged_kernel<64>>(grid, dim3(kChunkThreads), 0, stream, ra);
+}
+
+}  // namespace quip
