@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 12
+#define QUIP_ABI_VERSION 13
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -506,6 +506,24 @@ int quip_rope_attn_ragged_f16(const void* q, const void* k, const void* v, const
  * row b (torch.argmax's tie rule; an all-NaN / all -inf row gives 0), pos[b] += 1 -- one workgroup per row. */
 int quip_argmax_step_batched_f16(const void* logits, int32_t batch, int32_t n, void* tok, void* pos,
                                  quip_stream_t stream);
+
+/* ---- scoring tail: what a perplexity / log-likelihood needs of `rows` rows of n fp16 logits, one launch ---------------
+ *   logits [rows, n] fp16 row-major, contiguous; target [rows] int64 on the device
+ *   logprob [rows] fp32; lse [rows] fp32 or NULL; argmax [rows] int64 or NULL
+ * Per row r, in fp32 and without an fp32 copy of the logits (one workgroup per row; rows of an odd n are read with 2-byte
+ * loads and give the same bits):
+ *   lse[r]     = log sum_i exp(x[r][i])  (maximum first, then the sum of exp(x - max))
+ *   logprob[r] = x[r][target[r]] - lse[r];  target[r] < 0 ("not scored", HF's -100 included): exactly 0.0f;
+ *                target[r] >= n: NaN, nothing is read out of range
+ *   argmax[r]  = first index of the largest logit (torch.argmax's tie rule); a row without one gives 0
+ * A NaN in the row gives lse NaN, a +inf gives lse +inf, a row of all -inf gives lse -inf (torch.logsumexp's answers),
+ * and a row whose lse is not finite has logprob NaN for every target >= 0.
+ * Which thread adds which logit does not depend on the row's address or on `rows`: row r of a call has the bits of a
+ * call on that row alone.  |lse - exact| <= 1.3e-5 + 2^-23 |lse| up to n = 152064 (csrc/nll_rows.hip.h).
+ * rows >= 1 and 1 <= n <= 2^30 (else QUIP_ERR_BAD_SHAPE); logits 2-byte, logprob / lse 4-byte, target / argmax 8-byte
+ * aligned (else QUIP_ERR_MISALIGNED). */
+int quip_nll_rows_f16(const void* logits, int32_t rows, int32_t n, const int64_t* target, float* logprob, float* lse,
+                      int64_t* argmax, quip_stream_t stream);
 
 /* Which kernel a bs=1 E8P12 GEMV launch of `count` matrices (ns[i] rows, common k) is dispatched to by default, without
  * launching anything: 1 = e8p_gemv_mfma_kernel, 2 = e8p_gemv_v2_kernel (needs the workspace of the *_ws entry points when

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 from . import capi
 from . import ragged_attn as _ragged_attn
 from . import register_lib as _R
+from . import score as _score
 from .decode import PROJECTIONS, capture_graph
 from .qlinear import QuantLinear
 
@@ -132,6 +133,36 @@ def _check_ragged(dec, slots, token_lists, what):
     return slots, toks
 
 
+def _check_passes(dec, what, slots, token_lists, chunk):
+    """the argument checks of extend_slots / score_slots -> (slots, 1-D id tensors on the device)"""
+    slots, toks = _check_ragged(dec, slots, token_lists, what)
+    if int(chunk) < 1:
+        raise ValueError(f"{what}: chunk {int(chunk)} < 1")
+    return slots, toks
+
+
+def _ragged_passes(dec, slots, toks, chunk, on_pass):
+    """the pass loop of extend_slots() / score_slots() on checked arguments: per pass of plan_ragged_passes every block
+    over the pass's rows and the positions advanced on the device; on_pass(pieces, h) gets the pass's pieces
+    [(list, start, rows)] and its hidden rows h (n, hidden)"""
+    p, s = dec.parent, dec.s
+    for pieces in plan_ragged_passes([t.numel() for t in toks], int(chunk)):
+        seg_slot, seg_rows = [slots[j] for j, _, _ in pieces], [r for _, _, r in pieces]
+        n = sum(seg_rows)
+
+        def attend(i, q, k, v):
+            return torch.ops.quip_lib.rope_attn_ragged(
+                q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim), v.view(n, s.kv_heads, s.head_dim),
+                dec.cos, dec.sin, dec.pos, seg_slot, seg_rows, dec.kcache[i], dec.vcache[i],
+                dec.window).reshape(n, s.hidden)
+        h = p.embed[torch.cat([toks[j][a:a + r] for j, a, r in pieces])]      # (n, hidden)
+        for i, L in enumerate(p.layers):
+            h = p._block(L, h, partial(attend, i))
+        dec.pos.index_add_(0, torch.tensor(seg_slot, dtype=torch.long, device=dec.dev),
+                            torch.tensor(seg_rows, dtype=torch.long, device=dec.dev))
+        on_pass(pieces, h)
+
+
 class BatchDecoder:
     """B sequences decoded in lockstep on the modules of a LlamaDecoder (see the module docstring).
 
@@ -235,32 +266,48 @@ class BatchDecoder:
         (quip_lib::rope_attn_ragged: per segment the bits of rope_attn_chunk).  Nothing reads pos on the host.  Tokens
         that do not fit a slot's max_len append nothing and give that slot NaN logits (the launch's range rule, per
         segment).  Returns the last-token logits of every list, (len(slots), vocab), in the order of `slots`."""
-        chunk = int(chunk)
-        slots, toks = _check_ragged(self, slots, token_lists, "extend_slots")
-        if chunk < 1:
-            raise ValueError(f"extend_slots: chunk {chunk} < 1")
-        p, s = self.parent, self.s
+        slots, toks = _check_passes(self, "extend_slots", slots, token_lists, chunk)
         last = [None] * len(slots)
-        for pieces in plan_ragged_passes([t.numel() for t in toks], chunk):
-            seg_slot, seg_rows = [slots[j] for j, _, _ in pieces], [r for _, _, r in pieces]
-            n = sum(seg_rows)
 
-            def attend(i, q, k, v):
-                return torch.ops.quip_lib.rope_attn_ragged(
-                    q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim), v.view(n, s.kv_heads, s.head_dim),
-                    self.cos, self.sin, self.pos, seg_slot, seg_rows, self.kcache[i], self.vcache[i],
-                    self.window).reshape(n, s.hidden)
-            h = p.embed[torch.cat([toks[j][a:a + r] for j, a, r in pieces])]      # (n, hidden)
-            for i, L in enumerate(p.layers):
-                h = p._block(L, h, partial(attend, i))
-            self.pos.index_add_(0, torch.tensor(seg_slot, dtype=torch.long, device=self.dev),
-                                torch.tensor(seg_rows, dtype=torch.long, device=self.dev))
+        def keep(pieces, h):
             row = 0
             for j, a, r in pieces:
                 row += r
                 if a + r == toks[j].numel():
                     last[j] = h[row - 1]
-        return F.rms_norm(torch.stack(last), (s.hidden,), p.final_norm, s.rms_eps) @ p.lm_head.T
+        _ragged_passes(self, slots, toks, chunk, keep)
+        return F.rms_norm(torch.stack(last), (self.s.hidden,), self.parent.final_norm, self.s.rms_eps) @ self.parent.lm_head.T
+
+    @torch.no_grad()
+    def score_slots(self, slots, token_lists, targets=None, chunk=512):
+        """extend_slots that scores its tokens (LlamaDecoder.score for several slots in the ragged passes): token_lists[j]
+        is appended behind pos[slots[j]] exactly as extend_slots appends it -- same passes, same launches, the slots that
+        are not named keep cache, tok and pos bit for bit -- and after each pass ALL its rows take the final norm, the
+        lm_head product and the scoring tail (quip_lib::nll_rows).  Row i of list j is scored against targets[j][i];
+        the default is the list's own next token, the last row not scored (-1 -> exactly 0).  Argument errors are
+        extend_slots's, raised before anything is written.  Returns (logprobs, argmaxes): per list one (len_j,) fp32
+        and one (len_j,) int64 tensor on the device, in the order of `slots`."""
+        slots, toks = _check_passes(self, "score_slots", slots, token_lists, chunk)
+        if targets is None:
+            tgts = [_score.shifted_targets(t) for t in toks]
+        else:
+            tgts = [torch.as_tensor(t, dtype=torch.long, device=self.dev).reshape(-1) for t in targets]
+            if [t.numel() for t in tgts] != [t.numel() for t in toks]:
+                raise ValueError("score_slots: every token list needs a target list of its own length")
+        p, s = self.parent, self.s
+        lps = [torch.empty(t.numel(), dtype=torch.float32, device=self.dev) for t in toks]
+        ams = [torch.empty(t.numel(), dtype=torch.long, device=self.dev) for t in toks]
+
+        def tail(pieces, h):
+            logits = F.rms_norm(h, (s.hidden,), p.final_norm, s.rms_eps) @ p.lm_head.T
+            lp, am = _score.score_tail(logits, torch.cat([tgts[j][a:a + r] for j, a, r in pieces]))
+            row = 0
+            for j, a, r in pieces:
+                lps[j][a:a + r] = lp[row:row + r]
+                ams[j][a:a + r] = am[row:row + r]
+                row += r
+        _ragged_passes(self, slots, toks, chunk, tail)
+        return lps, ams
 
     @torch.no_grad()
     def fill_slots(self, slots, prompts):

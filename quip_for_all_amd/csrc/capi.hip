@@ -723,6 +723,16 @@ int quip_argmax_step_batched_f16(const void* logits, int32_t batch, int32_t n, v
   return argmax_step_batched_launch(logits, batch, n, tok, pos, (hipStream_t)stream);
 }
 
+int quip_nll_rows_f16(const void* logits, int32_t rows, int32_t n, const int64_t* target, float* logprob, float* lse,
+                      int64_t* argmax, quip_stream_t stream) {
+  if (!logits || !target || !logprob) return QUIP_ERR_NULL_POINTER;
+  if ((reinterpret_cast<uintptr_t>(logits) & 1) || (reinterpret_cast<uintptr_t>(target) & 7) ||
+      (reinterpret_cast<uintptr_t>(logprob) & 3) || (reinterpret_cast<uintptr_t>(lse) & 3) ||
+      (reinterpret_cast<uintptr_t>(argmax) & 7))
+    return QUIP_ERR_MISALIGNED;
+  return nll_rows_launch(logits, rows, n, target, logprob, lse, argmax, (hipStream_t)stream);
+}
+
 int quip_rope_attn_decode_z_supported(int32_t heads, int32_t kv_heads, int32_t head_dim) {
   return rope_attn_decode_z_supported(heads, kv_heads, head_dim) ? 1 : 0;
 }

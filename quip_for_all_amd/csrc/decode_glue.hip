@@ -493,3 +493,5 @@ int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, 
 // the prompt-side launch: rope + cache append + causal attention for a chunk of rows (uses rope8 above)
 #include "chunk_attn.hip.h"
 #include "ragged_attn.hip.h"
+// the scoring tail: log-sum-exp, target log-probability and arg-max of every row of a chunk's logits
+#include "nll_rows.hip.h"

@@ -199,6 +199,10 @@ int rope_attn_ragged_launch(const void* q, const void* k, const void* v, const f
                             const int64_t* pos, void* kcache, void* vcache, void* out, int rows, int heads, int kv_heads,
                             int head_dim, int max_len, int batch, const int32_t* seg_slot, const int32_t* seg_rows,
                             int nseg, float scale, int window, hipStream_t stream);
+// nll_rows.hip.h (in decode_glue.hip): per row of (rows, n) fp16 logits the log-sum-exp, the log-probability of target[row] and
+// the arg-max; lse / argmax may be null
+int nll_rows_launch(const void* logits, int rows, int n, const int64_t* target, float* logprob, float* lse,
+                    int64_t* argmax, hipStream_t stream);
 // persistent decode engine, stage 1 (decode_engine.hip): GEMV[gate, up] -> output transforms -> SiLU product ->
 // input transform of down -> GEMV[down] of one decoder block in one launch
 struct FfnEngineArgs {

@@ -24,6 +24,7 @@ import torch.nn.functional as F
 
 from . import chunk_attn as _chunk_attn  # noqa: F401  (defines quip_lib::rope_attn_chunk)
 from . import register_lib as _R
+from . import score as _score  # (defines quip_lib::nll_rows)
 from . import token_tail as _token_tail  # noqa: F401  (defines quip_lib::block_engine_token)
 from .codebook import codebook_id
 from .qlinear import (QuantLinear, _engine_had3, chain_planes, chain_supported, ffn_engine, ffn_engine_ok, forward_group,
@@ -197,6 +198,36 @@ def capture_graph(warmup, body):
         out = body()
     torch.cuda.synchronize()
     return graph, out
+
+
+def _extend_chunks(dec, what, tokens, chunk, kv, pos, on_chunk):
+    """the chunk loop of extend() / score(): `tokens` behind the position in chunks of at most `chunk` rows, every block
+    over each chunk, the position advanced on the device; on_chunk(c0, h) gets the hidden rows h (n, hidden) of the
+    chunk that starts at token c0"""
+    s = dec.s
+    tokens = torch.as_tensor(tokens, dtype=torch.long, device=dec.dev).reshape(-1)
+    P, chunk = tokens.numel(), int(chunk)
+    if P < 1:
+        raise ValueError(f"{what}: an empty token list")
+    if chunk < 1:
+        raise ValueError(f"{what}: chunk {chunk} < 1")
+    if s.head_dim not in (64, 128):
+        raise NotImplementedError(f"head_dim {s.head_dim}: the chunk attention launch serves 64 and 128")
+    kcache, vcache = (dec.kcache, dec.vcache) if kv is None else kv
+    pos = dec.pos if pos is None else pos
+
+    def attend(i, q, k, v):
+        n, kc, vc = q.shape[0], kcache[i], vcache[i]
+        return torch.ops.quip_lib.rope_attn_chunk(
+            q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim), v.view(n, s.kv_heads, s.head_dim),
+            dec.cos[:kc.shape[1]], dec.sin[:kc.shape[1]], pos, kc, vc, dec.window).reshape(n, s.hidden)
+    for c0 in range(0, P, chunk):
+        n = min(chunk, P - c0)
+        h = dec.embed[tokens[c0:c0 + n]]                           # (n, hidden)
+        for i, L in enumerate(dec.layers):
+            h = dec._block(L, h, partial(attend, i))
+        pos.add_(n)
+        on_chunk(c0, h)
 
 
 class LlamaDecoder:
@@ -815,31 +846,66 @@ class LlamaDecoder:
         host, so the pass can be captured once and replayed at any position (extend_graph).  Tokens that do not fit
         (position + rows > max_len) write nothing and give NaN logits -- the launch's range rule is the guard.
         Returns the logits of the last token (1, vocab).  `kv` / `pos`: as in prefill()."""
+        last = [None]
+
+        def keep(c0, h):
+            last[0] = h
+        _extend_chunks(self, "extend", tokens, chunk, kv, pos, keep)
+        return F.rms_norm(last[0][-1:], (self.s.hidden,), self.final_norm, self.s.rms_eps) @ self.lm_head.T
+
+    @torch.no_grad()
+    def score(self, tokens, targets=None, chunk=512, kv=None, pos=None):
+        """extend() that scores its tokens: `tokens` go behind the current position exactly as extend() sends them (same
+        chunks, same launches, same cache rows and counter, `kv` / `pos` as there -- a cached context conditions the
+        scores), and after each chunk ALL its rows take the final norm, the lm_head product and the scoring tail
+        (quip_lib::nll_rows: no fp32 copy of the (chunk, vocab) logits).  Row i is scored against targets[i]; the
+        default is tokens[1:] followed by -1 -- a negative target means "not scored" and gives exactly 0.  Returns
+        (logprob, argmax), both (P,) on the device: log p(targets[i] | context, tokens[:i + 1]) in fp32 and the most
+        likely next token of every row.  Nothing is read on the host.  Tokens that do not fit max_len behave as in
+        extend(): their rows' logits are NaN, so scored rows give NaN.  QUIP_NLL_ROWS=0 swaps the tail for the torch
+        expression (score.nll_rows_torch), for A/B runs."""
         s = self.s
         tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
-        P, chunk = tokens.numel(), int(chunk)
-        if P < 1:
-            raise ValueError("extend: an empty token list")
-        if chunk < 1:
-            raise ValueError(f"extend: chunk {chunk} < 1")
-        if s.head_dim not in (64, 128):
-            raise NotImplementedError(f"head_dim {s.head_dim}: the chunk attention launch serves 64 and 128")
-        kcache, vcache = (self.kcache, self.vcache) if kv is None else kv
-        pos = self.pos if pos is None else pos
+        if tokens.numel() < 1:
+            raise ValueError("score: an empty token list")
+        targets = _score.shifted_targets(tokens) if targets is None else \
+            torch.as_tensor(targets, dtype=torch.long, device=self.dev).reshape(-1)
+        if targets.numel() != tokens.numel():
+            raise ValueError(f"score: {targets.numel()} targets for {tokens.numel()} tokens")
+        lps, ams = [], []
 
-        def attend(i, q, k, v):
-            n, kc, vc = q.shape[0], kcache[i], vcache[i]
-            return torch.ops.quip_lib.rope_attn_chunk(
-                q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim), v.view(n, s.kv_heads, s.head_dim),
-                self.cos[:kc.shape[1]], self.sin[:kc.shape[1]], pos, kc, vc, self.window).reshape(n, s.hidden)
-        h = None
-        for c0 in range(0, P, chunk):
-            n = min(chunk, P - c0)
-            h = self.embed[tokens[c0:c0 + n]]                           # (n, hidden)
-            for i, L in enumerate(self.layers):
-                h = self._block(L, h, partial(attend, i))
-            pos.add_(n)
-        return F.rms_norm(h[-1:], (s.hidden,), self.final_norm, s.rms_eps) @ self.lm_head.T
+        def tail(c0, h):
+            logits = F.rms_norm(h, (s.hidden,), self.final_norm, s.rms_eps) @ self.lm_head.T
+            lp, am = _score.score_tail(logits, targets[c0:c0 + h.shape[0]])
+            lps.append(lp)
+            ams.append(am)
+        _extend_chunks(self, "score", tokens, chunk, kv, pos, tail)
+        return torch.cat(lps), torch.cat(ams)
+
+    @torch.no_grad()
+    def perplexity(self, tokens, window=2048, stride=None, chunk=512):
+        """Perplexity of `tokens` (1-D ids, >= 2) by the usual protocol (score.plan_score_windows): windows of at most
+        `window` tokens start every `stride` tokens (default: window, no overlap), each is scored from position 0 with
+        score(), and from the second window on only the rows no earlier window scored count -- the others are context.
+        The log-probabilities are summed in float64 on the device; the host reads the totals once, at the end.
+        -> {"nll_sum": -sum of log p, "n_scored": counted targets (len(tokens) - 1), "ppl": exp(nll_sum / n_scored),
+        "argmax_hits": counted rows whose most likely token is the target}.
+        Restores nothing: the cache and the position counter are left at the end of the last window."""
+        tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
+        plan = _score.plan_score_windows(tokens.numel(), window, stride, max_len=self.max_len)
+        total = torch.zeros((), dtype=torch.float64, device=self.dev)
+        hits = torch.zeros((), dtype=torch.long, device=self.dev)
+        n_scored = 0
+        for start, length, first in plan:
+            targets = tokens[start + 1:start + length + 1].clone()
+            targets[:first] = -1                                        # context rows: exactly 0, never a hit
+            self.pos.zero_()
+            lp, am = self.score(tokens[start:start + length], targets, chunk=chunk)
+            total -= lp.double().sum()
+            hits += (am == targets).sum()
+            n_scored += length - first
+        nll_sum, hits = float(total), int(hits)
+        return {"nll_sum": nll_sum, "n_scored": n_scored, "ppl": math.exp(nll_sum / n_scored), "argmax_hits": hits}
 
     @torch.no_grad()
     def extend_graph(self, tokens):
