@@ -1,0 +1,153 @@
+// Single-query attention over a KV cache: the arithmetic that rope_attn_decode_kernel (decode_glue.hip) and the attention
+// phases of the persistent launches (decode_block.hip, decode_block_gqa.hip) share bit for bit -- and, for rope8, the
+// prompt-side launches (chunk_attn.hip.h), whose cache rows are the decode launch's.  This is the one place of it: the
+// kernels keep their own walks over the cached rows (which rows a lane group visits, what is in flight) and call into this
+// file for what they do to a key, a state or a pair of states.  A few call sites spell a primitive out instead, each with a
+// remark at the site: update and both merges in rope_attn_decode_kernel, the merge of the head's parts in decode_block.hip
+// (DESIGN.md 4.10 lists them, profiles/attn_primitives_refactor.txt has the reasons).
+//
+// A head vector of HD fp16 is spread over LPK = HD / 8 lanes, 16 bytes (8 dims) per lane; such a lane group walks its
+// keys with an online-softmax state (m, l, acc[8]): running maximum, denominator, this lane's 8 unnormalised sums.
+#pragma once
+#include "had_device.hip.h"
+#include "quip_device.hip.h"
+
+namespace quip {
+namespace attn {
+
+__device__ __forceinline__ void unpack8h(const uint4& u, float o[8]) {
+  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const f16x2 h = as_f16x2(w[i]);
+    o[2 * i] = (float)h.x;
+    o[2 * i + 1] = (float)h.y;
+  }
+}
+
+// rotary embedding (HF half-rotation) of the 8 dims [d0, d0 + 8) of one head vector; result
+// rounded to fp16 like the eager graph does
+template <int HD>
+__device__ __forceinline__ void rope8(const f16* vec, const float c8[8], const float s8[8], int d0, float o[8]) {
+  float a[8], b[8];
+  unpack8h(*reinterpret_cast<const uint4*>(vec + d0), a);
+  const int dp = d0 < HD / 2 ? d0 + HD / 2 : d0 - HD / 2;
+  unpack8h(*reinterpret_cast<const uint4*>(vec + dp), b);
+  const float sgn = d0 < HD / 2 ? -1.f : 1.f;
+#pragma unroll
+  // x * cos + rot * sin with every operation rounded on its own, as the eager graph does (and so that the
+  // instantiations of the kernels cannot contract the expression differently: an fma in one of them moved single
+  // cache elements by one fp16 ulp)
+  // (had::fmul / fadd: compiled with contraction switched off; __fmul_rn and friends are plain operators to hipcc)
+  for (int i = 0; i < 8; ++i) o[i] = (float)(f16)had::fadd(had::fmul(a[i], c8[i]), had::fmul(sgn * b[i], s8[i]));
+}
+
+// one key against q: this lane's 8 products, then the lane group's sum on DPP moves (had::sum16_xor: the additions of
+// `s += __shfl_xor(s, o)`, o = 1, 2, 4, 8) -- every lane of the group holds the score
+template <int LPK>
+__device__ __forceinline__ float score(const float (&q8)[8], const float (&k8)[8]) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s = __builtin_fmaf(q8[i], k8[i], s);
+  return had::sum16_xor<LPK>(s);
+}
+
+// online-softmax step of one lane group's state with a key's score s and this lane's 8 values of its v row
+// (spelled out: left to the compiler, the instantiations of a kernel contract a * c + p * v differently -- one element in
+//  8192 moved by an ulp between the grouped-query prologue and the plain kernel)
+__device__ __forceinline__ void update(float& m, float& l, float (&acc)[8], float s, const float (&v8)[8]) {
+  const float mn = fmaxf(m, s);
+  const float c = __expf(m - mn), p = __expf(s - mn);
+  l = __builtin_fmaf(l, c, p);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = __builtin_fmaf(acc[i], c, had::fmul(p, v8[i]));
+  m = mn;
+}
+
+// Two lane groups of a wave merge their states in registers.  swap(x) hands every lane both partners' copies of x as
+// {[0], [1]} -- v_permlane16_swap / 32_swap of a value with ITSELF: (even row, odd row) / (lower half, upper half) -- so
+// both sides compute the same merged state and nobody selects.
+template <class Swap>
+__device__ __forceinline__ void merge2(float& m, float& l, float (&acc)[8], Swap swap) {
+  const auto tm = swap(as_u32(m)), tl = swap(as_u32(l));
+  const float mA = as_f32((uint32_t)tm[0]), mB = as_f32((uint32_t)tm[1]);
+  const float M = fmaxf(mA, mB);
+  const float wA = mA == -INFINITY ? 0.f : __expf(mA - M), wB = mB == -INFINITY ? 0.f : __expf(mB - M);
+  l = __builtin_fmaf(as_f32((uint32_t)tl[1]), wB, had::fmul(as_f32((uint32_t)tl[0]), wA));
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const auto ta = swap(as_u32(acc[i]));
+    acc[i] = __builtin_fmaf(as_f32((uint32_t)ta[1]), wB, had::fmul(as_f32((uint32_t)ta[0]), wA));
+  }
+  m = M;
+}
+
+// Weighted merge of N states (m_i, l_i, o_i), i in order, for ONE output dimension: the states of a workgroup's lane
+// groups or waves out of LDS, the partial states of a head's workgroups out of the workspace.  State i: m[i * ml_stride],
+// l[i * ml_stride], o[i * o_stride] (o: already moved to the caller's dimension).  (M, L, O) come in as (-inf, 0, 0).
+// A state that saw no key (m = -inf) has weight 0.
+template <int N>
+__device__ __forceinline__ void merge_states(const float* m, const float* l, int ml_stride, const float* o, int o_stride,
+                                             float& M, float& L, float& O) {
+  for (int i = 0; i < N; ++i) M = fmaxf(M, m[i * ml_stride]);
+  for (int i = 0; i < N; ++i) {
+    const float mi = m[i * ml_stride];
+    const float w = mi == -INFINITY ? 0.f : __expf(mi - M);
+    L = __builtin_fmaf(l[i * ml_stride], w, L);
+    O = __builtin_fmaf(o[i * o_stride], w, O);
+  }
+}
+
+// ---- the cached rows of a head in the persistent launches (decode_block.hip, decode_block_gqa.hip) ------------------------
+// A workgroup is part `part` of the `nparts` that share a head: it owns the positions part + nparts i below pos, i its
+// local index.  Lane group g of NG takes the local indices g + NG j; a ROUND is U of them, i0 + u NG, u < U, their 16-byte
+// pieces of the K and V rows in (kr, vr).  The kernels keep two rounds in flight and request a round two rounds ahead of
+// its use; that loop, and the new row behind it, are theirs.
+// Both structs hold references to the kernel's own variables and nothing else -- what its lambdas used to capture.
+template <int HD, int U, int NG>
+struct CachedRows {
+  const f16* const& kc;      // the KV head's rows, [max_len, HD]
+  const f16* const& vc;
+  const int& part;
+  const int& nparts;
+  const int& pos;
+  const int& d0;             // this lane's 8 dims
+  __device__ __forceinline__ int position(int i) const { return part + nparts * i; }      // of local index i
+  // request the round at local index i0 (a row at or past pos: row 0, never used).  Also called on its own, long before
+  // q exists.
+  __device__ __forceinline__ void load_round(uint4 (&kr)[U], uint4 (&vr)[U], int i0) const {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int t = position(i0 + u * NG);
+      const int tc = t < pos ? t : 0;
+      kr[u] = *reinterpret_cast<const uint4*>(kc + (size_t)tc * HD + d0);
+      vr[u] = *reinterpret_cast<const uint4*>(vc + (size_t)tc * HD + d0);
+    }
+  }
+};
+
+// One round against q: all of its scores first (independent chains), then the updates of the group's state in key order
+// -- the same operations on the same operands as key after key.
+template <int HD, int U, int NG>
+struct Round {
+  const CachedRows<HD, U, NG>& rows;
+  const float (&q8)[8];
+  float& m;
+  float& l;
+  float (&acc)[8];
+  __device__ __forceinline__ void operator()(const uint4 (&kr)[U], const uint4 (&vr)[U], int i0) const {
+    float k8[U][8], v8[U][8], sc[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      unpack8h(kr[u], k8[u]);
+      unpack8h(vr[u], v8[u]);
+      sc[u] = score<HD / 8>(q8, k8[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (rows.position(i0 + u * NG) < rows.pos) update(m, l, acc, sc[u], v8[u]);
+  }
+};
+
+}  // namespace attn
+}  // namespace quip

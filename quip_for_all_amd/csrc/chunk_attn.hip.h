@@ -1,4 +1,4 @@
-// Prompt-side counterpart of rope_attn_decode_kernel (decode_glue.hip, which includes this file behind rope8): rotary
+// Prompt-side counterpart of rope_attn_decode_kernel (decode_glue.hip, whose translation unit this file is part of): rotary
 // embedding, KV-cache append and causal softmax attention for a CHUNK of `rows` queries at positions [*pos, *pos + rows)
 // against cache rows [0, *pos + rows), one launch.  q / out are token major ([rows, heads, HD], what the projections
 // produce and o_proj consumes), the position is read on the device, so one captured launch serves every start position.
@@ -18,7 +18,7 @@
 //
 // Two rules shape the code:
 //   (1) No workgroup reads a cache row that another workgroup of the launch writes.  Keys below *pos come from the
-//       cache; keys of the chunk itself come from the k / v INPUTS and are rotated here by rope8 -- the bits of the
+//       cache; keys of the chunk itself come from the k / v INPUTS and are rotated here by attn::rope8 -- the bits of the
 //       cached row, as the decode launch takes key t == pos from registers.  Chunk row i is appended by exactly one
 //       workgroup: the first query head of its KV group in the query tile that holds row i (which stages that key
 //       anyway: a row attends to itself).
@@ -28,13 +28,16 @@
 //       rescale is unconditional and per row, and an MFMA output column depends on its own B column only.  So any
 //       split of a chunk into consecutive launches gives the same bits.
 //
-// Arithmetic: q and k rotated by rope8 and rounded to fp16 (the decode launch's cache rows, bit for bit); scores
+// Arithmetic: q and k rotated by attn::rope8 and rounded to fp16 (the decode launch's cache rows, bit for bit); scores
 // fp32, the softmax scale applied to them in fp32; running max / sum fp32; P rounded to fp16 for P V; fp32
 // accumulation; one rounding of the output to fp16.
 //
 // Range rule (the decode launch's, for the whole chunk): *pos < 0 or *pos + rows > max_len -> nothing is appended
 // and every out row is NaN.
 #pragma once
+#include "attn_query.hip.h"
+#include "launch.hip.h"
+#include "quip_device.hip.h"
 
 namespace quip {
 namespace {
@@ -118,7 +121,7 @@ __device__ __forceinline__ void chunk_tile_body(const ChunkArgs& a, const int ti
       float c8[8], s8[8], o[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) { c8[i] = cs[d0 + i]; s8[i] = sn[d0 + i]; }
-      rope8<HD>(qrow, c8, s8, d0, o);
+      attn::rope8<HD>(qrow, c8, s8, d0, o);
 #pragma unroll
       for (int i = 0; i < 8; ++i) qf[ks][i] = (f16)o[i];
     }
@@ -151,7 +154,7 @@ __device__ __forceinline__ void chunk_tile_body(const ChunkArgs& a, const int ti
           float c8[8], s8[8], o[8];
 #pragma unroll
           for (int x = 0; x < 8; ++x) { c8[x] = cs[x]; s8[x] = sn[x]; }
-          rope8<HD>(krow, c8, s8, c * 8, o);
+          attn::rope8<HD>(krow, c8, s8, c * 8, o);
           kk.x = pack_f16(o[0], o[1]); kk.y = pack_f16(o[2], o[3]);
           kk.z = pack_f16(o[4], o[5]); kk.w = pack_f16(o[6], o[7]);
           vv = *reinterpret_cast<const uint4*>(a.v + ((size_t)i * a.kv_heads + kvh) * HD + c * 8);

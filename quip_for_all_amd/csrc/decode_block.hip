@@ -29,6 +29,7 @@
 // Liveness: all 256 workgroups must be resident (one per CU by LDS footprint; nothing else may run on the device);
 // every wait is bounded and a launch that gives up leaves a code in ctl[1] (engine_sync.hip.h).
 #include "e8p_gemv_core.hip.h"
+#include "attn_query.hip.h"
 #include "engine_sync.hip.h"
 #include "fht_wg512x.hip.h"
 #include "token_tail.hip.h"
@@ -1069,18 +1070,11 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       const f16* vc = Ld.vcache + (size_t)kvh * a.max_len * HD;
       uint4 kr0[U], vr0[U], kr1[U], vr1[U];
       // local index i of this workgroup <-> position part + nparts i; a round = local indices i0 + u NG, u < U
-      auto load_round = [&](uint4 (&kr)[U], uint4 (&vr)[U], int i0) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int t = part + nparts * (i0 + u * NG);
-          const int tc = t < pos ? t : 0;
-          kr[u] = *reinterpret_cast<const uint4*>(kc + (size_t)tc * HD + d0);
-          vr[u] = *reinterpret_cast<const uint4*>(vc + (size_t)tc * HD + d0);
-        }
-      };
+      // (attn::CachedRows: references to these variables, nothing of its own)
+      const attn::CachedRows<HD, U, NG> rows{kc, vc, part, nparts, pos, d0};
       if (tid < ATH) {
-        load_round(kr0, vr0, g);
-        if (part + nparts * NG * U < pos) load_round(kr1, vr1, g + NG * U);
+        rows.load_round(kr0, vr0, g);
+        if (part + nparts * NG * U < pos) rows.load_round(kr1, vr1, g + NG * U);
       }
       // SV of this head's q / k / v values (waves 0..2 finish one vector each below): requested HERE, in front of the hand-off's
       // wait -- read at its use it was a memory latency on the heads' critical path
@@ -1184,32 +1178,15 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       BSTAMP(5);
       ++hop;                                           // hand-off inside the head's group (long contexts): partial states
       const uint32_t tagg = ebase | hop;
-      auto unpack8h = [](const uint4& u, float o[8]) {
-        const uint32_t ww[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const f16x2 hh = as_f16x2(ww[i]);
-          o[2 * i] = (float)hh.x;
-          o[2 * i + 1] = (float)hh.y;
-        }
-      };
-      auto rope8 = [&](const f16* vec, float o[8]) {
-        float x[8], y[8];
-        unpack8h(*reinterpret_cast<const uint4*>(vec + d0), x);
-        const int dp = d0 < HD / 2 ? d0 + HD / 2 : d0 - HD / 2;
-        unpack8h(*reinterpret_cast<const uint4*>(vec + dp), y);
-        const float sgn = d0 < HD / 2 ? -1.f : 1.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = (float)(f16)had::fadd(had::fmul(x[i], c8[i]), had::fmul(sgn * y[i], s8[i]));
-      };
       {
         const float* cs = reinterpret_cast<const float*>(smem + B::kCs);
 #pragma unroll
         for (int i = 0; i < 8; ++i) { c8[i] = cs[d0 + i]; s8[i] = cs[HD + d0 + i]; }
       }
       {
-      // single-query attention of head hd over positions [0, pos] (decode_glue.hip's arithmetic): 16 lanes per key,
-      // 16 key groups with their own online-softmax state, merged through LDS
+      // single-query attention of head hd over positions [0, pos]: 16 lanes per key, 16 key groups with their own
+      // online-softmax state, merged through LDS.  Every operation on a key or a state is attn_query.hip.h's (the arithmetic
+      // of decode_glue.hip, bit for bit); the loop over the rounds and what is in flight are this kernel's.
       float* s_m = reinterpret_cast<float*>(smem + B::kArea);
       float* s_l = s_m + NST;
       float* s_acc = s_l + NST;                        // [NST][HD + 4]
@@ -1217,32 +1194,14 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       float m = -INFINITY, lsum = 0.f, acc8[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) { acc8[i] = 0.f; kn[i] = 0.f; vn[i] = 0.f; }
-      // one key: score against q (16 lanes), online-softmax update of this group's state
-      // one key: score against q (16 lanes: the group's sum on DPP moves, had::sum16_xor), online-softmax update of this
-      // group's state.  A round scores all of its keys first (independent chains), then updates the state in key order:
-      // the same operations on the same operands as key after key.
-      auto score = [&](const float (&k8)[8]) -> float {
-        float sc = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sc = __builtin_fmaf(q8[i], k8[i], sc);
-        return had::sum16_xor(sc);
-      };
-      auto update = [&](float sc, const float (&v8)[8]) {
-        const float mn = fmaxf(m, sc);
-        const float cc = __expf(m - mn), pp = __expf(sc - mn);
-        lsum = __builtin_fmaf(lsum, cc, pp);          // (decode_glue.hip's arithmetic, spelled out there and here)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc8[i] = __builtin_fmaf(acc8[i], cc, had::fmul(pp, v8[i]));
-        m = mn;
-      };
       if (tid < ATH) {
-        rope8(s_qkv, q8);
+        attn::rope8<HD>(s_qkv, c8, s8, d0, q8);
 #pragma unroll
         for (int i = 0; i < 8; ++i) q8[i] *= a.attn_scale;
         {
-          rope8(s_qkv + HD, kn);
+          attn::rope8<HD>(s_qkv + HD, c8, s8, d0, kn);
           const uint4 vraw = *reinterpret_cast<const uint4*>(s_qkv + 2 * HD + d0);
-          unpack8h(vraw, vn);
+          attn::unpack8h(vraw, vn);
           if (g == 0 && pos_ok && (hd % GQH) == 0 && part == (split ? (pos & (kParts - 1)) : 0)) {   // append the new row (StaticCache.update): once per KV head
             uint4 kr;
             kr.x = pack_f16(kn[0], kn[1]); kr.y = pack_f16(kn[2], kn[3]);
@@ -1252,55 +1211,28 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
           }
         }
         ASTAMP(0);
-        // one round: positions t0 + u NG of this key group, rows in (kr, vr)
-        auto round = [&](const uint4 (&kr)[U], const uint4 (&vr)[U], int i0) {
-          float k8[U][8], v8[U][8], sc[U];
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const int t = part + nparts * (i0 + u * NG);
-            (void)t;
-            unpack8h(kr[u], k8[u]);
-            unpack8h(vr[u], v8[u]);
-            sc[u] = score(k8[u]);
-          }
-#pragma unroll
-          for (int u = 0; u < U; ++u)
-            if (part + nparts * (i0 + u * NG) < pos) update(sc[u], v8[u]);
-        };
+        const attn::Round<HD, U, NG> round{rows, q8, m, lsum, acc8};
         // (uniform trip count: the lanes of a wave differ in g < NG only)
         const int n_loc = pos > part ? (pos - part + nparts - 1) / nparts : 0;       // local indices of this workgroup's cached rows
         for (int ib = 0; ib < n_loc; ib += 2 * NG * U) {
           round(kr0, vr0, ib + g);
-          if (ib + 2 * NG * U < n_loc) load_round(kr0, vr0, ib + g + 2 * NG * U);
+          if (ib + 2 * NG * U < n_loc) rows.load_round(kr0, vr0, ib + g + 2 * NG * U);
           if (ib + NG * U < n_loc) {
             round(kr1, vr1, ib + g + NG * U);
-            if (ib + 3 * NG * U < n_loc) load_round(kr1, vr1, ib + g + 3 * NG * U);
+            if (ib + 3 * NG * U < n_loc) rows.load_round(kr1, vr1, ib + g + 3 * NG * U);
           }
         }
         // the new row (position pos, still in registers) is the LAST key of its group: the rounds visit cached rows only -- as
         // a case inside them it cost sixteen register moves per key
-        if (part == (split ? (pos & (kParts - 1)) : 0) && g == (((pos - part) / nparts) & (NG - 1))) update(score(kn), vn);
+        if (part == (split ? (pos & (kParts - 1)) : 0) && g == (((pos - part) / nparts) & (NG - 1))) attn::update(m, lsum, acc8, attn::score<LPK>(q8, kn), vn);
       }
       ASTAMP(1);
       if (tid < ATH) {
         // The four key groups of a wave (its four rows of 16 lanes) merge in registers first: v_permlane16_swap / 32_swap of a
         // value with ITSELF hands every lane both partners' copies -- (even row, odd row) / (lower half, upper half) -- so both
         // sides compute the same merged state and nobody selects.  Eight states meet in LDS instead of sixteen.
-        auto merge2 = [&](auto swap) {
-          const auto tm = swap(as_u32(m)), tl = swap(as_u32(lsum));
-          const float mA = as_f32((uint32_t)tm[0]), mB = as_f32((uint32_t)tm[1]);
-          const float M = fmaxf(mA, mB);
-          const float wA = mA == -INFINITY ? 0.f : __expf(mA - M), wB = mB == -INFINITY ? 0.f : __expf(mB - M);
-          lsum = __builtin_fmaf(as_f32((uint32_t)tl[1]), wB, had::fmul(as_f32((uint32_t)tl[0]), wA));
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const auto ta = swap(as_u32(acc8[i]));
-            acc8[i] = __builtin_fmaf(as_f32((uint32_t)ta[1]), wB, had::fmul(as_f32((uint32_t)ta[0]), wA));
-          }
-          m = M;
-        };
-        merge2([](uint32_t x) { return __builtin_amdgcn_permlane16_swap(x, x, false, false); });
-        merge2([](uint32_t x) { return __builtin_amdgcn_permlane32_swap(x, x, false, false); });
+        attn::merge2(m, lsum, acc8, [](uint32_t x) { return __builtin_amdgcn_permlane16_swap(x, x, false, false); });
+        attn::merge2(m, lsum, acc8, [](uint32_t x) { return __builtin_amdgcn_permlane32_swap(x, x, false, false); });
         if (lane < LPK) {
           if (lane == 0) { s_m[wave] = m; s_l[wave] = lsum; }
 #pragma unroll
@@ -1311,14 +1243,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       ASTAMP(2);
       f16* s_a = s_qkv + 3 * HD;
       float pM = -INFINITY, pL = 0.f, pO = 0.f;        // this workgroup's state for dimension tid: maximum, denominator, sum
-      if (tid < HD) {
-        for (int g2 = 0; g2 < NST; ++g2) pM = fmaxf(pM, s_m[g2]);
-        for (int g2 = 0; g2 < NST; ++g2) {
-          const float ww = s_m[g2] == -INFINITY ? 0.f : __expf(s_m[g2] - pM);
-          pL = __builtin_fmaf(s_l[g2], ww, pL);
-          pO = __builtin_fmaf(s_acc[g2 * (HD + 4) + tid], ww, pO);
-        }
-      }
+      if (tid < HD) attn::merge_states<NST>(s_m, s_l, 1, s_acc + tid, HD + 4, pM, pL, pO);
       if (split) {
         // hand-off: the partial states of the head's eight workgroups -> its first one
         const uint32_t tagp = tagg;
@@ -1358,6 +1283,8 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
           had::wg_barrier<true>();
           if (tid < HD) {
             float M = -INFINITY, Lsum = 0.f, o = 0.f;
+            // attn::merge_states over the head's parts, written out: as the call (decode_block_gqa.hip has it) the branch
+            // around this merge came out inverted in every instantiation
             for (int q2 = 0; q2 < kParts; ++q2) M = fmaxf(M, s_p[q2 * kPartGran + HD]);
             for (int q2 = 0; q2 < kParts; ++q2) {
               const float mq = s_p[q2 * kPartGran + HD];

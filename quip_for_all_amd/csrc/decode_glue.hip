@@ -23,6 +23,7 @@
 // its own cache slice [b] (the bs=1 layout), its own partial states and arrival counters.  Per sequence the code path
 // is the bs=1 kernel's (same lane groups, key order, split rule and merge), so every sequence's output and cache rows
 // are bit identical to a bs=1 launch on that sequence alone.
+#include "attn_query.hip.h"
 #include "had_device.hip.h"
 #include "quip_device.hip.h"
 #include "launch.hip.h"
@@ -57,33 +58,6 @@ struct AttnArgs {
 
 constexpr int kSplits = 8;  // workgroups per head for long contexts (grid.y)
 constexpr int kSplitFromPos = 256;    // shorter contexts: split 0 does everything, no workspace traffic
-
-__device__ __forceinline__ void unpack8h(const uint4& u, float o[8]) {
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const f16x2 h = as_f16x2(w[i]);
-    o[2 * i] = (float)h.x;
-    o[2 * i + 1] = (float)h.y;
-  }
-}
-
-// rotary embedding (HF half-rotation) of the 8 dims [d0, d0 + 8) of one head vector; result
-// rounded to fp16 like the eager graph does
-template <int HD>
-__device__ __forceinline__ void rope8(const f16* vec, const float c8[8], const float s8[8], int d0, float o[8]) {
-  float a[8], b[8];
-  unpack8h(*reinterpret_cast<const uint4*>(vec + d0), a);
-  const int dp = d0 < HD / 2 ? d0 + HD / 2 : d0 - HD / 2;
-  unpack8h(*reinterpret_cast<const uint4*>(vec + dp), b);
-  const float sgn = d0 < HD / 2 ? -1.f : 1.f;
-#pragma unroll
-  // x * cos + rot * sin with every operation rounded on its own, as the eager graph does (and so that the two
-  // instantiations of the kernel cannot contract the expression differently: an fma in one of them moved single
-  // cache elements by one fp16 ulp)
-  // (had::fmul / fadd: compiled with contraction switched off; __fmul_rn and friends are plain operators to hipcc)
-  for (int i = 0; i < 8; ++i) o[i] = (float)(f16)had::fadd(had::fmul(a[i], c8[i]), had::fmul(sgn * b[i], s8[i]));
-}
 
 // barriers inside fht16_fixed<LOGL, false> (had_device.hip.h): two around the lane stages, two per pass through LDS
 __host__ __device__ constexpr int fht16_barriers(int logl) { return logl <= 8 ? 2 : 2 + 2 * ((logl + 3) / 4 - 2); }
@@ -202,10 +176,10 @@ void rope_attn_decode_kernel(AttnArgs a, AttnZ zz) {
     vh = s_qkv[2];
   }
   float q8[8], kn[8], vn[8];
-  rope8<HD>(qh, c8, s8, d0, q8);
-  rope8<HD>(kh, c8, s8, d0, kn);
+  attn::rope8<HD>(qh, c8, s8, d0, q8);
+  attn::rope8<HD>(kh, c8, s8, d0, kn);
   const uint4 vraw = *reinterpret_cast<const uint4*>(vh + d0);
-  unpack8h(vraw, vn);
+  attn::unpack8h(vraw, vn);
 #pragma unroll
   for (int i = 0; i < 8; ++i) q8[i] *= a.scale;
   f16* kc = a.kcache + (size_t)kvh * a.max_len * HD;
@@ -230,22 +204,18 @@ void rope_attn_decode_kernel(AttnArgs a, AttnZ zz) {
       kr[u] = *reinterpret_cast<const uint4*>(kc + (size_t)tc * HD + d0);
       vr[u] = *reinterpret_cast<const uint4*>(vc + (size_t)tc * HD + d0);
     }
-    // the round's scores first (independent chains; the 16-lane sums on DPP moves, had::sum16_xor: the additions of
-    // `s += __shfl_xor(s, o)`, o = 1, 2, 4, 8), then the online-softmax updates in key order
+    // the round's scores first (independent chains), then the online-softmax updates in key order
     float k8a[U][8], v8a[U][8], sa[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = t0 + u * NG;
-      unpack8h(kr[u], k8a[u]);
-      unpack8h(vr[u], v8a[u]);
+      attn::unpack8h(kr[u], k8a[u]);
+      attn::unpack8h(vr[u], v8a[u]);
       if (t == pos) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) { k8a[u][i] = kn[i]; v8a[u][i] = vn[i]; }
       }
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s = __builtin_fmaf(q8[i], k8a[u][i], s);
-      sa[u] = had::sum16_xor<LPK>(s);
+      sa[u] = attn::score<LPK>(q8, k8a[u]);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -253,10 +223,9 @@ void rope_attn_decode_kernel(AttnArgs a, AttnZ zz) {
       const float s = sa[u];
       const float (&v8)[8] = v8a[u];
       if (t < t_hi) {
+        // attn::update, written out (as a call it moved the registers and the schedule of every instantiation)
         const float mn = fmaxf(m, s);
         const float c = __expf(m - mn), p = __expf(s - mn);
-        // (spelled out: left to the compiler, the instantiations of this kernel contract a * c + p * v differently -- one
-        //  element in 8192 moved by an ulp between the grouped-query prologue and the plain kernel)
         l = __builtin_fmaf(l, c, p);
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i] = __builtin_fmaf(acc[i], c, had::fmul(p, v8[i]));
@@ -270,6 +239,8 @@ void rope_attn_decode_kernel(AttnArgs a, AttnZ zz) {
   __syncthreads();
   float M = -INFINITY, Lsum = 0.f, o = 0.f;
   if (tid < HD) {
+    // attn::merge_states, written out (s_m / s_l / s_acc are LDS arrays here: read through pointers they were scheduled
+    // differently)
     for (int g = 0; g < NG; ++g) M = fmaxf(M, s_m[g]);
     for (int g = 0; g < NG; ++g) {
       const float w = s_m[g] == -INFINITY ? 0.f : __expf(s_m[g] - M);
@@ -307,7 +278,7 @@ void rope_attn_decode_kernel(AttnArgs a, AttnZ zz) {
       ls[s2] = __hip_atomic_load(base + s2 * (HD + 4) + HD + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       os[s2] = __hip_atomic_load(base + s2 * (HD + 4) + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    float Mx = -INFINITY;
+    float Mx = -INFINITY;                              // attn::merge_states, written out (as a call: other registers)
 #pragma unroll
     for (int s2 = 0; s2 < kSplits; ++s2) Mx = fmaxf(Mx, ms[s2]);
     float L2 = 0.f, o2 = 0.f;
@@ -429,6 +400,8 @@ int rope_attn_decode_z_launch(const void* const* z, const void* const* post, con
 // (rows, n) logits -- row r sets tok[r] and advances pos[r]; the bs=1 tail is one row: the three framework launches it
 // replaces (reduce, copy, add) cost ~20 us of a 2.5 ms token.  The first index of the maximum does not depend on the
 // order of the scan, so rows whose start is not 16-byte aligned (odd n) take 2-byte loads and give the same token.
+// (The rule is argmax_better, quip_device.hip.h; this kernel and nll_rows.hip.h spell it out: called as a function the
+// comparisons compile to other code.)
 namespace {
 __global__ __launch_bounds__(1024) void argmax_step_kernel(const f16* __restrict__ logits, int n,
                                                            int64_t* __restrict__ tok, int64_t* __restrict__ pos) {
@@ -490,7 +463,7 @@ int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, 
 
 }  // namespace quip
 
-// the prompt-side launch: rope + cache append + causal attention for a chunk of rows (uses rope8 above)
+// the prompt-side launches: rope + cache append + causal attention for a chunk of rows, for a ragged batch of chunks
 #include "chunk_attn.hip.h"
 #include "ragged_attn.hip.h"
 // the scoring tail: log-sum-exp, target log-probability and arg-max of every row of a chunk's logits

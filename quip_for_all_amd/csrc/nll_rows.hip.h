@@ -1,4 +1,4 @@
-// Scoring tail of a prompt pass (decode_glue.hip includes this file behind argmax_step_kernel, whose family it joins): for
+// Scoring tail of a prompt pass (part of decode_glue.hip's translation unit; it joins the family of argmax_step_kernel): for
 // every row of (rows, n) fp16 logits the log-sum-exp, the log-probability of the row's target token and the arg-max, one
 // launch, no fp32 copy of the logits.  One workgroup of 1024 threads per row.
 //
@@ -28,6 +28,8 @@
 // 32 units of 2^-24 (one rounding of the difference, |x - m| 2^-24, carried through exp, plus expf's own unit): relative
 // error of the sum < 205 * 2^-24 = 1.3e-5, which is the absolute error of its logarithm.
 #pragma once
+#include "launch.hip.h"
+#include "quip_device.hip.h"
 
 namespace quip {
 namespace {

@@ -78,6 +78,10 @@ __device__ __forceinline__ uint32_t pack_f16(float lo, float hi) {
   return as_u32(h);
 }
 
+// The arg-max rule of every kernel that picks a token (torch.argmax's): larger value, then lower index; a NaN never wins.
+// Is (v, i) better than the best so far?
+__device__ __forceinline__ bool argmax_better(float v, int i, float best, int bi) { return v > best || (v == best && i < bi); }
+
 // ---- wave64 sum; total lands in lane 63 (DPP only, no LDS traffic) ----------
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_add(float v) {

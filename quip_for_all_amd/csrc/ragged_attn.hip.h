@@ -1,4 +1,4 @@
-// The chunk attention launch (chunk_attn.hip.h, included just before this file by decode_glue.hip) for a RAGGED batch of
+// The chunk attention launch (chunk_attn.hip.h) for a RAGGED batch of
 // chunks: S segments of consecutive rows of token-major q / k / v / out, segment s = seg_rows[s] rows that continue
 // slot seg_slot[s] of a batched cache (B, kv_heads, max_len, HD) at the position the launch reads from pos[seg_slot[s]]
 // (pos: the (B,) device counters of the batched decoder).  Per segment: rotary embedding, append to that slot's cache,
@@ -22,6 +22,8 @@
 // Range rule, per segment: pos[slot] < 0 or pos[slot] + seg_rows[s] > max_len -> nothing is appended to that slot and
 // that segment's out rows are NaN; every other segment is unaffected.
 #pragma once
+#include "chunk_attn.hip.h"
+#include "launch.hip.h"
 
 namespace quip {
 namespace {

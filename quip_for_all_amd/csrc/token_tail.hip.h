@@ -13,8 +13,8 @@
 //            reduction per row, the sum rounded to fp16 and stored (device scope);
 //   arg-max  per wave, per workgroup, then ONE 8-byte granule {fp16 bits << 16 | local row, tag} per workgroup through the
 //            launch's hand-off protocol (engine_sync.hip.h); workgroup 0 polls the 256 granules (bounded), reduces them and
-//            stores the token and position + 1.  Rule of argmax_step_kernel (decode_glue.hip): larger value, then lower
-//            index, NaN never wins, nothing found = token 0.
+//            stores the token and position + 1.  Rule of argmax_step_kernel (decode_glue.hip): argmax_better (quip_device.hip.h:
+//            larger value, then lower index, NaN never wins), nothing found = token 0.
 // A launch that gave up (ctl[1] != 0) answers like the separate launches do on an all-NaN hidden state: every logit NaN,
 // token 0, position + 1.
 #pragma once
@@ -45,8 +45,6 @@ constexpr int kRowU4 = kHid / 8;                     // 16-byte pieces of a row
 constexpr int kRoundingChain = 8 * 2 + 2 + 6;
 constexpr int kLdsBytes = kHid * 2 + 256;            // x as fp16 | reduction slots
 constexpr uint32_t kGiveUpCode = 0x9000u;
-
-__device__ __forceinline__ bool better(float v, int i, float best, int bi) { return v > best || (v == best && i < bi); }
 
 __device__ __forceinline__ void st_half_device(f16* p, uint16_t bits) {
   asm volatile("global_store_short %0, %1, off sc1" : : "v"(p), "v"((uint32_t)bits) : "memory");
@@ -149,7 +147,7 @@ __device__ __forceinline__ void run(const Args& t, const uint32_t (&hreg)[4], ch
     const f16 hv = failed ? __builtin_bit_cast(f16, (uint16_t)0x7e00) : (f16)s;
     if (lane == 0) st_half_device(t.logits + row0 + lr, __builtin_bit_cast(uint16_t, hv));
     const float v = (float)hv;                         // the arg-max sees the logit as stored
-    if (better(v, lr, best, bi)) { best = v; bi = lr; }
+    if (argmax_better(v, lr, best, bi)) { best = v; bi = lr; }
   };
   u32x4 A[8], Bw[8];
   if (wave < nrows) request(wave, A);
@@ -174,7 +172,7 @@ __device__ __forceinline__ void run(const Args& t, const uint32_t (&hreg)[4], ch
     best = redv[0]; bi = redi[0];
 #pragma unroll
     for (int i = 1; i < kWvs; ++i)
-      if (better(redv[i], redi[i], best, bi)) { best = redv[i]; bi = redi[i]; }
+      if (argmax_better(redv[i], redi[i], best, bi)) { best = redv[i]; bi = redi[i]; }
     const uint32_t word = ((uint32_t)__builtin_bit_cast(uint16_t, (f16)best) << 16) | (bi == INT_MAX ? 0xffffu : (uint32_t)bi);
     if (lane == 0) esync::st_granule(gran + w, word, tag);
   }
@@ -201,7 +199,7 @@ __device__ __forceinline__ void run(const Args& t, const uint32_t (&hreg)[4], ch
     for (int o = 32; o >= 1; o >>= 1) {
       const float ov = __shfl_xor(v, o, 64);
       const int oi = __shfl_xor(idx, o, 64);
-      if (better(ov, oi, v, idx)) { v = ov; idx = oi; }
+      if (argmax_better(ov, oi, v, idx)) { v = ov; idx = oi; }
     }
     if (lane == 0) { redv[wave] = v; redi[wave] = idx; }
   }
@@ -209,7 +207,7 @@ __device__ __forceinline__ void run(const Args& t, const uint32_t (&hreg)[4], ch
   best = redv[0]; bi = redi[0];
 #pragma unroll
   for (int i = 1; i < 4; ++i)
-    if (better(redv[i], redi[i], best, bi)) { best = redv[i]; bi = redi[i]; }
+    if (argmax_better(redv[i], redi[i], best, bi)) { best = redv[i]; bi = redi[i]; }
   uint32_t err2;
   esync::ld4(err2, ctl + 1);
   esync::drain();
