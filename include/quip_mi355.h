@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 13
+#define QUIP_ABI_VERSION 14
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -502,6 +502,34 @@ int quip_rope_attn_ragged_f16(const void* q, const void* k, const void* v, const
                               int32_t kv_heads, int32_t head_dim, int32_t max_len, int32_t batch,
                               const int32_t* seg_slot, const int32_t* seg_rows, int32_t nseg, float scale,
                               int32_t window, quip_stream_t stream);
+/* ---- the two batched launches on a PAGED KV cache (ABI 14) -----------------------------------------------------------
+ * A page is 64 consecutive positions of every KV head of one sequence.  kpool / vpool [n_pages, kv_heads, 64, head_dim]
+ * fp16; table [batch, max_pages] int32 on the device, contiguous: entry [b][j] is the page of positions
+ * [64 j, 64 j + 64) of slot b, -1 where none is assigned.  Row t of KV head g of slot b lives at
+ *   pool + ((table[b][t >> 6] * kv_heads + g) * 64 + (t & 63)) * head_dim.
+ * max_len is the row count of cos / sin and the bound of the range rule, max_len <= 64 max_pages.
+ * quip_rope_attn_decode_paged_f16 is quip_rope_attn_decode_batched_f16 and quip_rope_attn_ragged_paged_f16 is
+ * quip_rope_attn_ragged_f16 with that address for every cached and appended row and nothing else changed: outputs and
+ * cache rows are bit identical to the contiguous call on the rows gathered through the table.  (The split grid of the
+ * decode call is chosen with 64 max_pages in place of max_len; workspace as for the batched call.)
+ * Table validity is part of the range rule: an entry outside [0, n_pages) among the pages of the keys a sequence
+ * (decode: window's first key .. pos) or a segment (ragged: first key of its first row .. its last row) touches
+ * appends nothing for it and makes its output rows NaN; the others are unaffected.  Entries below a window's first page
+ * are not examined.
+ * The caller guarantees (not checked): a page that a slot of the call appends to is referenced by that slot only.
+ * Errors as the contiguous calls; n_pages, max_pages >= 1, max_len <= 64 max_pages (else QUIP_ERR_BAD_SHAPE);
+ * decode: max_pages <= 8192 (else QUIP_ERR_UNSUPPORTED); table 4-byte aligned (else QUIP_ERR_MISALIGNED). */
+int quip_rope_attn_decode_paged_f16(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                    const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                    int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t max_len,
+                                    int32_t n_pages, int32_t max_pages, float scale, int32_t window, void* workspace,
+                                    quip_stream_t stream);
+int quip_rope_attn_ragged_paged_f16(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                    const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                    int32_t rows, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t max_len,
+                                    int32_t batch, int32_t n_pages, int32_t max_pages, const int32_t* seg_slot,
+                                    const int32_t* seg_rows, int32_t nseg, float scale, int32_t window,
+                                    quip_stream_t stream);
 /* Greedy tail over `batch` rows of n fp16 logits (row-major, [batch, n]): tok[b] = first index of the largest logit of
  * row b (torch.argmax's tie rule; an all-NaN / all -inf row gives 0), pos[b] += 1 -- one workgroup per row. */
 int quip_argmax_step_batched_f16(const void* logits, int32_t batch, int32_t n, void* tok, void* pos,

@@ -151,10 +151,8 @@ def _ragged_passes(dec, slots, toks, chunk, on_pass):
         n = sum(seg_rows)
 
         def attend(i, q, k, v):
-            return torch.ops.quip_lib.rope_attn_ragged(
-                q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim), v.view(n, s.kv_heads, s.head_dim),
-                dec.cos, dec.sin, dec.pos, seg_slot, seg_rows, dec.kcache[i], dec.vcache[i],
-                dec.window).reshape(n, s.hidden)
+            return dec._attend_ragged(i, q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim),
+                                      v.view(n, s.kv_heads, s.head_dim), seg_slot, seg_rows).reshape(n, s.hidden)
         h = p.embed[torch.cat([toks[j][a:a + r] for j, a, r in pieces])]      # (n, hidden)
         for i, L in enumerate(p.layers):
             h = p._block(L, h, partial(attend, i))
@@ -185,14 +183,30 @@ class BatchDecoder:
         self.parent, self.batch, self.max_len, self.s, self.dev = parent, batch, max_len, s, parent.dev
         self.window = parent.window
         self.cos, self.sin = parent.cos[:max_len], parent.sin[:max_len]
-        self.kcache = torch.zeros(s.layers, batch, s.kv_heads, max_len, s.head_dim, dtype=torch.float16, device=self.dev)
-        self.vcache = torch.zeros_like(self.kcache)
+        self._alloc_cache()
         self.tok = torch.zeros(batch, dtype=torch.long, device=self.dev)
         self.pos = torch.zeros(batch, dtype=torch.long, device=self.dev)
         self.attn_ws = rope_attn_batched_workspace(batch, s.heads, s.head_dim, self.dev)
         self.graph = None
         self.sampling = None
         self.step_logits = None
+
+    # the cache and the two attention launches on it: what paged_cache.PagedBatchDecoder replaces
+    def _alloc_cache(self):
+        s = self.s
+        self.kcache = torch.zeros(s.layers, self.batch, s.kv_heads, self.max_len, s.head_dim, dtype=torch.float16,
+                                  device=self.dev)
+        self.vcache = torch.zeros_like(self.kcache)
+
+    def _attend_step(self, i, q, k, v):
+        """block i of step(): q (B, heads, hd), k / v (B, kv_heads, hd) -> (B, heads, hd)"""
+        return torch.ops.quip_lib.rope_attn_decode_batched(q, k, v, self.cos, self.sin, self.pos, self.kcache[i],
+                                                           self.vcache[i], self.attn_ws, self.window)
+
+    def _attend_ragged(self, i, q, k, v, seg_slot, seg_rows):
+        """block i of a ragged pass: q (rows, heads, hd), k / v (rows, kv_heads, hd) -> (rows, heads, hd)"""
+        return torch.ops.quip_lib.rope_attn_ragged(q, k, v, self.cos, self.sin, self.pos, seg_slot, seg_rows,
+                                                   self.kcache[i], self.vcache[i], self.window)
 
     def regimes(self):
         """the product path of every module of a block at M = B (QuantLinear.regime)"""
@@ -206,9 +220,8 @@ class BatchDecoder:
         h = p.embed[self.tok]                                       # (B, hidden)
 
         def attend(i, q, k, v):
-            return torch.ops.quip_lib.rope_attn_decode_batched(
-                q.view(B, s.heads, s.head_dim), k.view(B, s.kv_heads, s.head_dim), v.view(B, s.kv_heads, s.head_dim),
-                self.cos, self.sin, self.pos, self.kcache[i], self.vcache[i], self.attn_ws, self.window).reshape(B, s.hidden)
+            return self._attend_step(i, q.view(B, s.heads, s.head_dim), k.view(B, s.kv_heads, s.head_dim),
+                                     v.view(B, s.kv_heads, s.head_dim)).reshape(B, s.hidden)
         for i, L in enumerate(p.layers):
             h = p._block(L, h, partial(attend, i))
         return self._head(h)
@@ -267,6 +280,10 @@ class BatchDecoder:
         that do not fit a slot's max_len append nothing and give that slot NaN logits (the launch's range rule, per
         segment).  Returns the last-token logits of every list, (len(slots), vocab), in the order of `slots`."""
         slots, toks = _check_passes(self, "extend_slots", slots, token_lists, chunk)
+        return self._extend_passes(slots, toks, chunk)
+
+    def _extend_passes(self, slots, toks, chunk):
+        """extend_slots on checked arguments"""
         last = [None] * len(slots)
 
         def keep(pieces, h):
@@ -288,12 +305,18 @@ class BatchDecoder:
         extend_slots's, raised before anything is written.  Returns (logprobs, argmaxes): per list one (len_j,) fp32
         and one (len_j,) int64 tensor on the device, in the order of `slots`."""
         slots, toks = _check_passes(self, "score_slots", slots, token_lists, chunk)
+        return self._score_passes(slots, toks, self._check_targets(toks, targets), chunk)
+
+    def _check_targets(self, toks, targets):
         if targets is None:
-            tgts = [_score.shifted_targets(t) for t in toks]
-        else:
-            tgts = [torch.as_tensor(t, dtype=torch.long, device=self.dev).reshape(-1) for t in targets]
-            if [t.numel() for t in tgts] != [t.numel() for t in toks]:
-                raise ValueError("score_slots: every token list needs a target list of its own length")
+            return [_score.shifted_targets(t) for t in toks]
+        tgts = [torch.as_tensor(t, dtype=torch.long, device=self.dev).reshape(-1) for t in targets]
+        if [t.numel() for t in tgts] != [t.numel() for t in toks]:
+            raise ValueError("score_slots: every token list needs a target list of its own length")
+        return tgts
+
+    def _score_passes(self, slots, toks, tgts, chunk):
+        """score_slots on checked arguments"""
         p, s = self.parent, self.s
         lps = [torch.empty(t.numel(), dtype=torch.float32, device=self.dev) for t in toks]
         ams = [torch.empty(t.numel(), dtype=torch.long, device=self.dev) for t in toks]
@@ -321,7 +344,7 @@ class BatchDecoder:
         self.pos.index_fill_(0, idx, 0)
         longer = [j for j, pr in enumerate(prompts) if pr.numel() > 1]
         if longer:
-            self.extend_slots([slots[j] for j in longer], [prompts[j][:-1] for j in longer])
+            self._extend_passes([slots[j] for j in longer], [prompts[j][:-1] for j in longer], 512)
         self.tok.index_copy_(0, idx, torch.stack([pr[-1] for pr in prompts]))
 
     @torch.no_grad()

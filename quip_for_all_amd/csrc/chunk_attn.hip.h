@@ -56,6 +56,15 @@ struct ChunkArgs {
   int tile0;           // first query tile of this launch
   int heads, kv_heads, max_len, window;
   float scale;
+  static constexpr bool kPaged = false;
+};
+
+// A chunk on a PAGED cache (paged_attn.hip.h): kcache / vcache are page pools [n_pages, kv_heads, 64, HD], key tile j
+// of the slot is page table[j].  max_len stays the row count of cos / sin and the bound of the range rule.
+struct PagedChunkArgs : ChunkArgs {
+  const int32_t* table;    // the slot's row of the block table: max_pages entries, -1: none
+  int n_pages, max_pages;
+  static constexpr bool kPaged = true;
 };
 
 typedef float cf32x16 __attribute__((ext_vector_type(16)));
@@ -75,9 +84,11 @@ __device__ __forceinline__ cf16x4 lds_read_tr16(const unsigned char* p) {
 
 // One (64-row query tile, head) of a chunk: the whole body of the launch.  `tile` is the query tile inside the chunk
 // `a` describes (wave uniform).  Shared, inlined, by rope_attn_chunk_kernel and the ragged launch (ragged_attn.hip.h),
-// which points `a` at one segment of its rows first.
-template <int HD>
-__device__ __forceinline__ void chunk_tile_body(const ChunkArgs& a, const int tile) {
+// which points `a` at one segment of its rows first.  A: ChunkArgs, or PagedChunkArgs -- the same code with the cached
+// rows of key tile jt read from, and the chunk's rows appended to, page table[jt] (one wave-uniform lookup per tile).
+template <int HD, class A>
+__device__ __forceinline__ void chunk_tile_body(const A& a, const int tile) {
+  constexpr bool PAGED = A::kPaged;
   constexpr int NCH = HD / 8;                       // 16-byte chunks per row
   constexpr int KROW = HD * 2, VROW = HD * 2 + 64;  // bytes per K / V row in LDS
   constexpr int NIT = kChunkTile * NCH / kChunkThreads;
@@ -89,7 +100,20 @@ __device__ __forceinline__ void chunk_tile_body(const ChunkArgs& a, const int ti
   const int nrow = min(kChunkTile, a.rows - i0);
   const int group = a.heads / a.kv_heads, kvh = h / group;
   const long long pos64 = *a.pos;
-  if (pos64 < 0 || pos64 + (long long)a.rows > (long long)a.max_len) {
+  bool refuse = pos64 < 0 || pos64 + (long long)a.rows > (long long)a.max_len;
+  if constexpr (PAGED) {
+    // Table validity, part of the range rule: the pages of the SEGMENT's keys, first key of its first row .. its last
+    // row, whatever this workgroup's tile is -- every workgroup of the segment scans the same entries (each wave all
+    // of them, one per lane and round) and reaches the same verdict.  Pages below the window's first are not looked at.
+    if (!refuse) {
+      const int p0 = (int)pos64;
+      const int lo = a.window > 0 ? max(0, p0 + 1 - a.window) >> 6 : 0, hi = (p0 + a.rows - 1) >> 6;
+      bool bad = false;
+      for (int pg = lo + lane; pg <= hi; pg += 64) bad |= (unsigned)a.table[pg] >= (unsigned)a.n_pages;
+      refuse = __any(bad);
+    }
+  }
+  if (refuse) {
     const uint32_t nan2 = 0x7e007e00u;
     for (int e = tid; e < nrow * NCH; e += kChunkThreads)
       *reinterpret_cast<uint4*>(a.out + ((size_t)(i0 + e / NCH) * a.heads + h) * HD + (e % NCH) * 8) =
@@ -106,7 +130,7 @@ __device__ __forceinline__ void chunk_tile_body(const ChunkArgs& a, const int ti
   const int p_hi = pos + i0 + nrow - 1;
   const int kfirst = a.window > 0 ? max(0, pos + i0 + 1 - a.window) : 0;
   const bool appender = h % group == 0;
-  const f16* kc = a.kcache + (size_t)kvh * a.max_len * HD;
+  const f16* kc = a.kcache + (size_t)kvh * a.max_len * HD;      // (contiguous: this head's KV head, row 0)
   const f16* vc = a.vcache + (size_t)kvh * a.max_len * HD;
 
   // Q^T fragments (B operand): lane (r, hh) holds dims [16 ks + 8 hh, + 8) of its query row, rotated, fp16
@@ -138,14 +162,21 @@ __device__ __forceinline__ void chunk_tile_body(const ChunkArgs& a, const int ti
     // ---- stage keys [64 jt, 64 jt + 64): cache rows below *pos, the chunk's own rows from k / v (rotated here, and
     //      appended by the designated workgroup); rows no query of this tile attends to are zero
     uint4 kreg[NIT], vreg[NIT];
+    size_t page0 = 0;     // paged: this KV head's part of the tile's page, row kr of it is key 64 jt + kr
+    if constexpr (PAGED) page0 = ((size_t)a.table[jt] * a.kv_heads + kvh) * kChunkTile * HD;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int e = tid + kChunkThreads * it, kr = e / NCH, c = e % NCH, t = kChunkTile * jt + kr;
       uint4 kk = make_uint4(0, 0, 0, 0), vv = make_uint4(0, 0, 0, 0);
       if (t >= kfirst && t <= p_hi) {
         if (t < pos) {
-          kk = *reinterpret_cast<const uint4*>(kc + (size_t)t * HD + c * 8);
-          vv = *reinterpret_cast<const uint4*>(vc + (size_t)t * HD + c * 8);
+          if constexpr (PAGED) {
+            kk = *reinterpret_cast<const uint4*>(a.kcache + page0 + (size_t)kr * HD + c * 8);
+            vv = *reinterpret_cast<const uint4*>(a.vcache + page0 + (size_t)kr * HD + c * 8);
+          } else {
+            kk = *reinterpret_cast<const uint4*>(kc + (size_t)t * HD + c * 8);
+            vv = *reinterpret_cast<const uint4*>(vc + (size_t)t * HD + c * 8);
+          }
         } else {
           const int i = t - pos;
           const f16* krow = a.k + ((size_t)i * a.kv_heads + kvh) * HD;
@@ -159,8 +190,9 @@ __device__ __forceinline__ void chunk_tile_body(const ChunkArgs& a, const int ti
           kk.z = pack_f16(o[4], o[5]); kk.w = pack_f16(o[6], o[7]);
           vv = *reinterpret_cast<const uint4*>(a.v + ((size_t)i * a.kv_heads + kvh) * HD + c * 8);
           if (appender && i >= i0) {   // (i <= i0 + nrow - 1 by t <= p_hi): this tile's own rows
-            *reinterpret_cast<uint4*>(a.kcache + ((size_t)kvh * a.max_len + t) * HD + c * 8) = kk;
-            *reinterpret_cast<uint4*>(a.vcache + ((size_t)kvh * a.max_len + t) * HD + c * 8) = vv;
+            const size_t at = PAGED ? page0 + (size_t)kr * HD : ((size_t)kvh * a.max_len + t) * HD;
+            *reinterpret_cast<uint4*>(a.kcache + at + c * 8) = kk;
+            *reinterpret_cast<uint4*>(a.vcache + at + c * 8) = vv;
           }
         }
       }

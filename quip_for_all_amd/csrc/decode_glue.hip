@@ -54,6 +54,16 @@ struct AttnArgs {
   float* ws;           // split mode: partial (acc[HD], m, l) per (head, split); null: one workgroup per head
   unsigned* counters;  // split mode: arrivals per head (zero between launches)  (batched: per (sequence, head))
   int window;          // sliding-window attention (Mistral: config.sliding_window): positions (pos - window, pos]; <= 0: [0, pos]
+  static constexpr bool kPaged = false;
+};
+
+// The batched launch on a PAGED cache (paged_attn.hip.h): kcache / vcache are page pools, a row is found through the
+// block table.  max_len stays the row count of cos / sin and the bound of the range rule.
+constexpr int kPage = 64;             // positions per page == kChunkTile (chunk_attn.hip.h)
+struct PagedAttnArgs : AttnArgs {
+  const int32_t* table;   // [B, max_pages]: page of positions [64 j, 64 j + 64) of sequence b, -1: none
+  int n_pages, max_pages; // kcache / vcache: [n_pages, kv_heads, kPage, HD]
+  static constexpr bool kPaged = true;
 };
 
 constexpr int kSplits = 8;  // workgroups per head for long contexts (grid.y)
@@ -65,13 +75,17 @@ __host__ __device__ constexpr int fht16_barriers(int logl) { return logl <= 8 ? 
 // ZIN with LQ == 0: q, k, v of one common width on 3 x 256 threads (run-time length).  LQ > 0 (grouped queries): q of
 // width 2^LQ on the first 2^LQ / 16 threads, k and v of width 2^LKV on the next 2 x 2^LKV / 16 (whole waves each).
 // SEQ: the batched launch -- blockIdx.z selects the sequence; the pointers move to its tensors before anything is read.
-template <int HD, bool ZIN, int LQ = 0, int LKV = 0, bool SEQ = false>
+// Args: AttnArgs, or PagedAttnArgs (SEQ only) -- the same walk, split rule, window rule and merge with every cache row
+// addressed through the sequence's block-table row, which the workgroup validates and brings into LDS first.
+template <int HD, bool ZIN, int LQ = 0, int LKV = 0, bool SEQ = false, class Args = AttnArgs>
 __global__ __launch_bounds__(!ZIN ? 256 : (LQ == 0 ? 768 : (1 << LQ) / 16 + 2 * ((1 << LKV) / 16)))
-void rope_attn_decode_kernel(AttnArgs a, AttnZ zz) {
+void rope_attn_decode_kernel(Args a, AttnZ zz) {
+  constexpr bool PAGED = Args::kPaged;
   constexpr int LPK = HD / 8;        // lanes per key
   constexpr int NG = 256 / LPK;      // key groups per workgroup
   constexpr int U = 4;               // keys in flight per group
   static_assert(!(SEQ && ZIN), "the raw-GEMV-input variants are bs=1 only");
+  static_assert(!PAGED || SEQ, "the paged cache belongs to the batched launch");
   __shared__ float s_m[NG], s_l[NG];
   __shared__ float s_acc[NG][HD + 4];
   const int tid = threadIdx.x, h = blockIdx.x;
@@ -81,8 +95,12 @@ void rope_attn_decode_kernel(AttnArgs a, AttnZ zz) {
     a.k += b * a.kv_heads * HD;
     a.v += b * a.kv_heads * HD;
     a.pos += b;
-    a.kcache += b * a.kv_heads * (size_t)a.max_len * HD;
-    a.vcache += b * a.kv_heads * (size_t)a.max_len * HD;
+    if constexpr (PAGED) {
+      a.table += b * a.max_pages;
+    } else {
+      a.kcache += b * a.kv_heads * (size_t)a.max_len * HD;
+      a.vcache += b * a.kv_heads * (size_t)a.max_len * HD;
+    }
     a.out += b * a.heads * HD;
     if (a.ws) {
       a.ws += b * a.heads * kSplits * (HD + 4);
@@ -126,6 +144,25 @@ void rope_attn_decode_kernel(AttnArgs a, AttnZ zz) {
   const int chunk = split ? (pos - first + kSplits) / kSplits : pos + 1 - first;      // ceil((pos + 1 - first) / kSplits)
   const int t_lo = first + (split ? sidx * chunk : 0);
   const int t_hi = split ? min(pos + 1, t_lo + chunk) : pos + 1;       // exclusive (a split past the end walks nothing: m = -inf)
+  if constexpr (PAGED) {
+    // Table validity, part of the range rule: an entry of pages first >> 6 .. pos >> 6 outside [0, n_pages) -> no
+    // append, NaN heads, no workspace traffic.  Every wave scans the whole range itself (one entry per lane and
+    // round), so all waves of all workgroups of the sequence reach the same verdict without an exchange; wave 0
+    // leaves the row in LDS on the way, and the key loop's addresses come from there.  Pages below the window's first
+    // page are not looked at.
+    extern __shared__ int s_tab[];
+    bool bad = false;
+    for (int pg = (first >> 6) + (tid & 63); pg <= (pos >> 6); pg += 64) {
+      const int e = a.table[pg];
+      bad |= (unsigned)e >= (unsigned)a.n_pages;
+      if (tid < 64) s_tab[pg] = e;
+    }
+    if (__any(bad)) {
+      if (sidx == 0 && tid < HD) a.out[(size_t)h * HD + tid] = __builtin_bit_cast(f16, (unsigned short)0x7e00);
+      return;
+    }
+    __syncthreads();
+  }
   const float* cs = a.cos + (size_t)pos * HD;
   const float* sn = a.sin + (size_t)pos * HD;
 
@@ -182,14 +219,23 @@ void rope_attn_decode_kernel(AttnArgs a, AttnZ zz) {
   attn::unpack8h(vraw, vn);
 #pragma unroll
   for (int i = 0; i < 8; ++i) q8[i] *= a.scale;
-  f16* kc = a.kcache + (size_t)kvh * a.max_len * HD;
-  f16* vc = a.vcache + (size_t)kvh * a.max_len * HD;
+  // row t of this head's KV head: contiguous, base + t rows; paged, row t & 63 of the head's part of page table[t >> 6]
+  f16* kc = PAGED ? a.kcache : a.kcache + (size_t)kvh * a.max_len * HD;
+  f16* vc = PAGED ? a.vcache : a.vcache + (size_t)kvh * a.max_len * HD;
+  const auto row = [&](int t) -> size_t {
+    if constexpr (PAGED) {
+      extern __shared__ int s_tab[];
+      return (((size_t)s_tab[t >> 6] * a.kv_heads + kvh) * kPage + (t & (kPage - 1))) * HD;
+    } else {
+      return (size_t)t * HD;
+    }
+  };
   if (h % group == 0 && grp == 0 && sidx == 0) {   // append the new row (StaticCache.update)
     uint4 kr;
     kr.x = pack_f16(kn[0], kn[1]); kr.y = pack_f16(kn[2], kn[3]);
     kr.z = pack_f16(kn[4], kn[5]); kr.w = pack_f16(kn[6], kn[7]);
-    *reinterpret_cast<uint4*>(kc + (size_t)pos * HD + d0) = kr;
-    *reinterpret_cast<uint4*>(vc + (size_t)pos * HD + d0) = vraw;
+    *reinterpret_cast<uint4*>(kc + row(pos) + d0) = kr;
+    *reinterpret_cast<uint4*>(vc + row(pos) + d0) = vraw;
   }
 
   float m = -INFINITY, l = 0.f, acc[8];
@@ -200,9 +246,10 @@ void rope_attn_decode_kernel(AttnArgs a, AttnZ zz) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = t0 + u * NG;
-      const int tc = t < pos ? t : 0;   // t == pos comes from registers, t > pos is masked
-      kr[u] = *reinterpret_cast<const uint4*>(kc + (size_t)tc * HD + d0);
-      vr[u] = *reinterpret_cast<const uint4*>(vc + (size_t)tc * HD + d0);
+      // t == pos comes from registers, t > pos is masked: a dummy row (paged: one of a validated page)
+      const int tc = t < pos ? t : (PAGED ? first : 0);
+      kr[u] = *reinterpret_cast<const uint4*>(kc + row(tc) + d0);
+      vr[u] = *reinterpret_cast<const uint4*>(vc + row(tc) + d0);
     }
     // the round's scores first (independent chains), then the online-softmax updates in key order
     float k8a[U][8], v8a[U][8], sa[U];
@@ -466,5 +513,7 @@ int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, 
 // the prompt-side launches: rope + cache append + causal attention for a chunk of rows, for a ragged batch of chunks
 #include "chunk_attn.hip.h"
 #include "ragged_attn.hip.h"
+// both batched launches on a paged cache: rows addressed through a block table
+#include "paged_attn.hip.h"
 // the scoring tail: log-sum-exp, target log-probability and arg-max of every row of a chunk's logits
 #include "nll_rows.hip.h"

@@ -1,0 +1,140 @@
+// The two batched attention launches on a PAGED KV cache (part of decode_glue.hip's translation unit).
+//
+// Layout.  A page is kPage = 64 consecutive positions of every KV head of one sequence -- exactly one key tile of the
+// prompt-side launch (kPage == kChunkTile).  Per layer one pool for K and one for V, fp16 (n_pages, kv_heads, 64, HD):
+// one KV head's part of a page is 64 HD contiguous values.  The block table, int32 (B, max_pages), contiguous, on the
+// device, names the page of positions [64 j, 64 j + 64) of slot b in entry [b][j]; -1 is "none".  Row t of KV head g of
+// slot b:  pool + ((table[b][t >> 6] * kv_heads + g) * 64 + (t & 63)) * HD.
+//
+// rope_attn_decode_paged_launch is rope_attn_decode_batched_launch and rope_attn_ragged_paged_launch is
+// rope_attn_ragged_launch with that address in place of the contiguous one: the kernels are the same templates
+// (rope_attn_decode_kernel over PagedAttnArgs, chunk_tile_body over PagedChunkArgs), so the walk, the split rule, the
+// window rule, taking the new rows from registers / the inputs and all arithmetic are shared text.  Hence the oracle:
+// a paged launch is BIT IDENTICAL, outputs and cache rows, to the contiguous launch on the rows gathered through the
+// table.  The decode launch brings the sequence's table row into LDS once per workgroup (the key loop's loads depend
+// on an LDS read, not on a second global load); the ragged launch looks up one page per key tile, wave uniform.
+//
+// Table validity is part of the range rule -- a bad entry never becomes an address:
+//   decode: an entry of pages first >> 6 .. pos >> 6 outside [0, n_pages) -> nothing appended, the sequence's heads NaN
+//           (first: the window's first key, 0 without a window);
+//   ragged: the same for pages kfirst >> 6 .. (pos + rows - 1) >> 6 of a segment (kfirst: first key of its first row)
+//           -> that segment's rows NaN, nothing appended to it, the other segments keep their bits.
+// Every workgroup of a sequence / segment scans the same entries and reaches the same verdict: no partial append.
+// Entries below a window's first page are not examined (they may have been released).
+//
+// HOST INVARIANT, not checked on the device: a page that any slot of the launch appends to is referenced by that slot
+// only.  Rule (1) of chunk_attn.hip.h (no workgroup reads a cache row another workgroup of the launch writes) then
+// holds across slots that share read-only prefix pages: shared pages are read by several slots and written by none.
+#pragma once
+#include "chunk_attn.hip.h"
+#include "ragged_attn.hip.h"
+
+namespace quip {
+namespace {
+
+static_assert(kPage == kChunkTile, "a page is one key tile of the prompt-side launch");
+constexpr int kPagedMaxPages = 8192;     // the decode launch keeps a table row in LDS: 32 KiB, 524288 positions
+
+struct PagedRaggedArgs {
+  PagedChunkArgs c;   // as RaggedArgs::c; kcache / vcache: the pools, table: row 0 of the block table
+  int nseg;
+  int slot[kRaggedMaxSegments], row0[kRaggedMaxSegments], rows[kRaggedMaxSegments];
+};
+
+template <int HD>
+__global__ __launch_bounds__(kChunkThreads) void rope_attn_paged_ragged_kernel(PagedRaggedArgs ra) {
+  // the segment scan of the contiguous ragged launch (ragged_attn.hip.h)
+  int s = 0, t0 = 0;
+  for (; s < ra.nseg - 1; ++s) {
+    const int n = (ra.rows[s] + kChunkTile - 1) / kChunkTile;
+    if ((int)blockIdx.y < t0 + n) break;
+    t0 += n;
+  }
+  const int slot = ra.slot[s];
+  const size_t r0 = (size_t)ra.row0[s];
+  PagedChunkArgs a = ra.c;
+  a.q += r0 * a.heads * HD;
+  a.out += r0 * a.heads * HD;
+  a.k += r0 * a.kv_heads * HD;
+  a.v += r0 * a.kv_heads * HD;
+  a.table += (size_t)slot * a.max_pages;
+  a.pos += slot;
+  a.rows = ra.rows[s];
+  chunk_tile_body<HD>(a, (int)blockIdx.y - t0);
+}
+
+bool paged_shape_ok(int max_len, int n_pages, int max_pages) {
+  return n_pages >= 1 && max_pages >= 1 && max_len >= 1 && (long long)max_len <= (long long)max_pages * kPage;
+}
+
+}  // namespace
+
+int rope_attn_decode_paged_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                  const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                  int batch, int heads, int kv_heads, int head_dim, int max_len, int n_pages,
+                                  int max_pages, float scale, hipStream_t stream, void* workspace, int window) {
+  if (batch < 1 || batch > 65535 || heads < 1 || kv_heads < 1 || heads % kv_heads != 0 ||
+      !paged_shape_ok(max_len, n_pages, max_pages))
+    return QUIP_ERR_BAD_SHAPE;
+  if ((head_dim != 64 && head_dim != 128) || max_pages > kPagedMaxPages) return QUIP_ERR_UNSUPPORTED;
+  PagedAttnArgs a{};
+  static_cast<AttnArgs&>(a) =
+      AttnArgs{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
+               cos, sin, pos, reinterpret_cast<f16*>(kpool), reinterpret_cast<f16*>(vpool),
+               reinterpret_cast<f16*>(out), heads, kv_heads, max_len, scale, nullptr, nullptr, window};
+  a.table = table;
+  a.n_pages = n_pages;
+  a.max_pages = max_pages;
+  // the grid rule of rope_attn_decode_batched_launch with the table's capacity for max_len
+  const bool split = workspace != nullptr && (long long)max_pages * kPage > kSplitFromPos;
+  if (split) {
+    a.ws = reinterpret_cast<float*>(workspace);
+    a.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) +
+                                             (size_t)batch * heads * kSplits * (head_dim + 4) * sizeof(float));
+  }
+  const dim3 grid(heads, split ? kSplits : 1, batch);
+  const int lds = max_pages * (int)sizeof(int32_t);
+  const AttnZ none{};
+  if (head_dim == 128)
+    return launch<rope_attn_decode_kernel<128, false, 0, 0, true, PagedAttnArgs>>(grid, dim3(256), lds, stream, a, none);
+  return launch<rope_attn_decode_kernel<64, false, 0, 0, true, PagedAttnArgs>>(grid, dim3(256), lds, stream, a, none);
+}
+
+int rope_attn_ragged_paged_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                  const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                  int rows, int heads, int kv_heads, int head_dim, int max_len, int batch, int n_pages,
+                                  int max_pages, const int32_t* seg_slot, const int32_t* seg_rows, int nseg,
+                                  float scale, int window, hipStream_t stream) {
+  if (nseg < 1 || nseg > kRaggedMaxSegments || rows < 1 || batch < 1 || heads < 1 || kv_heads < 1 ||
+      heads % kv_heads != 0 || window < 0 || !paged_shape_ok(max_len, n_pages, max_pages))
+    return QUIP_ERR_BAD_SHAPE;
+  PagedRaggedArgs ra{};
+  long long total = 0, tiles = 0;
+  for (int s = 0; s < nseg; ++s) {
+    if (seg_rows[s] < 1 || seg_slot[s] < 0 || seg_slot[s] >= batch) return QUIP_ERR_BAD_SHAPE;
+    for (int t = 0; t < s; ++t)
+      if (seg_slot[t] == seg_slot[s]) return QUIP_ERR_BAD_SHAPE;     // rule (1) needs distinct slots
+    if (total + seg_rows[s] > rows) return QUIP_ERR_BAD_SHAPE;
+    ra.slot[s] = seg_slot[s];
+    ra.row0[s] = (int)total;
+    ra.rows[s] = seg_rows[s];
+    total += seg_rows[s];
+    tiles += (seg_rows[s] - 1) / kChunkTile + 1;
+  }
+  if (total != rows) return QUIP_ERR_BAD_SHAPE;
+  if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
+  if (tiles > kChunkMaxTilesY) return QUIP_ERR_UNSUPPORTED;           // callers chunk their passes
+  static_cast<ChunkArgs&>(ra.c) =
+      ChunkArgs{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
+                cos, sin, pos, reinterpret_cast<f16*>(kpool), reinterpret_cast<f16*>(vpool),
+                reinterpret_cast<f16*>(out), 0, 0, heads, kv_heads, max_len, window, scale};
+  ra.c.table = table;
+  ra.c.n_pages = n_pages;
+  ra.c.max_pages = max_pages;
+  ra.nseg = nseg;
+  const dim3 grid(heads, (unsigned)tiles);
+  return head_dim == 128 ? launch<rope_attn_paged_ragged_kernel<128>>(grid, dim3(kChunkThreads), 0, stream, ra)
+                         : launch<rope_attn_paged_ragged_kernel<64>>(grid, dim3(kChunkThreads), 0, stream, ra);
+}
+
+}  // namespace quip

@@ -199,6 +199,17 @@ int rope_attn_ragged_launch(const void* q, const void* k, const void* v, const f
                             const int64_t* pos, void* kcache, void* vcache, void* out, int rows, int heads, int kv_heads,
                             int head_dim, int max_len, int batch, const int32_t* seg_slot, const int32_t* seg_rows,
                             int nseg, float scale, int window, hipStream_t stream);
+// paged_attn.hip.h (in decode_glue.hip): the batched decode launch and the ragged launch on a paged cache -- kpool / vpool
+// (n_pages, kv_heads, 64, head_dim), table (batch, max_pages) int32 on the device; max_len: rows of cos / sin
+int rope_attn_decode_paged_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                  const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                  int batch, int heads, int kv_heads, int head_dim, int max_len, int n_pages,
+                                  int max_pages, float scale, hipStream_t stream, void* workspace, int window);
+int rope_attn_ragged_paged_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                  const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                  int rows, int heads, int kv_heads, int head_dim, int max_len, int batch, int n_pages,
+                                  int max_pages, const int32_t* seg_slot, const int32_t* seg_rows, int nseg,
+                                  float scale, int window, hipStream_t stream);
 // nll_rows.hip.h (in decode_glue.hip): per row of (rows, n) fp16 logits the log-sum-exp, the log-probability of target[row] and
 // the arg-max; lse / argmax may be null
 int nll_rows_launch(const void* logits, int rows, int n, const int64_t* target, float* logprob, float* lse,

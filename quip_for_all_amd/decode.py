@@ -772,8 +772,15 @@ class LlamaDecoder:
         q = torch.empty_like(probs).exponential_(1)
         return torch.argmax(probs / q, dim=-1)
 
-    def batched(self, batch, max_len=None):
-        """a decoder of `batch` independent sequences on this decoder's modules (batch_decode.BatchDecoder)"""
+    def batched(self, batch, max_len=None, paged=False, pages=None):
+        """a decoder of `batch` independent sequences on this decoder's modules (batch_decode.BatchDecoder); paged: its
+        KV cache is a pool of `pages` 64-position pages shared by the slots (paged_cache.PagedBatchDecoder; default: as
+        many pages as the contiguous cache has rows for)"""
+        if paged:
+            from .paged_cache import PagedBatchDecoder
+            return PagedBatchDecoder(self, batch, max_len, pages)
+        if pages is not None:
+            raise ValueError("pages: only with paged=True")
         from .batch_decode import BatchDecoder
         return BatchDecoder(self, batch, max_len)
 
