@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 14
+#define QUIP_ABI_VERSION 15
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -606,6 +606,7 @@ int quip_ffn_engine(const quip_ffn_engine_args* args, quip_stream_t stream);
  * partition; occupancy query).
  * layers: n_layers descriptors of quip_block_engine_layer_bytes() = 256 bytes each, in device memory:
  *   uint64 W[7]   Qidxs of q, k, v, o, gate, up, down        uint64 ln[2]  input / post-attention RMSNorm weights (fp16)
+ *                 (codebook 5: their launch-tiled copies, see quip_tile_codes_view below)
  *   uint64 su[7]  SU of the same seven modules (fp16)          uint64 sv[7]  SV (fp16)
  *   uint64 had3   the K x K factors packed as for quip_ffn_engine
  *   uint64 kcache, vcache   fp16 [heads, max_len, 128], row *pos is written
@@ -631,7 +632,10 @@ typedef struct quip_block_engine_args {
                               * 2: E8P12RVQ4B (int32 codes, e8p12_rvq4.py:37-45); 3: HI (int32 codes = 8 nibbles,
                               * hi.py:41-63; grid_packed_abs = the fp16 (256, 4) table [lo - 7.5, hi - 7.5, 0, 0] of a
                               * code BYTE: the row reads as a D4 row of twice the width); 4: E8P12RVQ3B (the checkpoint's
-                              * 3-byte codes, int32 (n, 3 k / 32), e8p12_rvq3.py:81-107; grid2 = the E81B table) */
+                              * 3-byte codes, int32 (n, 3 k / 32), e8p12_rvq3.py:81-107; grid2 = the E81B table);
+                              * 5: E8P12 with the seven code matrices W[0..6] in the LAUNCH-TILED layout (shape 0 only, shapes
+                              * 1 and 2: QUIP_ERR_UNSUPPORTED): q, k, v, o, down through quip_tile_codes, gate and up through
+                              * quip_tile_codes_view; everything else as for 0, and the same bits out */
   float resid_scale;         /* codebooks 2, 4: the residual scale rounded to fp16 (origin_order.cu:337-385), else ignored */
   int32_t shape;             /* 0: hidden 4096, 32 heads, n_ffn 43 x 256 (Llama-2-7B); 1: hidden 8192, 64 heads on 8 KV heads,
                               * n_ffn 7 x 4096 (Llama-2-70B; E8P12 only) -- see quip_block_engine_gqa_* below */
@@ -683,13 +687,29 @@ size_t quip_block_engine_gqa_workspace_bytes(void);
  * -- so that one load instruction of the product (16 rows x 64 bytes of a row-major matrix: origin_order.cu:388-555 walks the rows)
  * covers 1 KB of consecutive bytes: a pure read stream in the row-major pattern tops at 0.72 of the HBM peak on this part, in full
  * lines at 0.85-0.88 (tools/ubench/hbm_read.hip).  quip_tile_codes writes that copy (same size; not in place; rows % 16 == 0,
- * row_bytes % 64 == 0, both pointers 16-byte aligned): once per matrix at model load.  Shapes 0 and 2 read the checkpoint's layout. */
+ * row_bytes % 64 == 0, both pointers 16-byte aligned): once per matrix at model load.  Shape 2 reads the checkpoint's layout; shape 0
+ * reads it with codebook 0..4 and launch-tiled copies with codebook 5 (below). */
 int quip_tile_codes(const void* qidxs, void* tiled, int64_t rows, int64_t row_bytes, quip_stream_t stream);
 /* the inverse (round 6): the checkpoint's row-major matrix back from its tiled copy (same constraints).  A decode-only server keeps
  * ONE copy of the codes of a shape-1 model -- the tiled one -- and materialises a matrix in the layout the other operators read
  * (decompress_*_origorder, *_mm_origorder: register_lib.py:8-192 of the reference) into a scratch buffer only where a prompt pass
  * or the stage-wise fallback needs it (decode.py: LlamaDecoder(single_copy=True)). */
 int quip_untile_codes(const void* tiled, void* qidxs, int64_t rows, int64_t row_bytes, quip_stream_t stream);
+/* shape 0 with codebook 5 (E8P12 on launch-tiled codes): a weight request of the launch is one instruction of 64 lanes x 16 bytes for
+ * 16 rows x 64 bytes; in the checkpoint's layout its lanes touch 16 cache lines 1 KB (q, k, v, o), 2752 bytes (down) or -- gate / up, whose
+ * rows the launch reads through the (43, 256) view: rows k * 256 + j -- 256 KB apart.  The launch-tiled copies make every request one run
+ * of consecutive bytes (lane l reads base + 16 l):
+ *   q, k, v, o (4096 x 1024 bytes), down (4096 x 2752 bytes): quip_tile_codes as above;
+ *   gate, up (11008 x 1024 bytes): quip_tile_codes_view -- the (K, 256) view, K = rows / 256, column by column, each column in blocks
+ *   of 16 view rows with the last block short (K = 43: 16, 16, 11 rows) and NO padding:
+ *     view[j][b][c][q][n] (16 bytes) = bytes [64 c + 16 q, +16) of row (16 b + n) * 256 + j,
+ *     j < 256, b < ceil(K / 16), c < row_bytes / 64, q < 4, n < nb(b) = min(16, K - 16 b)
+ *   -- a column is K * row_bytes consecutive bytes, the two columns of a workgroup one run of 88064.
+ * Same size as the source; not in place, no overlap; rows % 256 == 0, row_bytes % 64 == 0, both pointers 16-byte aligned; on the GPU,
+ * once per matrix at model load (+1.63 GB resident for Llama-2-7B: the checkpoint's matrices stay what every other operator reads).
+ * quip_untile_codes_view is the inverse. */
+int quip_tile_codes_view(const void* qidxs, void* tiled, int64_t rows, int64_t row_bytes, quip_stream_t stream);
+int quip_untile_codes_view(const void* tiled, void* qidxs, int64_t rows, int64_t row_bytes, quip_stream_t stream);
 /* shape 2 (round 5): hidden 4096, 32 heads of 128 on 8 KV heads, n_ffn = 14336 = 7 x 2048 (Llama-3-8B, Mistral-7B; E8P12 only): the
  * shape-0 launch compiled for this shape.  Descriptors as for shape 0, except had3 = the 56 x 56 factors R_7 (x) H_8 of gate.had_right,
  * up.had_right (row major, 3136 fp16 each) and of down.had_left TRANSPOSED (64 rows of 72 fp16, zero padded): see decode_block.hip, QUIP_BLOCK_G8. */

@@ -625,7 +625,55 @@ int retile_codes(bool inverse, const void* src, void* dst, int64_t rows, int64_t
   return inverse ? launch<untile_codes_kernel>(grid, block, 0, (hipStream_t)stream, s, d, pieces, (int)(row_bytes / 16))
                  : launch<tile_codes_kernel>(grid, block, 0, (hipStream_t)stream, s, d, pieces, (int)(row_bytes / 16));
 }
+
+// The (K, 256) view of a gate / up matrix (rows k * 256 + j: column j of the view), column by column, in blocks of 16 view rows, the
+// last one short, without padding: view[j][b][c][q][n < nb(b)] = bytes [64 c + 16 q, +16) of row (16 b + n) * 256 + j.  One 16-byte
+// piece per thread, in the order of the tiled side; `inverse` scatters it back.
+__global__ void tile_codes_view_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, long long pieces, int row_u4, int K, int inverse) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= pieces) return;
+  const int col_u4 = K * row_u4;                       // pieces of a column: K rows
+  const int j = (int)(i / col_u4);
+  int r = (int)(i - (long long)j * col_u4);
+  const int b = r / (16 * row_u4);                     // (the blocks in front of a block are full ones)
+  r -= b * 16 * row_u4;
+  const int nb = K - 16 * b < 16 ? K - 16 * b : 16;
+  const int c = r / (4 * nb);
+  r -= c * 4 * nb;
+  const int q = r / nb, n = r - q * nb;
+  const long long rm = ((long long)(16 * b + n) * 256 + j) * row_u4 + c * 4 + q;
+  if (inverse) dst[rm] = src[i];
+  else dst[i] = src[rm];
+}
+
+int retile_codes_view(bool inverse, const void* src, void* dst, int64_t rows, int64_t row_bytes, quip_stream_t stream) {
+  if (!src || !dst) return QUIP_ERR_NULL_POINTER;
+  if (rows < 0 || row_bytes <= 0 || rows % 256 != 0 || row_bytes % 64 != 0 || row_bytes > (1 << 24) || rows > (1 << 24))
+    return QUIP_ERR_BAD_SHAPE;
+  if (rows == 0) return QUIP_OK;
+  if (!aligned16(src) || !aligned16(dst)) return QUIP_ERR_MISALIGNED;
+  {
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
+    const uintptr_t bytes = (uintptr_t)rows * (uintptr_t)row_bytes;
+    if (s0 < d0 + bytes && d0 < s0 + bytes) return QUIP_ERR_UNSUPPORTED;
+  }
+  const long long pieces = rows * (row_bytes / 16);
+  if ((rows / 256) * (row_bytes / 16) > (1ll << 30)) return QUIP_ERR_BAD_SHAPE;      // (a column's pieces: int arithmetic in the kernel)
+  const dim3 grid((unsigned)((pieces + 255) / 256)), block(256);
+  const uint4* s = reinterpret_cast<const uint4*>(src);
+  uint4* d = reinterpret_cast<uint4*>(dst);
+  const int row_u4 = (int)(row_bytes / 16), K = (int)(rows / 256);
+  return launch<tile_codes_view_kernel>(grid, block, 0, (hipStream_t)stream, s, d, pieces, row_u4, K, inverse ? 1 : 0);
+}
 }  // namespace
+
+int quip_tile_codes_view(const void* qidxs, void* tiled, int64_t rows, int64_t row_bytes, quip_stream_t stream) {
+  return retile_codes_view(false, qidxs, tiled, rows, row_bytes, stream);
+}
+
+int quip_untile_codes_view(const void* tiled, void* qidxs, int64_t rows, int64_t row_bytes, quip_stream_t stream) {
+  return retile_codes_view(true, tiled, qidxs, rows, row_bytes, stream);
+}
 
 int quip_tile_codes(const void* qidxs, void* tiled, int64_t rows, int64_t row_bytes, quip_stream_t stream) {
   return retile_codes(false, qidxs, tiled, rows, row_bytes, stream);

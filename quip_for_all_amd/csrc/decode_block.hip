@@ -146,6 +146,18 @@ constexpr int HID = 4096, NWG = 256, RPW = 16, HD = 128, NH = 32;
 #define QUIP_BLOCK_G8 0
 #endif
 constexpr bool G8 = QUIP_BLOCK_G8 != 0;
+// The launch-tiled layout of the codes (decode_block_tiled.hip compiles this file a third time with QUIP_BLOCK_TILED = 1; codebook
+// id 5 of quip_block_engine, shape 0, E8P12 in nibble mode only).  In the checkpoint's layout the 64 lanes of a weight request touch
+// 16 rows x 64 bytes: 16 cache lines 1 KB (q k v o), 2752 B (down) or 256 KB (gate / up: rows k * 256 + column) apart.  Here the
+// matrices were re-tiled once at model load so that lane l of a request reads base + 16 l:
+//   q, k, v, o, down: quip_tile_codes, tiled[rb][c][q][n] -- item (row block rb, slice s) = the 2 KB at (rb * C + 2 s) KB, C pieces per row;
+//   gate, up: quip_tile_codes_view, view[j][b][c][q][n < nb(b)] of the (43, 256) view -- a workgroup's two columns are ONE run of 88064 bytes.
+// The same codes reach the same lanes in the same order: every ISSUE requests as many loads into the same slots as before.
+#ifndef QUIP_BLOCK_TILED
+#define QUIP_BLOCK_TILED 0
+#endif
+constexpr bool TILED = QUIP_BLOCK_TILED != 0;
+static_assert(!(TILED && G8), "the launch-tiled layout: shape 0 only");
 constexpr int NKVH = G8 ? 8 : NH, GQH = NH / NKVH;              // KV heads; query heads per KV head
 constexpr int FK = G8 ? 56 : 43, FLOGL = 8, FL = 256, NFFN = FK * FL, FRB = 3;
 constexpr int NGU = G8 ? 7 : 6;                                 // gate / up items per wave (G8: 2 columns x 56 rows = 7 row blocks)
@@ -330,6 +342,29 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         vo_d[i] = (uint32_t)(((w * RPW + n) * kRowU4D + sl * 8 + q) * 16);
       }
       vo_d2b = 0u;
+    } else if constexpr (TILED) {
+      static_assert(!TILED || (!RVQ && PB == 16u), "the launch-tiled layout: plain E8P12 rows");
+      constexpr int C = kRowU4V / 4, CD = kRowU4D / 4;          // 64-byte pieces of a row: 16; down: 43 (the last slice is half a one)
+      const uint32_t lo = (uint32_t)lane * 16u;                 // (lane = 16 q + n: the tile's [q][n] order)
+      vo_row = (uint32_t)((w * C + 2 * wave) * 1024) + lo;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) vo_q[i] = (uint32_t)((((3 * w + i) & 255) * C + 2 * wave) * 1024) + lo;
+#pragma unroll
+      for (int rb = 0; rb < FRB; ++rb) {        // column 2 (w & 127) of the view: 43 KB per column, row blocks of 16, 16, 11 rows
+        constexpr int kColB = FK * kRowB;
+        const int nb = FK - 16 * rb < 16 ? FK - 16 * rb : 16;
+        const int nn = n < nb ? n : nb - 1;     // (the short block: lanes n >= 11 repeat lane 10's address, never multiplied)
+        vo_gu[rb] = (uint32_t)(2 * (w & 127) * kColB + 16 * rb * kRowB + 2 * wave * 64 * nb + (q * nb + nn) * 16);
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const int sl0 = i * kWaves + wave;
+        const int sl = sl0 < JD ? sl0 : 0;
+        vo_d[i] = (uint32_t)((w * CD + 2 * sl) * 1024) + lo;
+        // the row's last slice is a half one: piece 43 does not exist (behind the last row block: not even the bytes) -- piece 42
+        // again, its digits are zero
+        if (i == 2) vo_d2b = vo_d[i] + (2 * sl + 1 < CD ? 1024u : 0u);
+      }
     } else {
 #pragma unroll
     for (int i = 0; i < 3; ++i) vo_q[i] = (uint32_t)((((3 * w + i) & 255) * 16 + n) * kRowU4V + wave * 8 + q) * PB;
@@ -385,6 +420,30 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
   };
   // slot of an item kind: q k v -> X0-2, o -> X3, gate -> X0-2, up -> X3-5, down -> X6-8
 #define SLOT_OF(kind) ((kind) < 4 ? (kind) : (kind) - 4)
+#if QUIP_BLOCK_TILED
+  // the launch-tiled layout: the item's second piece lies 64 bytes x the rows of its block on (1 KB; 704 bytes in gate / up's block
+  // of 11 rows), the second column of gate / up 43 KB on (beyond the instruction's offset field: added to the scalar base)
+  auto ld_item_t = [&](auto off2_c, auto base_c, slot_t& da, slot_t& db, const uint4* base0, uint32_t vo) {
+    constexpr int OFF2 = decltype(off2_c)::value, BASE = decltype(base_c)::value;
+    const uint4* base = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(uni(base0)) + BASE);
+    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 nt" : "=v"(da) : "v"(vo), "s"(base) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3 nt" : "=v"(db) : "v"(vo), "s"(base), "n"(OFF2) : "memory");
+  };
+#define GU_RB(kind) ((kind) >= 4 ? ((kind) - 4) % FRB : 0)
+#define GU_OFF2(kind) std::integral_constant<int, 64 * (FK - 16 * GU_RB(kind) < 16 ? FK - 16 * GU_RB(kind) : 16)>{}
+#define GU_COL(kind) std::integral_constant<int, (kind) >= 7 ? FK * kRowB : 0>{}
+#define ISSUE(Ld, kind) do {                                                                                          \
+    if ((kind) < 3) ld_item_t(OFFC(1024), OFFC(0), qa[SLOT_OF(kind)], qb[SLOT_OF(kind)], Ld.W[(3 * w + ((kind) < 3 ? (kind) : 0)) >> 8], vo_q[(kind) < 3 ? (kind) : 0]); \
+    else if ((kind) == 3) ld_item_t(OFFC(1024), OFFC(0), qa[3], qb[3], Ld.W[3], vo_row);                               \
+    else if ((kind) < 10) ld_item_t(GU_OFF2(kind), GU_COL(kind), qa[SLOT_OF(kind)], qb[SLOT_OF(kind)], Ld.W[4 + mgu], vo_gu[GU_RB(kind)]); \
+    else if ((kind) < 12) ld_item_t(OFFC(1024), OFFC(0), qa[SLOT_OF(kind)], qb[SLOT_OF(kind)], Ld.W[6], vo_d[(kind) >= 10 ? ((kind) - 10) % 3 : 0]); \
+    else {                                                                                                             \
+      const uint4* bd_ = uni(Ld.W[6]);                                                                                 \
+      asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 nt" : "=v"(qa[8]) : "v"(vo_d[2]), "s"(bd_) : "memory");    \
+      asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(qb[8]) : "v"(vo_d2b), "s"(bd_) : "memory");              \
+    }                                                                                                                  \
+  } while (0)
+#else
 #define ISSUE(Ld, kind) do {                                                                                          \
     if ((kind) < 3) ld_item(qa[SLOT_OF(kind)], qb[SLOT_OF(kind)], Ld.W[(3 * w + ((kind) < 3 ? (kind) : 0)) >> 8], vo_q[(kind) < 3 ? (kind) : 0]); \
     else if ((kind) == 3) ld_item(qa[3], qb[3], Ld.W[3], vo_row);                                                      \
@@ -397,6 +456,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(qb[8]) : "v"(vo_d2b), "s"(bd_) : "memory");              \
     }                                                                                                                  \
   } while (0)
+#endif
   // RVQ: the same with a compile-time byte offset (the second virtual slice of a row block is 1 KB further in the row)
   auto ld_item_o = [&](auto off_c, slot_t& da, slot_t& db, const uint4* base0, uint32_t vo) {
     constexpr int OFF = decltype(off_c)::value / 16 * (int)PB;      // (written in RVQ4B's bytes)
@@ -2028,6 +2088,9 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
   }
 #undef BSTAMP
 #undef ISSUE
+#undef GU_RB
+#undef GU_OFF2
+#undef GU_COL
 #undef SLOTS
 #undef OFFC
 #undef ISSUE_RVQ_QKV
@@ -2079,6 +2142,16 @@ int block_engine_g8_launch(const BlockEngineArgs& in, hipStream_t stream) {
   if (eng_rep_env() == 24) return launch_persistent<decode_block_kernel<24>>(NWG, kThreads, BLds<24>::kBytes, stream, a);
   return launch_persistent<decode_block_kernel<4>>(NWG, kThreads, BLds<4>::kBytes, stream, a);
 }
+#elif QUIP_BLOCK_TILED
+// shape 0 on the launch-tiled layout of the codes (codebook id 5): the shipped E8P12 nibble kernel; workspace, descriptors and the
+// support query are shape 0's (block_engine_workspace_bytes, block_engine_layer_bytes, block_engine_supported)
+int block_engine_tiled_launch(const BlockEngineArgs& in, hipStream_t stream) {
+  if (in.n_layers < 1 || in.n_layers > 146) return QUIP_ERR_BAD_SHAPE;     // up to 7 hand-offs per block, 10-bit counter
+  if (in.codebook != 5) return QUIP_ERR_UNSUPPORTED;
+  BlockArgs a = block_args_of<BlockArgs, BlockLayer>(in);   // (resid_scale 0, no grid2)
+  a.tail = tail_args(in);
+  return launch_persistent<decode_block_kernel<4>>(NWG, kThreads, BLds<4>::kBytes, stream, a);
+}
 #else
 size_t block_engine_workspace_bytes() { return kWsBytes; }
 size_t block_engine_layer_bytes() { return sizeof(BlockLayer); }
@@ -2103,6 +2176,7 @@ int block_engine_launch(const BlockEngineArgs& in, hipStream_t stream) {
   if (in.codebook == 3) return go(kernel_c<decode_block_kernel<64, true, true>>, BLds<64, true>::kBytes);
   if (in.codebook == 2) { a.resid_scale = in.resid_scale; return go(kernel_c<decode_block_kernel<16, true>>, BLds<16, true>::kBytes); }
   if (in.codebook == 1) return go(kernel_c<decode_block_kernel<64>>, BLds<64>::kBytes);
+  if (in.codebook == 5) return block_engine_tiled_launch(in, stream);     // E8P12 on the launch-tiled codes: decode_block_tiled.hip
   if (in.codebook != 0) return QUIP_ERR_UNSUPPORTED;
   // A/B: QUIP_ENG_REP=16: byte tables, two-way conflicts on both; 24: byte tables, 32 / 16 copies (round 5); default: nibble mode
   if (eng_rep_env() == 16) return go(kernel_c<decode_block_kernel<16>>, BLds<16>::kBytes);

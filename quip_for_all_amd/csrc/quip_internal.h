@@ -250,7 +250,7 @@ struct BlockEngineArgs {
   void* dbg = nullptr;
   int n_layers = 0, max_len = 0, dbg_layer = -1;
   float rms_eps = 1e-5f, attn_scale = 1.f;
-  int codebook = 0;                  // 0: E8P12 (grid = grid_packed_abs), 1: D4 (grid = the fp16 (256, 4) table), 2: E8P12RVQ4B, 3: HI (grid = the byte table), 4: E8P12RVQ3B
+  int codebook = 0;                  // 0: E8P12 (grid = grid_packed_abs), 1: D4 (grid = the fp16 (256, 4) table), 2: E8P12RVQ4B, 3: HI (grid = the byte table), 4: E8P12RVQ3B, 5: E8P12 on launch-tiled codes (shape 0)
   float resid_scale = 0.f;           // codebooks 2, 4: the fp16 residual scale
   const void* grid2 = nullptr;       // codebook 4 (E8P12RVQ3B): int8 (256, 8) E81B table
   // the whole token in the launch (token_tail.hip.h; shapes 0 and 2).  lm_head == nullptr: blocks only, h_in -> h_out.  Else
@@ -267,6 +267,9 @@ bool block_engine_supported(int hidden, int heads, int kv_heads, int head_dim, i
 size_t block_engine_workspace_bytes();
 size_t block_engine_layer_bytes();
 int block_engine_launch(const BlockEngineArgs& in, hipStream_t stream);
+// shape 0, codebook 5: E8P12 with the code matrices in the launch-tiled layout (decode_block.hip compiled with QUIP_BLOCK_TILED:
+// decode_block_tiled.hip); block_engine_launch hands it over
+int block_engine_tiled_launch(const BlockEngineArgs& in, hipStream_t stream);
 // the same for the grouped-query 8192-wide shape (decode_block_gqa.hip: Llama-2-70B; E8P12): its own descriptor vectors
 // (permuted, see include/quip_mi355.h) and workspace
 bool block_engine_gqa_supported(int hidden, int heads, int kv_heads, int head_dim, int n_ffn, int K);

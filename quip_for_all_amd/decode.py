@@ -31,6 +31,7 @@ from .qlinear import (QuantLinear, _engine_had3, chain_planes, chain_supported, 
                       fused_in_supported, gemv_chain, gemv_fused, gemv_group_unfused, gemv_unfused, out_transform_group)
 
 PROJECTIONS = ("q", "k", "v", "o", "gate", "up", "down")      # the seven QuantLinear modules of a decoder block
+_ENGINE_CODEBOOK_TILED = 5     # E8P12 on launch-tiled copies of the codes (shape 0: LlamaDecoder._init_block_engine)
 _ENGINE_CODEBOOK = {"E8P12": 0, "D4": 1, "E8P12RVQ4B": 2, "HI": 3, "E8P12RVQ3B": 4}     # the persistent launch's table modes
 
 
@@ -115,6 +116,32 @@ def untile_codes(tiled, rows, row_bytes, out):
         capi.check(capi.lib().quip_untile_codes(tiled.data_ptr(), out.data_ptr(), rows, row_bytes,
                                                 torch.cuda.current_stream(tiled.device).cuda_stream), "quip_untile_codes")
     return out
+
+
+def tile_codes_view(qidxs, inverse=False):
+    """The shape-0 launch's layout of a gate / up matrix (include/quip_mi355.h: quip_tile_codes_view; decode_block_tiled.hip): the
+    (K, 256) view of its rows -- rows k * 256 + j -- column by column, each column in blocks of 16 view rows with the last one short
+    and no padding: view[j][b][c][q][n < nb(b)] = bytes [64 c + 16 q, +16) of row (16 b + n) * 256 + j.  `qidxs`: the (rows, ...)
+    matrix on the GPU -> a flat uint8 tensor of the same size; inverse=True: the tiled bytes (given with the matrix's 2-D shape)
+    -> the row-major bytes."""
+    from . import capi
+    b = qidxs.detach().contiguous().view(torch.uint8).reshape(qidxs.shape[0], -1)
+    rows, rb = b.shape
+    if not b.is_cuda:
+        raise capi.QuipNativeError("tile_codes_view: the codes must be on the GPU (there is no CPU path)")
+    out = torch.empty(rows * rb, dtype=torch.uint8, device=b.device)
+    fn = capi.lib().quip_untile_codes_view if inverse else capi.lib().quip_tile_codes_view
+    with torch.cuda.device(b.device):
+        capi.check(fn(b.data_ptr(), out.data_ptr(), rows, rb, torch.cuda.current_stream(b.device).cuda_stream),
+                   "quip_untile_codes_view" if inverse else "quip_tile_codes_view")
+    return out
+
+
+def _launch_tiled_codes(L):
+    """shape 0 with E8P12: the seven code matrices of block L in the launch's own layout (decode_block_tiled.hip: every weight
+    request one run of consecutive bytes) -- one more copy of the codes in HBM (+1.63 GB for Llama-2-7B), made once per model and
+    again by every rebuild of the descriptors; the modules' `Qidxs` stay what everything else reads"""
+    return [tile_codes_view(L[k].Qidxs) if k in ("gate", "up") else tile_codes(L[k].Qidxs) for k in PROJECTIONS]
 
 
 def qidxs_nbytes(m):
@@ -424,6 +451,9 @@ class LlamaDecoder:
         self.eng_codebook, self.eng_resid_scale, self.eng_shape = 0, 0.0, 0
         self._eng_keep = self._eng_sig = self._kv_ptr_host = None
         self.token_tail = os.environ.get("QUIP_TOKEN_TAIL", "1") != "0"     # the token's tail inside that launch (step())
+        # shape 0 with E8P12: the launch streams launch-tiled copies of the codes (QUIP_ENG_TILED=0: the checkpoint's layout, for A/B);
+        # read once, so that a rebuild of the descriptors (reset()) keeps the layout the decoder was built with
+        self.eng_tiled = os.environ.get("QUIP_ENG_TILED", "1") != "0"
         d4 = all(getattr(m.codebook, "id", None) in ("D4", "E8P12RVQ4B", "HI", "E8P12RVQ3B") for m in L0.values() if isinstance(m, QuantLinear))
         gqa_shape = self.fused_prologue and self.chain and s.kv_heads != s.heads and s.hidden in (8192, 4096)   # (csrc/decode_block_gqa.hip; decode_block_g8.hip)
         if ((self.ffn_eng or gqa_shape or (d4 and self.fused_prologue and self.chain and os.environ.get("QUIP_FFN_ENGINE", "1") != "0"))
@@ -464,6 +494,9 @@ class LlamaDecoder:
                 ok = ok and plain(L["down"], s.ffn, s.hidden) and L["down"].K_right == 1
             if not ok:
                 return
+            # shape 0 with E8P12 streams launch-tiled copies of the codes (codebook id 5; QUIP_ENG_TILED=0: the checkpoint's layout,
+            # id 0, for A/B).  They live in _eng_keep only: `Qidxs` stays the truth (_engine_signature reads ITS pointer and version)
+            launch_tiled = not gqa and not g8 and cbid == "E8P12" and self.eng_tiled
             keep, rec = [], np.zeros((len(self.layers), 32), dtype=np.uint64)
             # (a rebuild -- reset() after the modules were edited: the previous descriptors' tensors, for shape 1 a whole tiled
             #  copy of the codes, go BEFORE the new ones are made, not after: no third copy of the weights in between)
@@ -474,8 +507,9 @@ class LlamaDecoder:
                 su, sv, ln = _engine_vectors(L, 16 if gqa else 8)
                 had3 = _had3_mix(L, self.dev) if gqa else (_had3_k56(L, self.dev) if g8
                                                            else _engine_had3(L["gate"], L["up"], L["down"]))
-                wq = _tiled_codes(mods, self.single_copy) if gqa else [m.Qidxs for m in mods]
-                keep += su + sv + ln + [had3] + (wq if gqa else [])
+                wq = (_tiled_codes(mods, self.single_copy) if gqa else
+                      (_launch_tiled_codes(L) if launch_tiled else [m.Qidxs for m in mods]))
+                keep += su + sv + ln + [had3] + (wq if gqa or launch_tiled else [])
                 ptrs = ([t.data_ptr() for t in wq] + [t.data_ptr() for t in ln] + [t.data_ptr() for t in su]
                         + [t.data_ptr() for t in sv] + [had3.data_ptr(), self.kcache[i].data_ptr(), self.vcache[i].data_ptr()])
                 rec[i, :26] = np.array(ptrs, dtype=np.uint64)
@@ -485,7 +519,7 @@ class LlamaDecoder:
             self.eng_layers = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to(self.dev)
             self.eng_shape = 1 if gqa else (2 if g8 else 0)
             self.eng_ws = _R.block_engine_workspace(self.dev, self.eng_shape)
-            self.eng_codebook = _ENGINE_CODEBOOK[cbid]
+            self.eng_codebook = _ENGINE_CODEBOOK_TILED if launch_tiled else _ENGINE_CODEBOOK[cbid]
             cb0 = L0["q"].codebook
             self.eng_grid = cb0.grid if cbid == "D4" else (cb0._virtual_grid(self.dev) if cbid == "HI" else cb0.grid_packed_abs)
             self.eng_resid_scale = float(getattr(cb0, "planes_resid_scale", 0.0)) if cbid in ("E8P12RVQ4B", "E8P12RVQ3B") else 0.0

@@ -25,7 +25,7 @@ args = (dec.eng_layers, h, dec.pos, dec.cos, dec.sin, dec.eng_grid, dec.eng_ws, 
 acc = []
 for it in range(8):
     dbg.zero_()
-    torch.ops.quip_lib.block_engine(*args, dbg, dl | 0x10000)
+    torch.ops.quip_lib.block_engine(*args, dbg, dl | 0x10000, dec.eng_codebook)
     torch.cuda.synchronize()
     if it >= 2:
         acc.append(dbg.cpu().numpy().reshape(256, 32).astype(np.float64))

@@ -37,7 +37,7 @@ if tail:
         dec.pos.fill_(pos0)
         torch.ops.quip_lib.block_engine_token(dec.eng_layers, dec.tok, dec.pos, dec.embed, dec.final_norm, dec.lm_head, logits,
                                               dec.cos, dec.sin, dec.eng_grid, dec.eng_ws, layers, dec.max_len, shape.rms_eps,
-                                              1.0 / math.sqrt(128), dbg, dl | 0x10000, 0, 0.0, dec.eng_shape)
+                                              1.0 / math.sqrt(128), dbg, dl | 0x10000, dec.eng_codebook, 0.0, dec.eng_shape)
         torch.cuda.synchronize()
         if it >= 2:
             runs.append(dbg.cpu().numpy().reshape(256, 32)[:, :5].astype(np.float64) / 100.0)      # us
@@ -63,7 +63,7 @@ for it in range(6):
     dbg.zero_()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    torch.ops.quip_lib.block_engine(*args, dbg, dl, 0, 0.0, dec.eng_shape)
+    torch.ops.quip_lib.block_engine(*args, dbg, dl, dec.eng_codebook, 0.0, dec.eng_shape)
     e1.record()
     torch.cuda.synchronize()
     if it >= 2:

@@ -26,7 +26,8 @@ with torch.no_grad():
     (hf,) = out_transform_group([L["down"]], [zd], residual=[h2])
     # engine
     out = torch.ops.quip_lib.block_engine(dec.eng_layers, h.reshape(-1), dec.pos, dec.cos, dec.sin,
-                                          L["q"].codebook.grid_packed_abs, dec.eng_ws, 1, dec.max_len, s.rms_eps, 1.0 / math.sqrt(128))
+                                          L["q"].codebook.grid_packed_abs, dec.eng_ws, 1, dec.max_len, s.rms_eps, 1.0 / math.sqrt(128),
+                                          None, -1, dec.eng_codebook)
     torch.cuda.synchronize()
 print("status", dec.engine_status())
 ws = dec.eng_ws.cpu().numpy()
