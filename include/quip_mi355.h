@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 15
+#define QUIP_ABI_VERSION 16
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -530,6 +530,32 @@ int quip_rope_attn_ragged_paged_f16(const void* q, const void* k, const void* v,
                                     int32_t batch, int32_t n_pages, int32_t max_pages, const int32_t* seg_slot,
                                     const int32_t* seg_rows, int32_t nseg, float scale, int32_t window,
                                     quip_stream_t stream);
+/* ---- the two paged launches on an FP8 (OCP e4m3fn) KV cache (ABI 16) --------------------------------------------------
+ * The _f16 signatures plus k_exp, v_exp.  kpool / vpool [n_pages, kv_heads, 64, head_dim] hold ONE BYTE per element;
+ * q, k, v, out stay fp16.  Same table, same 64-position pages, same address rule (in bytes), same range rule.
+ * Format: a stored byte c of the K pool means e4m3fn(c) * 2^k_exp, of the V pool e4m3fn(c) * 2^v_exp -- one
+ *   power-of-two scale per pool and call, an integer in [-8, 7] (else QUIP_ERR_BAD_SHAPE).  For these exponents every
+ *   one of the 254 non-NaN codes times 2^e is an exact, finite fp16 value: dequantisation is exact, and a call gives the
+ *   output bits of the _f16 call on pools holding the dequantised bytes whenever the rows it appends are representable.
+ * Quantisation on append: x * 2^-e in fp32 (exact); finite values beyond +-448 and +-inf saturate to +-448 (0x7e /
+ *   0xfe); NaN stays NaN ((byte & 0x7f) == 0x7f), so a poisoned row stays visible; everything else rounds to nearest
+ *   even, subnormals included.
+ * Round-trip rule: the rows a call appends are used by that call as dequant(quant(row)) -- the decode call scores and
+ *   accumulates the current token's key / value as stored, the ragged call does so for every row of its own chunk.  A
+ *   row's result is therefore the same whether a later call finds its keys in the cache or this call found them in its
+ *   inputs: any split of a chunk into consecutive ragged calls gives the same output bits and the same pool bytes.
+ * Everything the _f16 calls refuse is refused alike. */
+int quip_rope_attn_decode_paged_f8(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                   const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                   int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t max_len,
+                                   int32_t n_pages, int32_t max_pages, float scale, int32_t window, void* workspace,
+                                   quip_stream_t stream, int32_t k_exp, int32_t v_exp);
+int quip_rope_attn_ragged_paged_f8(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                   const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                   int32_t rows, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t max_len,
+                                   int32_t batch, int32_t n_pages, int32_t max_pages, const int32_t* seg_slot,
+                                   const int32_t* seg_rows, int32_t nseg, float scale, int32_t window,
+                                   quip_stream_t stream, int32_t k_exp, int32_t v_exp);
 /* Greedy tail over `batch` rows of n fp16 logits (row-major, [batch, n]): tok[b] = first index of the largest logit of
  * row b (torch.argmax's tie rule; an all-NaN / all -inf row gives 0), pos[b] += 1 -- one workgroup per row. */
 int quip_argmax_step_batched_f16(const void* logits, int32_t batch, int32_t n, void* tok, void* pos,

@@ -25,6 +25,40 @@ __device__ __forceinline__ void unpack8h(const uint4& u, float o[8]) {
   }
 }
 
+// ---- OCP e4m3fn cache rows (the fp8 paged launches, paged_attn.hip.h): a stored byte c means e4m3fn(c) * 2^e ----------
+// 8 stored bytes -> the eight floats unpack8h gets from the fp16 row of the same values; sc = 2^e, the product is exact
+__device__ __forceinline__ void unpack8f8(const uint2& u, float sc, float o[8]) {
+  const uint32_t w[2] = {u.x, u.y};
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+    o[4 * i] = had::fmul(lo[0], sc);
+    o[4 * i + 1] = had::fmul(lo[1], sc);
+    o[4 * i + 2] = had::fmul(hi[0], sc);
+    o[4 * i + 3] = had::fmul(hi[1], sc);
+  }
+}
+
+// eight floats -> 8 bytes: x * 2^-e (isc, exact), finite values beyond +-448 and +-inf saturate to +-448, NaN stays NaN
+// (compares, not fminf / fmaxf: those would swallow it), everything else rounds to nearest even, subnormals included.
+// The saturation is done here: the conversion's own overflow behaviour is never reached.
+__device__ __forceinline__ uint2 quant8f8(const float x[8], float isc) {
+  float y[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    y[i] = had::fmul(x[i], isc);
+    y[i] = y[i] > 448.f ? 448.f : y[i];
+    y[i] = y[i] < -448.f ? -448.f : y[i];
+  }
+  uint2 u;
+  u.x = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false), true);
+  u.y = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], 0, false), true);
+  return u;
+}
+
+// 2^e as a float, e in [-126, 127]
+__device__ __forceinline__ float exp2i(int e) { return as_f32((uint32_t)(127 + e) << 23); }
+
 // rotary embedding (HF half-rotation) of the 8 dims [d0, d0 + 8) of one head vector; result
 // rounded to fp16 like the eager graph does
 template <int HD>

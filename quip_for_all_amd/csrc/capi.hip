@@ -796,6 +796,39 @@ int quip_rope_attn_ragged_paged_f16(const void* q, const void* k, const void* v,
                                        (hipStream_t)stream);
 }
 
+int quip_rope_attn_decode_paged_f8(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                   const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                   int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t max_len,
+                                   int32_t n_pages, int32_t max_pages, float scale, int32_t window, void* workspace,
+                                   quip_stream_t stream, int32_t k_exp, int32_t v_exp) {
+  if (!q || !k || !v || !cos || !sin || !pos || !table || !kpool || !vpool || !out) return QUIP_ERR_NULL_POINTER;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kpool) || !aligned16(vpool) ||
+      (reinterpret_cast<uintptr_t>(pos) & 7) || (reinterpret_cast<uintptr_t>(table) & 3))
+    return QUIP_ERR_MISALIGNED;
+  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
+  if (window < 0) return QUIP_ERR_BAD_SHAPE;
+  return rope_attn_decode_paged_f8_launch(q, k, v, cos, sin, pos, table, kpool, vpool, out, batch, heads, kv_heads,
+                                          head_dim, max_len, n_pages, max_pages, scale, (hipStream_t)stream, workspace,
+                                          window, k_exp, v_exp);
+}
+
+int quip_rope_attn_ragged_paged_f8(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                   const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                   int32_t rows, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t max_len,
+                                   int32_t batch, int32_t n_pages, int32_t max_pages, const int32_t* seg_slot,
+                                   const int32_t* seg_rows, int32_t nseg, float scale, int32_t window,
+                                   quip_stream_t stream, int32_t k_exp, int32_t v_exp) {
+  if (!q || !k || !v || !cos || !sin || !pos || !table || !kpool || !vpool || !out || !seg_slot || !seg_rows)
+    return QUIP_ERR_NULL_POINTER;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kpool) || !aligned16(vpool) || !aligned16(out) ||
+      !aligned16(cos) || !aligned16(sin) || (reinterpret_cast<uintptr_t>(pos) & 7) ||
+      (reinterpret_cast<uintptr_t>(table) & 3))
+    return QUIP_ERR_MISALIGNED;
+  return rope_attn_ragged_paged_f8_launch(q, k, v, cos, sin, pos, table, kpool, vpool, out, rows, heads, kv_heads,
+                                          head_dim, max_len, batch, n_pages, max_pages, seg_slot, seg_rows, nseg, scale,
+                                          window, (hipStream_t)stream, k_exp, v_exp);
+}
+
 int quip_argmax_step_batched_f16(const void* logits, int32_t batch, int32_t n, void* tok, void* pos,
                                  quip_stream_t stream) {
   if (!logits || !tok || !pos) return QUIP_ERR_NULL_POINTER;

@@ -57,6 +57,7 @@ struct ChunkArgs {
   int heads, kv_heads, max_len, window;
   float scale;
   static constexpr bool kPaged = false;
+  static constexpr bool kFp8 = false;
 };
 
 // A chunk on a PAGED cache (paged_attn.hip.h): kcache / vcache are page pools [n_pages, kv_heads, 64, HD], key tile j
@@ -65,6 +66,15 @@ struct PagedChunkArgs : ChunkArgs {
   const int32_t* table;    // the slot's row of the block table: max_pages entries, -1: none
   int n_pages, max_pages;
   static constexpr bool kPaged = true;
+};
+
+// The same on pools of OCP e4m3fn bytes (one byte per element; a stored byte c means e4m3fn(c) * 2^k_exp in the K pool,
+// e4m3fn(c) * 2^v_exp in the V pool).  A cached 8-byte chunk is converted to the 16-byte fp16 chunk that goes to LDS
+// (exact); a row of the chunk itself is quantised, stored as those bytes and staged as dequant(quant(.)), so rule (1)'s
+// "the bits of the cached row" and with it rule (2) keep holding.
+struct PagedChunkArgsF8 : PagedChunkArgs {
+  int k_exp, v_exp;        // in [-8, 7] (the launcher checks)
+  static constexpr bool kFp8 = true;
 };
 
 typedef float cf32x16 __attribute__((ext_vector_type(16)));
@@ -85,10 +95,13 @@ __device__ __forceinline__ cf16x4 lds_read_tr16(const unsigned char* p) {
 // One (64-row query tile, head) of a chunk: the whole body of the launch.  `tile` is the query tile inside the chunk
 // `a` describes (wave uniform).  Shared, inlined, by rope_attn_chunk_kernel and the ragged launch (ragged_attn.hip.h),
 // which points `a` at one segment of its rows first.  A: ChunkArgs, or PagedChunkArgs -- the same code with the cached
-// rows of key tile jt read from, and the chunk's rows appended to, page table[jt] (one wave-uniform lookup per tile).
+// rows of key tile jt read from, and the chunk's rows appended to, page table[jt] (one wave-uniform lookup per tile);
+// or PagedChunkArgsF8, the paged code on byte pools (see the struct).  From LDS onwards nothing differs.
 template <int HD, class A>
 __device__ __forceinline__ void chunk_tile_body(const A& a, const int tile) {
   constexpr bool PAGED = A::kPaged;
+  constexpr bool FP8 = A::kFp8;
+  static_assert(!FP8 || PAGED, "the fp8 cache is a paged cache");
   constexpr int NCH = HD / 8;                       // 16-byte chunks per row
   constexpr int KROW = HD * 2, VROW = HD * 2 + 64;  // bytes per K / V row in LDS
   constexpr int NIT = kChunkTile * NCH / kChunkThreads;
@@ -132,6 +145,17 @@ __device__ __forceinline__ void chunk_tile_body(const A& a, const int tile) {
   const bool appender = h % group == 0;
   const f16* kc = a.kcache + (size_t)kvh * a.max_len * HD;      // (contiguous: this head's KV head, row 0)
   const f16* vc = a.vcache + (size_t)kvh * a.max_len * HD;
+  float ksc = 1.f, vsc = 1.f, kisc = 1.f, visc = 1.f;      // fp8: 2^e and 2^-e of the two pools
+  if constexpr (FP8) {
+    ksc = attn::exp2i(a.k_exp), kisc = attn::exp2i(-a.k_exp);
+    vsc = attn::exp2i(a.v_exp), visc = attn::exp2i(-a.v_exp);
+  }
+  // fp8: 8 stored bytes -> the fp16 chunk of the values they mean
+  const auto chunk_of = [](const uint2& u, float sc) {
+    float f[8];
+    attn::unpack8f8(u, sc, f);
+    return make_uint4(pack_f16(f[0], f[1]), pack_f16(f[2], f[3]), pack_f16(f[4], f[5]), pack_f16(f[6], f[7]));
+  };
 
   // Q^T fragments (B operand): lane (r, hh) holds dims [16 ks + 8 hh, + 8) of its query row, rotated, fp16
   f16x8 qf[KS];
@@ -170,7 +194,11 @@ __device__ __forceinline__ void chunk_tile_body(const A& a, const int tile) {
       uint4 kk = make_uint4(0, 0, 0, 0), vv = make_uint4(0, 0, 0, 0);
       if (t >= kfirst && t <= p_hi) {
         if (t < pos) {
-          if constexpr (PAGED) {
+          if constexpr (FP8) {      // (offsets count elements: bytes here)
+            const size_t at = page0 + (size_t)kr * HD + c * 8;
+            kk = chunk_of(*reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(a.kcache) + at), ksc);
+            vv = chunk_of(*reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(a.vcache) + at), vsc);
+          } else if constexpr (PAGED) {
             kk = *reinterpret_cast<const uint4*>(a.kcache + page0 + (size_t)kr * HD + c * 8);
             vv = *reinterpret_cast<const uint4*>(a.vcache + page0 + (size_t)kr * HD + c * 8);
           } else {
@@ -186,13 +214,26 @@ __device__ __forceinline__ void chunk_tile_body(const A& a, const int tile) {
 #pragma unroll
           for (int x = 0; x < 8; ++x) { c8[x] = cs[x]; s8[x] = sn[x]; }
           attn::rope8<HD>(krow, c8, s8, c * 8, o);
-          kk.x = pack_f16(o[0], o[1]); kk.y = pack_f16(o[2], o[3]);
-          kk.z = pack_f16(o[4], o[5]); kk.w = pack_f16(o[6], o[7]);
-          vv = *reinterpret_cast<const uint4*>(a.v + ((size_t)i * a.kv_heads + kvh) * HD + c * 8);
-          if (appender && i >= i0) {   // (i <= i0 + nrow - 1 by t <= p_hi): this tile's own rows
-            const size_t at = PAGED ? page0 + (size_t)kr * HD : ((size_t)kvh * a.max_len + t) * HD;
-            *reinterpret_cast<uint4*>(a.kcache + at + c * 8) = kk;
-            *reinterpret_cast<uint4*>(a.vcache + at + c * 8) = vv;
+          if constexpr (FP8) {
+            float f[8];
+            attn::unpack8h(*reinterpret_cast<const uint4*>(a.v + ((size_t)i * a.kv_heads + kvh) * HD + c * 8), f);
+            const uint2 kq = attn::quant8f8(o, kisc), vq = attn::quant8f8(f, visc);
+            kk = chunk_of(kq, ksc);
+            vv = chunk_of(vq, vsc);
+            if (appender && i >= i0) {
+              const size_t at = page0 + (size_t)kr * HD + c * 8;
+              *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(a.kcache) + at) = kq;
+              *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(a.vcache) + at) = vq;
+            }
+          } else {
+            kk.x = pack_f16(o[0], o[1]); kk.y = pack_f16(o[2], o[3]);
+            kk.z = pack_f16(o[4], o[5]); kk.w = pack_f16(o[6], o[7]);
+            vv = *reinterpret_cast<const uint4*>(a.v + ((size_t)i * a.kv_heads + kvh) * HD + c * 8);
+            if (appender && i >= i0) {   // (i <= i0 + nrow - 1 by t <= p_hi): this tile's own rows
+              const size_t at = PAGED ? page0 + (size_t)kr * HD : ((size_t)kvh * a.max_len + t) * HD;
+              *reinterpret_cast<uint4*>(a.kcache + at + c * 8) = kk;
+              *reinterpret_cast<uint4*>(a.vcache + at + c * 8) = vv;
+            }
           }
         }
       }

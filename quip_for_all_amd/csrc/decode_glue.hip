@@ -23,6 +23,8 @@
 // its own cache slice [b] (the bs=1 layout), its own partial states and arrival counters.  Per sequence the code path
 // is the bs=1 kernel's (same lane groups, key order, split rule and merge), so every sequence's output and cache rows
 // are bit identical to a bs=1 launch on that sequence alone.
+#include <type_traits>
+
 #include "attn_query.hip.h"
 #include "had_device.hip.h"
 #include "quip_device.hip.h"
@@ -55,6 +57,7 @@ struct AttnArgs {
   unsigned* counters;  // split mode: arrivals per head (zero between launches)  (batched: per (sequence, head))
   int window;          // sliding-window attention (Mistral: config.sliding_window): positions (pos - window, pos]; <= 0: [0, pos]
   static constexpr bool kPaged = false;
+  static constexpr bool kFp8 = false;
 };
 
 // The batched launch on a PAGED cache (paged_attn.hip.h): kcache / vcache are page pools, a row is found through the
@@ -64,6 +67,12 @@ struct PagedAttnArgs : AttnArgs {
   const int32_t* table;   // [B, max_pages]: page of positions [64 j, 64 j + 64) of sequence b, -1: none
   int n_pages, max_pages; // kcache / vcache: [n_pages, kv_heads, kPage, HD]
   static constexpr bool kPaged = true;
+};
+// The same on pools of OCP e4m3fn bytes (paged_attn.hip.h): kcache / vcache point at one byte per element, a stored
+// byte c of the K pool means e4m3fn(c) * 2^k_exp, of the V pool e4m3fn(c) * 2^v_exp.
+struct PagedAttnArgsF8 : PagedAttnArgs {
+  int k_exp, v_exp;       // in [-8, 7] (the launcher checks): every code times 2^e is an exact fp16 value
+  static constexpr bool kFp8 = true;
 };
 
 constexpr int kSplits = 8;  // workgroups per head for long contexts (grid.y)
@@ -77,15 +86,20 @@ __host__ __device__ constexpr int fht16_barriers(int logl) { return logl <= 8 ? 
 // SEQ: the batched launch -- blockIdx.z selects the sequence; the pointers move to its tensors before anything is read.
 // Args: AttnArgs, or PagedAttnArgs (SEQ only) -- the same walk, split rule, window rule and merge with every cache row
 // addressed through the sequence's block-table row, which the workgroup validates and brings into LDS first.
+// PagedAttnArgsF8: the paged walk on byte pools -- a lane loads 8 bytes per key instead of 16 and converts them to the
+// eight floats the fp16 kernel unpacks (exact), and the new row is replaced by dequant(quant(.)) before it is used at
+// t == pos, so what is scored now is what a later launch finds in the cache.
 template <int HD, bool ZIN, int LQ = 0, int LKV = 0, bool SEQ = false, class Args = AttnArgs>
 __global__ __launch_bounds__(!ZIN ? 256 : (LQ == 0 ? 768 : (1 << LQ) / 16 + 2 * ((1 << LKV) / 16)))
 void rope_attn_decode_kernel(Args a, AttnZ zz) {
   constexpr bool PAGED = Args::kPaged;
+  constexpr bool FP8 = Args::kFp8;
   constexpr int LPK = HD / 8;        // lanes per key
   constexpr int NG = 256 / LPK;      // key groups per workgroup
   constexpr int U = 4;               // keys in flight per group
   static_assert(!(SEQ && ZIN), "the raw-GEMV-input variants are bs=1 only");
   static_assert(!PAGED || SEQ, "the paged cache belongs to the batched launch");
+  static_assert(!FP8 || PAGED, "the fp8 cache is a paged cache");
   __shared__ float s_m[NG], s_l[NG];
   __shared__ float s_acc[NG][HD + 4];
   const int tid = threadIdx.x, h = blockIdx.x;
@@ -217,6 +231,17 @@ void rope_attn_decode_kernel(Args a, AttnZ zz) {
   attn::rope8<HD>(kh, c8, s8, d0, kn);
   const uint4 vraw = *reinterpret_cast<const uint4*>(vh + d0);
   attn::unpack8h(vraw, vn);
+  // fp8: the row as stored -- its bytes, and in kn / vn the values those bytes mean
+  uint2 knq{}, vnq{};
+  float ksc = 1.f, vsc = 1.f;
+  if constexpr (FP8) {
+    ksc = attn::exp2i(a.k_exp);
+    vsc = attn::exp2i(a.v_exp);
+    knq = attn::quant8f8(kn, attn::exp2i(-a.k_exp));
+    vnq = attn::quant8f8(vn, attn::exp2i(-a.v_exp));
+    attn::unpack8f8(knq, ksc, kn);
+    attn::unpack8f8(vnq, vsc, vn);
+  }
 #pragma unroll
   for (int i = 0; i < 8; ++i) q8[i] *= a.scale;
   // row t of this head's KV head: contiguous, base + t rows; paged, row t & 63 of the head's part of page table[t >> 6]
@@ -230,7 +255,12 @@ void rope_attn_decode_kernel(Args a, AttnZ zz) {
       return (size_t)t * HD;
     }
   };
-  if (h % group == 0 && grp == 0 && sidx == 0) {   // append the new row (StaticCache.update)
+  if constexpr (FP8) {   // (row offsets count elements: bytes here)
+    if (h % group == 0 && grp == 0 && sidx == 0) {
+      *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(kc) + row(pos) + d0) = knq;
+      *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(vc) + row(pos) + d0) = vnq;
+    }
+  } else if (h % group == 0 && grp == 0 && sidx == 0) {   // append the new row (StaticCache.update)
     uint4 kr;
     kr.x = pack_f16(kn[0], kn[1]); kr.y = pack_f16(kn[2], kn[3]);
     kr.z = pack_f16(kn[4], kn[5]); kr.w = pack_f16(kn[6], kn[7]);
@@ -242,22 +272,32 @@ void rope_attn_decode_kernel(Args a, AttnZ zz) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc[i] = 0.f;
   for (int t0 = t_lo + grp; t0 < t_hi; t0 += NG * U) {
-    uint4 kr[U], vr[U];
+    typename std::conditional<FP8, uint2, uint4>::type kr[U], vr[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = t0 + u * NG;
       // t == pos comes from registers, t > pos is masked: a dummy row (paged: one of a validated page)
       const int tc = t < pos ? t : (PAGED ? first : 0);
-      kr[u] = *reinterpret_cast<const uint4*>(kc + row(tc) + d0);
-      vr[u] = *reinterpret_cast<const uint4*>(vc + row(tc) + d0);
+      if constexpr (FP8) {
+        kr[u] = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(kc) + row(tc) + d0);
+        vr[u] = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(vc) + row(tc) + d0);
+      } else {
+        kr[u] = *reinterpret_cast<const uint4*>(kc + row(tc) + d0);
+        vr[u] = *reinterpret_cast<const uint4*>(vc + row(tc) + d0);
+      }
     }
     // the round's scores first (independent chains), then the online-softmax updates in key order
     float k8a[U][8], v8a[U][8], sa[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = t0 + u * NG;
-      attn::unpack8h(kr[u], k8a[u]);
-      attn::unpack8h(vr[u], v8a[u]);
+      if constexpr (FP8) {
+        attn::unpack8f8(kr[u], ksc, k8a[u]);
+        attn::unpack8f8(vr[u], vsc, v8a[u]);
+      } else {
+        attn::unpack8h(kr[u], k8a[u]);
+        attn::unpack8h(vr[u], v8a[u]);
+      }
       if (t == pos) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) { k8a[u][i] = kn[i]; v8a[u][i] = vn[i]; }

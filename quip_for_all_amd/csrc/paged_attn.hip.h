@@ -25,6 +25,21 @@
 // HOST INVARIANT, not checked on the device: a page that any slot of the launch appends to is referenced by that slot
 // only.  Rule (1) of chunk_attn.hip.h (no workgroup reads a cache row another workgroup of the launch writes) then
 // holds across slots that share read-only prefix pages: shared pages are read by several slots and written by none.
+//
+// FP8 POOLS (the _f8 launches).  The same two launches on pools of one byte per element, uint8 (n_pages, kv_heads, 64,
+// HD): a stored byte c of the K pool means e4m3fn(c) * 2^k_exp, of the V pool e4m3fn(c) * 2^v_exp (OCP e4m3fn; one
+// power-of-two scale per pool, by value in the launch arguments, an integer in [-8, 7]: every code times 2^e is then an
+// exact, finite fp16 value, so dequantisation is exact).  Same table, same pages, same walks: the kernels are the paged
+// templates over PagedAttnArgsF8 / PagedChunkArgsF8.  A cached row is loaded as 8 bytes per lane / chunk and converted
+// to the values the fp16 kernels unpack; from there on the arithmetic is theirs, so an fp8 launch is BIT IDENTICAL, in
+// its outputs, to the fp16 paged launch on pools that hold the dequantised bytes whenever the new rows are
+// representable.  Appending quantises: x * 2^-e in fp32 (exact), finite values beyond +-448 and +-inf saturate to +-448
+// (explicitly, by compares), NaN stays NaN ((byte & 0x7f) == 0x7f), the rest rounds to nearest even, subnormals included.
+// THE ROUND-TRIP RULE: the rows a launch appends are used BY THAT LAUNCH as dequant(quant(.)) -- the decode kernel
+// replaces the new key and value before t == pos is scored, the chunk body stages every own-chunk row that way and
+// stores exactly those bytes.  "The bits of the cached row" (rule (1) of chunk_attn.hip.h) stays true, a row's result
+// does not depend on whether its keys were found in the cache or in the launch's inputs, and rule (2) -- any split of
+// a chunk into consecutive launches gives the same bits -- keeps holding.
 #pragma once
 #include "chunk_attn.hip.h"
 #include "ragged_attn.hip.h"
@@ -62,6 +77,36 @@ __global__ __launch_bounds__(kChunkThreads) void rope_attn_paged_ragged_kernel(P
   a.rows = ra.rows[s];
   chunk_tile_body<HD>(a, (int)blockIdx.y - t0);
 }
+
+struct PagedRaggedArgsF8 {
+  PagedChunkArgsF8 c;
+  int nseg;
+  int slot[kRaggedMaxSegments], row0[kRaggedMaxSegments], rows[kRaggedMaxSegments];
+};
+
+// rope_attn_paged_ragged_kernel on fp8 pools: the same scan in front of chunk_tile_body over PagedChunkArgsF8
+template <int HD>
+__global__ __launch_bounds__(kChunkThreads) void rope_attn_paged_ragged_f8_kernel(PagedRaggedArgsF8 ra) {
+  int s = 0, t0 = 0;
+  for (; s < ra.nseg - 1; ++s) {
+    const int n = (ra.rows[s] + kChunkTile - 1) / kChunkTile;
+    if ((int)blockIdx.y < t0 + n) break;
+    t0 += n;
+  }
+  const int slot = ra.slot[s];
+  const size_t r0 = (size_t)ra.row0[s];
+  PagedChunkArgsF8 a = ra.c;
+  a.q += r0 * a.heads * HD;
+  a.out += r0 * a.heads * HD;
+  a.k += r0 * a.kv_heads * HD;
+  a.v += r0 * a.kv_heads * HD;
+  a.table += (size_t)slot * a.max_pages;
+  a.pos += slot;
+  a.rows = ra.rows[s];
+  chunk_tile_body<HD>(a, (int)blockIdx.y - t0);
+}
+
+bool fp8_exp_ok(int e) { return e >= -8 && e <= 7; }
 
 bool paged_shape_ok(int max_len, int n_pages, int max_pages) {
   return n_pages >= 1 && max_pages >= 1 && max_len >= 1 && (long long)max_len <= (long long)max_pages * kPage;
@@ -135,6 +180,82 @@ int rope_attn_ragged_paged_launch(const void* q, const void* k, const void* v, c
   const dim3 grid(heads, (unsigned)tiles);
   return head_dim == 128 ? launch<rope_attn_paged_ragged_kernel<128>>(grid, dim3(kChunkThreads), 0, stream, ra)
                          : launch<rope_attn_paged_ragged_kernel<64>>(grid, dim3(kChunkThreads), 0, stream, ra);
+}
+
+// ---- the same two launches on fp8 pools (see the header of this file) ----------------------------------------------------
+int rope_attn_decode_paged_f8_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                     const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                     int batch, int heads, int kv_heads, int head_dim, int max_len, int n_pages,
+                                     int max_pages, float scale, hipStream_t stream, void* workspace, int window,
+                                     int k_exp, int v_exp) {
+  if (batch < 1 || batch > 65535 || heads < 1 || kv_heads < 1 || heads % kv_heads != 0 ||
+      !paged_shape_ok(max_len, n_pages, max_pages) || !fp8_exp_ok(k_exp) || !fp8_exp_ok(v_exp))
+    return QUIP_ERR_BAD_SHAPE;
+  if ((head_dim != 64 && head_dim != 128) || max_pages > kPagedMaxPages) return QUIP_ERR_UNSUPPORTED;
+  PagedAttnArgsF8 a{};
+  // (kcache / vcache carry the byte pools: the fp8 code addresses them as bytes)
+  static_cast<AttnArgs&>(a) =
+      AttnArgs{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
+               cos, sin, pos, reinterpret_cast<f16*>(kpool), reinterpret_cast<f16*>(vpool),
+               reinterpret_cast<f16*>(out), heads, kv_heads, max_len, scale, nullptr, nullptr, window};
+  a.table = table;
+  a.n_pages = n_pages;
+  a.max_pages = max_pages;
+  a.k_exp = k_exp;
+  a.v_exp = v_exp;
+  // the grid rule of rope_attn_decode_paged_launch
+  const bool split = workspace != nullptr && (long long)max_pages * kPage > kSplitFromPos;
+  if (split) {
+    a.ws = reinterpret_cast<float*>(workspace);
+    a.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) +
+                                             (size_t)batch * heads * kSplits * (head_dim + 4) * sizeof(float));
+  }
+  const dim3 grid(heads, split ? kSplits : 1, batch);
+  const int lds = max_pages * (int)sizeof(int32_t);
+  const AttnZ none{};
+  if (head_dim == 128)
+    return launch<rope_attn_decode_kernel<128, false, 0, 0, true, PagedAttnArgsF8>>(grid, dim3(256), lds, stream, a, none);
+  return launch<rope_attn_decode_kernel<64, false, 0, 0, true, PagedAttnArgsF8>>(grid, dim3(256), lds, stream, a, none);
+}
+
+int rope_attn_ragged_paged_f8_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                     const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                     int rows, int heads, int kv_heads, int head_dim, int max_len, int batch,
+                                     int n_pages, int max_pages, const int32_t* seg_slot, const int32_t* seg_rows,
+                                     int nseg, float scale, int window, hipStream_t stream, int k_exp, int v_exp) {
+  if (nseg < 1 || nseg > kRaggedMaxSegments || rows < 1 || batch < 1 || heads < 1 || kv_heads < 1 ||
+      heads % kv_heads != 0 || window < 0 || !paged_shape_ok(max_len, n_pages, max_pages) || !fp8_exp_ok(k_exp) ||
+      !fp8_exp_ok(v_exp))
+    return QUIP_ERR_BAD_SHAPE;
+  PagedRaggedArgsF8 ra{};
+  long long total = 0, tiles = 0;
+  for (int s = 0; s < nseg; ++s) {
+    if (seg_rows[s] < 1 || seg_slot[s] < 0 || seg_slot[s] >= batch) return QUIP_ERR_BAD_SHAPE;
+    for (int t = 0; t < s; ++t)
+      if (seg_slot[t] == seg_slot[s]) return QUIP_ERR_BAD_SHAPE;     // rule (1) needs distinct slots
+    if (total + seg_rows[s] > rows) return QUIP_ERR_BAD_SHAPE;
+    ra.slot[s] = seg_slot[s];
+    ra.row0[s] = (int)total;
+    ra.rows[s] = seg_rows[s];
+    total += seg_rows[s];
+    tiles += (seg_rows[s] - 1) / kChunkTile + 1;
+  }
+  if (total != rows) return QUIP_ERR_BAD_SHAPE;
+  if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
+  if (tiles > kChunkMaxTilesY) return QUIP_ERR_UNSUPPORTED;
+  static_cast<ChunkArgs&>(ra.c) =
+      ChunkArgs{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
+                cos, sin, pos, reinterpret_cast<f16*>(kpool), reinterpret_cast<f16*>(vpool),
+                reinterpret_cast<f16*>(out), 0, 0, heads, kv_heads, max_len, window, scale};
+  ra.c.table = table;
+  ra.c.n_pages = n_pages;
+  ra.c.max_pages = max_pages;
+  ra.c.k_exp = k_exp;
+  ra.c.v_exp = v_exp;
+  ra.nseg = nseg;
+  const dim3 grid(heads, (unsigned)tiles);
+  return head_dim == 128 ? launch<rope_attn_paged_ragged_f8_kernel<128>>(grid, dim3(kChunkThreads), 0, stream, ra)
+                         : launch<rope_attn_paged_ragged_f8_kernel<64>>(grid, dim3(kChunkThreads), 0, stream, ra);
 }
 
 }  // namespace quip

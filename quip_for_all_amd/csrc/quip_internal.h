@@ -210,6 +210,18 @@ int rope_attn_ragged_paged_launch(const void* q, const void* k, const void* v, c
                                   int rows, int heads, int kv_heads, int head_dim, int max_len, int batch, int n_pages,
                                   int max_pages, const int32_t* seg_slot, const int32_t* seg_rows, int nseg,
                                   float scale, int window, hipStream_t stream);
+// the same two on fp8 pools: uint8 (n_pages, kv_heads, 64, head_dim), a byte c means e4m3fn(c) * 2^k_exp / 2^v_exp;
+// exponents in [-8, 7]
+int rope_attn_decode_paged_f8_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                     const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                     int batch, int heads, int kv_heads, int head_dim, int max_len, int n_pages,
+                                     int max_pages, float scale, hipStream_t stream, void* workspace, int window,
+                                     int k_exp, int v_exp);
+int rope_attn_ragged_paged_f8_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                     const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
+                                     int rows, int heads, int kv_heads, int head_dim, int max_len, int batch,
+                                     int n_pages, int max_pages, const int32_t* seg_slot, const int32_t* seg_rows,
+                                     int nseg, float scale, int window, hipStream_t stream, int k_exp, int v_exp);
 // nll_rows.hip.h (in decode_glue.hip): per row of (rows, n) fp16 logits the log-sum-exp, the log-probability of target[row] and
 // the arg-max; lse / argmax may be null
 int nll_rows_launch(const void* logits, int rows, int n, const int64_t* target, float* logprob, float* lse,

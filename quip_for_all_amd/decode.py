@@ -806,13 +806,16 @@ class LlamaDecoder:
         q = torch.empty_like(probs).exponential_(1)
         return torch.argmax(probs / q, dim=-1)
 
-    def batched(self, batch, max_len=None, paged=False, pages=None):
+    def batched(self, batch, max_len=None, paged=False, pages=None, kv_dtype=None, kv_exp=None):
         """a decoder of `batch` independent sequences on this decoder's modules (batch_decode.BatchDecoder); paged: its
         KV cache is a pool of `pages` 64-position pages shared by the slots (paged_cache.PagedBatchDecoder; default: as
-        many pages as the contiguous cache has rows for)"""
+        many pages as the contiguous cache has rows for).  kv_dtype="fp8" (paged only): the pools hold one OCP e4m3fn
+        byte per element, kv_exp the (layers, 2) power-of-two exponents of K | V (default 0; see paged_cache)"""
         if paged:
             from .paged_cache import PagedBatchDecoder
-            return PagedBatchDecoder(self, batch, max_len, pages)
+            return PagedBatchDecoder(self, batch, max_len, pages, kv_dtype, kv_exp)
+        if kv_dtype not in (None, "fp16") or kv_exp is not None:
+            raise ValueError("kv_dtype='fp8' / kv_exp: only with paged=True")
         if pages is not None:
             raise ValueError("pages: only with paged=True")
         from .batch_decode import BatchDecoder

@@ -9,12 +9,20 @@ slots share the full pages of a common prefix.  Per slot the bits -- logits, tok
 contiguous BatchDecoder given the same calls.
 
 The invariant the launches rely on (csrc/paged_attn.hip.h): a page a slot appends to is referenced by that slot only.
-PagePool keeps it by construction: only FULL pages are ever shared, and a full page is never appended to."""
+PagePool keeps it by construction: only FULL pages are ever shared, and a full page is never appended to.
+
+`kv_dtype="fp8"` (`LlamaDecoder.batched(B, paged=True, kv_dtype="fp8", kv_exp=None)`): the pools are torch.uint8, one OCP
+e4m3fn byte per element -- the same pages, table and PagePool in half the bytes.  A stored byte c of layer i means
+e4m3fn(c) * 2^e, e = kv_exp[i][0] for K and kv_exp[i][1] for V, integers in [-8, 7], default 0; they travel by value in
+the launch arguments and are constant for a decoder.  The launches are the _f8 ops of paged_attn.py; the rows a launch
+appends are used by it as stored (the round-trip rule of csrc/paged_attn.hip.h), so chunking, captured replays and
+forked slots keep giving identical bits.  Against the fp16 cache the results differ by the rounding of K / V to three
+mantissa bits."""
 import torch
 
 from .batch_decode import BatchDecoder, _check_passes, _check_ragged
 from .decode import capture_graph
-from .paged_attn import PAGE, gather
+from .paged_attn import F8_EXP_MAX, F8_EXP_MIN, PAGE, dequant_f8, gather
 
 
 class PoolExhausted(RuntimeError):
@@ -144,9 +152,36 @@ class PagedBatchDecoder(BatchDecoder):
     extending or forking onto it revives it.  The SDPA prompt route writes contiguous views and does not exist here:
     fill_slot / extend_slot / prefill_slot go through the ragged pass."""
 
-    def __init__(self, parent, batch, max_len=None, pages=None):
+    def __init__(self, parent, batch, max_len=None, pages=None, kv_dtype=None, kv_exp=None):
+        if kv_dtype not in (None, "fp16", "fp8"):
+            raise ValueError(f"kv_dtype {kv_dtype!r}: None, 'fp16' or 'fp8'")
+        self.fp8 = kv_dtype == "fp8"
+        if kv_exp is not None and not self.fp8:
+            raise ValueError("kv_exp: only with kv_dtype='fp8'")
+        self.kv_exp = self._check_kv_exp(kv_exp, parent.s.layers) if self.fp8 else None
         self._pages_arg = pages
         super().__init__(parent, batch, max_len)
+
+    @staticmethod
+    def _check_kv_exp(kv_exp, layers):
+        """None (all 0), or (layers, 2) ints in [-8, 7] as nested lists or a tensor -> [[k_exp, v_exp]] per layer"""
+        if kv_exp is None:
+            return [[0, 0] for _ in range(layers)]
+        if isinstance(kv_exp, torch.Tensor):
+            if kv_exp.is_floating_point() or kv_exp.dtype == torch.bool:
+                raise ValueError("kv_exp: an integer tensor")
+            kv_exp = kv_exp.tolist()
+        try:
+            rows = [list(r) for r in kv_exp]
+        except TypeError:
+            raise ValueError(f"kv_exp: a ({layers}, 2) list or tensor of ints") from None
+        if len(rows) != layers or any(len(r) != 2 for r in rows):
+            raise ValueError(f"kv_exp: a ({layers}, 2) list or tensor of ints")
+        for r in rows:
+            for e in r:
+                if isinstance(e, bool) or not isinstance(e, int) or not F8_EXP_MIN <= e <= F8_EXP_MAX:
+                    raise ValueError(f"kv_exp: ints in [{F8_EXP_MIN}, {F8_EXP_MAX}], got {e!r}")
+        return rows
 
     def _alloc_cache(self):
         s = self.s
@@ -155,17 +190,26 @@ class PagedBatchDecoder(BatchDecoder):
         if n < 1:
             raise ValueError(f"pages {n}: at least one")
         self.n_pages = n
-        self.kpool = torch.zeros(s.layers, n, s.kv_heads, PAGE, s.head_dim, dtype=torch.float16, device=self.dev)
+        self.kpool = torch.zeros(s.layers, n, s.kv_heads, PAGE, s.head_dim,
+                                 dtype=torch.uint8 if self.fp8 else torch.float16, device=self.dev)
         self.vpool = torch.zeros_like(self.kpool)
         self.table = torch.full((self.batch, self.max_pages), -1, dtype=torch.int32, device=self.dev)
         self.pool = PagePool(n, self.batch, self.max_pages)
         self.live = [True] * self.batch
 
     def _attend_step(self, i, q, k, v):
+        if self.fp8:
+            return torch.ops.quip_lib.rope_attn_decode_paged_f8(q, k, v, self.cos, self.sin, self.pos, self.table,
+                                                                self.kpool[i], self.vpool[i], self.attn_ws, self.window,
+                                                                self.kv_exp[i][0], self.kv_exp[i][1])
         return torch.ops.quip_lib.rope_attn_decode_paged(q, k, v, self.cos, self.sin, self.pos, self.table, self.kpool[i],
                                                          self.vpool[i], self.attn_ws, self.window)
 
     def _attend_ragged(self, i, q, k, v, seg_slot, seg_rows):
+        if self.fp8:
+            return torch.ops.quip_lib.rope_attn_ragged_paged_f8(q, k, v, self.cos, self.sin, self.pos, seg_slot, seg_rows,
+                                                                self.table, self.kpool[i], self.vpool[i], self.window,
+                                                                self.kv_exp[i][0], self.kv_exp[i][1])
         return torch.ops.quip_lib.rope_attn_ragged_paged(q, k, v, self.cos, self.sin, self.pos, seg_slot, seg_rows,
                                                          self.table, self.kpool[i], self.vpool[i], self.window)
 
@@ -200,7 +244,16 @@ class PagedBatchDecoder(BatchDecoder):
         self._push_table()
 
     def gather_slot(self, b):
-        """slot b's cache rows [0, length) as contiguous copies -> (K, V), each (layers, kv_heads, length, hd)"""
+        """slot b's cache rows [0, length) as contiguous copies -> (K, V), each (layers, kv_heads, length, hd) fp16 (an
+        fp8 cache: the values its bytes mean, exact)"""
+        k, v = self.gather_slot_raw(b)
+        if not self.fp8:
+            return k, v
+        return tuple(torch.stack([dequant_f8(x[i], self.kv_exp[i][j]) for i in range(self.s.layers)])
+                     if x.numel() else x.to(torch.float16) for j, x in enumerate((k, v)))
+
+    def gather_slot_raw(self, b):
+        """gather_slot in the pools' own dtype: fp16 rows, or the stored e4m3fn bytes (uint8) of an fp8 cache"""
         n = self.pool.length[b]
         row = torch.tensor(self.pool.table[b][:self.pool.pages_of(n)], dtype=torch.int32, device=self.dev).view(1, -1)
         if n == 0:
@@ -208,6 +261,35 @@ class PagedBatchDecoder(BatchDecoder):
             return e, e.clone()
         return tuple(torch.stack([gather(pool[i], row)[0, :, :n] for i in range(self.s.layers)])
                      for pool in (self.kpool, self.vpool))
+
+    @torch.no_grad()
+    def suggest_kv_exp(self, slots, token_lists):
+        """exponents for `kv_exp` from sample prompts: the prompts are cached by a scratch fp16 paged decoder of this
+        one's parent, batch and max_len (prompt j in slot slots[j]; this decoder is not touched); per layer and K | V the
+        smallest e with absmax * 2^-e <= 448, clipped to [-8, 7] -> [[k_exp, v_exp]] per layer"""
+        import math
+        slots, toks = _check_ragged(self, slots, token_lists, "suggest_kv_exp")
+        if not slots:
+            raise ValueError("suggest_kv_exp: at least one prompt")
+        scratch = PagedBatchDecoder(self.parent, self.batch, self.max_len,
+                                    pages=sum(self.pool.pages_of(t.numel()) for t in toks))
+        scratch._assign({b: t.numel() for b, t in zip(slots, toks)})
+        scratch._extend_passes(slots, toks, 512)
+        out = []
+        for i in range(self.s.layers):
+            row = []
+            for pool in (scratch.kpool, scratch.vpool):
+                amax = float(pool[i].float().abs().max())          # (unused pages are zero)
+                if not math.isfinite(amax):
+                    raise ValueError(f"suggest_kv_exp: layer {i} cached a non-finite value")
+                e = math.ceil(math.log2(amax / 448.0)) if amax > 0 else F8_EXP_MIN
+                while amax * 2.0 ** -e > 448.0:                     # (log2's rounding)
+                    e += 1
+                while e > F8_EXP_MIN and amax * 2.0 ** -(e - 1) <= 448.0:
+                    e -= 1
+                row.append(min(max(e, F8_EXP_MIN), F8_EXP_MAX))
+            out.append(row)
+        return out
 
     # ---- slots
     def reset(self, first_token=1):
