@@ -244,6 +244,7 @@ def test_rope_attn_decode_matches_torch(heads, kv_heads, hd, pos):
     """fused rope + cache append + single-query attention == the eager torch ops it replaces"""
     import quip_for_all_amd  # noqa: F401
     import torch.nn.functional as F
+    from tests.test_attn_hard_cases_host import BOUND_DECODE_U
     dev = "cuda"
     g = torch.Generator().manual_seed(pos + heads)
     max_len = pos + 9
@@ -284,6 +285,9 @@ def test_rope_attn_decode_matches_torch(heads, kv_heads, hd, pos):
     ref = torch.einsum("ht,htd->hd", torch.softmax(s, -1), V)
     err = (out.double() - ref).abs().max().item()
     assert err <= 2e-3 * max(1.0, ref.abs().max().item()), err
+    for o in (out, out_s):                  # ... and inside the bound of the decode family, in u = 2^-11 max|v| of the head's keys
+        err_u = ((o.double() - ref).abs().amax(1) / (V.abs().amax(dim=(1, 2)) * 2.0 ** -11)).max().item()
+        assert err_u <= BOUND_DECODE_U(pos + 1), (err_u, BOUND_DECODE_U(pos + 1))
 
 
 def test_fused_prologue_step_equals_unfused_step():
@@ -373,6 +377,7 @@ def test_rope_attn_decode_sliding_window(heads, kv_heads, hd, pos, window):
     linear cache; with and without the split-mode workspace; a window that covers the context is the plain launch bit for bit"""
     import quip_for_all_amd  # noqa: F401
     from quip_for_all_amd.register_lib import rope_attn_workspace
+    from tests.test_attn_hard_cases_host import BOUND_DECODE_U
     dev = "cuda"
     g = torch.Generator().manual_seed(pos + heads + window)
     max_len = pos + 9
@@ -407,6 +412,9 @@ def test_rope_attn_decode_sliding_window(heads, kv_heads, hd, pos, window):
     ref = torch.einsum("ht,htd->hd", torch.softmax(s, -1), V)
     err = (out.double() - ref).abs().max().item()
     assert err <= 2e-3 * max(1.0, ref.abs().max().item()), err
+    for o in (out, out_s):                  # ... and inside the bound of the decode family, in u = 2^-11 max|v| of the head's keys
+        err_u = ((o.double() - ref).abs().amax(1) / (V.abs().amax(dim=(1, 2)) * 2.0 ** -11)).max().item()
+        assert err_u <= BOUND_DECODE_U(pos + 1 - lo), (err_u, BOUND_DECODE_U(pos + 1 - lo))
 
 
 @pytest.mark.parametrize("shape_name,window,plen", [("TINY", 4, 0), ("TINY", 5, 9), ("SMALL", 7, 12)])
