@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 16
+#define QUIP_ABI_VERSION 17
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -578,6 +578,28 @@ int quip_argmax_step_batched_f16(const void* logits, int32_t batch, int32_t n, v
  * aligned (else QUIP_ERR_MISALIGNED). */
 int quip_nll_rows_f16(const void* logits, int32_t rows, int32_t n, const int64_t* target, float* logprob, float* lse,
                       int64_t* argmax, quip_stream_t stream);
+
+/* ---- sampling tail (ABI 17): one token per row of n fp16 logits, every row with its own parameters, one launch --------
+ *   logits [rows, n] fp16 row-major, contiguous; temperature / top_p [rows] fp32, top_k [rows] int32, seed [rows] int64;
+ *   tok / pos [rows] int64; kept [rows] int32 or NULL -- all on the device
+ * Per row r, with c = pos[r] as read before it is advanced (csrc/sample_rows.hip.h):
+ *   greedy row  temperature[r] is not > 0, or the row's maximum is not finite: the token of quip_argmax_step_batched_f16
+ *   classes     the distinct finite values v_1 > v_2 > ..., weights exp((v_j - v_1) / T); NaN and -inf carry no mass
+ *   top_k[r]    1 <= k < n, else off: the classes >= the k-th largest logit stay (ties at the k-th value all stay)
+ *   top_p[r]    0 < p < 1, else off, after top-k: a class stays iff the kept mass strictly above it is < p * (kept mass)
+ *   draw        u = ((h >> 40) + 0.5) 2^-24, h = mix(mix(seed[r] + G) + G (c + 1)), G = 0x9E3779B97F4A7C15, mix =
+ *               splitmix64's finaliser; the token is the first one in canonical order (classes descending, inside a class
+ *               by ascending index) whose cumulative mass exceeds u * (kept mass)
+ *   tok[r] = token, pos[r] += 1, kept[r] = number of kept tokens (1 for a greedy row)
+ * The token depends on the row's bits, the four parameters and c alone: not on r, rows, the row's alignment or the other
+ * rows.  Masses are integers (2^-40 units), so nothing depends on an order of summation; any prefix mass is within a
+ * relative 2^-18 of its float64 value on the same logits.
+ * rows >= 1 and 1 <= n <= 2^20 (else QUIP_ERR_BAD_SHAPE); logits 2-byte, temperature / top_k / top_p / kept 4-byte,
+ * seed / tok / pos 8-byte aligned (else QUIP_ERR_MISALIGNED).  Out-of-range parameters never fault: they read as off /
+ * greedy. */
+int quip_sample_step_f16(const void* logits, int32_t rows, int32_t n, const float* temperature, const int32_t* top_k,
+                         const float* top_p, const int64_t* seed, int64_t* tok, int64_t* pos, int32_t* kept,
+                         quip_stream_t stream);
 
 /* Which kernel a bs=1 E8P12 GEMV launch of `count` matrices (ns[i] rows, common k) is dispatched to by default, without
  * launching anything: 1 = e8p_gemv_mfma_kernel, 2 = e8p_gemv_v2_kernel (needs the workspace of the *_ws entry points when

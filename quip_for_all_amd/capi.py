@@ -62,6 +62,7 @@ SIGNATURES = {
     "quip_rope_attn_ragged_paged_f8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32,
                                        _I32, _P, _P, _I32, _F, _I32, _P, _I32, _I32],
     "quip_nll_rows_f16": [_P, _I32, _I32, _P, _P, _P, _P, _P],
+    "quip_sample_step_f16": [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
     "quip_block_engine_supported": [_I32, _I32, _I32, _I32, _I32, _I32],
     "quip_block_engine_workspace_bytes": [],
     "quip_block_engine_layer_bytes": [],

@@ -847,6 +847,18 @@ int quip_nll_rows_f16(const void* logits, int32_t rows, int32_t n, const int64_t
   return nll_rows_launch(logits, rows, n, target, logprob, lse, argmax, (hipStream_t)stream);
 }
 
+int quip_sample_step_f16(const void* logits, int32_t rows, int32_t n, const float* temperature, const int32_t* top_k,
+                         const float* top_p, const int64_t* seed, int64_t* tok, int64_t* pos, int32_t* kept,
+                         quip_stream_t stream) {
+  if (!logits || !temperature || !top_k || !top_p || !seed || !tok || !pos) return QUIP_ERR_NULL_POINTER;
+  if ((reinterpret_cast<uintptr_t>(logits) & 1) || (reinterpret_cast<uintptr_t>(temperature) & 3) ||
+      (reinterpret_cast<uintptr_t>(top_k) & 3) || (reinterpret_cast<uintptr_t>(top_p) & 3) ||
+      (reinterpret_cast<uintptr_t>(seed) & 7) || (reinterpret_cast<uintptr_t>(tok) & 7) ||
+      (reinterpret_cast<uintptr_t>(pos) & 7) || (reinterpret_cast<uintptr_t>(kept) & 3))
+    return QUIP_ERR_MISALIGNED;
+  return sample_rows_launch(logits, rows, n, temperature, top_k, top_p, seed, tok, pos, kept, (hipStream_t)stream);
+}
+
 int quip_rope_attn_decode_z_supported(int32_t heads, int32_t kv_heads, int32_t head_dim) {
   return rope_attn_decode_z_supported(heads, kv_heads, head_dim) ? 1 : 0;
 }

@@ -557,3 +557,5 @@ int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, 
 #include "paged_attn.hip.h"
 // the scoring tail: log-sum-exp, target log-probability and arg-max of every row of a chunk's logits
 #include "nll_rows.hip.h"
+// the sampling tail: one token per row, every row with its own temperature, top-k, top-p and seed
+#include "sample_rows.hip.h"

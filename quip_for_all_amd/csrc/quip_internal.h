@@ -226,6 +226,11 @@ int rope_attn_ragged_paged_f8_launch(const void* q, const void* k, const void* v
 // the arg-max; lse / argmax may be null
 int nll_rows_launch(const void* logits, int rows, int n, const int64_t* target, float* logprob, float* lse,
                     int64_t* argmax, hipStream_t stream);
+// sample_rows.hip.h (in decode_glue.hip): per row of (rows, n) fp16 logits one token by the row's own temperature, top-k,
+// top-p and seed at counter pos[row]; tok[row] = token, pos[row] += 1; kept may be null
+int sample_rows_launch(const void* logits, int rows, int n, const float* temperature, const int32_t* top_k,
+                       const float* top_p, const int64_t* seed, int64_t* tok, int64_t* pos, int32_t* kept,
+                       hipStream_t stream);
 // persistent decode engine, stage 1 (decode_engine.hip): GEMV[gate, up] -> output transforms -> SiLU product ->
 // input transform of down -> GEMV[down] of one decoder block in one launch
 struct FfnEngineArgs {
