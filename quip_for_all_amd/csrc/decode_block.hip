@@ -53,6 +53,21 @@
 #ifndef QUIP_ATT_STAMPS
 #define QUIP_ATT_STAMPS 0          // tools/dbg: the stamps 18..22 inside the attention instead of inside the gate / up edge
 #endif
+#ifndef QUIP_MLP_STAMPS
+#define QUIP_MLP_STAMPS 0          // tools/dbg: the stamps 18..24 and 28..31 (the two 4096-wide edges' and a free one) inside the MLP edge
+#endif
+#if QUIP_MLP_STAMPS
+#define MSTAMP(i) BSTAMP((i) < 7 ? 18 + (i) : 21 + (i))
+#else
+#define MSTAMP(i) do { } while (0)
+#endif
+#ifndef QUIP_ROWS_DIRECT
+#define QUIP_ROWS_DIRECT 1         // the MLP rows straight from the hand-off into the K-mix's A operands (1) or through an LDS image (0: rounds 5-6)
+#endif
+#ifndef QUIP_MLP_PREFETCH
+#define QUIP_MLP_PREFETCH 1        // the MLP's factor image and the row owners' vectors requested in front of the gate / up edge's gather and
+                                   // stored behind it (1), or loaded behind the edge, in front of the products (0: rounds 3-6)
+#endif
 #if QUIP_ATT_STAMPS
 #define ASTAMP(i) BSTAMP(18 + (i))
 #else
@@ -177,9 +192,9 @@ constexpr int RPO = 2, NRO = (FK + RPO - 1) / RPO;
 constexpr size_t kWsInbox = kWsZ + 6 * kWsVec, kWsRows = kWsInbox + (size_t)NRO * FL * 2 * RPO * 8;
 // long contexts: the eight workgroups of a head each take every eighth position; their partial softmax states (128 sums +
 // maximum + denominator, padded to 132 granules) meet at the head's first workgroup
-// rows hand-off: wave 0 polls the last column before everybody sweeps the 90 KB.  Without it (every workgroup sweeping
-// until its pieces are all there) the hand-off takes 29.5K clocks instead of 21.4K: 256 x 90 KB of polls per retry crowd out
-// the owners' stores
+// rows hand-off: wave 0 polls the last column before everybody sweeps the rows (45 KB of granules since round 5's fp16 rows; 90 KB
+// when this was measured).  Without it (every workgroup sweeping until its pieces are all there) the hand-off took 29.5K clocks
+// instead of 21.4K: 256 x 90 KB of polls per retry crowd out the owners' stores
 constexpr bool kCheapPoll = true;
 constexpr int kParts = 8, kPartGran = 132, kSplitPos = 128;      // (measured: 1.83 ms per token at 200 positions on one workgroup per head, 1.74 at 256 split)
 constexpr size_t kWsPart = kWsRows + (size_t)FL * 48 * 8;
@@ -220,9 +235,10 @@ struct BLds {
   // ONE transient area for everything that lives between two products (E8P12: T1 x 32 + T2 x 16 = 96 KB of tables leave 50.3 KB).
   // In time: the transforms' exchange buffers (16.5 KB per transform from the base: 1, 2 or -- attention -- 3) -> digit planes
   // of the consumers (12 / 24 KB from the base, written after the transforms' last reads) | attention partials; for the MLP:
-  // planes [0, 24 K) + the K x K factor image [24 K, 36 K) + the row owners' vectors [36 K, 48 K) -> row owners: inbox rows
-  // [0, 8 K), rows on the way out [8 K, 16 K) -> the gathered rows [0, 48 K) (the factor image is in registers by then) ->
-  // down's planes [0, 35.1 K).
+  // planes [0, 24 K) + the K x K factor image [24 K, 36 K) + the row owners' vectors [36 K, 48 K) (both stored while the gate / up
+  // edge's exchange buffer is alive, QUIP_MLP_PREFETCH: they lie behind it) -> row owners: inbox rows [0, 8 K), rows on the way
+  // out [8 K, 16 K) -> (QUIP_ROWS_DIRECT: the gathered rows never touch LDS; before: their image [0, 24 K)) -> down's planes
+  // [0, 35.1 K), over the factor image once every wave's K-mix has read it.
   static constexpr int kArea = kCs + 2 * HD * 4;
   static constexpr int kBufBytes = ((had::buf_floats(HID) * 4) + 15) & ~15;
   static constexpr int kAreaBytes = (160 * 1024 - kArea) & ~15;
@@ -232,9 +248,9 @@ struct BLds {
   // fp16 image of the three K x K factors (12 KB; G8: 20.3 KB), behind the planes of gate / up and behind the rows' LDS image
   // ([KP16 / 2][256] fp16 pairs = 24 KB; G8: 32 KB)
   static constexpr int kHad = kArea + (G8 ? 32 * 1024 : 2 * 3 * PSH);
-  // MLP row owners: SV_gate / SV_up / SU_down of their rows (6 KB): behind the factor image; G8: at 16 K (free while they are alive:
-  // the planes of the ONE consumer end at 12 K, the owners' rows and staging at 12 K)
-  static constexpr int kStash = G8 ? kArea + 16 * 1024 : kHad + 12 * 1024;
+  // MLP row owners: SV_gate / SV_up / SU_down of their rows (3 KB): behind the factor image; G8: at 17 K (free while they are alive:
+  // the gate / up edge's exchange buffer ends at 16.5 K, the planes of the ONE consumer at 12.5 K, the owners' rows and staging at 12 K)
+  static constexpr int kStash = G8 ? kArea + 17 * 1024 : kHad + 12 * 1024;
   // down's planes.  Byte tables: every 256 digits padded by 16 bytes (the K-mix writes a dword per lane, 256 digits apart).  Nibble
   // mode: a half plane = (KPDV / 256) blocks of 128 + 16 bytes (the same writers: 144-byte steps land on 16 different banks; without
   // the pad their dwords, 128 bytes apart, met on two: 6.5K instead of 3.9K clocks for the K-mix + planes), "hi" half at HOD = 16
@@ -247,6 +263,8 @@ struct BLds {
   static_assert(kAreaBytes >= 3 * kBufBytes && kAreaBytes >= FL * KP16 * 2 && kAreaBytes >= 3 * kPlaneD &&
                 kHad + kHadElems * 2 <= kArea + kAreaBytes && kStash + 6 * 1024 <= (G8 ? kHad : kArea + kAreaBytes),
                 "transient area");
+  // (QUIP_MLP_PREFETCH: both are written while the gate / up edge's ONE exchange buffer is alive, in front of its planes)
+  static_assert(kHad >= kBuf0 + kBufBytes && kStash >= kBuf0 + kBufBytes && kStash >= kArea + 3 * PSH, "factor image and owner vectors: clear of the gate / up edge");
 };
 #if QUIP_BLOCK_G8
 static_assert(BLds<24>::kBytes <= 160 * 1024 && BLds<4>::kBytes <= 160 * 1024, "LDS budget");
@@ -768,7 +786,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
                   const f16* su0, const f16* su1, float sc0, float sc1, bool two, auto after_gather, auto drip1, auto drip2, int sb, auto ag_tag) {
     // ag_tag: VMEM requests `after_gather` issues (a hand count: the wait for the gather's second read set is said in them)
     // stamps of the edge's stages: 18..22 (sb = 18: the gate / up edge) or 23, 24, 28, 29, 30 (sb = 23: the q / k / v edge)
-#if QUIP_ATT_STAMPS
+#if QUIP_ATT_STAMPS || QUIP_MLP_STAMPS
 #define ESTAMP(i) do { } while (0)
 #else
 #define ESTAMP(i) do { if (sb >= 0) BSTAMP(sb + (i) + ((sb == 23 && (i) >= 2) ? 3 : 0)); } while (0)
@@ -1569,16 +1587,50 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       for (int i = 0; i < kPreG; ++i) decode_pre(i, Bg[i]);
     }
 #endif
+#if QUIP_MLP_PREFETCH
+    // The MLP edge's K x K factor image (everybody) and SV_gate / SV_up / SU_down of the row owners' rows: plain loads HERE, next to
+    // the edge's own vectors -- the gather's polls drain the queue, after_gather takes them over and stores them into the free
+    // tail of the area (clear of the edge's exchange buffer and planes).  Rounds 3-6 loaded them behind the edge: a memory
+    // latency between the planes and the first product.
+    constexpr int HPIECES = B::kHadElems / 8, NHP = (HPIECES + kThreads - 1) / kThreads, OPIECES = RPO * 3 * (FL / 8);
+    static_assert(OPIECES <= kThreads, "one piece of the owner vectors per thread");
+    u32x4 fim[NHP], ovec = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < NHP; ++i) {
+      const int pi = tid + kThreads * i;
+      fim[i] = reinterpret_cast<const u32x4*>(Ld.had3)[pi < HPIECES ? pi : tid];
+    }
+    if (w < NRO) {
+      const int p = tid < OPIECES ? tid : 0;
+      const int row = p / (3 * (FL / 8)), rem = p - row * (3 * (FL / 8));
+      const int vsel = rem / (FL / 8), piece = rem - vsel * (FL / 8);
+      const int kr = RPO * w + row < FK ? RPO * w + row : FK - 1;
+      ovec = *reinterpret_cast<const u32x4*>((vsel == 0 ? Ld.sv[4] : (vsel == 1 ? Ld.sv[5] : Ld.su[6])) + (size_t)kr * FL + piece * 8);
+    }
+    auto land_mlp_vectors = [&]() {
+#pragma unroll
+      for (int i = 0; i < NHP; ++i) {
+        asm volatile("" : "+v"(fim[i]));
+        if (tid + kThreads * i < HPIECES) *reinterpret_cast<u32x4*>(smem + B::kHad + (tid + kThreads * i) * 16) = fim[i];
+      }
+      asm volatile("" : "+v"(ovec));
+      // piece p = (row, vector, 16-byte piece) in this order: byte p * 16 of the stash
+      if (w < NRO && tid < OPIECES) *reinterpret_cast<u32x4*>(smem + B::kStash + tid * 16) = ovec;
+    };
+#else
+    auto land_mlp_vectors = []() { };
+#endif
     // (ONE consumer per workgroup: its half of the machine multiplies gate, the other half up)
     edge(std::true_type{}, std::integral_constant<int, 2>{}, SLOTS(M_GATE), 4, ebase | hop, 0x7000u, Ld.sv[3], Ld.ln[1], Ld.su[4 + mgu], Ld.su[4 + mgu], Ld.sc[4 + mgu], Ld.sc[4 + mgu], false,
          // up's row blocks (RVQ: their first virtual slice) behind the hand-off, one at a time between the edge's stages
-         [&]() { BSTAMP(10); if constexpr (RVQ) ISSUE_RVQ_UP_A_G(Ld, 0); else if constexpr (G8) { ISSUE8_GU(Ld, 3); ISSUE8_GU(Ld, 4); } else ISSUE(Ld, 7); },
+         [&]() { land_mlp_vectors(); BSTAMP(10); if constexpr (RVQ) ISSUE_RVQ_UP_A_G(Ld, 0); else if constexpr (G8) { ISSUE8_GU(Ld, 3); ISSUE8_GU(Ld, 4); } else ISSUE(Ld, 7); },
          [&]() { if constexpr (RVQ) ISSUE_RVQ_UP_A_G(Ld, 1); else if constexpr (G8) ISSUE8_GU(Ld, 5); else ISSUE(Ld, 8); },
          [&]() { if constexpr (RVQ) ISSUE_RVQ_UP_A_G(Ld, 2); else if constexpr (G8) ISSUE8_GU(Ld, 6); else ISSUE(Ld, 9); }, 18,
          std::integral_constant<int, G8 ? 4 : 2>{});
     BSTAMP(11);
     // row owners (w < NRO: rows k' = RPO w .. RPO w + RPO - 1, one per wave): SV_gate / SV_up / SU_down of their rows into the free
     // tail of the area; everybody: the image of the K x K factors, for the MLP edge
+#if !QUIP_MLP_PREFETCH
     {
       if (w < NRO) {
         for (int p = tid; p < RPO * 3 * (FL / 8); p += kThreads) {
@@ -1593,8 +1645,11 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       for (int i = tid; i < HPIECES; i += kThreads)
         *reinterpret_cast<uint4*>(smem + B::kHad + i * 16) = reinterpret_cast<const uint4*>(Ld.had3)[i];
     }
+#endif
+    MSTAMP(0);
     esync::drain();
     own_slots(SLOTS(M_GATE | M_UP));
+    MSTAMP(1);
     static_assert(FRB == 3, "three row blocks per matrix");
     if constexpr (RVQ) {
       const uint32_t xu = xlane;                                                  // (the second column: the same planes)
@@ -1621,6 +1676,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
 #endif
         add_rows(item_vs(std::integral_constant<int, 0>{}, PRE_G(0), A), B::AGU);
         add_rows(item_vs(std::integral_constant<int, 1>{}, PRE_G(1), A), B::AGU + 16);
+        MSTAMP(2);
         add_rows(item_vs(std::integral_constant<int, 2>{}, nullptr, A), B::AGU + 32);
         add_rows(item_vs(std::integral_constant<int, 3>{}, nullptr, A), B::AGU + 48);
         ISSUE8_DOWN(Ld, 0); ISSUE8_DOWN(Ld, 1); ISSUE8_DOWN(Ld, 2); ISSUE8_DOWN(Ld, 3);
@@ -1632,6 +1688,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       ISSUE(Ld, 10); ISSUE(Ld, 11); ISSUE(Ld, 12);
 #if QUIP_PREDECODE_GATE
       run_items3_pre(std::integral_constant<int, kPreG>{}, Bg, 0, xlane, xlane, xlane, 64);
+      MSTAMP(2);
       if constexpr (kPreQkv && QUIP_QKV_ISSUE_EARLY) { ISSUE(Ln, 0); ISSUE(Ln, 1); ISSUE(Ln, 2); }
 #else
       run_items3(0, xlane, xlane, xlane, 64);                                     // first column's three row blocks
@@ -1639,6 +1696,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       run_items3(FRB, xlane, xlane, xlane, 64 + 16 * FRB);                         // second column's
       }
     }
+    MSTAMP(3);
     had::wg_barrier<true>();
     BSTAMP(12);
 
@@ -1728,6 +1786,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
             rowbuf[((kl + 1) * 2 + mm) * FL + col] = pc[jj].z;
           }
           had::wg_barrier<true>();
+          MSTAMP(4);
         }
         // a row on a PAIR of waves: wave rw its gate half, wave 4 + rw its up half, 4 consecutive elements per lane (index bits
         // 0..1 in registers, 2..7 = lane bits 0..5; ascending bit order: the same additions as fht16_lanes, fht_wg512.hip.h);
@@ -1766,7 +1825,9 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         }
         float* xch = reinterpret_cast<float*>(smem + B::kStage + RPO * FL * 4);     // [RPO][256]: the up halves
         if (act && mh == 1) *reinterpret_cast<float4*>(xch + rw * FL + lane * 4) = float4{o[0], o[1], o[2], o[3]};
+        MSTAMP(5);
         had::wg_barrier<true>();
+        MSTAMP(6);
         uint32_t* stage = reinterpret_cast<uint32_t*>(smem + B::kStage);
         if (act && mh == 0) {
           const float4 u4 = *reinterpret_cast<const float4*>(xch + rw * FL + lane * 4);
@@ -1787,6 +1848,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
           for (int r = 0; r < 4; ++r)
             stage16[(4 * lane + r) * RPO + rw] = __builtin_bit_cast(uint16_t, (f16)(e[r] * kPre));
         }
+        MSTAMP(7);
         had::wg_barrier<true>();
         // ... and out: granule (owner w, column j) = {rows 2 w | 2 w + 1 of column j, tag}: [owner][256], two columns per store
         if (tid < FL / 2) {
@@ -1794,10 +1856,110 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
           const uint2 d = *reinterpret_cast<const uint2*>(stage + 2 * tid);
           esync::st_granule2(frow + ((size_t)w * FL + 2 * tid), d.x, d.y, tag2);
         }
+#if !QUIP_ROWS_DIRECT
         had::wg_barrier<true>();                         // the staging area is free again (the gather below zeroes over it)
+#endif
+        // (QUIP_ROWS_DIRECT: nothing writes the area before down's planes, two barriers on)
       }
       BSTAMP(14);
       typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+      constexpr int KCT = B::KP16 / 16;                 // 16 x 16 tiles of the K x K factor per side (3; G8: 4)
+#if QUIP_ROWS_DIRECT
+      // gather the rows STRAIGHT INTO THE K-MIX'S A OPERANDS: granule (owner o, column j) = {fp16 rows 2 o | 2 o + 1 of column j,
+      // tag}, and the A fragment of lane (n, q) for tile = wave + 8 jt, k step s -- A[column 16 tile + n][rows 16 s + 4 q .. + 3] --
+      // IS the value words of the granules (8 s + 2 q, column) and (8 s + 2 q + 1, column).  So every thread requests its own
+      // 2 x KCT x 2 granules (the 16 lanes of an n group: 128 consecutive bytes; every granule goes to exactly one thread of the
+      // workgroup) and checks their tags itself: no LDS image, no zero-fill of its padding, no barrier between sweep and K-mix.
+      // (Rounds 5-6 swept 16-byte pieces into an LDS image [row pair][256] and read the fragments back, the four q groups of a
+      //  wave on the same banks.)  Owners >= NRO do not exist: their lanes -- whole q groups of the last k step -- request the
+      // step's first owners once more (no request depends on a branch), check no tag and hold zero.
+      u32x2_t arow[2][KCT];
+      {
+        static_assert(NRO % 2 == 0 && NRO > 8 * (KCT - 1) && NRO <= 8 * KCT, "only q groups of the last k step are beyond the owners");
+        if (kCheapPoll && wave == 0) {
+          uint32_t spins0 = 0;
+          // (eight of the last columns: 32 workgroups per polled line instead of 256 -- 256 pollers of ONE line delay the owners' stores to it)
+          const uint64_t* last = frow + ((size_t)(lane < NRO ? lane : 0) * FL + (FL - 1 - (w & 7)));
+          for (;;) {
+            u32x2_t f;
+            esync::ld8(f, last);
+            esync::drain();
+            esync::own(f);
+            if (esync::spin_step(f.y == tag2, spins0, ctl + 1, 0x3000u + (uint32_t)w)) break;
+          }
+        }
+        had::wg_barrier<true>();
+        BSTAMP(26);
+        const bool beyond = 8 * (KCT - 1) + 2 * q >= NRO;                 // this lane's owners of the last k step do not exist
+        // byte offsets from frow: owner 2 q (the last step: 0 where beyond), column 16 wave + n; + 8 s owners (the base),
+        // + 8 tiles per jt and + one owner per h (the instruction's offset)
+        const uint32_t vo_r = (uint32_t)((2 * q * FL + 16 * wave + n) * 8), vo_rl = (uint32_t)(((beyond ? 0 : 2 * q) * FL + 16 * wave + n) * 8);
+        u32x2_t g[2][KCT][2];
+        uint32_t spins = 0;
+        for (;;) {
+#pragma unroll
+          for (int s = 0; s < KCT; ++s) {
+            const char* base = reinterpret_cast<const char*>(frow) + (size_t)s * 8 * FL * 8;
+            const uint32_t vo = s == KCT - 1 ? vo_rl : vo_r;
+            if (s == 0) esync::ld8_at<0, true>(g[0][s][0], base, vo); else esync::ld8_at<0>(g[0][s][0], base, vo);
+            esync::ld8_at<FL * 8>(g[0][s][1], base, vo);
+            esync::ld8_at<kWaves * 16 * 8>(g[1][s][0], base, vo);
+            esync::ld8_at<kWaves * 16 * 8 + FL * 8>(g[1][s][1], base, vo);
+          }
+          esync::drain();
+          uint32_t diff = 0u;                            // (no branch per tag: the twelve differences OR-ed)
+#pragma unroll
+          for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+            for (int s = 0; s < KCT; ++s)
+#pragma unroll
+              for (int hh = 0; hh < 2; ++hh) {
+                esync::own(g[jt][s][hh]);
+                diff |= (s == KCT - 1 && beyond) ? 0u : (g[jt][s][hh].y ^ tag2);
+              }
+          if (esync::spin_step(diff == 0u, spins, ctl + 1, 0x2000u + (uint32_t)w)) break;
+        }
+        // the value words pair up into the A fragments HERE, in front of the requests below: the {value, tag} pairs are dead
+        // before the next block's codes claim their registers
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+          for (int s = 0; s < KCT; ++s) {
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+              const int o = 8 * s + 2 * q + hh;
+              const uint32_t msk = (s == KCT - 1 && beyond) ? 0u : ((2 * o + 1 < FK) ? 0xffffffffu : 0x0000ffffu);   // (row 43 does not exist)
+              arow[jt][s][hh] = g[jt][s][hh].x & msk;
+            }
+            esync::own(arow[jt][s]);
+          }
+        if constexpr (!RVQ) own_slots(SLOTS(M_DOWN));
+        BSTAMP(27);
+        if constexpr (RVQ) ISSUE_RVQ_DOWN_G0(Ld);
+        // the NEXT block's q, k, v rows (gate's slots: consumed): they land under the K-mix and down's product and are
+        // decoded inside the wait for z_d (rounds 3-4 requested them behind that hand-off)
+        if constexpr (kPreQkv && !QUIP_QKV_ISSUE_EARLY) {
+          // (the third item behind the K-mix: while the twelve A words wait for their MFMAs its eight registers do not fit --
+          //  the tiled kernel would need 242 VGPRs instead of 240 at most)
+          if constexpr (G8) { ISSUE8_QKV(Ln, 0); ISSUE8_QKV(Ln, 1); } else { ISSUE(Ln, 0); ISSUE(Ln, 1); }
+        }
+        // (the sum of squares of the rows on the way: down's block exponent comes from the norm bound |(H^T (x) I) r|_inf <=
+        //  |r|_2 -- the rows of the orthogonal factor are unit vectors (G8: of norm sqrt 8) -- known BEFORE the K-mix: no maximum over its results,
+        //  no reduction behind it; 4-5 of the 22 bits idle, as on the 4096-wide edges)
+        float ssr = 0.f;
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+          for (int s = 0; s < KCT; ++s)
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+              const f16x2 a0 = as_f16x2(arow[jt][s][hh]);
+              ssr = __builtin_fmaf((float)a0.x, (float)a0.x, ssr); ssr = __builtin_fmaf((float)a0.y, (float)a0.y, ssr);
+            }
+        ssr = had::wave_reduce_to_lane63<false>(ssr);
+        if (lane == 63) red[wave] = ssr;                 // (read behind the K-mix's barrier)
+      }
+#else
       // gather the rows: granule (owner o, column j) = {fp16 rows 2 o | 2 o + 1 of column j, tag}; a 16-byte piece = two columns
       {
         constexpr int PIECES = NRO * (FL / 2), NP = (PIECES + kThreads - 1) / kThreads;
@@ -1865,18 +2027,20 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         if (lane == 63) red[wave] = ssr;
       }
       had::wg_barrier<true>();
+#endif
       if constexpr (RVQ) ISSUE_RVQ_DOWN_G1(Ld);
       BSTAMP(15);
       typedef float f32x4 __attribute__((ext_vector_type(4)));
-      constexpr int KCT = B::KP16 / 16;                 // 16 x 16 tiles of the K x K factor per side (3; G8: 4)
       f32x4 acc[2][KCT];
 #pragma unroll
       for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
         for (int ct = 0; ct < KCT; ++ct) acc[jt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
       {
+#if !QUIP_ROWS_DIRECT
         const uint32_t* ft = reinterpret_cast<const uint32_t*>(smem + B::kArea);
-        // B fragments of the K-mix: had_d^T (the fp16 rows take [0, 24 K) of the area, the factor image behind them stays), a
+#endif
+        // B fragments of the K-mix: had_d^T (the factor image stays behind gate / up's planes until down's planes land), a
         // k step at a time
         const f16* hdT = reinterpret_cast<const f16*>(smem + B::kHad) + 2 * B::KKP;
 #pragma unroll
@@ -1888,7 +2052,12 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
           for (int jt = 0; jt < 2; ++jt) {
             const int tile = wave + jt * kWaves;
             // A[column 16 tile + n][rows 16 s + 4 q .. + 3] = the row pairs 8 s + 2 q and + 1 of that column
+#if QUIP_ROWS_DIRECT
+            (void)tile;
+            const uint2 apr = make_uint2(arow[jt][s].x, arow[jt][s].y);
+#else
             const uint2 apr = make_uint2(ft[(8 * s + 2 * q) * FL + 16 * tile + n], ft[(8 * s + 2 * q + 1) * FL + 16 * tile + n]);
+#endif
             const f16x4 ah = __builtin_bit_cast(f16x4, apr);
 #pragma unroll
             for (int ct = 0; ct < KCT; ++ct)
@@ -1897,12 +2066,22 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         }
       }
       if constexpr (RVQ) ISSUE_RVQ_DOWN_G2(Ld);
+      MSTAMP(8);
+#if QUIP_ROWS_DIRECT
+      if constexpr (kPreQkv && !QUIP_QKV_ISSUE_EARLY && !G8) ISSUE(Ln, 2);
+      // ONE barrier for both: every wave's K-mix has read the factor image (down's planes land on it), and the eight partial
+      // sums of squares are in red[]
+      had::wg_barrier<true>();
+#endif
       const float in_scale = Ld.sc[6] * 16.f;
       // (in_scale carries the prescale 1 / 16 of the rows back: the bound is for acc * in_scale, |acc|_inf <= |rows|_2)
       // (G8: the rows of the 56 x 56 factor R_7 (x) H_8 have norm sqrt 8, not 1 -- in_scale carries the 1 / sqrt 8 that undoes it)
       const float bound = sqrtf(red_sum8(0)) * fabsf(in_scale) * (1.0625f / kMixScale);
       const int sh_d = had::shift_for(bound * ((RVQ && !HI) ? fmaxf(1.f, fabsf(a.resid_scale)) : 1.f));
+#if !QUIP_ROWS_DIRECT
       had::wg_barrier<true>();                         // every wave's K-mix has read the rows: the planes land on them
+#endif
+      MSTAMP(9);
       {
         uint8_t* pl = reinterpret_cast<uint8_t*>(smem + B::kArea);
         const float s2 = had::fmul(in_scale, as_f32((uint32_t)(sh_d + 127) << 23));
@@ -1963,6 +2142,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
           for (int d = 0; d < 3; ++d) *reinterpret_cast<uint32_t*>(pl + d * B::kPlaneD + off) = 0u;
         }
       }
+      MSTAMP(10);
       had::wg_barrier<true>();
       BSTAMP(16);
       esync::drain();                                  // down's codes (and, behind them, the next block's q, k, v)

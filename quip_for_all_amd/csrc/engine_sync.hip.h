@@ -52,6 +52,13 @@ __device__ __forceinline__ void ld16_keep(u32x4_t& dst, const void* p) {
 __device__ __forceinline__ void ld8(u32x2_t& dst, const void* p) {
   asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(dst) : "v"(p) : "memory");
 }
+// a granule at scalar base + this lane's 32-bit byte offset + OFF (no 64-bit address per request: a burst of them costs one
+// offset register).  NOP: the first request behind a base that a VALU instruction may just have written (5 wait states)
+template <int OFF, bool NOP = false>
+__device__ __forceinline__ void ld8_at(u32x2_t& dst, const void* sbase, uint32_t voff) {
+  if constexpr (NOP) asm volatile("s_nop 4\n\tglobal_load_dwordx2 %0, %1, %2 offset:%3 sc1" : "=v"(dst) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
+  else asm volatile("global_load_dwordx2 %0, %1, %2 offset:%3 sc1" : "=v"(dst) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
+}
 __device__ __forceinline__ void ld4(uint32_t& dst, const void* p) {
   asm volatile("global_load_dword %0, %1, off sc1" : "=v"(dst) : "v"(p) : "memory");
 }

@@ -2,7 +2,9 @@
 """Phase clocks of one block inside the persistent token launch (csrc/decode_block.hip, BSTAMP), Llama-2-7B shape.
 usage: python tools/block_stamps.py [layers] [dbg_layer] [pos] [g8]      (g8: the Llama-3-8B shape, decode_block_g8.hip)
        python tools/block_stamps.py [layers] tail [pos] [g8]           the token's tail behind the last block (csrc/token_tail.hip.h:
-                                                                       dbg_layer = layers reuses the slots; the device-wide 100 MHz clock)"""
+                                                                       dbg_layer = layers reuses the slots; the device-wide 100 MHz clock)
+QUIP_MLP_STAMPS=1 with a library built with -DQUIP_MLP_STAMPS=1 (tools/dbg/build_variant.sh, QUIP_LIB_PATH): the finer stamps inside
+the MLP edge (gate / up products, row owners, K-mix and planes) instead of those inside the two 4096-wide edges."""
 import math
 import os
 import sys
@@ -94,15 +96,32 @@ for i in order:
     print(f"  {i:2d} {names[i]:34s} {seg.mean():9.0f} {seg[:, head].mean():9.0f} {seg[:, ~head].mean():9.0f}")
 span = D_[:, :, 3] - D_[:, :, 0]
 print(f"  block span (stamp 0 -> 3 of the next block): {span.mean():.0f} ticks")
+ro = np.arange(256) < (28 if g8 else 22)
+mlp_stamps = bool(os.environ.get("QUIP_MLP_STAMPS"))
+if mlp_stamps:     # a library built with -DQUIP_MLP_STAMPS=1: the two 4096-wide edges' slots (and 31) sit inside the MLP edge
+    M = [18, 19, 20, 21, 22, 23, 24, 28, 29, 30, 31]
+
+    def chain(title, pts, labels, sel):
+        print(title)
+        for i, lab in enumerate(labels):
+            print(f"  {lab:60s} {(D_[:, sel, pts[i + 1]] - D_[:, sel, pts[i]]).mean():9.0f}")
+    ev = np.ones(256, dtype=bool)
+    chain("inside 11 -> 12 (the gate / up products; everybody):", [11, M[0], M[1], M[2], M[3], 12],
+          ["factor image + owner vectors through registers into LDS", "drain (the codes of gate / up)",
+           "the items decoded ahead (7B: three; G8: two)", "the live items", "barrier"], ev)
+    chain("row owners, 13 -> 14 (wave 0: the gate half of the owner's first row):", [13, 25, M[4], M[5], M[6], M[7], 14],
+          ["down's items decoded ahead + inbox complete", "rows in LDS + barrier", "out-transform (256 points, SV), up half to LDS",
+           "crossing (barrier)", "SiLU product, SU, in-transform, rows staged", "barrier + published (+ barrier: parent)"], ro)
+    chain("inside 15 -> 16 (everybody):", [15, M[8], M[9], M[10], 16],
+          ["K-mix (MFMAs)", "norm bound + barrier", "down's planes", "barrier"], ev)
 # round 5: the edges' stages (fwd / rev): gate-up edge stamps 18..22, q-k-v edge stamps 23, 24, 28, 29, 30
 en = ["gathered", "fwd<1>", "h update + sums + ln, su", "rev<NT>", "planes + barrier"]
-for title, st, before, after in (("gate / up edge", [18, 19, 20, 21, 22], 10, 11), ("q / k / v edge", [23, 24, 28, 29, 30], 1, 2)):
+for title, st, before, after in (() if mlp_stamps else (("gate / up edge", [18, 19, 20, 21, 22], 10, 11), ("q / k / v edge", [23, 24, 28, 29, 30], 1, 2))):
     print(f"inside the {title} (stamps {st}):")
     for i in range(1, 5):
         seg = D_[:, :, st[i]] - D_[:, :, st[i - 1]]
         print(f"  {en[i]:28s} {seg.mean():9.0f}")
     print(f"  (stamp {before} -> {st[0]}: {(D_[:, :, st[0]] - D_[:, :, before]).mean():.0f}, {st[4]} -> {after}: {(D_[:, :, after] - D_[:, :, st[4]]).mean():.0f})")
-ro = np.arange(256) < (28 if g8 else 22)
 print("inside the MLP edge: row owners: publish(13) -> inbox complete %.0f, -> rows published(14) %.0f; everyone: 14 -> poll done(26) %.0f (row owners %.0f), sweep(27) %.0f, staging + barrier(15) %.0f" % (
     (D_[:, ro, 25] - D_[:, ro, 13]).mean(), (D_[:, ro, 14] - D_[:, ro, 25]).mean(), (D_[:, :, 26] - D_[:, :, 14]).mean(),
     (D_[:, ro, 26] - D_[:, ro, 14]).mean(), (D_[:, :, 27] - D_[:, :, 26]).mean(), (D_[:, :, 15] - D_[:, :, 27]).mean()))
