@@ -28,6 +28,10 @@
 // shapes stay on the stage-wise step.
 // Liveness: all 256 workgroups must be resident (one per CU by LDS footprint; nothing else may run on the device);
 // every wait is bounded and a launch that gives up leaves a code in ctl[1] (engine_sync.hip.h).
+#if defined(QUIP_POLL2) || defined(QUIP_POLL2_STAGGER) || defined(QUIP_ROWS_DIRECT) || defined(QUIP_MLP_PREFETCH) || defined(QUIP_INO_EXACT) || \
+    defined(QUIP_QKV_ISSUE_EARLY) || defined(QUIP_OWNER_PREDECODE) || defined(QUIP_ATT_THREADS) || defined(QUIP_OHEAD)
+#error "retired A/B switch (QUIP_POLL2, _POLL2_STAGGER, _ROWS_DIRECT, _MLP_PREFETCH, _INO_EXACT, _QKV_ISSUE_EARLY, _OWNER_PREDECODE, _ATT_THREADS, _OHEAD): the alternative was measured and its code removed; DESIGN.md 4.11 (QUIP_OHEAD: 4.13) has the result and the commit that still contains it"
+#endif
 #include "e8p_gemv_core.hip.h"
 #include "attn_query.hip.h"
 #include "engine_sync.hip.h"
@@ -35,20 +39,11 @@
 #include "token_tail.hip.h"
 #include "block_engine_host.hip.h"
 
-#ifndef QUIP_INO_EXACT
-#define QUIP_INO_EXACT 0
-#endif
 #ifndef QUIP_PREDECODE_DOWN
 #define QUIP_PREDECODE_DOWN 2      // items of down decoded inside the wait for the MLP rows (3: the register allocator spills 36 bytes)
 #endif
 #ifndef QUIP_PREDECODE_QKV
 #define QUIP_PREDECODE_QKV 2       // items of the NEXT block's q / k / v decoded inside the wait for z_d (0 | 2)
-#endif
-#ifndef QUIP_QKV_ISSUE_EARLY
-#define QUIP_QKV_ISSUE_EARLY 0     // A/B: the next block's q / k / v requested between the two halves of the gate / up products (1) or behind the rows' sweep (0)
-#endif
-#ifndef QUIP_OWNER_PREDECODE
-#define QUIP_OWNER_PREDECODE 1     // A/B: the MLP row owners decode down's items ahead like everybody (1) or at the product (0)
 #endif
 #ifndef QUIP_ATT_STAMPS
 #define QUIP_ATT_STAMPS 0          // tools/dbg: the stamps 18..22 inside the attention instead of inside the gate / up edge
@@ -61,29 +56,10 @@
 #else
 #define MSTAMP(i) do { } while (0)
 #endif
-#ifndef QUIP_ROWS_DIRECT
-#define QUIP_ROWS_DIRECT 1         // the MLP rows straight from the hand-off into the K-mix's A operands (1) or through an LDS image (0: rounds 5-6)
-#endif
-#ifndef QUIP_MLP_PREFETCH
-#define QUIP_MLP_PREFETCH 1        // the MLP's factor image and the row owners' vectors requested in front of the gate / up edge's gather and
-                                   // stored behind it (1), or loaded behind the edge, in front of the products (0: rounds 3-6)
-#endif
 #if QUIP_ATT_STAMPS
 #define ASTAMP(i) BSTAMP(18 + (i))
 #else
 #define ASTAMP(i) do { } while (0)
-#endif
-#ifndef QUIP_ATT_THREADS
-#define QUIP_ATT_THREADS 256       // threads of a workgroup that visit cached positions (A/B: 512 -- the rounds are VALU-issue bound, the
-                                   // second wave of a SIMD only makes the first one wait at the barrier: 6.9K -> 7.1K clocks at 100 positions)
-#endif
-#ifndef QUIP_POLL2
-#define QUIP_POLL2 0               // A/B: the edges' gathers poll with TWO staggered read sets (1) or one (0).  Measured: two sets make
-                                   // the hand-offs LONGER (z_o 3.6K -> 4.0K clocks, z_d 3.8K -> 4.4K; stagger 5 / 10 / 16 alike) -- the
-                                   // polls' traffic delays the stores they wait for by more than the finer grid gains
-#endif
-#ifndef QUIP_POLL2_STAGGER
-#define QUIP_POLL2_STAGGER 10      // s_sleep units (64 clocks) between the first requests of the two sets
 #endif
 // nibble mode: a decoded item waits as 16 scalar registers, not 32 -- more of them fit
 #ifndef QUIP_NIB_PREDECODE_QKV
@@ -95,15 +71,12 @@
 #ifndef QUIP_NIB_PREDECODE_DOWN
 #define QUIP_NIB_PREDECODE_DOWN 3
 #endif
-// o_proj's input transform split over its producers (round 6; 1 | 0 = every workgroup transforms all 4096 points of a (.) SU, rounds
-// 3-5), for the codebooks whose planes are the plain ones (E8P12, D4): H_4096 = H_32 (x) H_128 with the head index on top -- the head's
-// workgroup multiplies its 128 attention outputs by SU_o and runs their 128-point transform in ONE wave before it publishes them (two
-// fp32 per granule, esync::pack20x2: the same 64 granules per head); everybody gathers two heads x four columns per thread and finishes
-// with H_32 ACROSS heads -- one register stage and four lane stages, no LDS exchange -- and writes a dword of digits per head and
-// plane.  (decode_block_gqa.hip: QUIP_GQA_OHEAD.)
-#ifndef QUIP_OHEAD
-#define QUIP_OHEAD 1
-#endif
+// o_proj's input transform is split over its producers (round 6) for the codebooks whose planes are the plain ones (E8P12, D4):
+// H_4096 = H_32 (x) H_128 with the head index on top -- the head's workgroup multiplies its 128 attention outputs by SU_o and runs
+// their 128-point transform in ONE wave before it publishes them (two fp32 per granule, esync::pack20x2: the same 64 granules per
+// head); everybody gathers two heads x four columns per thread and finishes with H_32 ACROSS heads -- one register stage and four
+// lane stages, no LDS exchange -- and writes a dword of digits per head and plane (kOHead; decode_block_gqa.hip does the same).  The
+// RVQ codebooks and HI transform all 4096 points of a (.) SU on every workgroup, as rounds 3-5 did.
 #ifndef QUIP_PREDECODE_GATE
 #define QUIP_PREDECODE_GATE 2      // items of gate / up decoded inside the wait for z_o (3: spills 60 bytes)
 #endif
@@ -195,7 +168,6 @@ constexpr size_t kWsInbox = kWsZ + 6 * kWsVec, kWsRows = kWsInbox + (size_t)NRO 
 // rows hand-off: wave 0 polls the last column before everybody sweeps the rows (45 KB of granules since round 5's fp16 rows; 90 KB
 // when this was measured).  Without it (every workgroup sweeping until its pieces are all there) the hand-off took 29.5K clocks
 // instead of 21.4K: 256 x 90 KB of polls per retry crowd out the owners' stores
-constexpr bool kCheapPoll = true;
 constexpr int kParts = 8, kPartGran = 132, kSplitPos = 128;      // (measured: 1.83 ms per token at 200 positions on one workgroup per head, 1.74 at 256 split)
 constexpr size_t kWsPart = kWsRows + (size_t)FL * 48 * 8;
 // short contexts: the head's second / third workgroup transform k / v of the new position and hand its 128 values over
@@ -236,17 +208,16 @@ struct BLds {
   // In time: the transforms' exchange buffers (16.5 KB per transform from the base: 1, 2 or -- attention -- 3) -> digit planes
   // of the consumers (12 / 24 KB from the base, written after the transforms' last reads) | attention partials; for the MLP:
   // planes [0, 24 K) + the K x K factor image [24 K, 36 K) + the row owners' vectors [36 K, 48 K) (both stored while the gate / up
-  // edge's exchange buffer is alive, QUIP_MLP_PREFETCH: they lie behind it) -> row owners: inbox rows [0, 8 K), rows on the way
-  // out [8 K, 16 K) -> (QUIP_ROWS_DIRECT: the gathered rows never touch LDS; before: their image [0, 24 K)) -> down's planes
-  // [0, 35.1 K), over the factor image once every wave's K-mix has read it.
+  // edge's exchange buffer is alive: they lie behind it) -> row owners: inbox rows [0, 8 K), rows on the way out [8 K, 16 K) ->
+  // (the gathered rows never touch LDS: they are the K-mix's A operands) -> down's planes [0, 35.1 K), over the factor image once
+  // every wave's K-mix has read it.
   static constexpr int kArea = kCs + 2 * HD * 4;
   static constexpr int kBufBytes = ((had::buf_floats(HID) * 4) + 15) & ~15;
   static constexpr int kAreaBytes = (160 * 1024 - kArea) & ~15;
   static constexpr int kBuf0 = kArea;
   static constexpr int kHadElems = 2 * KKP + KP16 * KPS;
   static constexpr int kStage = kArea + 8 * 1024;            // MLP row owners: their four rows, transposed, on the way out (4 KB)
-  // fp16 image of the three K x K factors (12 KB; G8: 20.3 KB), behind the planes of gate / up and behind the rows' LDS image
-  // ([KP16 / 2][256] fp16 pairs = 24 KB; G8: 32 KB)
+  // fp16 image of the three K x K factors (12 KB; G8: 20.3 KB), behind the planes of gate / up (G8: at 32 K)
   static constexpr int kHad = kArea + (G8 ? 32 * 1024 : 2 * 3 * PSH);
   // MLP row owners: SV_gate / SV_up / SU_down of their rows (3 KB): behind the factor image; G8: at 17 K (free while they are alive:
   // the gate / up edge's exchange buffer ends at 16.5 K, the planes of the ONE consumer at 12.5 K, the owners' rows and staging at 12 K)
@@ -260,10 +231,10 @@ struct BLds {
   static constexpr int HOD = up256(kHalfD, 16);
   static constexpr int kPlaneD = kNib ? up256(HOD + kHalfD, 64) : (KPDV / 256) * 272;
   static constexpr int kBytes = kArea + kAreaBytes;
-  static_assert(kAreaBytes >= 3 * kBufBytes && kAreaBytes >= FL * KP16 * 2 && kAreaBytes >= 3 * kPlaneD &&
+  static_assert(kAreaBytes >= 3 * kBufBytes && kAreaBytes >= 3 * kPlaneD &&
                 kHad + kHadElems * 2 <= kArea + kAreaBytes && kStash + 6 * 1024 <= (G8 ? kHad : kArea + kAreaBytes),
                 "transient area");
-  // (QUIP_MLP_PREFETCH: both are written while the gate / up edge's ONE exchange buffer is alive, in front of its planes)
+  // (both are written while the gate / up edge's ONE exchange buffer is alive, in front of its planes)
   static_assert(kHad >= kBuf0 + kBufBytes && kStash >= kBuf0 + kBufBytes && kStash >= kArea + 3 * PSH, "factor image and owner vectors: clear of the gate / up edge");
 };
 #if QUIP_BLOCK_G8
@@ -332,7 +303,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
   auto qblk = [](int b) { return b < 256 ? b : (b < 320 ? b - 256 : b - 320); };
   uint32_t lane_c, lane_c2, lane_c3 = 0u, xlane;
   constexpr bool NIB = T::kNib;
-  constexpr bool kOHead = QUIP_OHEAD != 0 && !RVQ;     // (the RVQ codebooks' and HI's virtual rows scatter their planes differently)
+  constexpr bool kOHead = !RVQ;                         // (the RVQ codebooks' and HI's virtual rows scatter their planes differently)
   constexpr int kPreW = NIB ? 16 : 32;                  // dwords of a decoded item that waits in registers
   constexpr int kUnsc = T::kD4 ? 1 : (NIB ? 5 : 2);     // the accumulator rows hold 2^kUnsc x sum of digit x w (table entries 4 w / 2 w; nibble mode 8 x 4 w)
   NibLane nlf = {0, 0, 0u};                             // nibble mode: this lane's factors of an item's rows (item_rows_nib)
@@ -614,91 +585,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       had::unpack8(make_uint4(p[2 * c].x, p[2 * c].z, p[2 * c + 1].x, p[2 * c + 1].z), out[c]);
     own_slots(slots);
   };
-  // The same with TWO read sets in flight, half a round trip apart.  A hand-off ends when the LAST of 2048 waves has seen its
-  // pieces: with one set a wave notices them up to a full round trip (~0.7 us) after they became visible, with two up to half
-  // of one.  The loop is ONE asm statement on sixteen NAMED registers (v[236:251]): written in C++ the sets are in flight
-  // across the loop's back edge, where the allocator is free to split a live range -- it copied the registers BEFORE the
-  // wait (tools/check_inflight.py).  On success the other set is still in flight: its registers stay bound to `pa`, `pb`
-  // until the caller has said poll2_settle with N = the VMEM requests it has issued since (vmcnt retires in order).
-  auto gather2 = [&](auto slots, int first, uint32_t tag, uint32_t code, float (&out)[1][8], u32x4_t (&pa)[2], u32x4_t (&pb)[2]) {
-    const uint64_t* src = zbufs + (size_t)first * 2048 + 4 * tid;
-    uint32_t o0, o1, o2, o3, st, cnt, rounds = 0;
-    uint64_t tmp;
-#pragma nounroll
-    for (;;) {
-      asm volatile(
-          "global_load_dwordx4 v[236:239], %[src], off sc1\n\t"
-          "global_load_dwordx4 v[240:243], %[src], off offset:16 sc1\n\t"
-          "s_sleep %[stag]\n\t"
-          "global_load_dwordx4 v[244:247], %[src], off sc1\n\t"
-          "global_load_dwordx4 v[248:251], %[src], off offset:16 sc1\n\t"
-          "s_movk_i32 %[cnt], 64\n"
-          ".Lp2_top_%=:\n\t"
-          "s_waitcnt vmcnt(2)\n\t"
-          "v_cmp_eq_u32_e32 vcc, %[tag], v237\n\t"
-          "v_cmp_eq_u32_e64 %[tmp], %[tag], v239\n\t"
-          "s_and_b64 vcc, vcc, %[tmp]\n\t"
-          "v_cmp_eq_u32_e64 %[tmp], %[tag], v241\n\t"
-          "s_and_b64 vcc, vcc, %[tmp]\n\t"
-          "v_cmp_eq_u32_e64 %[tmp], %[tag], v243\n\t"
-          "s_and_b64 vcc, vcc, %[tmp]\n\t"
-          "s_cmp_eq_u64 vcc, exec\n\t"
-          "s_cbranch_scc1 .Lp2_a_%=\n\t"
-          "global_load_dwordx4 v[236:239], %[src], off sc1\n\t"
-          "global_load_dwordx4 v[240:243], %[src], off offset:16 sc1\n\t"
-          "s_waitcnt vmcnt(2)\n\t"
-          "v_cmp_eq_u32_e32 vcc, %[tag], v245\n\t"
-          "v_cmp_eq_u32_e64 %[tmp], %[tag], v247\n\t"
-          "s_and_b64 vcc, vcc, %[tmp]\n\t"
-          "v_cmp_eq_u32_e64 %[tmp], %[tag], v249\n\t"
-          "s_and_b64 vcc, vcc, %[tmp]\n\t"
-          "v_cmp_eq_u32_e64 %[tmp], %[tag], v251\n\t"
-          "s_and_b64 vcc, vcc, %[tmp]\n\t"
-          "s_cmp_eq_u64 vcc, exec\n\t"
-          "s_cbranch_scc1 .Lp2_b_%=\n\t"
-          "global_load_dwordx4 v[244:247], %[src], off sc1\n\t"
-          "global_load_dwordx4 v[248:251], %[src], off offset:16 sc1\n\t"
-          "s_sleep 1\n\t"
-          "s_sub_u32 %[cnt], %[cnt], 1\n\t"
-          "s_cmp_lg_u32 %[cnt], 0\n\t"
-          "s_cbranch_scc1 .Lp2_top_%=\n\t"
-          "s_waitcnt vmcnt(0)\n\t"                    // nothing yet: everything lands, the caller looks at the error word
-          "s_mov_b32 %[st], 0\n\t"
-          "s_branch .Lp2_end_%=\n"
-          ".Lp2_a_%=:\n\t"
-          "v_mov_b32 %[o0], v236\n\t"
-          "v_mov_b32 %[o1], v238\n\t"
-          "v_mov_b32 %[o2], v240\n\t"
-          "v_mov_b32 %[o3], v242\n\t"
-          "s_mov_b32 %[st], 1\n\t"
-          "s_branch .Lp2_end_%=\n"
-          ".Lp2_b_%=:\n\t"
-          "v_mov_b32 %[o0], v244\n\t"
-          "v_mov_b32 %[o1], v246\n\t"
-          "v_mov_b32 %[o2], v248\n\t"
-          "v_mov_b32 %[o3], v250\n\t"
-          "s_mov_b32 %[st], 1\n"
-          ".Lp2_end_%=:"
-          : "={v[236:239]}"(pa[0]), "={v[240:243]}"(pa[1]), "={v[244:247]}"(pb[0]), "={v[248:251]}"(pb[1]), [o0] "=&v"(o0), [o1] "=&v"(o1),
-            [o2] "=&v"(o2), [o3] "=&v"(o3), [st] "=&s"(st), [cnt] "=&s"(cnt), [tmp] "=&s"(tmp)
-          : [src] "v"(src), [tag] "s"(tag), [stag] "n"(QUIP_POLL2_STAGGER)
-          : "vcc", "scc", "memory");
-      if (st != 0u) break;
-      // 128 polls without the pieces: the launch-wide error word, the bound (spin_step's arithmetic)
-      uint32_t e;
-      esync::ld4(e, ctl + 1);
-      esync::drain();
-      esync::own(e);
-      if (__builtin_amdgcn_readfirstlane(e) != 0u) break;
-      rounds += 128u;
-      if (rounds >= esync::kSpinLimit) {
-        if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u) esync::st_word(ctl + 1, code + (uint32_t)w);
-        break;
-      }
-    }
-    had::unpack8(make_uint4(o0, o1, o2, o3), out[0]);
-    own_slots(slots);
-  };
   // this workgroup's 16 values of a product (accumulator rows [row0, row0 + 16), block exponent sh) -> 8 granules
   auto publish16 = [&](int vec, int gr0, int row0, int sh, uint32_t tag) {      // gr0: first granule of the block in its vector
     if (tid < 8) {
@@ -783,8 +669,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
     return r;
   };
   auto edge = [&](auto z_tag, auto nc_tag, auto slots, int zvec, uint32_t tag, uint32_t code, const f16* sv_prev, const f16* ln,
-                  const f16* su0, const f16* su1, float sc0, float sc1, bool two, auto after_gather, auto drip1, auto drip2, int sb, auto ag_tag) {
-    // ag_tag: VMEM requests `after_gather` issues (a hand count: the wait for the gather's second read set is said in them)
+                  const f16* su0, const f16* su1, float sc0, float sc1, bool two, auto after_gather, auto drip1, auto drip2, int sb) {
     // stamps of the edge's stages: 18..22 (sb = 18: the gate / up edge) or 23, 24, 28, 29, 30 (sb = 23: the q / k / v edge)
 #if QUIP_ATT_STAMPS || QUIP_MLP_STAMPS
 #define ESTAMP(i) do { } while (0)
@@ -803,12 +688,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
     auto u4 = [](const u32x4& v) { return make_uint4(v.x, v.y, v.z, v.w); };
     if constexpr (HAVE_Z) {
       float v[1][8];
-#if QUIP_POLL2
-      u32x4_t pa[2], pb[2];
-      gather2(slots, zvec, tag, code, v, pa, pb);
-#else
       gather(std::integral_constant<int, 1>{}, slots, zvec, tag, code, v);
-#endif
       // The vectors have landed (the gather drained the queue).  Take them over HERE: the compiler counts only its own
       // loads, so the wait it would place at their first use would also wait for the burst requested below.
       asm volatile("" : "+v"(psv));
@@ -816,12 +696,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       after_gather();
       ESTAMP(0);
       hadw::fwd<12, 1, true>(v, xbuf, tid);
-#if QUIP_POLL2
-      // the read set that was still in flight when the other one succeeded has had the transform's time to land
-      if (dbg_on) esync::drain();                      // (a stamp is a store: one more request than counted)
-      asm volatile("s_waitcnt vmcnt(%0)" : : "n"(decltype(ag_tag)::value), "{v[236:239]}"(pa[0]), "{v[240:243]}"(pa[1]), "{v[244:247]}"(pb[0]),
-                   "{v[248:251]}"(pb[1]) : "memory");
-#endif
       ESTAMP(1);
       float svf[8];
       had::unpack8(u4(psv), svf);
@@ -1103,7 +977,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
     rederive();
     const int c_lo = qc_lo, c_hi = qc_hi;
     edge(std::false_type{}, std::integral_constant<int, 2>{}, SLOTS(M_QKV), -1, 0u, 0u, nullptr, Ld.ln[0], Ld.su[c_lo], Ld.su[c_hi],
-         Ld.sc[c_lo], Ld.sc[c_hi], c_hi != c_lo, [&]() {}, [&]() {}, [&]() {}, -1, std::integral_constant<int, 0>{});
+         Ld.sc[c_lo], Ld.sc[c_hi], c_hi != c_lo, [&]() {}, [&]() {}, [&]() {}, -1);
     uint32_t none[NPQ][kPreW];                          // (block 0: nothing decoded ahead; never read)
     P1_products(std::false_type{}, none);
   }
@@ -1139,7 +1013,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       // written: 2 us per dependent round otherwise); later rounds are requested two rounds ahead of their use
       // (U: cached rows per key group and round; E8P12RVQ4B, at 256 registers, prefetches half as many -- the keys are
       //  visited in the same order either way)
-      constexpr int ATH = QUIP_ATT_THREADS;
+      constexpr int ATH = 256;                         // threads of a workgroup that visit cached positions
       constexpr int LPK = HD / 8, NG = ATH / LPK, U = (RVQ && !HI && !R3) ? 2 : 4;
       constexpr int NST = ATH / 64;                    // online-softmax states that meet in LDS: one per wave
       const int g = (tid & (ATH - 1)) / LPK;
@@ -1510,15 +1384,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         // of o's input side: they have o's product, a hand-off and an edge to land
         if constexpr (RVQ) ISSUE_RVQ_GATE_G(Ld, 0); else if constexpr (G8) ISSUE8_GU(Ld, 0); else ISSUE(Ld, 4);
         BSTAMP(7);
-#if QUIP_INO_EXACT      /* A/B (tools/dbg): rounds 3-4's o input side -- the exact maximum behind the transform */
-        had::mul8(v[0], make_uint4(psu.x, psu.y, psu.z, psu.w));
-        had8::fht4096<1, true>(v, xbuf, tid);
-        if constexpr (RVQ) ISSUE_RVQ_GATE_G(Ld, 1); else if constexpr (G8) ISSUE8_GU(Ld, 1); else ISSUE(Ld, 5);
-        const float sco = Ld.sc[3];
-        const float mx = had8::max4096<true>(had8::absmax8(v[0], sco), red, tid);
-        if constexpr (RVQ) ISSUE_RVQ_GATE_G(Ld, 2); else if constexpr (G8) ISSUE8_GU(Ld, 2); else ISSUE(Ld, 6);
-        const int sh = had::shift_for(mx * ((RVQ && !HI) ? fmaxf(1.f, fabsf(a.resid_scale)) : 1.f));
-#else
         had::mul8(v[0], make_uint4(psu.x, psu.y, psu.z, psu.w));
         {
           // the planes' block exponent from the norm bound (see edge()): the sum of squares of the transform's INPUT, per-wave
@@ -1536,7 +1401,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         had::wg_barrier<true>();                         // the transform's last reads of the exchange buffer: the planes land on it
         const int sh = norm_shift(red_sum8(0), sco);
         if constexpr (RVQ) ISSUE_RVQ_GATE_G(Ld, 2); else if constexpr (G8) ISSUE8_GU(Ld, 2); else ISSUE(Ld, 6);
-#endif
         if constexpr (HI) had8::planes_scatter_hi(v[0], sco, sh, reinterpret_cast<uint8_t*>(smem + B::kArea), tid);
         else if constexpr (RVQ) had8::planes_scatter_rvq(v[0], sco, a.resid_scale, sh, reinterpret_cast<uint8_t*>(smem + B::kArea), tid);
         else if constexpr (NIB) {
@@ -1587,7 +1451,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       for (int i = 0; i < kPreG; ++i) decode_pre(i, Bg[i]);
     }
 #endif
-#if QUIP_MLP_PREFETCH
     // The MLP edge's K x K factor image (everybody) and SV_gate / SV_up / SU_down of the row owners' rows: plain loads HERE, next to
     // the edge's own vectors -- the gather's polls drain the queue, after_gather takes them over and stores them into the free
     // tail of the area (clear of the edge's exchange buffer and planes).  Rounds 3-6 loaded them behind the edge: a memory
@@ -1617,35 +1480,13 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       // piece p = (row, vector, 16-byte piece) in this order: byte p * 16 of the stash
       if (w < NRO && tid < OPIECES) *reinterpret_cast<u32x4*>(smem + B::kStash + tid * 16) = ovec;
     };
-#else
-    auto land_mlp_vectors = []() { };
-#endif
     // (ONE consumer per workgroup: its half of the machine multiplies gate, the other half up)
     edge(std::true_type{}, std::integral_constant<int, 2>{}, SLOTS(M_GATE), 4, ebase | hop, 0x7000u, Ld.sv[3], Ld.ln[1], Ld.su[4 + mgu], Ld.su[4 + mgu], Ld.sc[4 + mgu], Ld.sc[4 + mgu], false,
          // up's row blocks (RVQ: their first virtual slice) behind the hand-off, one at a time between the edge's stages
          [&]() { land_mlp_vectors(); BSTAMP(10); if constexpr (RVQ) ISSUE_RVQ_UP_A_G(Ld, 0); else if constexpr (G8) { ISSUE8_GU(Ld, 3); ISSUE8_GU(Ld, 4); } else ISSUE(Ld, 7); },
          [&]() { if constexpr (RVQ) ISSUE_RVQ_UP_A_G(Ld, 1); else if constexpr (G8) ISSUE8_GU(Ld, 5); else ISSUE(Ld, 8); },
-         [&]() { if constexpr (RVQ) ISSUE_RVQ_UP_A_G(Ld, 2); else if constexpr (G8) ISSUE8_GU(Ld, 6); else ISSUE(Ld, 9); }, 18,
-         std::integral_constant<int, G8 ? 4 : 2>{});
+         [&]() { if constexpr (RVQ) ISSUE_RVQ_UP_A_G(Ld, 2); else if constexpr (G8) ISSUE8_GU(Ld, 6); else ISSUE(Ld, 9); }, 18);
     BSTAMP(11);
-    // row owners (w < NRO: rows k' = RPO w .. RPO w + RPO - 1, one per wave): SV_gate / SV_up / SU_down of their rows into the free
-    // tail of the area; everybody: the image of the K x K factors, for the MLP edge
-#if !QUIP_MLP_PREFETCH
-    {
-      if (w < NRO) {
-        for (int p = tid; p < RPO * 3 * (FL / 8); p += kThreads) {
-          const int row = p / (3 * (FL / 8)), rem = p - row * (3 * (FL / 8));
-          const int vsel = rem / (FL / 8), piece = rem - vsel * (FL / 8);
-          const int kr = RPO * w + row < FK ? RPO * w + row : FK - 1;
-          const f16* vsrc = (vsel == 0 ? Ld.sv[4] : (vsel == 1 ? Ld.sv[5] : Ld.su[6])) + (size_t)kr * FL + piece * 8;
-          *reinterpret_cast<uint4*>(smem + B::kStash + ((row * 3 + vsel) * FL + piece * 8) * 2) = *reinterpret_cast<const uint4*>(vsrc);
-        }
-      }
-      constexpr int HPIECES = B::kHadElems / 8;
-      for (int i = tid; i < HPIECES; i += kThreads)
-        *reinterpret_cast<uint4*>(smem + B::kHad + i * 16) = reinterpret_cast<const uint4*>(Ld.had3)[i];
-    }
-#endif
     MSTAMP(0);
     esync::drain();
     own_slots(SLOTS(M_GATE | M_UP));
@@ -1689,7 +1530,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
 #if QUIP_PREDECODE_GATE
       run_items3_pre(std::integral_constant<int, kPreG>{}, Bg, 0, xlane, xlane, xlane, 64);
       MSTAMP(2);
-      if constexpr (kPreQkv && QUIP_QKV_ISSUE_EARLY) { ISSUE(Ln, 0); ISSUE(Ln, 1); ISSUE(Ln, 2); }
 #else
       run_items3(0, xlane, xlane, xlane, 64);                                     // first column's three row blocks
 #endif
@@ -1856,27 +1696,22 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
           const uint2 d = *reinterpret_cast<const uint2*>(stage + 2 * tid);
           esync::st_granule2(frow + ((size_t)w * FL + 2 * tid), d.x, d.y, tag2);
         }
-#if !QUIP_ROWS_DIRECT
-        had::wg_barrier<true>();                         // the staging area is free again (the gather below zeroes over it)
-#endif
-        // (QUIP_ROWS_DIRECT: nothing writes the area before down's planes, two barriers on)
+        // (no barrier: nothing writes the area before down's planes, two barriers on)
       }
       BSTAMP(14);
       typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
       constexpr int KCT = B::KP16 / 16;                 // 16 x 16 tiles of the K x K factor per side (3; G8: 4)
-#if QUIP_ROWS_DIRECT
       // gather the rows STRAIGHT INTO THE K-MIX'S A OPERANDS: granule (owner o, column j) = {fp16 rows 2 o | 2 o + 1 of column j,
       // tag}, and the A fragment of lane (n, q) for tile = wave + 8 jt, k step s -- A[column 16 tile + n][rows 16 s + 4 q .. + 3] --
       // IS the value words of the granules (8 s + 2 q, column) and (8 s + 2 q + 1, column).  So every thread requests its own
       // 2 x KCT x 2 granules (the 16 lanes of an n group: 128 consecutive bytes; every granule goes to exactly one thread of the
-      // workgroup) and checks their tags itself: no LDS image, no zero-fill of its padding, no barrier between sweep and K-mix.
-      // (Rounds 5-6 swept 16-byte pieces into an LDS image [row pair][256] and read the fragments back, the four q groups of a
-      //  wave on the same banks.)  Owners >= NRO do not exist: their lanes -- whole q groups of the last k step -- request the
-      // step's first owners once more (no request depends on a branch), check no tag and hold zero.
+      // workgroup) and checks their tags itself: the rows never touch LDS, no barrier between sweep and K-mix.  Owners >= NRO do not
+      // exist: their lanes -- whole q groups of the last k step -- request the step's first owners once more (no request depends on a
+      // branch), check no tag and hold zero.
       u32x2_t arow[2][KCT];
       {
         static_assert(NRO % 2 == 0 && NRO > 8 * (KCT - 1) && NRO <= 8 * KCT, "only q groups of the last k step are beyond the owners");
-        if (kCheapPoll && wave == 0) {
+        if (wave == 0) {
           uint32_t spins0 = 0;
           // (eight of the last columns: 32 workgroups per polled line instead of 256 -- 256 pollers of ONE line delay the owners' stores to it)
           const uint64_t* last = frow + ((size_t)(lane < NRO ? lane : 0) * FL + (FL - 1 - (w & 7)));
@@ -1938,7 +1773,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         if constexpr (RVQ) ISSUE_RVQ_DOWN_G0(Ld);
         // the NEXT block's q, k, v rows (gate's slots: consumed): they land under the K-mix and down's product and are
         // decoded inside the wait for z_d (rounds 3-4 requested them behind that hand-off)
-        if constexpr (kPreQkv && !QUIP_QKV_ISSUE_EARLY) {
+        if constexpr (kPreQkv) {
           // (the third item behind the K-mix: while the twelve A words wait for their MFMAs its eight registers do not fit --
           //  the tiled kernel would need 242 VGPRs instead of 240 at most)
           if constexpr (G8) { ISSUE8_QKV(Ln, 0); ISSUE8_QKV(Ln, 1); } else { ISSUE(Ln, 0); ISSUE(Ln, 1); }
@@ -1959,75 +1794,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         ssr = had::wave_reduce_to_lane63<false>(ssr);
         if (lane == 63) red[wave] = ssr;                 // (read behind the K-mix's barrier)
       }
-#else
-      // gather the rows: granule (owner o, column j) = {fp16 rows 2 o | 2 o + 1 of column j, tag}; a 16-byte piece = two columns
-      {
-        constexpr int PIECES = NRO * (FL / 2), NP = (PIECES + kThreads - 1) / kThreads;
-        // LDS image [KP16 / 2 row pairs][256 columns] of fp16 pairs (rows 2 o, 2 o + 1): the sweep's pieces (one owner, two
-        // columns) land as 8-byte stores on consecutive addresses (a [column][pair] image put 32 lanes on two banks)
-        uint32_t* ft = reinterpret_cast<uint32_t*>(smem + B::kArea);
-        for (int j = tid; j < (B::KP16 / 2 - NRO) * FL; j += kThreads) ft[NRO * FL + j] = 0u;
-        if (kCheapPoll && wave == 0) {
-          uint32_t spins0 = 0;
-          // (eight of the last columns: 32 workgroups per polled line instead of 256 -- 256 pollers of ONE line delay the owners' stores to it)
-          const uint64_t* last = frow + ((size_t)(lane < NRO ? lane : 0) * FL + (FL - 1 - (w & 7)));
-          for (;;) {
-            u32x2_t f;
-            esync::ld8(f, last);
-            esync::drain();
-            esync::own(f);
-            if (esync::spin_step(f.y == tag2, spins0, ctl + 1, 0x3000u + (uint32_t)w)) break;
-          }
-        }
-        had::wg_barrier<true>();
-        BSTAMP(26);
-        u32x4_t p[NP];
-        uint32_t spins = 0;
-        for (;;) {
-#pragma unroll
-          for (int j = 0; j < NP; ++j) {
-            const int i = tid + kThreads * j;
-            esync::ld16(p[j], frow + 2 * (size_t)(i < PIECES ? i : 0));
-          }
-          esync::drain();
-          bool ok = true;
-#pragma unroll
-          for (int j = 0; j < NP; ++j) {
-            esync::own(p[j]);
-            ok = ok && p[j].y == tag2 && p[j].w == tag2;
-          }
-          if (esync::spin_step(ok, spins, ctl + 1, 0x2000u + (uint32_t)w)) break;
-        }
-        if constexpr (!RVQ) own_slots(SLOTS(M_DOWN));
-        BSTAMP(27);
-        if constexpr (RVQ) ISSUE_RVQ_DOWN_G0(Ld);
-        // the NEXT block's q, k, v rows (gate's slots: consumed): they land under the K-mix and down's product and are
-        // decoded inside the wait for z_d (rounds 3-4 requested them behind that hand-off)
-        if constexpr (kPreQkv && !QUIP_QKV_ISSUE_EARLY) {
-          if constexpr (G8) { ISSUE8_QKV(Ln, 0); ISSUE8_QKV(Ln, 1); } else { ISSUE(Ln, 0); ISSUE(Ln, 1); ISSUE(Ln, 2); }
-        }
-        // (the sum of squares of the rows on the way: down's block exponent comes from the norm bound |(H^T (x) I) r|_inf <=
-        //  |r|_2 -- the rows of the orthogonal factor are unit vectors (G8: of norm sqrt 8) -- known BEFORE the K-mix: no maximum over its results,
-        //  no reduction behind it; 4-5 of the 22 bits idle, as on the 4096-wide edges)
-        float ssr = 0.f;
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-          const int i = tid + kThreads * j;
-          if (i < PIECES) {
-            const int o = i / (FL / 2), cp = i - o * (FL / 2);
-            const uint32_t msk = (2 * o + 1 < FK) ? 0xffffffffu : 0x0000ffffu;       // (row 43 does not exist)
-            const uint32_t r0 = p[j].x & msk, r1 = p[j].z & msk;
-            *reinterpret_cast<uint2*>(ft + o * FL + 2 * cp) = make_uint2(r0, r1);
-            const f16x2 a0 = as_f16x2(r0), a1 = as_f16x2(r1);
-            ssr = __builtin_fmaf((float)a0.x, (float)a0.x, ssr); ssr = __builtin_fmaf((float)a0.y, (float)a0.y, ssr);
-            ssr = __builtin_fmaf((float)a1.x, (float)a1.x, ssr); ssr = __builtin_fmaf((float)a1.y, (float)a1.y, ssr);
-          }
-        }
-        ssr = had::wave_reduce_to_lane63<false>(ssr);
-        if (lane == 63) red[wave] = ssr;
-      }
-      had::wg_barrier<true>();
-#endif
       if constexpr (RVQ) ISSUE_RVQ_DOWN_G1(Ld);
       BSTAMP(15);
       typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -2037,9 +1803,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
 #pragma unroll
         for (int ct = 0; ct < KCT; ++ct) acc[jt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
       {
-#if !QUIP_ROWS_DIRECT
-        const uint32_t* ft = reinterpret_cast<const uint32_t*>(smem + B::kArea);
-#endif
         // B fragments of the K-mix: had_d^T (the factor image stays behind gate / up's planes until down's planes land), a
         // k step at a time
         const f16* hdT = reinterpret_cast<const f16*>(smem + B::kHad) + 2 * B::KKP;
@@ -2050,14 +1813,8 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
           for (int ct = 0; ct < KCT; ++ct) bfs[ct] = *reinterpret_cast<const f16x4*>(hdT + (16 * ct + n) * B::KPS + 16 * s + 4 * q);
 #pragma unroll
           for (int jt = 0; jt < 2; ++jt) {
-            const int tile = wave + jt * kWaves;
-            // A[column 16 tile + n][rows 16 s + 4 q .. + 3] = the row pairs 8 s + 2 q and + 1 of that column
-#if QUIP_ROWS_DIRECT
-            (void)tile;
+            // A[column 16 (wave + 8 jt) + n][rows 16 s + 4 q .. + 3] = the row pairs 8 s + 2 q and + 1 of that column
             const uint2 apr = make_uint2(arow[jt][s].x, arow[jt][s].y);
-#else
-            const uint2 apr = make_uint2(ft[(8 * s + 2 * q) * FL + 16 * tile + n], ft[(8 * s + 2 * q + 1) * FL + 16 * tile + n]);
-#endif
             const f16x4 ah = __builtin_bit_cast(f16x4, apr);
 #pragma unroll
             for (int ct = 0; ct < KCT; ++ct)
@@ -2067,20 +1824,15 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       }
       if constexpr (RVQ) ISSUE_RVQ_DOWN_G2(Ld);
       MSTAMP(8);
-#if QUIP_ROWS_DIRECT
-      if constexpr (kPreQkv && !QUIP_QKV_ISSUE_EARLY && !G8) ISSUE(Ln, 2);
+      if constexpr (kPreQkv && !G8) ISSUE(Ln, 2);
       // ONE barrier for both: every wave's K-mix has read the factor image (down's planes land on it), and the eight partial
       // sums of squares are in red[]
       had::wg_barrier<true>();
-#endif
       const float in_scale = Ld.sc[6] * 16.f;
       // (in_scale carries the prescale 1 / 16 of the rows back: the bound is for acc * in_scale, |acc|_inf <= |rows|_2)
       // (G8: the rows of the 56 x 56 factor R_7 (x) H_8 have norm sqrt 8, not 1 -- in_scale carries the 1 / sqrt 8 that undoes it)
       const float bound = sqrtf(red_sum8(0)) * fabsf(in_scale) * (1.0625f / kMixScale);
       const int sh_d = had::shift_for(bound * ((RVQ && !HI) ? fmaxf(1.f, fabsf(a.resid_scale)) : 1.f));
-#if !QUIP_ROWS_DIRECT
-      had::wg_barrier<true>();                         // every wave's K-mix has read the rows: the planes land on them
-#endif
       MSTAMP(9);
       {
         uint8_t* pl = reinterpret_cast<uint8_t*>(smem + B::kArea);
@@ -2224,8 +1976,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       edge(std::true_type{}, std::integral_constant<int, 2>{}, SLOTS(0u), 5, ebase | hop, 0x4000u, sv_d_prev, Ld.ln[0], Ld.su[c_lo], Ld.su[c_hi],
            Ld.sc[c_lo], Ld.sc[c_hi], c_hi != c_lo,
            [&]() { BSTAMP(1); if constexpr (RVQ) { ISSUE_RVQ_QKV_G(Ld, 0); ISSUE_RVQ_QKV_G(Ld, 1); } else if constexpr (!kPreQkv) { ISSUE(Ld, 0); ISSUE(Ld, 1); } },
-           [&]() { if constexpr (RVQ) ISSUE_RVQ_QKV_G(Ld, 2); else if constexpr (!kPreQkv) ISSUE(Ld, 2); }, [&]() {}, 23,
-           std::integral_constant<int, RVQ ? 8 : (kPreQkv ? 0 : 4)>{});
+           [&]() { if constexpr (RVQ) ISSUE_RVQ_QKV_G(Ld, 2); else if constexpr (!kPreQkv) ISSUE(Ld, 2); }, [&]() {}, 23);
       BSTAMP(2);
     }
     if (more) P1_products(std::integral_constant<bool, kPreQkv>{}, Bq);

@@ -25,6 +25,9 @@
 //
 // Hand-off protocol, liveness, error word: engine_sync.hip.h / decode_block.hip.  E8P12 (16 copies of both tables: 64 KB
 // of tables + 84 KB of planes of down's input fill the LDS).
+#if defined(QUIP_GQA_PIPE) || defined(QUIP_GQA_OHEAD) || defined(QUIP_GQA_INBOX_PACK) || defined(QUIP_GQA_ASMADD) || defined(QUIP_GQA_ZROWS)
+#error "retired A/B switch (QUIP_GQA_PIPE, _OHEAD, _INBOX_PACK, _ASMADD, _ZROWS): the alternative was measured and its code removed; DESIGN.md 4.13 has the result and the commit that still contains it"
+#endif
 #include "e8p_gemv_core.hip.h"
 #include "attn_query.hip.h"
 #include "engine_sync.hip.h"
@@ -47,13 +50,6 @@
 #ifndef QUIP_GQA_WAITSTAT
 #define QUIP_GQA_WAITSTAT 0
 #endif
-// 1 = the products as a software pipeline over half items (the look-ups of an item's first half issued before the second half of
-// the item in front of it is multiplied).  Measured and NOT shipped (profiles/r06_gqa_stream.txt): 1251 instead of 1270 clocks per
-// item and wave, the same 0.70-0.72 of 8 TB/s in wall time (the launch runs at the clock its power allows: 1.74-1.94 GHz against
-// 1.95-2.06 on the same box), 256 VGPRs instead of 238.
-#ifndef QUIP_GQA_PIPE
-#define QUIP_GQA_PIPE 0
-#endif
 // nibble mode: items whose table look-ups run INSIDE a wait (their codes landed long ago; a decoded item waits as 16 scalar
 // registers) and are multiplied from registers once the digit planes exist: the first ... items of gate / up (wait for z_o), of down
 // (wait for the chunk owners; the owners: for their inbox) and of the next block's q / k | v (wait for z_d), as decode_block.hip
@@ -71,27 +67,14 @@
 #ifndef QUIP_GQA_PRE_Q
 #define QUIP_GQA_PRE_Q 0
 #endif
-// hop 1 of the MLP edge (columns -> chunk owners): 1 = two values per 8-byte granule as 20-bit mantissas against the pair's larger
-// binary exponent (2^-19 of the larger one: far below the fp16 rounding of the modules' outputs that went into them) + a 16-bit tag;
-// 0 = one fp32 value per granule (rounds 4-5).  An owner's inbox is 64 KB at one value per granule -- ONE sweep of it is ~6K clocks at
-// the ~11 bytes per clock a CU loads (stamps 12 -> 28: 6.1K) -- and 32 KB packed.
-#ifndef QUIP_GQA_INBOX_PACK
-#define QUIP_GQA_INBOX_PACK 1
-#endif
-// o_proj's input transform split over its producers (1; 0 = rounds 4-6a: every workgroup transforms all 8192 points of a (.) SU).
-// H_8192 = H_64 (x) H_128 with the head index on top: a head's workgroup multiplies its 128 attention outputs by SU_o and runs their
-// 128-point transform in ONE wave before it publishes them (two fp32 per granule, esync::pack20x2: the same 64 granules per head);
-// everybody then gathers four heads x four columns per thread and finishes with H_64 ACROSS heads -- two register stages and four
-// lane stages, no LDS exchange, no barrier inside -- and writes a dword of digits per head and plane.  in(o): 5.8K -> ... clocks.
-#ifndef QUIP_GQA_OHEAD
-#define QUIP_GQA_OHEAD 1
-#endif
-#ifndef QUIP_GQA_ZROWS         /* tools/dbg A/B: 0 = the MFMA's unused A rows read digit plane 2 (as rounds 1-5) instead of zeros */
-#define QUIP_GQA_ZROWS 1
-#endif
-#ifndef QUIP_GQA_ASMADD        /* tools/dbg A/B: 0 = the rows' LDS adds as compiler-generated atomics under `if (q < 2)` */
-#define QUIP_GQA_ASMADD 1
-#endif
+// hop 1 of the MLP edge (columns -> chunk owners): two values per 8-byte granule as 20-bit mantissas against the pair's larger
+// binary exponent (2^-19 of the larger one: far below the fp16 rounding of the modules' outputs that went into them) + a 16-bit tag
+// (esync::pack20x2).  An owner's inbox is 32 KB; ONE sweep of 64 KB is ~6K clocks at the ~11 bytes per clock a CU loads.
+// o_proj's input transform is split over its producers.  H_8192 = H_64 (x) H_128 with the head index on top: a head's workgroup
+// multiplies its 128 attention outputs by SU_o and runs their 128-point transform in ONE wave before it publishes them (two fp32 per
+// granule, esync::pack20x2: the same 64 granules per head); everybody then gathers four heads x four columns per thread and finishes
+// with H_64 ACROSS heads -- two register stages and four lane stages, no LDS exchange, no barrier inside -- and writes a dword of
+// digits per head and plane.
 
 namespace quip {
 
@@ -147,7 +130,7 @@ constexpr int kParts = 4, kPartGran = 132, kSplitPos = 128;
 constexpr size_t kWsCtl = 0;
 constexpr size_t kWsZq = 64, kWsZk = kWsZq + (HID / 2) * 8, kWsZv = kWsZk + (NKV * HD / 2) * 8;
 constexpr size_t kWsA = kWsZv + (NKV * HD / 2) * 8, kWsZo = kWsA + (HID / 2) * 8, kWsZd = kWsZo + (HID / 2) * 8;
-constexpr size_t kWsInbox = kWsZd + (HID / 2) * 8;                    // [FK][2][FL] granules (fp32 payload)
+constexpr size_t kWsInbox = kWsZd + (HID / 2) * 8;                    // [FK][2][FL / 2] granules (two values each, esync::pack20x2) in the front half of a [FK][2][FL] region
 constexpr size_t kWsRows = kWsInbox + (size_t)FK * 2 * FL * 8;        // [FK][FL / 2] granules (two 24-bit values each)
 constexpr size_t kWsRowMax = kWsRows + (size_t)FK * FL * 8;           // [8 copies][16] granules: a 128-byte line per copy, workgroup w polls copy w & 7
 constexpr size_t kWsPart = kWsRowMax + 8 * 128;                       // [NH][kParts][132]
@@ -316,16 +299,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
     if constexpr (NIB) {
       int v[3];
       item_rows_nib(c.r, c.m, sx, nib_lane_factors(q), v);
-#if QUIP_GQA_ASMADD
       lds_add3_low32((uint32_t)B::kAcc + (uint32_t)(accrow + n) * 16u, v);
-#else
-      if (q < 2) {
-        int* dst = accs + (accrow + n) * 4;
-        __hip_atomic_fetch_add(dst + 0, v[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(dst + 1, v[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(dst + 2, v[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-#endif
     } else if (q == 0) {
       int* dst = accs + (accrow + n) * 4;
       __hip_atomic_fetch_add(dst + 0, c.r.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -394,105 +368,22 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
       }
     }
   };
-  // ---- nibble mode: a product's items as a software pipeline over HALF items (round 6) -------------------------------------
-  // rocprofv3 on the measurement mode said where an item's ~1400 clocks went: 45 % issuing its ~140 instructions (4 clocks each:
-  // ONE wave issues at most one instruction per 4 clocks, and there are two per SIMD), 23 % issue stalls, 32 % in s_waitcnt --
-  // most of it lgkmcnt: every item began with a burst of look-ups whose first result its first MFMA had to wait for, because no
-  // look-up may move above the asm statements (wait, request) of its own item.  So the look-ups of an item's first half now go out
-  // BEFORE the second half of the item in front of it is multiplied:
-  //     look(S, half 1) | multiply(S, half 0) | wait(S + 1), codes -> addresses, request(S + 1 + NS) | look(S + 1, half 0) |
-  //     multiply(S, half 1) | rows of S -> accumulators
-  // -- a look-up has half an item (~60 instructions) between its issue and its use; LDS results return in order, so consuming the
-  // older half while 16 newer look-ups are in flight is `lgkmcnt(15)`.  Same integers, same order of the MFMAs per accumulator.
-  ItemAddr adn;
-  uint32_t L0[16], L1[16];
-  // wait for item S's slot, its codes -> the 32 look-up addresses (adn), refill the slot with item S + NS
-  auto pre = [&](auto s_c, bool live) __attribute__((always_inline)) {
-    constexpr int S = decltype(s_c)::value, slot = S % NS;
-    u32x4& da = qa[slot];
-    u32x4& db = qb[slot];
-#if QUIP_GQA_WAITSTAT
-    const uint64_t ws_t0 = __builtin_amdgcn_s_memtime();
-#endif
-    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(da), "+v"(db) : "n"(2 * (NS - 1)) : "memory");
-#if QUIP_GQA_WAITSTAT
-    ws_wait += __builtin_amdgcn_s_memtime() - ws_t0;
-#endif
-    if (live) {
-      item_addresses_nib(da, db, lane_c, adn);
-#pragma unroll
-      for (int t = 0; t < 8; ++t) asm volatile("" : "+v"(adn.a1l[t]), "+v"(adn.a2l[t]), "+v"(adn.a1h[t]), "+v"(adn.a2h[t]));
-    }
-    issue(IC<S + NS>{});
-  };
-  // the 16 look-ups of half H (MFMA steps 2 H, 2 H + 1: dwords 4 H .. 4 H + 3 of the lane's 8) of the item whose addresses adn holds
-  auto look = [&](auto h_c, uint32_t (&L)[16]) __attribute__((always_inline)) {
-    constexpr int H = decltype(h_c)::value;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int t = 4 * H + u;
-      L[4 * u + 0] = lds_read4(adn.a1l[t]); L[4 * u + 1] = lds_read4(adn.a2l[t]);
-      L[4 * u + 2] = lds_read4(adn.a1h[t]); L[4 * u + 3] = lds_read4(adn.a2h[t]);
-    }
-  };
-  auto mulh = [&](auto h_c, const uint32_t (&L)[16], const i32x4 (&A)[4], Acc& acc) __attribute__((always_inline)) {
-    constexpr int H = decltype(h_c)::value;
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      const uint32_t* o = L + 8 * s2;
-      const i32x4 Br = {(int)(o[0] ^ o[1]), (int)(o[2] ^ o[3]), (int)(o[4] ^ o[5]), (int)(o[6] ^ o[7])};
-      const i32x4 Bm = {Br.x & 0x0f0f0f0f, Br.y & 0x0f0f0f0f, Br.z & 0x0f0f0f0f, Br.w & 0x0f0f0f0f};
-      acc.r = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[2 * H + s2], Br, acc.r, 0, 0, 0);
-      acc.m = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[2 * H + s2], Bm, acc.m, 0, 0, 0);
-    }
-  };
-  // the first item of a stream: nothing in front of it to hide its first look-ups behind
-  constexpr bool PIPE = NIB && QUIP_GQA_PIPE != 0;
-  auto first = [&](auto s_c, bool live) __attribute__((always_inline)) {
-    if constexpr (PIPE) {
-      pre(s_c, live);
-      if (live) look(IC<0>{}, L0);
-    }
-  };
-  // item S of a stream (its first half's look-ups are in flight: first() or the item in front of it); next_c: another item
-  // follows directly (live_next: and it is not a filler)
-  auto item = [&](auto s_c, auto next_c, const auto& A, Acc& acc, bool live, bool live_next) __attribute__((always_inline)) {
-    constexpr int S = decltype(s_c)::value;
-    constexpr bool NEXT = decltype(next_c)::value;
-    if constexpr (PIPE) {
-      if (live) {
-        look(IC<1>{}, L1);
-        mulh(IC<0>{}, L0, A, acc);
-      }
-      if constexpr (NEXT) {
-        pre(IC<S + 1>{}, live_next);
-        if (live_next) look(IC<0>{}, L0);
-      }
-      if (live) mulh(IC<1>{}, L1, A, acc);
-    } else {
-      consume(s_c, A, acc, live);
-    }
-  };
-  using TrueC = std::integral_constant<bool, true>;
-  using FalseC = std::integral_constant<bool, false>;
-  // CNT consecutive items that multiply the same K slice (A fragments at xa) into accumulator rows accrow0 + 16 c; last_c: the
-  // stream ends behind them
-  auto group = [&](auto s0_c, auto cnt_c, auto last_c, uint32_t xa, int accrow0) __attribute__((always_inline)) {
+  // CNT consecutive items that multiply the same K slice (A fragments at xa) into accumulator rows accrow0 + 16 c
+  auto group = [&](auto s0_c, auto cnt_c, uint32_t xa, int accrow0) __attribute__((always_inline)) {
     constexpr int S0 = decltype(s0_c)::value, CNT = decltype(cnt_c)::value;
-    constexpr bool LAST = decltype(last_c)::value;
     i32x4 A[NA];
     i32x4 sx = {0, 0, 0, 0};
     fragments(xa, A, sx);
     static_for<CNT>([&](auto c) {
       constexpr int C = decltype(c)::value;
       Acc acc = kAcc0;
-      item(IC<S0 + C>{}, std::integral_constant<bool, !(LAST && C == CNT - 1)>{}, A, acc, true, true);
+      consume(IC<S0 + C>{}, A, acc, true);
       add_rows(acc, sx, accrow0 + 16 * C);
     });
   };
 
   // ---- items decoded ahead (nibble mode) ------------------------------------------------------------------------------
-  constexpr bool kPre = NIB && !PIPE && !QUIP_GQA_NODECODE;
+  constexpr bool kPre = NIB && !QUIP_GQA_NODECODE;
   constexpr int kPreGU = kPre ? QUIP_GQA_PRE_GU : 0, kPreD = kPre ? QUIP_GQA_PRE_D : 0, kPreQ = kPre ? QUIP_GQA_PRE_Q : 0;
   static_assert(kPreGU <= 14 && kPreD <= 14 && kPreQ <= 2, "items decoded ahead: inside the first group of their product");
   // item S of the sequence, first half: wait for its slot, codes -> addresses -> the 32 look-ups (16 dwords).  I: how many items
@@ -525,9 +416,8 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
     }
   };
   // group() whose first NPRE items were decoded ahead
-  auto group_pre = [&](auto s0_c, auto cnt_c, auto last_c, auto npre_c, const auto& pre, uint32_t xa, int accrow0) __attribute__((always_inline)) {
+  auto group_pre = [&](auto s0_c, auto cnt_c, auto npre_c, const auto& pre, uint32_t xa, int accrow0) __attribute__((always_inline)) {
     constexpr int S0 = decltype(s0_c)::value, CNT = decltype(cnt_c)::value, NPRE = decltype(npre_c)::value;
-    constexpr bool LAST = decltype(last_c)::value;
     i32x4 A[NA];
     i32x4 sx = {0, 0, 0, 0};
     fragments(xa, A, sx);
@@ -535,7 +425,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
       constexpr int C = decltype(c)::value;
       Acc acc = kAcc0;
       if constexpr (C < NPRE) mul_raw(pre[C < NPRE ? C : 0], A, acc);
-      else item(IC<S0 + C>{}, std::integral_constant<bool, !(LAST && C == CNT - 1)>{}, A, acc, true, true);
+      else consume(IC<S0 + C>{}, A, acc, true);
       add_rows(acc, sx, accrow0 + 16 * C);
     });
   };
@@ -619,18 +509,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
     }
     own_ring();
   };
-  // a long wait is spent on ONE granule per wave (a line of its own choice), not on re-reading a whole vector per retry next to
-  // the stores that are awaited; the gather behind it re-checks every piece
-  auto prepoll = [&](const uint64_t* g1, uint32_t tag, uint32_t code) {
-    uint32_t sp = 0;
-    u32x2_t f;
-    for (;;) {
-      esync::ld8(f, g1);
-      esync::drain();
-      esync::own(f);
-      if (esync::spin_step(f.y == tag, sp, ctl + 1, code + (uint32_t)w)) break;
-    }
-  };
   // 16 fp16 of a permuted / natural vector at p + 16 t -> floats
   auto load16 = [&](const f16* p, u32x4 (&v)[2]) {
     v[0] = *reinterpret_cast<const u32x4*>(p + 16 * tid);
@@ -672,20 +550,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
       } else {
         *reinterpret_cast<uint4*>(smem + base + d * B::PSH + 16 * tid) = make_uint4(dg[d][0], dg[d][1], dg[d][2], dg[d][3]);
       }
-    }
-  };
-  // the same from the strided layout (values X[t + 512 k]): bytes
-  auto planes_str = [&](const float (&v)[16], float scale, int sh, uint32_t base) {
-#pragma clang fp contract(off)
-    const float s2 = had::fmul(scale, as_f32((uint32_t)(sh + 127) << 23));
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int X = (int)__builtin_rintf(v[k] * s2);
-      // (nibble mode: digit tid + 512 k of a plane sits at byte nib_byte_of() of its half plane)
-      uint8_t* p = reinterpret_cast<uint8_t*>(smem + base) + (NIB ? nib_half_of(tid) * B::HOH + nib_byte_of(tid) + 256 * k : tid + 512 * k);
-      p[0] = (uint8_t)((X + 0x8080) >> 16);
-      p[B::PSH] = (uint8_t)((X + 0x80) >> 8);
-      p[2 * B::PSH] = (uint8_t)X;
     }
   };
   auto wg_max = [&](float mx) __attribute__((always_inline)) {
@@ -830,7 +694,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
       const uint32_t xa = base + (uint32_t)(n < 4 ? min(n, 2) * ps + (int)half_off : min(n - 4, 2) * ps) + (uint32_t)q * 32u + (uint32_t)(wave + 8 * i) * 256u;
       // the ten rows that carry nothing read ZEROS (one broadcast address): the launch runs at the clock its power allows, and
       // ten sixteenths of every MFMA's multipliers switching on a copy of plane 2 is power without a result
-      return (QUIP_GQA_ZROWS && (n == 3 || n >= 7)) ? (uint32_t)B::kZero : xa;
+      return (n == 3 || n >= 7) ? (uint32_t)B::kZero : xa;
     } else {
       return base + (uint32_t)min(n, 2) * (uint32_t)ps + (uint32_t)q * 64u + (uint32_t)(wave + 8 * i) * 512u;
     }
@@ -871,27 +735,25 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
       const uint32_t pa = has_kv ? p1 : p0;
       i32x4 A[NA];
       static_for<kPreQ>([&](auto ic) { refill(IC<SQ_A + decltype(ic)::value>{}); });
-      first(IC<SQ_A>{}, true);
       {
         Acc acc = kAcc0;
         i32x4 sx = {0, 0, 0, 0};
         fragments(xaddr(pa, B::PSH, 0), A, sx);
-        if constexpr (kPreQ > 0) mul_raw(Pq[0], A, acc); else item(IC<SQ_A>{}, TrueC{}, A, acc, true, true);
+        if constexpr (kPreQ > 0) mul_raw(Pq[0], A, acc); else consume(IC<SQ_A>{}, A, acc, true);
         fragments(xaddr(pa, B::PSH, 1), A, sx);
-        if constexpr (kPreQ > 1) mul_raw(Pq[kPreQ > 1 ? 1 : 0], A, acc); else item(IC<SQ_A + 1>{}, FalseC{}, A, acc, true, true);
+        if constexpr (kPreQ > 1) mul_raw(Pq[kPreQ > 1 ? 1 : 0], A, acc); else consume(IC<SQ_A + 1>{}, A, acc, true);
         add_rows(acc, sx, B::AKV);
       }
       had::wg_barrier<true>();
       ++hop;                                           // hand-off: z_k / z_v, then z_q (the same index: they are different vectors)
       if (has_kv && !so) publish(kvm ? zv : zk, 8 * (kvb & 63), B::AKV, 8, shs[1], ebase | hop);
-      first(IC<SQ_B>{}, true);
       static_for<2>([&](auto ic) {
         constexpr int I = decltype(ic)::value;
         Acc acc0 = kAcc0, acc1 = kAcc0;
         i32x4 sx = {0, 0, 0, 0};
         fragments(xaddr(p0, B::PSH, I), A, sx);
-        item(IC<SQ_B + 2 * I>{}, TrueC{}, A, acc0, true, !has_kv);
-        item(IC<SQ_B + 2 * I + 1>{}, std::integral_constant<bool, I == 0>{}, A, acc1, !has_kv, true);
+        consume(IC<SQ_B + 2 * I>{}, A, acc0, true);
+        consume(IC<SQ_B + 2 * I + 1>{}, A, acc1, !has_kv);
         add_rows(acc0, sx, B::AQ);
         if (!has_kv) add_rows(acc1, sx, B::AQ + 16);
       });
@@ -934,10 +796,8 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
       // SV of this head's q values (wave 2 finishes them below): requested in front of the hand-off's wait, not at its use
       uint32_t svq_raw = 0u;
       if (wave == 2) svq_raw = *reinterpret_cast<const uint32_t*>(Ld.sv[0] + HD * hd + 2 * lane);
-#if QUIP_GQA_OHEAD
       uint32_t suo_raw = 0u;                           // SU_o of this head's 128 attention outputs (natural order)
       if (wave == 0) suo_raw = *reinterpret_cast<const uint32_t*>(Ld.su[3] + HD * hd + 2 * lane);
-#endif
       f16* s_qkv = reinterpret_cast<f16*>(smem + B::kQkv);
       {
         // gather z_q (everybody) and z_k / z_v (waves 0 / 1: they went out first, ahead of the q items) in one poll
@@ -1127,7 +987,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
         s_a[tid] = pos_ok ? (f16)(pO / pL) : __builtin_bit_cast(f16, (unsigned short)0x7e00);
       }
       had::wg_barrier<true>();
-#if QUIP_GQA_OHEAD
       if (head_wg && tid < 64) {
         // x = a (.) SU_o, its 128-point transform inside this wave (lane l: elements 2 l, 2 l + 1 before and after), two per granule
         const f16x2 av = as_f16x2(*reinterpret_cast<const uint32_t*>(s_a + 2 * tid)), su2 = as_f16x2(suo_raw);
@@ -1138,12 +997,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
         esync::pack20x2(y[0], y[1], ebase | (hop + 1u), w0, w1);
         esync::st_granule(za + hd * 64 + tid, w0, w1);
       }
-#else
-      if (head_wg && tid < 64) {
-        const uint32_t pr = *reinterpret_cast<const uint32_t*>(s_a + 2 * tid);
-        esync::st_granule(za + hd * 64 + tid, pr, ebase | (hop + 1u));
-      }
-#endif
       ++hop;                                           // hand-off: attention output
     } else {
       hop += 2;
@@ -1152,7 +1005,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
 
     // ================= o: input side (no norm), product, hand-off =========================================================
     rederive();
-#if QUIP_GQA_OHEAD
     if (!so) {
       // thread (wave, lane): columns [4 jq, +4) of heads 4 (lane >> 2) + r, r < 4 -- one 16-byte piece (two granules) per head
       const int jq = 4 * wave + (lane & 3), hg = lane >> 2;
@@ -1236,44 +1088,10 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
       if (tid == 0) shs[2] = sh;
       had::wg_barrier<true>();
     }
-#else
-    if (!so) {
-      u32x4 psu[2];
-      load16(Ld.su[3], psu);                           // natural order
-      float v[1][16], suf[16];
-      prepoll(za + (size_t)((8 * w + wave) & (NH - 1)) * 64, ebase | hop, 0x6100u);      // (the attention output is ~10 us away)
-      gather16(za, ebase | hop, 0x6000u, v[0]);
-      asm volatile("" : "+v"(psu[0]), "+v"(psu[1]));
-      BSTAMP(7);
-      unpack16(psu, suf);
-#pragma unroll
-      for (int k = 0; k < 16; ++k) v[0][k] = had::fmul(v[0][k], suf[k]);
-      {
-        // (round 5: the norm bound, as on the other edges -- the sum of squares of the transform's input, read behind its barriers)
-#pragma clang fp contract(off)
-        float n0 = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) n0 = __builtin_fmaf(v[0][r], v[0][r], n0);
-        n0 = had::wave_reduce_to_lane63<false>(n0);
-        if (lane == 63) red[wave] = n0;
-      }
-      hadw::fwd<13, 1, true>(v, xbuf, tid);
-      const float sco = Ld.sc[3];
-      had::wg_barrier<true>();                         // the transform's last reads of the exchange buffer: the planes land on it
-      float q0 = red[0];
-#pragma unroll
-      for (int i = 1; i < 8; ++i) q0 = had::fadd(q0, red[i]);
-      const int sh = had::shift_for(sqrtf(q0) * kSqrtH * fabsf(sco) * 1.0625f);
-      planes_str(v[0], sco, sh, (uint32_t)B::kArea);
-      if (tid == 0) shs[2] = sh;
-      had::wg_barrier<true>();
-    }
-#endif
     BSTAMP(8);
     rederive();
-    first(IC<SQ_O>{}, true);
-    group(IC<SQ_O>{}, IC<2>{}, FalseC{}, xaddr((uint32_t)B::kArea, B::PSH, 0), B::AO);
-    group(IC<SQ_O + 2>{}, IC<2>{}, TrueC{}, xaddr((uint32_t)B::kArea, B::PSH, 1), B::AO);
+    group(IC<SQ_O>{}, IC<2>{}, xaddr((uint32_t)B::kArea, B::PSH, 0), B::AO);
+    group(IC<SQ_O + 2>{}, IC<2>{}, xaddr((uint32_t)B::kArea, B::PSH, 1), B::AO);
     had::wg_barrier<true>();
     ++hop;                                             // hand-off: z_o
     if (!so) publish(zo, 16 * w, B::AO, 16, shs[2], ebase | hop);
@@ -1293,9 +1111,8 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
       // (AGU + 112 + 16 k + i) -- one set of A fragments per span
       const uint32_t pg = (uint32_t)B::kArea;
       static_for<kPreGU>([&](auto ic) { refill(IC<SQ_GU + decltype(ic)::value>{}); });
-      first(IC<SQ_GU>{}, true);
-      group_pre(IC<SQ_GU>{}, IC<14>{}, FalseC{}, IC<kPreGU>{}, Pg, xaddr(pg, B::PSH, 0), B::AGU);
-      group(IC<SQ_GU + 14>{}, IC<14>{}, TrueC{}, xaddr(pg, B::PSH, 1), B::AGU);
+      group_pre(IC<SQ_GU>{}, IC<14>{}, IC<kPreGU>{}, Pg, xaddr(pg, B::PSH, 0), B::AGU);
+      group(IC<SQ_GU + 14>{}, IC<14>{}, xaddr(pg, B::PSH, 1), B::AGU);
     }
     had::wg_barrier<true>();
     BSTAMP(11);
@@ -1326,17 +1143,12 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
 #pragma unroll
       for (int k = 0; k < FK; ++k) t = __builtin_fmaf(hs[k], zz[16 * k], t);
       const float tn = __shfl_down(t, 1, 64);
-#if QUIP_GQA_INBOX_PACK
       if ((i & 1) == 0) {
         // {m_a (20) | m_b low 12, m_b high 8 | exponent 8 | tag 16}: m = rint(value 2^(145 - e)), e = the larger biased exponent
         uint32_t w0, w1;
         esync::pack20x2(t, tn, tag1, w0, w1);
         esync::st_granule(inbox + ((size_t)(kq * 2 + mgu) * (FL / 2) + 16 * (w & 127) + 8 * cg + (i >> 1)), w0, w1);
       }
-#else
-      if ((i & 1) == 0)
-        esync::st_granule2(inbox + ((size_t)(kq * 2 + mgu) * FL + 32 * (w & 127) + 16 * cg + i), as_u32(t), as_u32(tn), tag1);
-#endif
     }
     ++hop;                                             // hand-off: rows -> everybody
     tag2 = ebase | hop;
@@ -1346,7 +1158,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
     static_for<kPreD>([&](auto ic) { predec(IC<SQ_D + decltype(ic)::value>{}, ic, Pd[decltype(ic)::value]); });
     if (!so) {
     if (w < FK) {
-      // chunk owner w: 4096 values of gate and of up (fp32 payloads) -> transforms, SV, SiLU product, SU, down's transform
+      // chunk owner w: 4096 values of gate and of up (two per granule) -> transforms, SV, SiLU product, SU, down's transform
       const f16* svg = Ld.sv[4] + (size_t)w * FL;
       const f16* svu = Ld.sv[5] + (size_t)w * FL;
       const f16* sud = Ld.su[6] + (size_t)w * FL;
@@ -1358,7 +1170,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
         psd[j] = reinterpret_cast<const uint16_t*>(sud)[tid + 512 * j];
       }
       float v[2][8];
-#if QUIP_GQA_INBOX_PACK
       {
         // this thread's 8 values of each vector = 4 granules = two 16-byte pieces
         u32x4_t pc[4];
@@ -1387,33 +1198,6 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
           unpack2(pc[jj].z, pc[jj].w, v[jj >> 1][4 * (jj & 1) + 2], v[jj >> 1][4 * (jj & 1) + 3]);
         }
       }
-#else
-      {
-        u32x4_t pc[8];
-        uint32_t spins = 0;
-        const uint64_t* src = inbox + (size_t)(w * 2) * FL + 8 * tid;
-        for (;;) {
-#pragma unroll
-          for (int jj = 0; jj < 8; ++jj) esync::ld16(pc[jj], src + (jj >> 2) * FL + 2 * (jj & 3));
-          esync::drain();
-          bool ok = true;
-#pragma unroll
-          for (int jj = 0; jj < 8; ++jj) {
-            esync::own(pc[jj]);
-            ok = ok && pc[jj].y == tag1 && pc[jj].w == tag1;
-          }
-          if (esync::spin_step(ok, spins, ctl + 1, 0x1000u + (uint32_t)w)) break;
-        }
-        own_ring();
-#pragma unroll
-        for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(psg[j]), "+v"(psu_[j]), "+v"(psd[j]));
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) {
-          v[jj >> 2][2 * (jj & 3)] = as_f32(pc[jj].x);
-          v[jj >> 2][2 * (jj & 3) + 1] = as_f32(pc[jj].z);
-        }
-      }
-#endif
       BSTAMP(28);
       hadw::fwd<12, 2, true>(v, xbuf, tid);
       BSTAMP(29);
@@ -1571,15 +1355,17 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
       Acc acc0 = kAcc0, acc1 = kAcc0;
       i32x4 sx = {0, 0, 0, 0};
       static_for<kPreD>([&](auto ic) { refill(IC<SQ_D + decltype(ic)::value>{}); });
-      first(IC<SQ_D>{}, true);
-      static_for<7>([&](auto ic) {
+      // the longest Acc chain of the launch: item_rows_nib's 24-bit multiply holds for |msk| < 2^23 (e8p_gemv_core.hip.h)
+      constexpr int kChain = 7;
+      static_assert(kChain * 256 * 128 * 15 < (1 << 23), "K slices per accumulator chain: |msk| must fit 24 bits");
+      static_for<kChain>([&](auto ic) {
         constexpr int I = decltype(ic)::value;
         i32x4 A[NA];
         fragments(xaddr((uint32_t)B::kArea, B::PSD, I), A, sx);
         if constexpr (2 * I < kPreD) mul_raw(Pd[2 * I < kPreD ? 2 * I : 0], A, acc0);
-        else item(IC<SQ_D + 2 * I>{}, TrueC{}, A, acc0, true, true);
+        else consume(IC<SQ_D + 2 * I>{}, A, acc0, true);
         if constexpr (2 * I + 1 < kPreD) mul_raw(Pd[2 * I + 1 < kPreD ? 2 * I + 1 : 0], A, acc1);
-        else item(IC<SQ_D + 2 * I + 1>{}, TrueC{}, A, acc1, true, I < 6);          // (behind the last one: the first filler)
+        else consume(IC<SQ_D + 2 * I + 1>{}, A, acc1, true);
       });
       add_rows(acc0, sx, B::AD);
       add_rows(acc1, sx, B::AD + 16);
@@ -1587,13 +1373,9 @@ __global__ __launch_bounds__(kThreads) void decode_block_gqa_kernel(GArgs a) {
 #pragma unroll
       for (int t = 0; t < NA; ++t) A0[t] = i32x4{0, 0, 0, 0};
       Acc accf = kAcc0;
-      // the two fillers keep the ring's period at 54 (nibble mode: SQ_F was waited for and refilled behind down's last item)
-      if constexpr (PIPE) {
-        pre(IC<SQ_F + 1>{}, false);
-      } else {
-        consume(IC<SQ_F>{}, A0, accf, false);
-        consume(IC<SQ_F + 1>{}, A0, accf, false);
-      }
+      // the two fillers keep the ring's period at 54
+      consume(IC<SQ_F>{}, A0, accf, false);
+      consume(IC<SQ_F + 1>{}, A0, accf, false);
     }
     had::wg_barrier<true>();
     ++hop;                                             // hand-off: z_d

@@ -518,7 +518,9 @@ __device__ __forceinline__ void item_rows_nib(const i32x4& raw, const i32x4& msk
   for (int d = 0; d < 3; ++d) v[d] = mad_i24(m[d], f.cm, mad_i24(s[d], f.cs, (int)((uint32_t)r[d] & f.rmask)));
 }
 // the three atomic adds of an item's rows into the int32 accumulators at LDS byte address `dst` (this lane's row), from
-// the low 32 lanes only (q < 2); the wave's exec mask is all ones before and after
+// the low 32 lanes only (q < 2); the wave's exec mask is all ones before and after.  Every call site must be reached with a
+// FULL exec mask (workgroup-uniform control flow only): exec_hi is set to -1 behind the adds, not restored, and the asm
+// declares no exec clobber -- inside a divergent branch the lanes that sat it out would run on from here.
 __device__ __forceinline__ void lds_add3_low32(uint32_t dst, const int (&v)[3]) {
   // (exec_hi alone: how a 32-bit literal extends into a 64-bit scalar move is not something to depend on)
   asm volatile("s_mov_b32 exec_hi, 0\n\tds_add_u32 %0, %1\n\tds_add_u32 %0, %2 offset:4\n\tds_add_u32 %0, %3 offset:8\n\ts_mov_b32 exec_hi, -1"

@@ -69,6 +69,11 @@ __device__ __forceinline__ void own(T& v) { asm volatile("" : "+v"(v)); }   // a
 // {m_a (20) | m_b low 12, m_b high 8 | e << 8 | tag16 << 16}, m = rint(value 2^(145 - e)): 2^-19 of the larger one of the pair.
 // e = 255: an inf / NaN in the pair (both read back as NaN).  A 16-bit tag suffices where every granule of the vector is
 // rewritten in every block (a stale one carries the tag of the block before, which differs in the hand-off index).
+// INVARIANT (the packed form is the only form of these hand-offs; the kernels do not enforce it): the 16 bits are 6 bits of the
+// launch generation + 10 bits of the hand-off index, so a packed granule that is NOT rewritten for 64 launches aliases a
+// current tag and would be taken for fresh.  Real launches rewrite every packed granule in every block.  Measurement-mode
+// launches (dbg_layer == -2) advance the generation but publish nothing: whoever runs them must engine_reset() the
+// workspace before the next real launch, as bench.py does.
 __device__ __forceinline__ void pack20x2(float a, float b, uint32_t tag, uint32_t& w0, uint32_t& w1) {
   const uint32_t ea = (__builtin_bit_cast(uint32_t, a) >> 23) & 0xffu, eb = (__builtin_bit_cast(uint32_t, b) >> 23) & 0xffu;
   uint32_t e = ea > eb ? ea : eb;
