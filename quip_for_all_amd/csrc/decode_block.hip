@@ -61,6 +61,20 @@
 #else
 #define ASTAMP(i) do { } while (0)
 #endif
+#ifndef QUIP_WAIT_STAMPS
+#define QUIP_WAIT_STAMPS 0        // tools/dbg: 1 = the stamps 18..24, 28, 29 around the waits of the four product phases (tools/block_stamps.py names
+                                   // them); 2 = 18..24, 28: one per WAVE in front of the barrier behind the K-mix, 29 behind it
+#endif
+#if (QUIP_ATT_STAMPS != 0) + (QUIP_MLP_STAMPS != 0) + (QUIP_WAIT_STAMPS != 0) > 1
+#error "QUIP_ATT_STAMPS, QUIP_MLP_STAMPS and QUIP_WAIT_STAMPS share the stamp slots 18..31: one at a time"
+#endif
+#if QUIP_WAIT_STAMPS == 1
+#define WSTAMP(i) BSTAMP((i) < 7 ? 18 + (i) : 21 + (i))
+#else
+#define WSTAMP(i) do { } while (0)
+#endif
+// (a stamp is a store: the next wait for the whole queue waits for it too, and a counted wait behind it waits for one operation
+//  more than it needs -- never for fewer.  Conclusions come from the phase totals of an unstamped build.)
 // nibble mode: a decoded item waits as 16 scalar registers, not 32 -- more of them fit
 #ifndef QUIP_NIB_PREDECODE_QKV
 #define QUIP_NIB_PREDECODE_QKV 3
@@ -671,7 +685,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
   auto edge = [&](auto z_tag, auto nc_tag, auto slots, int zvec, uint32_t tag, uint32_t code, const f16* sv_prev, const f16* ln,
                   const f16* su0, const f16* su1, float sc0, float sc1, bool two, auto after_gather, auto drip1, auto drip2, int sb) {
     // stamps of the edge's stages: 18..22 (sb = 18: the gate / up edge) or 23, 24, 28, 29, 30 (sb = 23: the q / k / v edge)
-#if QUIP_ATT_STAMPS || QUIP_MLP_STAMPS
+#if QUIP_ATT_STAMPS || QUIP_MLP_STAMPS || QUIP_WAIT_STAMPS
 #define ESTAMP(i) do { } while (0)
 #else
 #define ESTAMP(i) do { if (sb >= 0) BSTAMP(sb + (i) + ((sb == 23 && (i) >= 2) ? 3 : 0)); } while (0)
@@ -931,8 +945,13 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
   };
   auto P1_products = [&](auto pre_tag, const uint32_t (&preq)[NPQ][kPreW]) {
     const int c_lo = qc_lo;
+    // NEEDED for block 0 (its codes were requested in the prologue, whose counted waits leave them in flight) and, in every block,
+    // by the builds that request q / k / v behind the hand-off of z_d (RVQ codebooks, QUIP_PREDECODE_QKV = 0).  In the shipped
+    // E8P12 / D4 launches the later blocks' codes were waited for in front of down's product: nothing to wait for then.
+    WSTAMP(0);
     esync::drain();                                    // q, k, v have landed
     own_slots(SLOTS(M_QKV));
+    WSTAMP(1);
     if constexpr (G8) {
       // one or two items (slots X2, X3); the second one's planes are consumer 1's where it lies in the next matrix (workgroup 170)
       constexpr bool PRE = decltype(pre_tag)::value;
@@ -1280,8 +1299,11 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
     {
       // o's codes were requested a hand-off ago: their table lookups run HERE, inside the wait for the attention output
       // (RVQ: two items -- their fragments would be 64 registers: decoded with the product instead)
+      // NEEDED: o's codes were requested at the top of the block; the heads' workgroups drained them with their gathers, the
+      // other seven of a head's eight come here with both requests in flight.  The wait is for codes whose look-ups follow at once.
       esync::drain();
       own_slots(SLOTS(M_O));
+      WSTAMP(2);
       if constexpr (NIB) decode_pre(3, Bon);
       else if constexpr (!RVQ) decode_item(3, Bo);
       if constexpr (kOHead) {
@@ -1488,8 +1510,15 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
          [&]() { if constexpr (RVQ) ISSUE_RVQ_UP_A_G(Ld, 2); else if constexpr (G8) ISSUE8_GU(Ld, 6); else ISSUE(Ld, 9); }, 18);
     BSTAMP(11);
     MSTAMP(0);
-    esync::drain();
-    own_slots(SLOTS(M_GATE | M_UP));
+    // In flight HERE (E8P12 / D4, shape 0): the second column's items only, two requests each in the order of their slots -- X3, X4,
+    // X5, the last of them requested at the edge's drip2, less than a loaded memory latency ago.  The first column's codes landed
+    // before the edge (decoded ahead in the wait for z_o, or drained by its gather): nothing stands in front of their multiplies.
+    // The RVQ codebooks (all of gate's and half of up's items live) keep the one wait for everything, and so does G8: there the
+    // counted waits were measured and LOST (gate / up products 8.6K -> 9.07K clocks, profiles/product_waits_block_stamps.txt).
+    if constexpr (RVQ || G8) {
+      esync::drain();
+      own_slots(SLOTS(M_GATE | M_UP));
+    }
     MSTAMP(1);
     static_assert(FRB == 3, "three row blocks per matrix");
     if constexpr (RVQ) {
@@ -1526,16 +1555,45 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         add_rows(item_vs(std::integral_constant<int, 6>{}, nullptr, A), B::AGU + 96);
 #undef PRE_G
       } else {
-      ISSUE(Ld, 10); ISSUE(Ld, 11); ISSUE(Ld, 12);
+        // six items (slots X0..X5) against the same planes.  The first column's three at once, one of down's three requests behind
+        // each of them: out of the path to the first MFMA (a burst stalls the issuing waves for ~0.2K clocks; between two
+        // multiplies the other wave of the SIMD fills the gap), and still three multiplies, a barrier and the columns' publication
+        // ahead of the look-ups that need them (behind stamp 13).  Then the second column's, each as soon as ITS codes are there
+        // -- everything but the requests issued behind it has landed (esync::wait_all_but), and its slot is a plain register
+        // again: X3 multiplies while X4 and X5 land.
+        // (Measured, profiles/product_waits_block_stamps.txt: this phase 5.56K -> 5.15K clocks; all three requests behind the third
+        //  item instead: 5.30K; the third request behind X3's multiply: 5.15K, no better.)
+        Frag A;
+        frags(xlane, A);
+        auto first_col = [&](auto ic) {                  // (Bg by its compile-time index: behind a pointer the array goes to scratch)
+          constexpr int I = decltype(ic)::value;
 #if QUIP_PREDECODE_GATE
-      run_items3_pre(std::integral_constant<int, kPreG>{}, Bg, 0, xlane, xlane, xlane, 64);
-      MSTAMP(2);
-#else
-      run_items3(0, xlane, xlane, xlane, 64);                                     // first column's three row blocks
+          if constexpr (I < kPreG) { add_rows(mul_pre(Bg[I < kPreG ? I : 0], A), 64 + 16 * I); return; }
 #endif
-      run_items3(FRB, xlane, xlane, xlane, 64 + 16 * FRB);                         // second column's
+          add_rows(mul_slot(qa[I], qb[I], A), 64 + 16 * I);
+        };
+        auto live = [&](auto slot_c, auto behind_c) {    // slot X(3 + i) of the second column; `behind`: the requests issued behind it
+          constexpr int S = decltype(slot_c)::value;
+          esync::wait_all_but<decltype(behind_c)::value>();
+          own_slots(SLOTS(1u << S));
+          add_rows(mul_slot(qa[S], qb[S], A), 64 + 16 * S);
+        };
+        first_col(std::integral_constant<int, 0>{});
+        ISSUE(Ld, 10);
+        first_col(std::integral_constant<int, 1>{});
+        ISSUE(Ld, 11);
+        first_col(std::integral_constant<int, 2>{});
+        MSTAMP(2);
+        ISSUE(Ld, 12);
+        WSTAMP(3);
+        live(std::integral_constant<int, 3>{}, std::integral_constant<int, 4 + 6>{});      // behind X3: X4, X5 and down's six
+        WSTAMP(4);
+        live(std::integral_constant<int, 4>{}, std::integral_constant<int, 2 + 6>{});
+        live(std::integral_constant<int, 5>{}, std::integral_constant<int, 6>{});
+        WSTAMP(5);
       }
     }
+    WSTAMP(6);
     MSTAMP(3);
     had::wg_barrier<true>();
     BSTAMP(12);
@@ -1824,10 +1882,19 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       }
       if constexpr (RVQ) ISSUE_RVQ_DOWN_G2(Ld);
       MSTAMP(8);
+      // (the per-wave stamps of QUIP_WAIT_STAMPS = 2 say who is late at the barrier below: waves 4..7, the SECOND wave of every SIMD,
+      //  0.9K clocks behind waves 0..3 -- the eighteen dependent MFMAs of the two waves of a SIMD queue on its one matrix pipe; no
+      //  wait and no burst.  With this request behind the barrier instead the block span grew by 0.3K: it stays here.)
       if constexpr (kPreQkv && !G8) ISSUE(Ln, 2);
+#if QUIP_WAIT_STAMPS == 2
+      if (dbg_on && lane == 0) a.dbg[w * 32 + (wave < 7 ? 18 + wave : 28)] = dbg_rt ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();
+#endif
       // ONE barrier for both: every wave's K-mix has read the factor image (down's planes land on it), and the eight partial
       // sums of squares are in red[]
       had::wg_barrier<true>();
+#if QUIP_WAIT_STAMPS == 2
+      BSTAMP(29);
+#endif
       const float in_scale = Ld.sc[6] * 16.f;
       // (in_scale carries the prescale 1 / 16 of the rows back: the bound is for acc * in_scale, |acc|_inf <= |rows|_2)
       // (G8: the rows of the 56 x 56 factor R_7 (x) H_8 have norm sqrt 8, not 1 -- in_scale carries the 1 / sqrt 8 that undoes it)
@@ -1897,8 +1964,15 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       MSTAMP(10);
       had::wg_barrier<true>();
       BSTAMP(16);
+      // E8P12 / D4: down's own codes landed long ago -- behind stamp 13 the queue was drained for their look-ups, and the rows' sweep
+      // drained it again -- so this wait is for the NEXT block's q / k / v codes, which this product does not multiply.  It stays
+      // all the same: moved behind the multiplies (in front of the barrier) it took 0.4K clocks off this phase and the gather
+      // of z_d gave 0.2K back, the block span did not move (69.4K / 69.5K); behind the publication wave 0 waits for its granules'
+      // store BEFORE it requests the next descriptor instead of beside it: +0.7K here, -0.45K around, a loss
+      // (profiles/product_waits_block_stamps.txt).  RVQ: down's own items, requested in thirds around the K-mix.
       esync::drain();                                  // down's codes (and, behind them, the next block's q, k, v)
       own_slots(SLOTS(M_DOWN | (kPreQkv ? M_QKV : 0u)));
+      WSTAMP(7);
       const uint32_t xlane_d = NIB ? (uint32_t)B::kArea + nib_row_offset(n, B::kPlaneD, B::HOD) + (uint32_t)q * 32u
                                    : (uint32_t)B::kArea + (uint32_t)min(n, 2) * (uint32_t)B::kPlaneD + (uint32_t)q * 64u;
       constexpr uint32_t kSliceD = NIB ? 288u : 544u;          // bytes between the A fragments of consecutive K slices of down's planes
@@ -1945,6 +2019,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
           }
         }
       }
+      WSTAMP(8);
       had::wg_barrier<true>();
       ++hop;                                           // hand-off: z_d
       publish16(5, w * 8, B::AD, sh_d, ebase | hop);
@@ -1980,6 +2055,9 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       BSTAMP(2);
     }
     if (more) P1_products(std::integral_constant<bool, kPreQkv>{}, Bq);
+    // the back edge: no request in flight.  NEEDED where q / k / v are requested by the edge above (RVQ codebooks,
+    // QUIP_PREDECODE_QKV = 0: behind the last block nobody has consumed them); in the shipped E8P12 / D4 launches the edge requests
+    // nothing and the codes were waited for in front of down's product: nothing to wait for, and the wait costs nothing then.
     esync::drain();
     own_slots(SLOTS(M_QKV));
   }

@@ -39,6 +39,14 @@ __device__ __forceinline__ void st_word(void* p, uint32_t v) {
   asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
 }
 __device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// a counted wait: returns once at most N of this wave's vector-memory operations are outstanding.  The queue retires in
+// order, so those are the N youngest: "everything but the N operations issued last has landed".  N counts loads AND stores;
+// an operation the caller did not count (a debug stamp's store) only makes the wait longer, never shorter.
+template <int N>
+__device__ __forceinline__ void wait_all_but() {
+  static_assert(N >= 0 && N < 64, "vmcnt is a six-bit counter");
+  asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory");
+}
 
 // ---- loads (issued, not waited: the caller waits with drain() / a counted vmcnt) ------------
 __device__ __forceinline__ void ld16(u32x4_t& dst, const void* p) {

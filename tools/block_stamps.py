@@ -4,7 +4,10 @@ usage: python tools/block_stamps.py [layers] [dbg_layer] [pos] [g8]      (g8: th
        python tools/block_stamps.py [layers] tail [pos] [g8]           the token's tail behind the last block (csrc/token_tail.hip.h:
                                                                        dbg_layer = layers reuses the slots; the device-wide 100 MHz clock)
 QUIP_MLP_STAMPS=1 with a library built with -DQUIP_MLP_STAMPS=1 (tools/dbg/build_variant.sh, QUIP_LIB_PATH): the finer stamps inside
-the MLP edge (gate / up products, row owners, K-mix and planes) instead of those inside the two 4096-wide edges."""
+the MLP edge (gate / up products, row owners, K-mix and planes) instead of those inside the two 4096-wide edges.
+QUIP_WAIT_STAMPS=1 with a library built with -DQUIP_WAIT_STAMPS=1: the stamps around the waits of the four product phases (q / k / v,
+o, gate / up, down); QUIP_WAIT_STAMPS=2 (-DQUIP_WAIT_STAMPS=2): one stamp per wave in front of the barrier behind the K-mix.  A stamp
+is a store that the next wait for the whole queue waits for: take the phase totals from an unstamped library."""
 import math
 import os
 import sys
@@ -114,9 +117,32 @@ if mlp_stamps:     # a library built with -DQUIP_MLP_STAMPS=1: the two 4096-wide
            "crossing (barrier)", "SiLU product, SU, in-transform, rows staged", "barrier + published (+ barrier: parent)"], ro)
     chain("inside 15 -> 16 (everybody):", [15, M[8], M[9], M[10], 16],
           ["K-mix (MFMAs)", "norm bound + barrier", "down's planes", "barrier"], ev)
+wait_stamps = int(os.environ.get("QUIP_WAIT_STAMPS") or 0)
+if wait_stamps == 1:     # a library built with -DQUIP_WAIT_STAMPS=1: the slots 18..24, 28, 29 sit around the waits of the four product phases
+    def wchain(title, pts, labels):
+        print(title)
+        for i, lab in enumerate(labels):
+            print(f"  {lab:76s} {(D_[:, :, pts[i + 1]] - D_[:, :, pts[i]]).mean():9.0f}")
+    wchain("inside 2 -> 3 (the next block's q / k / v products; 18, 19):", [2, 18, 19, 3],
+           ["-> the wait", "wait for the whole queue (needed by block 0 and the builds without look-ups ahead)", "products, barrier, publication"])
+    wchain("inside 6 -> 8 (o's look-ups and input side; 20):", [6, 20, 8],
+           ["wait for o's codes (needed: requested at the top of the block)", "look-ups, wait for the attention output, input side"])
+    wchain("inside 11 -> 12 (the gate / up products, shape 0; 21..24):", [11, 21, 22, 23, 24, 12],
+           ["first column's three items (decoded ahead), one of down's requests behind each", "counted wait for X3 + its multiply",
+            "counted waits for X4, X5 + their multiplies", "(nothing)", "barrier"])
+    wchain("inside 16 -> 17 (down's product; 28, 29):", [16, 28, 29, 17],
+           ["wait for the whole queue (the next block's q / k / v codes)", "down's multiplies", "barrier, publication of z_d, barrier"])
+if wait_stamps == 2:     # -DQUIP_WAIT_STAMPS=2: one stamp per WAVE in front of the barrier behind the K-mix (18..24, 28), 29 behind it
+    WS = [18, 19, 20, 21, 22, 23, 24, 28]
+    arr = np.stack([D_[:, :, s] - D_[:, :, 15] for s in WS], axis=-1)          # (runs, workgroups, waves): clocks from stamp 15
+    print("the barrier behind the K-mix: arrival per wave, clocks from stamp 15 (mean over workgroups | row owners | the others; how often the wave is the last):")
+    lastw = arr.argmax(axis=-1)
+    for wv in range(8):
+        print(f"  wave {wv}: {arr[:, :, wv].mean():9.0f} {arr[:, ro, wv].mean():9.0f} {arr[:, ~ro, wv].mean():9.0f}   last in {100.0 * (lastw == wv).mean():5.1f} %")
+    print(f"  first wave -> last wave {(arr.max(axis=-1) - arr.min(axis=-1)).mean():9.0f}; last wave -> behind the barrier (29) {(D_[:, :, 29] - D_[:, :, 15] - arr.max(axis=-1)).mean():9.0f}")
 # round 5: the edges' stages (fwd / rev): gate-up edge stamps 18..22, q-k-v edge stamps 23, 24, 28, 29, 30
 en = ["gathered", "fwd<1>", "h update + sums + ln, su", "rev<NT>", "planes + barrier"]
-for title, st, before, after in (() if mlp_stamps else (("gate / up edge", [18, 19, 20, 21, 22], 10, 11), ("q / k / v edge", [23, 24, 28, 29, 30], 1, 2))):
+for title, st, before, after in (() if (mlp_stamps or wait_stamps) else (("gate / up edge", [18, 19, 20, 21, 22], 10, 11), ("q / k / v edge", [23, 24, 28, 29, 30], 1, 2))):
     print(f"inside the {title} (stamps {st}):")
     for i in range(1, 5):
         seg = D_[:, :, st[i]] - D_[:, :, st[i - 1]]
