@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 17
+#define QUIP_ABI_VERSION 18
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -462,6 +462,22 @@ int quip_rope_attn_decode_batched_f16(const void* q, const void* k, const void* 
                                       void* out, int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim,
                                       int32_t max_len, float scale, int32_t window, void* workspace,
                                       quip_stream_t stream);
+/* The same for sequences that do not begin at cache row 0 (ABI 18; a LEFT-PADDED batch: what HF generate keeps in its
+ * cache).  The batched call's arguments plus start: device int64 [batch], 8-byte aligned.  Sequence b's tokens are cache
+ * rows start[b] .. pos[b]; row t has rotary position t - start[b]: q and the new k are rotated with row pos[b] - start[b]
+ * of cos / sin, the new row is still appended at cache row pos[b], and the keys walked are
+ * max(start[b], window > 0 ? pos[b] + 1 - window : 0) .. pos[b] -- rows below that are never read (they may hold
+ * anything).  From the first key on, chunking, the split rule (on the absolute pos[b]), lane groups and merge are the
+ * batched call's, so sequence b's output and appended rows are bit identical to the batched call on that sequence with
+ * window' = pos - start + 1 (min(window, .) with a window) and tables whose row pos holds row pos - start; start all
+ * zeros gives the batched call's bits.  Range rule, per sequence: pos[b] outside [0, max_len), start[b] < 0 or
+ * start[b] > pos[b] -> NaN output row, nothing appended, no workspace traffic; the others are unaffected.
+ * Workspace and errors as the batched call; start NULL: QUIP_ERR_NULL_POINTER. */
+int quip_rope_attn_decode_batched_start_f16(const void* q, const void* k, const void* v, const float* cos,
+                                            const float* sin, const int64_t* pos, void* kcache, void* vcache,
+                                            void* out, int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                                            int32_t max_len, float scale, int32_t window, void* workspace,
+                                            quip_stream_t stream, const void* start);
 /* ---- prompt-side attention: a chunk of `rows` tokens appended behind a live cache, one launch ---------------------
  * Row i of the chunk is at position p = *pos + i (pos: device int64 scalar, read by the launch -- a captured call
  * serves every start position).  Its k row, rotated, and its v row are written to cache row p; out[i] is the softmax

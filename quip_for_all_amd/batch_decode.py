@@ -31,6 +31,9 @@ try:
                    "Tensor(a!) kcache, Tensor(b!) vcache, Tensor(c!)? workspace, int window=0) -> Tensor")
     # greedy tail over (B, vocab) logits: tok[b] <- argmax of row b, pos[b] += 1
     _R._lib.define("argmax_step_batched(Tensor logits, Tensor(a!) tok, Tensor(b!) pos) -> ()")
+    # rope_attn_decode_batched on sequences that begin at cache row start[b] (left-padded batches): start (B,) int64
+    _R._lib.define("rope_attn_decode_batched_start(Tensor q, Tensor k, Tensor v, Tensor cos, Tensor sin, Tensor pos, "
+                   "Tensor start, Tensor(a!) kcache, Tensor(b!) vcache, Tensor(c!)? workspace, int window=0) -> Tensor")
 except RuntimeError:
     pass
 
@@ -41,7 +44,8 @@ def rope_attn_batched_workspace(batch, heads, head_dim, device):
                        device=device)
 
 
-def _rope_attn_decode_batched_cuda(q, k, v, cos, sin, pos, kcache, vcache, workspace=None, window=0):
+def _check_batched_operands(q, k, v, cos, sin, pos, kcache, vcache, workspace):
+    """the operand checks of both batched decode launches -> (B, heads, kv_heads, hd, max_len)"""
     need = _R._need
     for t in (q, k, v, kcache, vcache):
         need(t.dtype == torch.float16 and t.is_contiguous() and t.is_cuda and t.device == q.device,
@@ -60,12 +64,32 @@ def _rope_attn_decode_batched_cuda(q, k, v, cos, sin, pos, kcache, vcache, works
         need(workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == q.device
              and workspace.numel() >= capi.lib().quip_rope_attn_batched_workspace_bytes(B, heads, hd),
              "workspace: use rope_attn_batched_workspace(batch, heads, head_dim, device)")
+    return B, heads, kvh, hd, max_len
+
+
+def _rope_attn_decode_batched_cuda(q, k, v, cos, sin, pos, kcache, vcache, workspace=None, window=0):
+    B, heads, kvh, hd, max_len = _check_batched_operands(q, k, v, cos, sin, pos, kcache, vcache, workspace)
     out = torch.empty_like(q)
     with torch.cuda.device(q.device):
         capi.check(capi.lib().quip_rope_attn_decode_batched_f16(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
             kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), B, heads, kvh, hd, max_len, 1.0 / math.sqrt(hd),
             int(window), _R._ptr(workspace), _R._stream(q)), "quip_rope_attn_decode_batched_f16")
+    return out
+
+
+def _rope_attn_decode_batched_start_cuda(q, k, v, cos, sin, pos, start, kcache, vcache, workspace=None, window=0):
+    """rope_attn_decode_batched for sequences whose tokens are cache rows start[b] .. pos[b] (csrc/decode_glue.hip,
+    StartAttnArgs): rotary position of row t is t - start[b], rows below start[b] are never read"""
+    B, heads, kvh, hd, max_len = _check_batched_operands(q, k, v, cos, sin, pos, kcache, vcache, workspace)
+    _R._need(start.dtype == torch.int64 and tuple(start.shape) == (B,) and start.is_contiguous() and start.device == q.device,
+             "start must be a contiguous int64 (B,) tensor on q's device")
+    out = torch.empty_like(q)
+    with torch.cuda.device(q.device):
+        capi.check(capi.lib().quip_rope_attn_decode_batched_start_f16(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
+            kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), B, heads, kvh, hd, max_len, 1.0 / math.sqrt(hd),
+            int(window), _R._ptr(workspace), _R._stream(q), start.data_ptr()), "quip_rope_attn_decode_batched_start_f16")
     return out
 
 
@@ -87,6 +111,9 @@ try:
     _R._reg_fake("rope_attn_decode_batched",
                  lambda q, k, v, cos, sin, pos, kcache, vcache, workspace=None, window=0: torch.empty_like(q))
     _R._reg_fake("argmax_step_batched", lambda logits, tok, pos: None)
+    _R._lib.impl("rope_attn_decode_batched_start", _rope_attn_decode_batched_start_cuda, "CUDA")
+    _R._reg_fake("rope_attn_decode_batched_start",
+                 lambda q, k, v, cos, sin, pos, start, kcache, vcache, workspace=None, window=0: torch.empty_like(q))
 except RuntimeError:
     pass
 
@@ -161,13 +188,27 @@ def _ragged_passes(dec, slots, toks, chunk, on_pass):
         on_pass(pieces, h)
 
 
+def _no_prompts(dec, what):
+    """the prompt-side passes are defined for sequences that begin at cache row 0: a padded decoder refuses them"""
+    if getattr(dec, "start", None) is not None:
+        raise NotImplementedError(f"{what}: the prompt-side passes write sequences that begin at cache row 0; a "
+                                  "padded=True decoder takes its cache rows, pos and start from the caller")
+
+
 class BatchDecoder:
     """B sequences decoded in lockstep on the modules of a LlamaDecoder (see the module docstring).
 
     tok / pos: (B,) int64 on the device, the current token and position of every slot.  A slot whose position left
-    [0, max_len) gets NaN logits and leaves its cache alone; the other slots are unaffected."""
+    [0, max_len) gets NaN logits and leaves its cache alone; the other slots are unaffected.
 
-    def __init__(self, parent, batch, max_len=None):
+    padded=True: every slot has a first cache row, start (B,) int64 on the device, zeros to begin with -- slot b's tokens
+    are cache rows start[b] .. pos[b] and row t has rotary position t - start[b] (a left-padded batch as HF generate
+    caches it; quip_lib::rope_attn_decode_batched_start).  The caller writes the cache rows, pos and start; step,
+    decode, capture and reset work (a captured step reads start in place), the prompt-side methods, which are defined
+    for sequences that begin at row 0, raise NotImplementedError.  A slot with start outside [0, pos] idles like one
+    whose position left the cache."""
+
+    def __init__(self, parent, batch, max_len=None, padded=False):
         batch = int(batch)
         if not 1 <= batch <= QuantLinear.skinny_max_rows:
             raise ValueError(f"batch {batch}: 1 .. QuantLinear.skinny_max_rows = {QuantLinear.skinny_max_rows} sequences")
@@ -186,6 +227,7 @@ class BatchDecoder:
         self._alloc_cache()
         self.tok = torch.zeros(batch, dtype=torch.long, device=self.dev)
         self.pos = torch.zeros(batch, dtype=torch.long, device=self.dev)
+        self.start = torch.zeros(batch, dtype=torch.long, device=self.dev) if padded else None
         self.attn_ws = rope_attn_batched_workspace(batch, s.heads, s.head_dim, self.dev)
         self.graph = None
         self.sampling = None
@@ -200,11 +242,16 @@ class BatchDecoder:
 
     def _attend_step(self, i, q, k, v):
         """block i of step(): q (B, heads, hd), k / v (B, kv_heads, hd) -> (B, heads, hd)"""
+        if self.start is not None:
+            return torch.ops.quip_lib.rope_attn_decode_batched_start(q, k, v, self.cos, self.sin, self.pos, self.start,
+                                                                     self.kcache[i], self.vcache[i], self.attn_ws,
+                                                                     self.window)
         return torch.ops.quip_lib.rope_attn_decode_batched(q, k, v, self.cos, self.sin, self.pos, self.kcache[i],
                                                            self.vcache[i], self.attn_ws, self.window)
 
     def _attend_ragged(self, i, q, k, v, seg_slot, seg_rows):
         """block i of a ragged pass: q (rows, heads, hd), k / v (rows, kv_heads, hd) -> (rows, heads, hd)"""
+        _no_prompts(self, "a ragged prompt pass")
         return torch.ops.quip_lib.rope_attn_ragged(q, k, v, self.cos, self.sin, self.pos, seg_slot, seg_rows,
                                                    self.kcache[i], self.vcache[i], self.window)
 
@@ -245,6 +292,8 @@ class BatchDecoder:
     def reset(self, first_token=1):
         self.tok.fill_(first_token)
         self.pos.zero_()
+        if self.start is not None:
+            self.start.zero_()
 
     def capture(self):
         """warm up and capture one step as a hipGraph (before any prompt is written: the warm-up steps write cache
@@ -256,6 +305,7 @@ class BatchDecoder:
     @torch.no_grad()
     def prefill_slot(self, b, tokens):
         """the parent's batched prompt pass over `tokens`, written into slot b's cache rows 0..P-1; pos[b] = P"""
+        _no_prompts(self, "prefill_slot")
         tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
         if not 0 <= b < self.batch or not 1 <= tokens.numel() <= self.max_len:
             raise ValueError(f"slot {b} of {self.batch}, {tokens.numel()} prompt tokens (1 .. {self.max_len})")
@@ -265,6 +315,7 @@ class BatchDecoder:
     def extend_slot(self, b, tokens, chunk=512):
         """the parent's extend() on slot b: `tokens` (>= 1 ids) appended behind pos[b] in slot b's cache, pos[b] advanced
         on the device; the other slots keep their state.  Returns the last token's logits (1, vocab)."""
+        _no_prompts(self, "extend_slot")
         tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
         if not 0 <= b < self.batch or tokens.numel() < 1:
             raise ValueError(f"slot {b} of {self.batch}, {tokens.numel()} tokens to append (>= 1)")
@@ -279,6 +330,7 @@ class BatchDecoder:
         (quip_lib::rope_attn_ragged: per segment the bits of rope_attn_chunk).  Nothing reads pos on the host.  Tokens
         that do not fit a slot's max_len append nothing and give that slot NaN logits (the launch's range rule, per
         segment).  Returns the last-token logits of every list, (len(slots), vocab), in the order of `slots`."""
+        _no_prompts(self, "extend_slots")
         slots, toks = _check_passes(self, "extend_slots", slots, token_lists, chunk)
         return self._extend_passes(slots, toks, chunk)
 
@@ -304,6 +356,7 @@ class BatchDecoder:
         the default is the list's own next token, the last row not scored (-1 -> exactly 0).  Argument errors are
         extend_slots's, raised before anything is written.  Returns (logprobs, argmaxes): per list one (len_j,) fp32
         and one (len_j,) int64 tensor on the device, in the order of `slots`."""
+        _no_prompts(self, "score_slots")
         slots, toks = _check_passes(self, "score_slots", slots, token_lists, chunk)
         return self._score_passes(slots, toks, self._check_targets(toks, targets), chunk)
 
@@ -337,6 +390,7 @@ class BatchDecoder:
         """fill_slot for several slots at once: every named slot restarts on its prompt (>= 1 ids) -- pos zeroed on the
         device, all but the last token of every prompt through ONE extend_slots call (one-token prompts contribute no
         segment), the last token becomes tok[slot]; the other slots keep their state"""
+        _no_prompts(self, "fill_slots")
         slots, prompts = _check_ragged(self, slots, prompts, "fill_slots")
         if not slots:
             return
@@ -351,6 +405,7 @@ class BatchDecoder:
     def fill_slot(self, b, prompt):
         """restart slot b on `prompt` (>= 1 ids): all but its last token through prefill_slot, the last one becomes
         tok[b]; the other slots keep their state"""
+        _no_prompts(self, "fill_slot")
         prompt = torch.as_tensor(prompt, dtype=torch.long, device=self.dev).reshape(-1)
         if prompt.numel() < 1:
             raise ValueError("an empty prompt")
@@ -379,6 +434,7 @@ class BatchDecoder:
         """decode n_tokens for each of the B prompts (1-D ids, ragged lengths >= 1) -> (B, n_tokens) token ids.
         ragged: fill all slots with one fill_slots call (the ragged prompt pass on the chunk-attention route: equivalent
         to the slot-by-slot passes, not bit equal) instead of one fill_slot per prompt"""
+        _no_prompts(self, "generate")
         prompts = [torch.as_tensor(pr, dtype=torch.long, device=self.dev).reshape(-1) for pr in prompts]
         if len(prompts) != self.batch:
             raise ValueError(f"{len(prompts)} prompts for {self.batch} slots")

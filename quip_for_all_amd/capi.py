@@ -49,6 +49,8 @@ SIGNATURES = {
     "quip_rope_attn_batched_workspace_bytes": [_I32, _I32, _I32],
     "quip_rope_attn_decode_batched_f16": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _I32,
                                           _P, _P],
+    "quip_rope_attn_decode_batched_start_f16": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F,
+                                                _I32, _P, _P, _P],
     "quip_argmax_step_batched_f16": [_P, _I32, _I32, _P, _P, _P],
     "quip_rope_attn_chunk_f16": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _I32, _P],
     "quip_rope_attn_ragged_f16": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _F,

@@ -737,6 +737,22 @@ int quip_rope_attn_decode_batched_f16(const void* q, const void* k, const void* 
                                          max_len, scale, (hipStream_t)stream, workspace, window);
 }
 
+int quip_rope_attn_decode_batched_start_f16(const void* q, const void* k, const void* v, const float* cos,
+                                            const float* sin, const int64_t* pos, void* kcache, void* vcache,
+                                            void* out, int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                                            int32_t max_len, float scale, int32_t window, void* workspace,
+                                            quip_stream_t stream, const void* start) {
+  if (!q || !k || !v || !cos || !sin || !pos || !kcache || !vcache || !out || !start) return QUIP_ERR_NULL_POINTER;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kcache) || !aligned16(vcache) ||
+      (reinterpret_cast<uintptr_t>(pos) & 7) || (reinterpret_cast<uintptr_t>(start) & 7))
+    return QUIP_ERR_MISALIGNED;
+  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
+  if (window < 0) return QUIP_ERR_BAD_SHAPE;
+  return rope_attn_decode_batched_start_launch(q, k, v, cos, sin, pos, reinterpret_cast<const int64_t*>(start), kcache,
+                                               vcache, out, batch, heads, kv_heads, head_dim, max_len, scale,
+                                               (hipStream_t)stream, workspace, window);
+}
+
 int quip_rope_attn_chunk_f16(const void* q, const void* k, const void* v, const float* cos, const float* sin,
                              const int64_t* pos, void* kcache, void* vcache, void* out, int32_t rows, int32_t heads,
                              int32_t kv_heads, int32_t head_dim, int32_t max_len, float scale, int32_t window,

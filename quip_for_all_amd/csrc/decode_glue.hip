@@ -58,6 +58,14 @@ struct AttnArgs {
   int window;          // sliding-window attention (Mistral: config.sliding_window): positions (pos - window, pos]; <= 0: [0, pos]
   static constexpr bool kPaged = false;
   static constexpr bool kFp8 = false;
+  static constexpr bool kStart = false;
+};
+
+// The batched launch on sequences that do not begin at cache row 0 (a left-padded batch): sequence b's tokens live in
+// cache rows [start[b], pos[b]], row t has rotary position t - start[b].  Rows below start[b] are never read.
+struct StartAttnArgs : AttnArgs {
+  const int64_t* start;   // [B] device int64: first cache row of every sequence
+  static constexpr bool kStart = true;
 };
 
 // The batched launch on a PAGED cache (paged_attn.hip.h): kcache / vcache are page pools, a row is found through the
@@ -89,17 +97,21 @@ __host__ __device__ constexpr int fht16_barriers(int logl) { return logl <= 8 ? 
 // PagedAttnArgsF8: the paged walk on byte pools -- a lane loads 8 bytes per key instead of 16 and converts them to the
 // eight floats the fp16 kernel unpacks (exact), and the new row is replaced by dequant(quant(.)) before it is used at
 // t == pos, so what is scored now is what a later launch finds in the cache.
+// StartAttnArgs (SEQ only): the contiguous walk from max(start[b], the window's first key) with q and the new k rotated
+// by row pos - start[b] of cos / sin; start[b] outside [0, pos] joins the range rule.  All zeros: the AttnArgs launch's bits.
 template <int HD, bool ZIN, int LQ = 0, int LKV = 0, bool SEQ = false, class Args = AttnArgs>
 __global__ __launch_bounds__(!ZIN ? 256 : (LQ == 0 ? 768 : (1 << LQ) / 16 + 2 * ((1 << LKV) / 16)))
 void rope_attn_decode_kernel(Args a, AttnZ zz) {
   constexpr bool PAGED = Args::kPaged;
   constexpr bool FP8 = Args::kFp8;
+  constexpr bool START = Args::kStart;
   constexpr int LPK = HD / 8;        // lanes per key
   constexpr int NG = 256 / LPK;      // key groups per workgroup
   constexpr int U = 4;               // keys in flight per group
   static_assert(!(SEQ && ZIN), "the raw-GEMV-input variants are bs=1 only");
   static_assert(!PAGED || SEQ, "the paged cache belongs to the batched launch");
   static_assert(!FP8 || PAGED, "the fp8 cache is a paged cache");
+  static_assert(!START || (SEQ && !PAGED), "a first row per sequence belongs to the contiguous batched launch");
   __shared__ float s_m[NG], s_l[NG];
   __shared__ float s_acc[NG][HD + 4];
   const int tid = threadIdx.x, h = blockIdx.x;
@@ -109,6 +121,7 @@ void rope_attn_decode_kernel(Args a, AttnZ zz) {
     a.k += b * a.kv_heads * HD;
     a.v += b * a.kv_heads * HD;
     a.pos += b;
+    if constexpr (START) a.start += b;
     if constexpr (PAGED) {
       a.table += b * a.max_pages;
     } else {
@@ -148,13 +161,25 @@ void rope_attn_decode_kernel(Args a, AttnZ zz) {
     return;
   }
   const int pos = (int)pos64;
+  int start = 0;
+  if constexpr (START) {
+    // the range rule's two further conditions: the sequence begins inside [0, pos]
+    const long long start64 = *a.start;
+    if (start64 < 0 || start64 > pos64) {
+      if (blockIdx.y == 0 && tid < HD) a.out[(size_t)h * HD + tid] = __builtin_bit_cast(f16, (unsigned short)0x7e00);
+      return;
+    }
+    start = (int)start64;
+  }
   // split mode (long context, workspace given): workgroup (h, s) takes positions [t_lo, t_hi); the last
   // workgroup of a head to arrive merges the partial softmax states (flash-decoding across CUs)
   const bool split = a.ws != nullptr && pos >= kSplitFromPos;
   const int sidx = blockIdx.y;
   if (!split && sidx > 0) return;
   // sliding window: the walk starts at `first` instead of 0 (the cache stays linear: rows [0, pos] all exist)
-  const int first = a.window > 0 ? max(0, pos + 1 - a.window) : 0;
+  // (START: never below the sequence's first row)
+  const int first = START ? max(start, a.window > 0 ? pos + 1 - a.window : 0)
+                          : (a.window > 0 ? max(0, pos + 1 - a.window) : 0);
   const int chunk = split ? (pos - first + kSplits) / kSplits : pos + 1 - first;      // ceil((pos + 1 - first) / kSplits)
   const int t_lo = first + (split ? sidx * chunk : 0);
   const int t_hi = split ? min(pos + 1, t_lo + chunk) : pos + 1;       // exclusive (a split past the end walks nothing: m = -inf)
@@ -177,8 +202,8 @@ void rope_attn_decode_kernel(Args a, AttnZ zz) {
     }
     __syncthreads();
   }
-  const float* cs = a.cos + (size_t)pos * HD;
-  const float* sn = a.sin + (size_t)pos * HD;
+  const float* cs = a.cos + (size_t)(pos - start) * HD;     // (start: 0 unless START)
+  const float* sn = a.sin + (size_t)(pos - start) * HD;
 
   const f16* qh = a.q + (size_t)h * HD;
   const f16* kh = a.k + (size_t)kvh * HD;
@@ -276,8 +301,8 @@ void rope_attn_decode_kernel(Args a, AttnZ zz) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = t0 + u * NG;
-      // t == pos comes from registers, t > pos is masked: a dummy row (paged: one of a validated page)
-      const int tc = t < pos ? t : (PAGED ? first : 0);
+      // t == pos comes from registers, t > pos is masked: a dummy row (paged: one of a validated page; START: none below start)
+      const int tc = t < pos ? t : (PAGED || START ? first : 0);
       if constexpr (FP8) {
         kr[u] = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(kc) + row(tc) + d0);
         vr[u] = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(vc) + row(tc) + d0);
@@ -452,6 +477,33 @@ int rope_attn_decode_batched_launch(const void* q, const void* k, const void* v,
   const AttnZ none{};
   if (head_dim == 128) return launch<rope_attn_decode_kernel<128, false, 0, 0, true>>(grid, dim3(256), 0, stream, a, none);
   return launch<rope_attn_decode_kernel<64, false, 0, 0, true>>(grid, dim3(256), 0, stream, a, none);
+}
+
+// rope_attn_decode_batched_launch with a first cache row per sequence (StartAttnArgs): same grid, same workspace
+int rope_attn_decode_batched_start_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                          const int64_t* pos, const int64_t* start, void* kcache, void* vcache, void* out,
+                                          int batch, int heads, int kv_heads, int head_dim, int max_len, float scale,
+                                          hipStream_t stream, void* workspace, int window) {
+  if (batch < 1 || batch > 65535 || heads < 1 || kv_heads < 1 || heads % kv_heads != 0 || max_len < 1)
+    return QUIP_ERR_BAD_SHAPE;
+  if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
+  StartAttnArgs a{};
+  static_cast<AttnArgs&>(a) =
+      AttnArgs{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
+               cos, sin, pos, reinterpret_cast<f16*>(kcache), reinterpret_cast<f16*>(vcache),
+               reinterpret_cast<f16*>(out), heads, kv_heads, max_len, scale, nullptr, nullptr, window};
+  a.start = start;
+  const bool split = workspace != nullptr && max_len > kSplitFromPos;
+  if (split) {
+    a.ws = reinterpret_cast<float*>(workspace);
+    a.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) +
+                                             (size_t)batch * heads * kSplits * (head_dim + 4) * sizeof(float));
+  }
+  const dim3 grid(heads, split ? kSplits : 1, batch);
+  const AttnZ none{};
+  if (head_dim == 128)
+    return launch<rope_attn_decode_kernel<128, false, 0, 0, true, StartAttnArgs>>(grid, dim3(256), 0, stream, a, none);
+  return launch<rope_attn_decode_kernel<64, false, 0, 0, true, StartAttnArgs>>(grid, dim3(256), 0, stream, a, none);
 }
 
 bool rope_attn_decode_z_supported(int heads, int kv_heads, int head_dim) {

@@ -188,6 +188,11 @@ int rope_attn_decode_batched_launch(const void* q, const void* k, const void* v,
                                     const int64_t* pos, void* kcache, void* vcache, void* out, int batch, int heads,
                                     int kv_heads, int head_dim, int max_len, float scale, hipStream_t stream,
                                     void* workspace, int window);
+// the same for sequences that begin at cache row start[b] (left-padded batches): row t has rotary position t - start[b]
+int rope_attn_decode_batched_start_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                          const int64_t* pos, const int64_t* start, void* kcache, void* vcache, void* out,
+                                          int batch, int heads, int kv_heads, int head_dim, int max_len, float scale,
+                                          hipStream_t stream, void* workspace, int window);
 int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, void* pos, hipStream_t stream);
 // chunk_attn.hip.h (in decode_glue.hip): rows queries at positions [*pos, *pos + rows) against cache rows [0, *pos + rows)
 int rope_attn_chunk_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,

@@ -806,11 +806,15 @@ class LlamaDecoder:
         q = torch.empty_like(probs).exponential_(1)
         return torch.argmax(probs / q, dim=-1)
 
-    def batched(self, batch, max_len=None, paged=False, pages=None, kv_dtype=None, kv_exp=None):
+    def batched(self, batch, max_len=None, paged=False, pages=None, kv_dtype=None, kv_exp=None, padded=False):
         """a decoder of `batch` independent sequences on this decoder's modules (batch_decode.BatchDecoder); paged: its
         KV cache is a pool of `pages` 64-position pages shared by the slots (paged_cache.PagedBatchDecoder; default: as
         many pages as the contiguous cache has rows for).  kv_dtype="fp8" (paged only): the pools hold one OCP e4m3fn
-        byte per element, kv_exp the (layers, 2) power-of-two exponents of K | V (default 0; see paged_cache)"""
+        byte per element, kv_exp the (layers, 2) power-of-two exponents of K | V (default 0; see paged_cache).
+        padded (contiguous cache only): every slot has a first cache row `start[b]` of its own -- the layout of a
+        left-padded HF generate batch; step / decode / capture / reset only (see BatchDecoder)"""
+        if paged and padded:
+            raise ValueError("padded=True: only with the contiguous cache (paged=False)")
         if paged:
             from .paged_cache import PagedBatchDecoder
             return PagedBatchDecoder(self, batch, max_len, pages, kv_dtype, kv_exp)
@@ -819,7 +823,7 @@ class LlamaDecoder:
         if pages is not None:
             raise ValueError("pages: only with paged=True")
         from .batch_decode import BatchDecoder
-        return BatchDecoder(self, batch, max_len)
+        return BatchDecoder(self, batch, max_len, padded=bool(padded))
 
     prefill_graph_cache_size = 8      # captured prompt lengths kept (each graph owns a memory pool)
 

@@ -20,7 +20,26 @@ That `position_ids` equals the cache length and that `attention_mask` has no hol
 batch 1 generation passes) is checked when the wrapper takes a cache object over -- one device synchronisation per
 generation, not per token; a padded sequence stays on the stock forward.
 Logits are those of `LlamaDecoder` (same arithmetic as the stage-wise ops, tests/test_gpu_hf_generate.py pins them against
-the stock forward); the cache rows are bit-compatible (rotated keys, fp16), so fast and stock steps may be mixed freely."""
+the stock forward); the cache rows are bit-compatible (rotated keys, fp16), so fast and stock steps may be mixed freely.
+
+BATCHES (opt-in: `enable_fast_decode(model, batch=True)`, or QUIP_FAST_DECODE_BATCH=1 for the wrapper that
+`load_quantized_model` installs; off by default).  A decode step of a LEFT-PADDED batch -- `input_ids` (B, 1) with
+2 <= B <= QuantLinear.skinny_max_rows, an initialised `DynamicCache` of `DynamicLayer`s holding (B, kv_heads, n, hd) fp16
+keys, a 2-D `attention_mask` (B, n + 1), eager mode, no extra outputs -- runs one step of a padded `BatchDecoder`
+(`LlamaDecoder.batched(B, padded=True)`: the products at M = B rows, ONE attention launch for all sequences,
+quip_lib::rope_attn_decode_batched_start) instead of the stock forward's ~45 launches per block.  The padded layout is
+kept: row t of sequence b is a real token for t >= start[b] = n + 1 - mask[b].sum() and has rotary position
+t - start[b].  When a cache object is first seen (one device read per generation) it is taken over only if every mask row
+is zeros followed by at least two ones and `position_ids`, if given, equals n - start; right padding, holes, 4-D masks
+and everything else stay on the stock forward.  Rows [0, n) of every layer are then copied into the decoder's buffers,
+and from there on every step hands the cache object views `buffer[i][:, :, :n + 1]` and reads nothing back from the
+device.  Ownership follows the rule of the batch-1 route (weak reference, data pointers of the first and last layer,
+length), a cache that loses the buffers keeps its contents, and stock and fast steps may be mixed: the next fast step
+imports again.  The buffers cost 2 * layers * B * kv_heads * cap * hd * 2 bytes with cap = QUIP_FAST_DECODE_BATCH_MAX_LEN
+(default 4096, capped by max_position_embeddings) -- 34 GB for the Llama-2-7B shape at B = 16 and the default; one
+decoder is resident at a time (a call with another B replaces it).  The steps are counted in `fast_batch_steps`.
+Not served: the prompt pass of a batch (the stock forward, already in the prefill regime), StaticCache batches and
+torch.compile'd callers, sliding-window layers, a captured step, batches above skinny_max_rows, right padding."""
 import torch
 
 from . import register_lib as _R
@@ -103,8 +122,16 @@ def _off_thread(fn):
 
 
 class _FastDecode:
-    def __init__(self, model, assume_llama_like=False):
+    def __init__(self, model, assume_llama_like=False, batch=False):
         self.model = model
+        self.batch = bool(batch)     # the route for left-padded batches (module docstring); off: batches take the stock forward
+        self.bdec = None             # padded BatchDecoder on self.dyn's modules, for the batch size seen last
+        self.batch_owner = None      # weakref of the cache object whose layers are views of bdec's buffers
+        self.batch_len = 0
+        self.batch_disabled = None   # the reason BatchDecoder refused this model, once known
+        self.batch_declined = None   # weakref of the cache object whose mask was looked at and found unfit
+        self.fast_batch_steps = 0
+        self.batch_imports = 0       # cache take-overs of the batch route (each one reads the mask: one synchronisation)
         self.orig_forward = model.forward
         self.assume_llama_like = assume_llama_like
         self.dec = None              # decoder on a StaticCache's tensors
@@ -245,9 +272,11 @@ class _FastDecode:
             self.dyn_owner = None
         return self.dyn
 
-    def _release_owner(self, cache):
-        """a cache object other than `cache` that holds views of the buffers keeps its contents: the views become its own tensors"""
-        owner = self.dyn_owner() if self.dyn_owner is not None else None
+    def _release_owner(self, cache, batch=False):
+        """a cache object other than `cache` that holds views of the buffers keeps its contents: the views become its own tensors
+        (batch: the buffers and the owner of the batch route instead of the batch-1 route's)"""
+        owner_ref = self.batch_owner if batch else self.dyn_owner
+        owner = owner_ref() if owner_ref is not None else None
         if owner is not None and owner is not cache:
             for L in getattr(owner, "layers", []):
                 if getattr(L, "is_initialized", False) and torch.is_tensor(L.keys) and L.keys.numel():
@@ -319,6 +348,110 @@ class _FastDecode:
         self.fast_steps += 1
         return logits.reshape(1, 1, -1)
 
+    # -- the batch route (module docstring, BATCHES)
+    def _batch_capacity(self):
+        import os
+        cap = int(os.environ.get("QUIP_FAST_DECODE_BATCH_MAX_LEN", "4096"))
+        return min(cap, self._dyn_capacity(), int(getattr(self.model.config, "max_position_embeddings", cap) or cap))
+
+    def _batch_layers(self, input_ids, cache, attention_mask, inputs_embeds, labels, kw):
+        """the layers of a call the batch route considers, else None: shapes and types only, nothing reads device memory"""
+        from .qlinear import QuantLinear
+        if (self.disabled is not None or self.batch_disabled is not None or input_ids is None or inputs_embeds is not None
+                or labels is not None or self.model.training or kw.get("output_attentions") or kw.get("output_hidden_states")):
+            return None
+        if input_ids.dim() != 2 or input_ids.shape[1] != 1 or not input_ids.is_cuda:
+            return None
+        B = input_ids.shape[0]
+        if not 2 <= B <= QuantLinear.skinny_max_rows or type(cache).__name__ != "DynamicCache":
+            return None
+        layers = getattr(cache, "layers", None)
+        if not layers or len(layers) != self.model.config.num_hidden_layers:
+            return None
+        for L in layers:
+            if (type(L).__name__ != "DynamicLayer" or not getattr(L, "is_initialized", False) or L.keys.dim() != 4
+                    or L.keys.shape[0] != B or L.keys.dtype != torch.float16 or L.keys.device != input_ids.device
+                    or L.values.shape != L.keys.shape):
+                return None
+        n = layers[0].keys.shape[-2]
+        if n < 1 or n + 1 > self._batch_capacity() or any(L.keys.shape != layers[0].keys.shape for L in layers):
+            return None
+        if not torch.is_tensor(attention_mask) or tuple(attention_mask.shape) != (B, n + 1):
+            return None
+        return layers
+
+    def _batch_decoder(self, B, dev):
+        dec = self._dynamic_decoder(dev)
+        if dec is None or dec.window:
+            return None
+        if self.bdec is None or self.bdec.batch != B or self.bdec.parent is not dec:
+            self._release_owner(None, batch=True)       # (whoever holds views of the buffers that go away keeps its rows)
+            self.batch_owner, self.bdec = None, None
+            try:
+                self.bdec = dec.batched(B, max_len=self._batch_capacity(), padded=True)
+            except (NotImplementedError, ValueError) as e:
+                self.batch_disabled = repr(e)
+                return None
+        return self.bdec
+
+    @staticmethod
+    def _left_padded(attention_mask, position_ids, n):
+        """start (B,) of a mask whose rows are zeros followed by >= 2 ones, with position_ids (if given) = n - start; else
+        None.  (reads device memory: called once per cache take-over)"""
+        real = attention_mask != 0
+        start = (n + 1) - real.sum(dim=1)
+        cols = torch.arange(n + 1, device=real.device)
+        ok = (real == (cols[None, :] >= start[:, None])).all() & (start <= n - 1).all()
+        if position_ids is not None:
+            if position_ids.numel() != start.numel():
+                return None
+            ok = ok & (position_ids.reshape(-1).to(start.device) == n - start).all()
+        return start if bool(ok) else None
+
+    @torch.compiler.disable
+    def _batch_step(self, input_ids, cache, layers, attention_mask, position_ids):
+        import weakref
+        B, n = input_ids.shape[0], layers[0].keys.shape[-2]
+        bd = self.bdec
+        owner = self.batch_owner() if self.batch_owner is not None else None
+        owned = (bd is not None and owner is cache and bd.batch == B and n <= self.batch_len
+                 and layers[0].keys.data_ptr() == bd.kcache[0].data_ptr()
+                 and layers[-1].values.data_ptr() == bd.vcache[-1].data_ptr())
+        with torch.no_grad():
+            if not owned:
+                # the mask is looked at before anything is allocated for the call
+                if self.batch_declined is not None and self.batch_declined() is cache:
+                    return None                         # (looked at once: a generation costs one device read either way)
+                start = self._left_padded(attention_mask, position_ids, n)
+                if start is None:
+                    self.batch_declined = weakref.ref(cache)
+                    return None
+                bd = self._batch_decoder(B, input_ids.device)
+                if bd is None or tuple(layers[0].keys.shape) != (B, bd.s.kv_heads, n, bd.s.head_dim):
+                    return None
+                self._release_owner(cache, batch=True)
+                for i, L in enumerate(layers):
+                    bd.kcache[i][:, :, :n].copy_(L.keys)
+                    bd.vcache[i][:, :, :n].copy_(L.values)
+                bd.start.copy_(start)
+                self.batch_owner = weakref.ref(cache)
+                self.batch_imports += 1
+            bd.tok.copy_(input_ids[:, 0])
+            bd.pos.fill_(n)
+            logits = bd.step()                          # (B, vocab) fp16, a fresh tensor; row n of every layer written
+            for i, L in enumerate(layers):              # DynamicLayer.update()'s result: tensors one row longer
+                L.keys = bd.kcache[i][:, :, :n + 1]
+                L.values = bd.vcache[i][:, :, :n + 1]
+        self.batch_len = n + 1
+        self.fast_batch_steps += 1
+        return logits.reshape(B, 1, -1)
+
+    def _output(self, logits, past_key_values, kw):
+        if kw.get("return_dict", getattr(self.model.config, "return_dict", True)) is False:
+            return (logits, past_key_values)
+        from transformers.modeling_outputs import CausalLMOutputWithPast
+        return CausalLMOutputWithPast(loss=None, logits=logits, past_key_values=past_key_values)
+
     @torch.compiler.disable      # (an opaque eager call inside a torch.compile'd generate loop: the decoder owns its launches)
     def _fast_step(self, input_ids, cache, kind_layers, attention_mask=None, position_ids=None):
         kind, layers = kind_layers
@@ -358,6 +491,11 @@ class _FastDecode:
     def __call__(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,
                  labels=None, use_cache=None, logits_to_keep=0, **kw):
         layers = self._eligible(input_ids, past_key_values, inputs_embeds, labels, kw)
+        if self.batch and layers is None and not torch.compiler.is_compiling():
+            blayers = self._batch_layers(input_ids, past_key_values, attention_mask, inputs_embeds, labels, kw)
+            logits = self._batch_step(input_ids, past_key_values, blayers, attention_mask, position_ids) if blayers else None
+            if logits is not None:
+                return self._output(logits, past_key_values, kw)
         if layers is not None and torch.compiler.is_compiling():
             # inside somebody's torch.compile: static caches go through the operator (traceable; padding is not checked
             # there -- it would be a graph break); anything else is the stock forward, which compiles as it always did
@@ -392,18 +530,19 @@ class _FastDecode:
             return self.orig_forward(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
                                      past_key_values=past_key_values, inputs_embeds=inputs_embeds, labels=labels,
                                      use_cache=use_cache, logits_to_keep=logits_to_keep, **kw)
-        if kw.get("return_dict", getattr(self.model.config, "return_dict", True)) is False:
-            return (logits, past_key_values)
-        from transformers.modeling_outputs import CausalLMOutputWithPast
-        return CausalLMOutputWithPast(loss=None, logits=logits, past_key_values=past_key_values)
+        return self._output(logits, past_key_values, kw)
 
 
-def enable_fast_decode(model, assume_llama_like=False):
-    """wrap `model.forward` (see the module docstring); returns the model.  `disable_fast_decode` undoes it."""
+def enable_fast_decode(model, assume_llama_like=False, batch=False):
+    """wrap `model.forward` (see the module docstring); returns the model.  `disable_fast_decode` undoes it.
+    batch=True: decode steps of left-padded batches run a padded BatchDecoder (module docstring, BATCHES; mind the size of its
+    buffers); on a model that is wrapped already it switches the route on."""
     if getattr(model, "_quip_fast_decode", None) is None:
-        fd = _FastDecode(model, assume_llama_like)
+        fd = _FastDecode(model, assume_llama_like, batch)
         model._quip_fast_decode = fd
         model.forward = fd
+    elif batch:
+        model._quip_fast_decode.batch = True
     return model
 
 

@@ -267,7 +267,8 @@ def load_quantized_model(save_folder: str, revision: Optional[str] = None,
     fast_decode (not in the reference; default on, QUIP_FAST_DECODE=0 or fast_decode=False switches it off): single-token
     forward calls on an initialised transformers StaticCache -- the reference's decode loop, example_generate.py:28-33, and
     `generate(cache_implementation="static")` -- run the fused decoder on the same modules and cache tensors (hf_fast.py);
-    every other call is the stock forward."""
+    every other call is the stock forward.  QUIP_FAST_DECODE_BATCH=1 also routes decode steps of left-padded `generate`
+    batches through the batched decoder (off by default; hf_fast.py, BATCHES, for what it serves and what its buffers cost)."""
     if _require_gpu and not torch.cuda.is_available():
         raise RuntimeError("No GPU found. A GPU is needed to run quantized model.")          # quantizer.py:799-801
     if not os.path.isdir(save_folder):
@@ -339,7 +340,7 @@ def load_quantized_model(save_folder: str, revision: Optional[str] = None,
         fast_decode = os.environ.get("QUIP_FAST_DECODE", "1") != "0"
     if fast_decode:
         from .hf_fast import enable_fast_decode
-        enable_fast_decode(model)
+        enable_fast_decode(model, batch=os.environ.get("QUIP_FAST_DECODE_BATCH", "0") != "0")
     return model
 
 
