@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 18
+#define QUIP_ABI_VERSION 19
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -616,6 +616,34 @@ int quip_nll_rows_f16(const void* logits, int32_t rows, int32_t n, const int64_t
 int quip_sample_step_f16(const void* logits, int32_t rows, int32_t n, const float* temperature, const int32_t* top_k,
                          const float* top_p, const int64_t* seed, int64_t* tok, int64_t* pos, int32_t* kept,
                          quip_stream_t stream);
+
+/* ---- per-head RMSNorm of q and k in front of the rotary embedding (ABI 19; Qwen3's q_norm / k_norm) ---------------------
+ * For one head vector x[0..HD) (fp16), weight w[0..HD) (fp16) and eps (fp32), HD = head_dim (csrc/attn_query.hip.h):
+ *   S = sum x_i^2 in fp32 (a lane's 8 squares in index order, the HD / 8 lanes of the head by a butterfly),
+ *   r = 1 / sqrt(S / HD + eps) in fp32, n_i = fp16(x_i r), y_i = fp16(float(n_i) float(w_i))
+ * -- HF's Qwen3RMSNorm.forward: normalised in fp32, cast back, then the weight in fp16.  r is within a relative 2^-19 of
+ * its float64 value on the same x.
+ *
+ * quip_qk_norm_rows_f16: every head of q [rows, heads * head_dim] and of k [rows, kv_heads * head_dim] (fp16, row-major,
+ * contiguous, 16-byte aligned) replaced by its y, in place, ONE launch; q_weight / k_weight [head_dim] fp16, 16-byte
+ * aligned.  A head's result depends on that head's data alone.  rows >= 1, heads / kv_heads in 1 .. 65536 (else
+ * QUIP_ERR_BAD_SHAPE); head_dim 64 or 128 (else QUIP_ERR_UNSUPPORTED). */
+int quip_qk_norm_rows_f16(void* q, void* k, const void* q_weight, const void* k_weight, int64_t rows, int32_t heads,
+                          int32_t kv_heads, int32_t head_dim, float eps, quip_stream_t stream);
+/* quip_rope_attn_decode_window_f16 / quip_rope_attn_decode_batched_f16 with that norm applied to q and to the new k row in
+ * registers, between the load and the rotation: the arguments of those calls plus q_weight, k_weight, eps.  Output and
+ * appended cache rows are bit identical to quip_qk_norm_rows_f16 on (q, k) followed by the plain call (q and k themselves
+ * are not written here).  Range rule, split mode, window, workspace and errors: the plain calls'. */
+int quip_rope_attn_decode_qknorm_f16(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                     const int64_t* pos, void* kcache, void* vcache, void* out, int32_t heads,
+                                     int32_t kv_heads, int32_t head_dim, int32_t max_len, float scale, int32_t window,
+                                     void* workspace, quip_stream_t stream, const void* q_weight, const void* k_weight,
+                                     float eps);
+int quip_rope_attn_decode_batched_qknorm_f16(const void* q, const void* k, const void* v, const float* cos,
+                                             const float* sin, const int64_t* pos, void* kcache, void* vcache, void* out,
+                                             int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                                             int32_t max_len, float scale, int32_t window, void* workspace,
+                                             quip_stream_t stream, const void* q_weight, const void* k_weight, float eps);
 
 /* Which kernel a bs=1 E8P12 GEMV launch of `count` matrices (ns[i] rows, common k) is dispatched to by default, without
  * launching anything: 1 = e8p_gemv_mfma_kernel, 2 = e8p_gemv_v2_kernel (needs the workspace of the *_ws entry points when

@@ -179,7 +179,7 @@ def _ragged_passes(dec, slots, toks, chunk, on_pass):
 
         def attend(i, q, k, v):
             return dec._attend_ragged(i, q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim),
-                                      v.view(n, s.kv_heads, s.head_dim), seg_slot, seg_rows).reshape(n, s.hidden)
+                                      v.view(n, s.kv_heads, s.head_dim), seg_slot, seg_rows).reshape(n, s.q_width)
         h = p.embed[torch.cat([toks[j][a:a + r] for j, a, r in pieces])]      # (n, hidden)
         for i, L in enumerate(p.layers):
             h = p._block(L, h, partial(attend, i))
@@ -240,8 +240,19 @@ class BatchDecoder:
                                   device=self.dev)
         self.vcache = torch.zeros_like(self.kcache)
 
+    def _fuses_norm(self):
+        """does _attend_step normalise q and k itself (a model with q / k norms: LlamaDecoder.qk_norm)?  The contiguous
+        launch has an instantiation that does; the padded-start launch -- and the paged ones -- get them normalised by
+        LlamaDecoder._block (quip_lib::qk_norm_rows in front: the same bits)"""
+        return self.parent.qk_norm and self.parent.qk_fused and self.start is None
+
     def _attend_step(self, i, q, k, v):
         """block i of step(): q (B, heads, hd), k / v (B, kv_heads, hd) -> (B, heads, hd)"""
+        if self._fuses_norm():
+            L = self.parent.layers[i]
+            return torch.ops.quip_lib.rope_attn_decode_batched_qknorm(q, k, v, self.cos, self.sin, self.pos, self.kcache[i],
+                                                                      self.vcache[i], self.attn_ws, self.window,
+                                                                      L["q_norm"], L["k_norm"], self.parent.qk_eps)
         if self.start is not None:
             return torch.ops.quip_lib.rope_attn_decode_batched_start(q, k, v, self.cos, self.sin, self.pos, self.start,
                                                                      self.kcache[i], self.vcache[i], self.attn_ws,
@@ -268,9 +279,10 @@ class BatchDecoder:
 
         def attend(i, q, k, v):
             return self._attend_step(i, q.view(B, s.heads, s.head_dim), k.view(B, s.kv_heads, s.head_dim),
-                                     v.view(B, s.kv_heads, s.head_dim)).reshape(B, s.hidden)
+                                     v.view(B, s.kv_heads, s.head_dim)).reshape(B, s.q_width)
+        fused = self._fuses_norm()
         for i, L in enumerate(p.layers):
-            h = p._block(L, h, partial(attend, i))
+            h = p._block(L, h, partial(attend, i), norm_in_attend=fused)
         return self._head(h)
 
     def _head(self, h):

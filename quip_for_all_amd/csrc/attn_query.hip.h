@@ -76,6 +76,56 @@ __device__ __forceinline__ void rope8(const f16* vec, const float c8[8], const f
   for (int i = 0; i < 8; ++i) o[i] = (float)(f16)had::fadd(had::fmul(a[i], c8[i]), had::fmul(sgn * b[i], s8[i]));
 }
 
+// ---- per-head RMSNorm of q / k in front of the rotation (Qwen3: q_norm / k_norm, a (HD,) weight each) ---------------------
+// The one place of this arithmetic: qk_norm_rows_kernel (qk_norm.hip.h) and the kNorm instantiations of
+// rope_attn_decode_kernel call these and nothing else for it, so the fused launch gives the bits of the stand-alone
+// launch followed by the plain one.  Two fp16 roundings, HF's Qwen3RMSNorm.forward: normalised in fp32 and cast back,
+// then the weight in fp16 (the product of two fp16 values is exact in fp32: one rounding).
+//
+// 1 / sqrt(mean(x^2) + eps) of a head vector; a8: this lane's 8 dims.  The lane's squares are added in index order from
+// 0, the lane group's sums by had::sum16_xor; every lane of the group holds the result.  (v_sqrt_f32 and v_rcp_f32:
+// one ulp each, the same instruction in every instantiation)
+template <int HD>
+__device__ __forceinline__ float inv_rms(const float (&a8)[8], float eps) {
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ss = __builtin_fmaf(a8[i], a8[i], ss);
+  const float S = had::sum16_xor<HD / 8>(ss);
+  return __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(had::fadd(had::fmul(S, 1.f / HD), eps)));
+}
+
+// 8 dims of a head vector times r, rounded to fp16, times their 8 weights, rounded to fp16 (in place, as floats)
+__device__ __forceinline__ void norm8(float (&a8)[8], float r, const f16* w8) {
+  float w[8];
+  unpack8h(*reinterpret_cast<const uint4*>(w8), w);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    // the fp32 product, THEN its conversion: left to the compiler, some of the products of an instantiation became
+    // v_fma_mixlo_f16 (the exact product rounded once, to fp16) and the others v_mul_f32 + v_cvt_f16_f32 (rounded twice)
+    // -- single elements of q moved by an fp16 ulp between the fused launch and the stand-alone one
+    float p = had::fmul(a8[i], r);
+    asm("" : "+v"(p));
+    a8[i] = (float)(f16)had::fmul((float)(f16)p, w[i]);
+  }
+}
+
+// rope8 of the NORMALISED head vector: the 8 dims at d0 and the 8 partner dims are normalised here, with the one r of
+// the head (the lanes of the group hold the whole head: all of them call this together)
+template <int HD>
+__device__ __forceinline__ void rope8_norm(const f16* vec, const f16* w, float eps, const float c8[8], const float s8[8],
+                                           int d0, float o[8]) {
+  float a[8], b[8];
+  unpack8h(*reinterpret_cast<const uint4*>(vec + d0), a);
+  const int dp = d0 < HD / 2 ? d0 + HD / 2 : d0 - HD / 2;
+  unpack8h(*reinterpret_cast<const uint4*>(vec + dp), b);
+  const float r = inv_rms<HD>(a, eps);
+  norm8(a, r, w + d0);
+  norm8(b, r, w + dp);
+  const float sgn = d0 < HD / 2 ? -1.f : 1.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) o[i] = (float)(f16)had::fadd(had::fmul(a[i], c8[i]), had::fmul(sgn * b[i], s8[i]));   // (rope8's expression)
+}
+
 // one key against q: this lane's 8 products, then the lane group's sum on DPP moves (had::sum16_xor: the additions of
 // `s += __shfl_xor(s, o)`, o = 1, 2, 4, 8) -- every lane of the group holds the score
 template <int LPK>

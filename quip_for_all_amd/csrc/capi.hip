@@ -875,6 +875,46 @@ int quip_sample_step_f16(const void* logits, int32_t rows, int32_t n, const floa
   return sample_rows_launch(logits, rows, n, temperature, top_k, top_p, seed, tok, pos, kept, (hipStream_t)stream);
 }
 
+int quip_qk_norm_rows_f16(void* q, void* k, const void* q_weight, const void* k_weight, int64_t rows, int32_t heads,
+                          int32_t kv_heads, int32_t head_dim, float eps, quip_stream_t stream) {
+  if (!q || !k || !q_weight || !k_weight) return QUIP_ERR_NULL_POINTER;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(q_weight) || !aligned16(k_weight)) return QUIP_ERR_MISALIGNED;
+  return qk_norm_rows_launch(q, k, q_weight, k_weight, rows, heads, kv_heads, head_dim, eps, (hipStream_t)stream);
+}
+
+int quip_rope_attn_decode_qknorm_f16(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                     const int64_t* pos, void* kcache, void* vcache, void* out, int32_t heads,
+                                     int32_t kv_heads, int32_t head_dim, int32_t max_len, float scale, int32_t window,
+                                     void* workspace, quip_stream_t stream, const void* q_weight, const void* k_weight,
+                                     float eps) {
+  if (!q || !k || !v || !cos || !sin || !pos || !kcache || !vcache || !out || !q_weight || !k_weight)
+    return QUIP_ERR_NULL_POINTER;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kcache) || !aligned16(vcache) ||
+      !aligned16(q_weight) || !aligned16(k_weight))
+    return QUIP_ERR_MISALIGNED;
+  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
+  if (window < 0) return QUIP_ERR_BAD_SHAPE;
+  return rope_attn_decode_qknorm_launch(q, k, v, cos, sin, pos, kcache, vcache, out, heads, kv_heads, head_dim, max_len,
+                                        scale, (hipStream_t)stream, workspace, window, q_weight, k_weight, eps);
+}
+
+int quip_rope_attn_decode_batched_qknorm_f16(const void* q, const void* k, const void* v, const float* cos,
+                                             const float* sin, const int64_t* pos, void* kcache, void* vcache, void* out,
+                                             int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                                             int32_t max_len, float scale, int32_t window, void* workspace,
+                                             quip_stream_t stream, const void* q_weight, const void* k_weight, float eps) {
+  if (!q || !k || !v || !cos || !sin || !pos || !kcache || !vcache || !out || !q_weight || !k_weight)
+    return QUIP_ERR_NULL_POINTER;
+  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kcache) || !aligned16(vcache) ||
+      !aligned16(q_weight) || !aligned16(k_weight) || (reinterpret_cast<uintptr_t>(pos) & 7))
+    return QUIP_ERR_MISALIGNED;
+  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
+  if (window < 0) return QUIP_ERR_BAD_SHAPE;
+  return rope_attn_decode_batched_qknorm_launch(q, k, v, cos, sin, pos, kcache, vcache, out, batch, heads, kv_heads,
+                                                head_dim, max_len, scale, (hipStream_t)stream, workspace, window, q_weight,
+                                                k_weight, eps);
+}
+
 int quip_rope_attn_decode_z_supported(int32_t heads, int32_t kv_heads, int32_t head_dim) {
   return rope_attn_decode_z_supported(heads, kv_heads, head_dim) ? 1 : 0;
 }

@@ -59,6 +59,7 @@ struct AttnArgs {
   static constexpr bool kPaged = false;
   static constexpr bool kFp8 = false;
   static constexpr bool kStart = false;
+  static constexpr bool kNorm = false;
 };
 
 // The batched launch on sequences that do not begin at cache row 0 (a left-padded batch): sequence b's tokens live in
@@ -83,6 +84,17 @@ struct PagedAttnArgsF8 : PagedAttnArgs {
   static constexpr bool kFp8 = true;
 };
 
+// Any of the argument types with a per-head RMSNorm of q and of the new k row in front of the rotation (Qwen3's q_norm /
+// k_norm; attn_query.hip.h: rope8_norm): the bits of qk_norm_rows_kernel (qk_norm.hip.h) on q and k followed by the launch
+// on Base.  An argument TYPE, not one more template parameter: the instantiations on the plain types keep their names.
+template <class Base>
+struct QkNormArgs : Base {
+  const f16* qw;          // [HD] weight of q's norm
+  const f16* kw;          // [HD] weight of k's norm
+  float eps;
+  static constexpr bool kNorm = true;
+};
+
 constexpr int kSplits = 8;  // workgroups per head for long contexts (grid.y)
 constexpr int kSplitFromPos = 256;    // shorter contexts: split 0 does everything, no workspace traffic
 
@@ -105,6 +117,7 @@ void rope_attn_decode_kernel(Args a, AttnZ zz) {
   constexpr bool PAGED = Args::kPaged;
   constexpr bool FP8 = Args::kFp8;
   constexpr bool START = Args::kStart;
+  constexpr bool NORM = Args::kNorm;
   constexpr int LPK = HD / 8;        // lanes per key
   constexpr int NG = 256 / LPK;      // key groups per workgroup
   constexpr int U = 4;               // keys in flight per group
@@ -112,6 +125,7 @@ void rope_attn_decode_kernel(Args a, AttnZ zz) {
   static_assert(!PAGED || SEQ, "the paged cache belongs to the batched launch");
   static_assert(!FP8 || PAGED, "the fp8 cache is a paged cache");
   static_assert(!START || (SEQ && !PAGED), "a first row per sequence belongs to the contiguous batched launch");
+  static_assert(!NORM || !ZIN, "the raw-GEMV-input variants have no q / k norm");
   __shared__ float s_m[NG], s_l[NG];
   __shared__ float s_acc[NG][HD + 4];
   const int tid = threadIdx.x, h = blockIdx.x;
@@ -252,8 +266,14 @@ void rope_attn_decode_kernel(Args a, AttnZ zz) {
     vh = s_qkv[2];
   }
   float q8[8], kn[8], vn[8];
-  attn::rope8<HD>(qh, c8, s8, d0, q8);
-  attn::rope8<HD>(kh, c8, s8, d0, kn);
+  if constexpr (NORM) {
+    // every lane group holds the whole head (and every split workgroup its own copy): normalised in registers
+    attn::rope8_norm<HD>(qh, a.qw, a.eps, c8, s8, d0, q8);
+    attn::rope8_norm<HD>(kh, a.kw, a.eps, c8, s8, d0, kn);
+  } else {
+    attn::rope8<HD>(qh, c8, s8, d0, q8);
+    attn::rope8<HD>(kh, c8, s8, d0, kn);
+  }
   const uint4 vraw = *reinterpret_cast<const uint4*>(vh + d0);
   attn::unpack8h(vraw, vn);
   // fp8: the row as stored -- its bytes, and in kn / vn the values those bytes mean
@@ -607,6 +627,8 @@ int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, 
 #include "ragged_attn.hip.h"
 // both batched launches on a paged cache: rows addressed through a block table
 #include "paged_attn.hip.h"
+// per-head RMSNorm of q / k (Qwen3): the stand-alone launch and the launchers of the kNorm instantiations
+#include "qk_norm.hip.h"
 // the scoring tail: log-sum-exp, target log-probability and arg-max of every row of a chunk's logits
 #include "nll_rows.hip.h"
 // the sampling tail: one token per row, every row with its own temperature, top-k, top-p and seed

@@ -227,6 +227,18 @@ int rope_attn_ragged_paged_f8_launch(const void* q, const void* k, const void* v
                                      int rows, int heads, int kv_heads, int head_dim, int max_len, int batch,
                                      int n_pages, int max_pages, const int32_t* seg_slot, const int32_t* seg_rows,
                                      int nseg, float scale, int window, hipStream_t stream, int k_exp, int v_exp);
+// qk_norm.hip.h (in decode_glue.hip): per-head RMSNorm of q (rows, heads * head_dim) and k (rows, kv_heads * head_dim) in
+// place, and the bs = 1 / contiguous batched decode launches with that norm on q and the new k row in registers
+int qk_norm_rows_launch(void* q, void* k, const void* qw, const void* kw, int64_t rows, int heads, int kv_heads,
+                        int head_dim, float eps, hipStream_t stream);
+int rope_attn_decode_qknorm_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                   const int64_t* pos, void* kcache, void* vcache, void* out, int heads, int kv_heads,
+                                   int head_dim, int max_len, float scale, hipStream_t stream, void* workspace, int window,
+                                   const void* qw, const void* kw, float eps);
+int rope_attn_decode_batched_qknorm_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
+                                           const int64_t* pos, void* kcache, void* vcache, void* out, int batch, int heads,
+                                           int kv_heads, int head_dim, int max_len, float scale, hipStream_t stream,
+                                           void* workspace, int window, const void* qw, const void* kw, float eps);
 // nll_rows.hip.h (in decode_glue.hip): per row of (rows, n) fp16 logits the log-sum-exp, the log-probability of target[row] and
 // the arg-max; lse / argmax may be null
 int nll_rows_launch(const void* logits, int rows, int n, const int64_t* target, float* logprob, float* lse,

@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 from . import chunk_attn as _chunk_attn  # noqa: F401  (defines quip_lib::rope_attn_chunk)
+from . import qk_norm as _qk_norm  # noqa: F401  (defines quip_lib::qk_norm_rows and the two _qknorm decode launches)
 from . import register_lib as _R
 from . import score as _score  # (defines quip_lib::nll_rows)
 from . import token_tail as _token_tail  # noqa: F401  (defines quip_lib::block_engine_token)
@@ -45,10 +46,16 @@ class LlamaShape:
     vocab: int = 32000
     rms_eps: float = 1e-5
     rope_theta: float = 10000.0
+    head_dim: int = None      # unset: hidden // heads; Qwen3 sets its own (q and o are heads * head_dim wide, not hidden)
+
+    def __post_init__(self):
+        if self.head_dim is None:
+            self.head_dim = self.hidden // self.heads
 
     @property
-    def head_dim(self):
-        return self.hidden // self.heads
+    def q_width(self):
+        """width of q_proj's output, of the attention output and of o_proj's input"""
+        return self.heads * self.head_dim
 
 
 LLAMA2_7B = LlamaShape()
@@ -247,7 +254,7 @@ def _extend_chunks(dec, what, tokens, chunk, kv, pos, on_chunk):
         n, kc, vc = q.shape[0], kcache[i], vcache[i]
         return torch.ops.quip_lib.rope_attn_chunk(
             q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim), v.view(n, s.kv_heads, s.head_dim),
-            dec.cos[:kc.shape[1]], dec.sin[:kc.shape[1]], pos, kc, vc, dec.window).reshape(n, s.hidden)
+            dec.cos[:kc.shape[1]], dec.sin[:kc.shape[1]], pos, kc, vc, dec.window).reshape(n, s.q_width)
     for c0 in range(0, P, chunk):
         n = min(chunk, P - c0)
         h = dec.embed[tokens[c0:c0 + n]]                           # (n, hidden)
@@ -268,7 +275,7 @@ class LlamaDecoder:
     E8P12: 17.1 GB of codes resident instead of 34.2 GB."""
 
     def __init__(self, shape: LlamaShape = LLAMA2_7B, codebook="E8P12", max_len=256, device="cuda", seed=0,
-                 device_init=False, window=0, single_copy=None, **cb_kwargs):
+                 device_init=False, window=0, single_copy=None, qk_norm=False, **cb_kwargs):
         if single_copy is None:
             single_copy = bool(int(os.environ.get("QUIP_SINGLE_COPY", "0")))
         self.s, self.dev, self.max_len = shape, torch.device(device), max_len
@@ -290,14 +297,20 @@ class LlamaDecoder:
         for _ in range(s.layers):
             self.layers.append(dict(
                 ln1=vec(s.hidden), ln2=vec(s.hidden),
-                q=ql(s.hidden, s.hidden), k=ql(s.hidden, kv), v=ql(s.hidden, kv), o=ql(s.hidden, s.hidden),
+                q=ql(s.hidden, s.q_width), k=ql(s.hidden, kv), v=ql(s.hidden, kv), o=ql(s.q_width, s.hidden),
                 gate=ql(s.hidden, s.ffn), up=ql(s.hidden, s.ffn), down=ql(s.ffn, s.hidden)))
+            if qk_norm:
+                # per-head RMSNorm of q and k in front of the rotation (Qwen3); drawn behind the block's other parameters,
+                # and only then: without the flag the random stream is untouched
+                for name in ("q_norm", "k_norm"):
+                    self.layers[-1][name] = (1.0 + 0.1 * torch.randn(s.head_dim, generator=g)).to(torch.float16).to(self.dev)
+        self.qk_eps = float(s.rms_eps)
         # (sliding-window attention, HF config.sliding_window: a window that covers the whole cache is full attention)
         self._init_runtime(window=int(window) if 0 < int(window) < max_len else 0, single_copy=single_copy)
 
     # architectures whose decoder block is Llama's: RMSNorm (weight only) -> q / k / v (+ bias) -> rotary -> softmax attention
     # -> o -> residual -> RMSNorm -> SiLU-gated MLP -> residual, embeddings and residuals unscaled
-    LLAMA_LIKE = ("llama", "mistral", "qwen2")
+    LLAMA_LIKE = ("llama", "mistral", "qwen2", "qwen3")
 
     @classmethod
     def from_hf(cls, model, max_len=256, device=None, assume_llama_like=False, kv_cache=None):
@@ -308,7 +321,8 @@ class LlamaDecoder:
         allocating one (hf_fast.py binds the tensors of a transformers StaticCache this way; bind_kv() swaps them later).
         Architectures outside LLAMA_LIKE are refused (Gemma scales embeddings and norms, StableLM uses LayerNorm, ...:
         the module names match, the arithmetic does not) unless `assume_llama_like` vouches for them; such checkpoints run
-        through `load_quantized_model` + the stock HF `generate`."""
+        through `load_quantized_model` + the stock HF `generate`.  `config.head_dim` is free (Qwen3: heads * head_dim need not be
+        hidden_size), and a `self_attn.q_norm` / `k_norm` pair that is an RMSNorm over head_dim is taken (_hf_qk_norm)."""
         cfg = model.config
         dev = torch.device(device) if device is not None else next(model.parameters()).device
         self = cls.__new__(cls)
@@ -332,9 +346,13 @@ class LlamaDecoder:
         if rope is None:
             rope = rp.get("rope_theta", 10000.0) if isinstance(rp, dict) else 10000.0
         # what this decoder does not implement must not pass silently (the HF forward of the same model would differ)
-        head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // heads
-        if head_dim * heads != cfg.hidden_size:
-            raise NotImplementedError(f"head_dim {head_dim} x {heads} heads != hidden_size {cfg.hidden_size}")
+        head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // heads      # (free: Qwen3-0.6B has 1024 / 16 heads of 128)
+        # q / k norms over head_dim (Qwen3) are taken, on any accepted architecture; any other norm there is refused
+        qk_norms = [cls._hf_qk_norm(blk.self_attn, head_dim) for blk in model.model.layers]
+        if any(n is None for n in qk_norms) and not all(n is None for n in qk_norms):
+            raise NotImplementedError("q_norm / k_norm on some blocks only")
+        if qk_norms[0] is not None and len({n[2] for n in qk_norms}) != 1:
+            raise NotImplementedError("q_norm / k_norm with different eps per block")
         prf = rp.get("partial_rotary_factor", None) if isinstance(rp, dict) else None
         prf = getattr(cfg, "partial_rotary_factor", prf)
         if prf not in (None, 1, 1.0):
@@ -372,14 +390,15 @@ class LlamaDecoder:
             inv_freq, att_scale = inv, float(getattr(rot, "attention_scaling", 1.0) or 1.0)
         self.s = LlamaShape(hidden=cfg.hidden_size, ffn=cfg.intermediate_size, layers=cfg.num_hidden_layers,
                             heads=heads, kv_heads=getattr(cfg, "num_key_value_heads", heads) or heads,
-                            vocab=cfg.vocab_size, rms_eps=cfg.rms_norm_eps, rope_theta=float(rope))
+                            vocab=cfg.vocab_size, rms_eps=cfg.rms_norm_eps, rope_theta=float(rope), head_dim=int(head_dim))
         self.dev, self.max_len = dev, max_len
         h16 = lambda t: t.detach().to(device=dev, dtype=torch.float16).contiguous()  # noqa: E731
         self.embed = h16(model.model.embed_tokens.weight)
         self.lm_head = h16(model.lm_head.weight)
         self.final_norm = h16(model.model.norm.weight)
         self.layers = []
-        for blk in model.model.layers:
+        self.qk_eps = float(cfg.rms_norm_eps)
+        for blk, norms in zip(model.model.layers, qk_norms):
             a, m = blk.self_attn, blk.mlp
             mods = dict(q=a.q_proj, k=a.k_proj, v=a.v_proj, o=a.o_proj, gate=m.gate_proj, up=m.up_proj, down=m.down_proj)
             for name, mod in mods.items():
@@ -388,8 +407,44 @@ class LlamaDecoder:
                 mod.to(dev).eval()
             self.layers.append(dict(ln1=h16(blk.input_layernorm.weight), ln2=h16(blk.post_attention_layernorm.weight),
                                     **mods))
+            if norms is not None:
+                self.layers[-1]["q_norm"], self.layers[-1]["k_norm"] = h16(norms[0].weight), h16(norms[1].weight)
+                self.qk_eps = norms[2]
         self._init_runtime(window=window, kv_cache=kv_cache, inv_freq=inv_freq, att_scale=att_scale, single_copy=False)
         return self
+
+    @staticmethod
+    def _hf_qk_norm(attn, head_dim):
+        """(q_norm, k_norm, eps) of an attention module that normalises every head of q and k over head_dim in front of the
+        rotation (Qwen3), None if it has no such pair.  As for input_layernorm the arithmetic is checked on numbers -- the
+        formula of qk_norm.py with the module's own eps, on an input of ordinary size and on one small enough for eps to
+        matter -- not on a class name; a weight of any other length (OLMo2 normalises the whole width) is refused."""
+        qn, kn = getattr(attn, "q_norm", None), getattr(attn, "k_norm", None)
+        if isinstance(qn, torch.nn.Identity) and isinstance(kn, torch.nn.Identity):
+            qn = kn = None
+        if qn is None and kn is None:
+            return None
+        if qn is None or kn is None:
+            raise NotImplementedError("q_norm without k_norm (or the reverse)")
+        eps = None
+        for n in (qn, kn):
+            w = getattr(n, "weight", None)
+            if w is None or w.dim() != 1 or w.numel() != head_dim:
+                raise NotImplementedError(f"{type(n).__name__} with a weight of shape "
+                                          f"{None if w is None else tuple(w.shape)}: only a norm over head_dim = {head_dim}")
+            e = getattr(n, "variance_epsilon", None)
+            e = getattr(n, "eps", None) if e is None else e
+            if e is None or getattr(n, "bias", None) is not None or (eps is not None and float(e) != eps):
+                raise NotImplementedError(f"{type(n).__name__}: no eps attribute, a bias, or two different eps")
+            eps = float(e)
+            with torch.no_grad():
+                for amp in (1.0, 1e-3):
+                    xt = amp * torch.linspace(-2.0, 3.0, head_dim, dtype=torch.float32, device=w.device)[None]
+                    xt = xt.to(w.dtype).float()
+                    want = xt / torch.sqrt((xt * xt).mean() + eps) * w.float()
+                    if not torch.allclose(n(xt.to(w.dtype)).float(), want, rtol=2e-2, atol=2e-2):
+                        raise NotImplementedError(f"{type(n).__name__} is not RMSNorm(x) * weight over head_dim")
+        return qn, kn, eps
 
     def _init_runtime(self, window=None, kv_cache=None, inv_freq=None, att_scale=1.0, single_copy=False):
         """Everything but the model (s, dev, max_len, embed, lm_head, final_norm, layers: the constructors' part).  Receives
@@ -426,6 +481,14 @@ class LlamaDecoder:
         self._prefill_graphs, self._extend_graphs = {}, {}      # length -> (graph, logits, static tokens)
         self._rm_scratch = {}               # projection name -> row-major scratch (_row_major)
         self.fused_attention = s.head_dim in (64, 128)
+        # per-head RMSNorm of q / k in front of the rotation (Qwen3): the layer dicts carry q_norm / k_norm.  qk_fused: the bs = 1
+        # and the contiguous batched decode step normalise inside the attention launch (quip_lib::rope_attn_decode_qknorm /
+        # _batched_qknorm); off (QUIP_QK_NORM_FUSED=0, or the attribute with `graph = None`): quip_lib::qk_norm_rows in front of
+        # the plain launch, the same bits -- the A/B of tools/qk_norm_bench.py.  Every other route takes the launch in front.
+        self.qk_norm = "q_norm" in self.layers[0]
+        self.qk_fused = os.environ.get("QUIP_QK_NORM_FUSED", "1") != "0"
+        if self.qk_norm and not self.fused_attention:
+            raise NotImplementedError(f"q_norm / k_norm with head_dim {s.head_dim}: the norm launches serve 64 and 128")
         self.attn_ws = _R.rope_attn_workspace(s.heads, s.head_dim, self.dev) if self.fused_attention else None
         L0 = self.layers[0]
         qkv0, gu0 = [L0["q"], L0["k"], L0["v"]], [L0["gate"], L0["up"]]
@@ -457,11 +520,13 @@ class LlamaDecoder:
         d4 = all(getattr(m.codebook, "id", None) in ("D4", "E8P12RVQ4B", "HI", "E8P12RVQ3B") for m in L0.values() if isinstance(m, QuantLinear))
         gqa_shape = self.fused_prologue and self.chain and s.kv_heads != s.heads and s.hidden in (8192, 4096)   # (csrc/decode_block_gqa.hip; decode_block_g8.hip)
         if ((self.ffn_eng or gqa_shape or (d4 and self.fused_prologue and self.chain and os.environ.get("QUIP_FFN_ENGINE", "1") != "0"))
-                and os.environ.get("QUIP_BLOCK_ENGINE", "1") != "0" and not self.window):   # (its attention walks [0, pos])
+                and os.environ.get("QUIP_BLOCK_ENGINE", "1") != "0" and not self.window     # (its attention walks [0, pos])
+                and not self.qk_norm):              # (the persistent launches have no q / k norm: not built)
             self._init_block_engine()
         # q / k / v output transforms inside the attention launch (multi-head attention with a power-of-two hidden <= 4096,
         # or 64 / 32 heads on 8 KV heads -- Llama-2-70B, Llama-3, Mistral-7B; plain SV output side)
         self.attn_z = (self.fused_prologue and self.fused_attention and os.environ.get("QUIP_ATTN_Z", "1") != "0"
+                       and not self.qk_norm                 # (the _z launch has no q / k norm: not built)
                        and _R.rope_attn_decode_z_supported(s.heads, s.kv_heads, s.head_dim)
                        and all(l.K_right == 1 and not l.per_channel and l.bias is None and l.SV is not None
                                and l.q_out_features == l.out_features == (s.heads if i == 0 else s.kv_heads) * s.head_dim
@@ -484,7 +549,7 @@ class LlamaDecoder:
             # shape 2: Llama-3-8B / Mistral-7B -- the shape-0 launch compiled for 32 / 8 heads and n_ffn = 14336 = 56 x 256
             g8 = (not gqa and cbid == "E8P12" and os.environ.get("QUIP_BLOCK_ENGINE_G8", "1") != "0" and not self.window
                   and _R.block_engine_g8_supported(*dims))
-            ok = ((gqa or g8 or _R.block_engine_supported(*dims))
+            ok = ((gqa or g8 or _R.block_engine_supported(*dims)) and s.q_width == s.hidden and not self.qk_norm
                   and len(self.layers) <= 146)      # (the launch's hand-off counter: 7 per block in 10 bits)
             kvw = s.kv_heads * s.head_dim
             for L in self.layers:
@@ -653,6 +718,15 @@ class LlamaDecoder:
 
     def _attention(self, i, q, k, v, cos, sin, mask):
         s = self.s
+        if self.qk_norm and self.qk_fused:
+            # the same launch with q and the new k row normalised in registers in front of the rotation
+            L = self.layers[i]
+            return torch.ops.quip_lib.rope_attn_decode_qknorm(
+                q.view(s.heads, s.head_dim), k.view(s.kv_heads, s.head_dim), v.view(s.kv_heads, s.head_dim),
+                self.cos, self.sin, self.pos, self.kcache[i], self.vcache[i], self.attn_ws, self.window,
+                L["q_norm"], L["k_norm"], self.qk_eps)
+        if self.qk_norm:
+            q, k = self._qk_norm_rows(self.layers[i], q, k)
         if self.fused_attention:
             # rope + cache append + attention over [0, pos]: one launch
             return torch.ops.quip_lib.rope_attn_decode(
@@ -665,14 +739,26 @@ class LlamaDecoder:
         return F.scaled_dot_product_attention(q, self.kcache[i][None], self.vcache[i][None], attn_mask=mask,
                                               enable_gqa=(s.kv_heads != s.heads))
 
-    def _block(self, L, h, attend):
-        """one decoder block on the rows of `h`, stage by stage; `attend(q, k, v)` -> the attention output, (rows, hidden):
-        the decode step, the prompt passes and BatchDecoder.step differ in nothing else"""
+    def _qk_norm_rows(self, L, q, k):
+        """q (rows, heads * hd) and k (rows, kv_heads * hd) with every head normalised (quip_lib::qk_norm_rows: in place, one
+        launch for both)"""
+        s = self.s
+        q, k = q.reshape(-1, s.q_width).contiguous(), k.reshape(-1, s.kv_heads * s.head_dim).contiguous()
+        torch.ops.quip_lib.qk_norm_rows(q, k, L["q_norm"], L["k_norm"], s.head_dim, self.qk_eps)
+        return q, k
+
+    def _block(self, L, h, attend, norm_in_attend=False):
+        """one decoder block on the rows of `h`, stage by stage; `attend(q, k, v)` -> the attention output, (rows, heads *
+        head_dim): the decode step, the prompt passes and BatchDecoder.step differ in nothing else.  A model with q / k norms
+        gets them here, behind the projections (quip_lib::qk_norm_rows), unless `norm_in_attend`: that `attend` takes the raw
+        q and k and normalises them itself (the decode launches that fuse the norm)"""
         s = self.s
         with self._row_major(L):
             # q / k / v (and gate / up below): one launch per stage for the whole group; RMSNorm rides on
             # the input-side Hadamard launch
             q, k, v = forward_group([L["q"], L["k"], L["v"]], h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
+            if self.qk_norm and not norm_in_attend:
+                q, k = self._qk_norm_rows(L, q, k)
             # residual adds ride on the output-side Hadamard launch, SiLU(gate)*up on down's input side
             h = L["o"].forward_fused(attend(q, k, v), residual=h)
             g, u = forward_group([L["gate"], L["up"]], h, rms_weight=L["ln2"], rms_eps=s.rms_eps)
@@ -711,9 +797,9 @@ class LlamaDecoder:
             return self._step_fused(h, cos, sin, mask)
 
         def attend(i, q, k, v):
-            return self._attention(i, q, k, v, cos, sin, mask).reshape(1, s.hidden)
+            return self._attention(i, q, k, v, cos, sin, mask).reshape(1, s.q_width)
         for i, L in enumerate(self.layers):
-            h = self._block(L, h, partial(attend, i))
+            h = self._block(L, h, partial(attend, i), norm_in_attend=True)     # (_attention: fused, or the launch in front)
         return self._head(h)
 
     def _token_tail_on(self):
@@ -751,9 +837,9 @@ class LlamaDecoder:
                     q, k, v = out_transform_group(qkv, zs)
                     a = self._attention(i, q, k, v, cos, sin, mask)
                 if self.o_fused:
-                    _, (zo,) = gemv_fused([L["o"]], x=a.reshape(1, s.hidden))
+                    _, (zo,) = gemv_fused([L["o"]], x=a.reshape(1, s.q_width))
                 else:
-                    zo = gemv_unfused(L["o"], a.reshape(1, s.hidden))
+                    zo = gemv_unfused(L["o"], a.reshape(1, s.q_width))
                 if self.ffn_eng:
                     h, planes = chain_planes([L["gate"], L["up"]], L["o"], zo, residual=h, rms_weight=L["ln2"],
                                              rms_eps=s.rms_eps)
@@ -877,7 +963,7 @@ class LlamaDecoder:
             else:
                 a = F.scaled_dot_product_attention(q[None], k[None], v[None], is_causal=True,
                                                    enable_gqa=(s.kv_heads != s.heads))[0]     # (heads, P, hd)
-            return a.transpose(0, 1).reshape(P, s.hidden)
+            return a.transpose(0, 1).reshape(P, s.q_width)
         for i, L in enumerate(self.layers):
             h = self._block(L, h, partial(attend, i))
         (self.pos if pos is None else pos).fill_(P)

@@ -163,8 +163,16 @@ class _FastDecode:
             rp = getattr(cfg, "rope_parameters", None) or getattr(cfg, "rope_scaling", None) or {}
             if isinstance(rp, dict) and rp.get("rope_type", "default") in ("dynamic", "longrope"):
                 raise NotImplementedError(f"rope_type {rp.get('rope_type')!r}")
+            heads = cfg.num_attention_heads
+            head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // heads
             for blk in self.model.model.layers:
                 a, m = blk.self_attn, blk.mlp
+                # q / k norms (Qwen3): over head_dim, and then on one of the two head sizes the norm launches serve
+                for n in (getattr(a, "q_norm", None), getattr(a, "k_norm", None)):
+                    w = getattr(n, "weight", None)
+                    if n is not None and not isinstance(n, torch.nn.Identity) and (
+                            w is None or w.dim() != 1 or w.numel() != head_dim or head_dim not in (64, 128)):
+                        raise NotImplementedError(f"{type(n).__name__}: not a norm over head_dim 64 or 128")
                 for mod in (a.q_proj, a.k_proj, a.v_proj, a.o_proj, m.gate_proj, m.up_proj, m.down_proj):
                     if not isinstance(mod, QuantLinear):
                         raise TypeError(f"{type(mod).__name__} where a QuantLinear is expected")

@@ -197,6 +197,9 @@ class PagedBatchDecoder(BatchDecoder):
         self.pool = PagePool(n, self.batch, self.max_pages)
         self.live = [True] * self.batch
 
+    def _fuses_norm(self):
+        return False                 # (the paged launches have no q / k norm: LlamaDecoder._block normalises in front)
+
     def _attend_step(self, i, q, k, v):
         if self.fp8:
             return torch.ops.quip_lib.rope_attn_decode_paged_f8(q, k, v, self.cos, self.sin, self.pos, self.table,

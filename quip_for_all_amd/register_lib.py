@@ -783,10 +783,9 @@ def rope_attn_workspace(heads, head_dim, device):
     return torch.zeros(capi.lib().quip_rope_attn_workspace_bytes(heads, head_dim), dtype=torch.uint8, device=device)
 
 
-def _rope_attn_decode_cuda(q, k, v, cos, sin, pos, kcache, vcache, workspace=None, window=0):
-    """q (heads, hd), k / v (kv_heads, hd) fp16; cos / sin (max_len, hd) fp32; pos int64 device scalar;
-    kcache / vcache (kv_heads, max_len, hd) fp16 (row pos is written) -> (heads, hd) fp16"""
-    import math
+def _check_rope_attn_decode(q, k, v, cos, sin, pos, kcache, vcache, workspace):
+    """the operand checks of the bs = 1 decode launch (rope_attn_decode, rope_attn_decode_qknorm) -> (heads, kv_heads, hd,
+    max_len)"""
     for t in (q, k, v, kcache, vcache):
         _need(t.dtype == torch.float16 and t.is_contiguous() and t.is_cuda, "rope_attn_decode: fp16 contiguous CUDA tensors")
     _need(cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous(),
@@ -797,11 +796,19 @@ def _rope_attn_decode_cuda(q, k, v, cos, sin, pos, kcache, vcache, workspace=Non
     _need(tuple(k.shape) == (kvh, hd) and tuple(v.shape) == (kvh, hd) and tuple(vcache.shape) == tuple(kcache.shape)
           and kcache.shape[2] == hd and tuple(cos.shape) == (max_len, hd) and tuple(sin.shape) == (max_len, hd),
           "rope_attn_decode: shape mismatch")
-    out = torch.empty_like(q)
     if workspace is not None:
         _need(workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == q.device
               and workspace.numel() >= capi.lib().quip_rope_attn_workspace_bytes(heads, hd),
               "workspace: use rope_attn_workspace(heads, head_dim, device)")
+    return heads, kvh, hd, max_len
+
+
+def _rope_attn_decode_cuda(q, k, v, cos, sin, pos, kcache, vcache, workspace=None, window=0):
+    """q (heads, hd), k / v (kv_heads, hd) fp16; cos / sin (max_len, hd) fp32; pos int64 device scalar;
+    kcache / vcache (kv_heads, max_len, hd) fp16 (row pos is written) -> (heads, hd) fp16"""
+    import math
+    heads, kvh, hd, max_len = _check_rope_attn_decode(q, k, v, cos, sin, pos, kcache, vcache, workspace)
+    out = torch.empty_like(q)
     with torch.cuda.device(q.device):
         capi.check(capi.lib().quip_rope_attn_decode_window_f16(
             q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
