@@ -170,11 +170,14 @@ constexpr int QKB = G8 ? 384 : 768;                             // 16-row blocks
 constexpr int kRowU4 = HID / 64, kRowU4D = NFFN / 64;
 constexpr int NSLOT = 9;                             // X0-2: q k v, then gate's row blocks | X3-5: o, then up's | X6-8: down
 
-// workspace: ctl | z_q z_k z_v | a | z_o | z_d (2048 granules each) | inbox [11 row owners][256 columns][2][4] | rows [256][48] |
+// workspace: ctl | z_q z_k z_v | a | z_o | z_d (2048 granules each) | inbox [NRO row owners][RPO rows][2 matrices][256 columns] | rows [256][48] |
 // attention partials [32 heads][8][132]
 constexpr size_t kWsCtl = 0, kWsZ = 64, kWsVec = 2048 * 8;
-// row-owner workgroups of the MLP edge: RPO rows k' each, a PAIR of waves per row (gate half, up half) on waves 0..2 RPO-1 (RPO = 2: four waves = one per SIMD, 22 owners; with RPO = 4 the eight waves shared SIMDs: 1390 -> 1354 us per 32-block launch, same box: the
-// row work is DPP-serial VALU code, two such waves on a SIMD take twice as long)
+// row-owner workgroups of the MLP edge: RPO rows k' each, ONE wave per row (gate half and up half side by side in its registers) on
+// waves 0..RPO-1 (RPO = 2: 22 owners, two waves on two SIMDs.  With a PAIR of waves per row and RPO = 4 the eight waves shared SIMDs:
+// 1390 -> 1354 us per 32-block launch for RPO = 2, same box: the row work is DPP-serial VALU code, two such waves on a SIMD take
+// twice as long).  The inbox keeps a row of a matrix contiguous -- [owner][row][matrix][column] granules -- so that the row's wave
+// reads its lanes' four columns as they lie
 constexpr int RPO = 2, NRO = (FK + RPO - 1) / RPO;
 constexpr size_t kWsInbox = kWsZ + 6 * kWsVec, kWsRows = kWsInbox + (size_t)NRO * FL * 2 * RPO * 8;
 // long contexts: the eight workgroups of a head each take every eighth position; their partial softmax states (128 sums +
@@ -222,7 +225,7 @@ struct BLds {
   // In time: the transforms' exchange buffers (16.5 KB per transform from the base: 1, 2 or -- attention -- 3) -> digit planes
   // of the consumers (12 / 24 KB from the base, written after the transforms' last reads) | attention partials; for the MLP:
   // planes [0, 24 K) + the K x K factor image [24 K, 36 K) + the row owners' vectors [36 K, 48 K) (both stored while the gate / up
-  // edge's exchange buffer is alive: they lie behind it) -> row owners: inbox rows [0, 8 K), rows on the way out [8 K, 16 K) ->
+  // edge's exchange buffer is alive: they lie behind it) -> row owners: rows on the way out [8 K, 9 K) (the inbox rows go from memory into registers) ->
   // (the gathered rows never touch LDS: they are the K-mix's A operands) -> down's planes [0, 35.1 K), over the factor image once
   // every wave's K-mix has read it.
   static constexpr int kArea = kCs + 2 * HD * 4;
@@ -230,11 +233,11 @@ struct BLds {
   static constexpr int kAreaBytes = (160 * 1024 - kArea) & ~15;
   static constexpr int kBuf0 = kArea;
   static constexpr int kHadElems = 2 * KKP + KP16 * KPS;
-  static constexpr int kStage = kArea + 8 * 1024;            // MLP row owners: their four rows, transposed, on the way out (4 KB)
+  static constexpr int kStage = kArea + 8 * 1024;            // MLP row owners: their RPO rows as fp16 [column][RPO], on the way out (1 KB)
   // fp16 image of the three K x K factors (12 KB; G8: 20.3 KB), behind the planes of gate / up (G8: at 32 K)
   static constexpr int kHad = kArea + (G8 ? 32 * 1024 : 2 * 3 * PSH);
   // MLP row owners: SV_gate / SV_up / SU_down of their rows (3 KB): behind the factor image; G8: at 17 K (free while they are alive:
-  // the gate / up edge's exchange buffer ends at 16.5 K, the planes of the ONE consumer at 12.5 K, the owners' rows and staging at 12 K)
+  // the gate / up edge's exchange buffer ends at 16.5 K, the planes of the ONE consumer at 12.5 K, the owners' staging at 9 K)
   static constexpr int kStash = G8 ? kArea + 17 * 1024 : kHad + 12 * 1024;
   // down's planes.  Byte tables: every 256 digits padded by 16 bytes (the K-mix writes a dword per lane, 256 digits apart).  Nibble
   // mode: a half plane = (KPDV / 256) blocks of 128 + 16 bytes (the same writers: 144-byte steps land on 16 different banks; without
@@ -1607,36 +1610,44 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         const int m = G8 ? (tid >= FK ? 1 : 0) : tid / 48, k = G8 ? tid - FK * m : tid - 48 * m;
         const int* s3 = accs + (B::AGU + tid) * 4;
         const float f = __builtin_fmaf((float)s3[0], 65536.f, __builtin_fmaf((float)s3[1], 256.f, (float)s3[2]));
-        zcol[m * B::KP16 + k] = (float)(f16)(f * unscale_of(shs[0], kUnsc));      // [column 2 (w & 127) + m][k]: one matrix, one exponent
+        // [column 2 (w & 127) + m][k & 3][k >> 2]: one matrix, one exponent.  (A thread of the K-mix below multiplies the k of ONE
+        // residue mod 4, in ascending order: they lie side by side and are read as 16-byte pieces, not one dword per product)
+        zcol[m * B::KP16 + (k & 3) * (B::KP16 / 4) + (k >> 2)] = (float)(f16)(f * unscale_of(shs[0], kUnsc));
       }
       had::wg_barrier<true>();
       zero_acc(B::AGU, 16 * NGU);
       ++hop;                                           // hand-off: column -> row owners
       const uint32_t tag1 = ebase | hop;
       {
+        // (the two columns of one row k' four lanes apart: the m = 0 quad publishes both)
         const int o = tid >> 2, part = tid & 3;
-        const int m = o >> 6, kq = o & 63;
+        const int m = o & 1, kq = o >> 1;
         const bool live = kq < FK;
         // (m: which of this workgroup's two columns; the factor is its matrix's: mgu)
         const f16* hs = reinterpret_cast<const f16*>(smem + B::kHad) + mgu * B::KKP + (live ? kq : 0) * FK;
-        const float* zz = zcol + m * B::KP16;
+        constexpr int K4 = (FK + 3) / 4, KQ = B::KP16 / 4;
+        static_assert(B::kZcol % 16 == 0 && KQ % 4 == 0 && K4 <= KQ, "a residue's z values: whole 16-byte pieces");
+        float zz[KQ];
+#pragma unroll
+        for (int i = 0; i < (K4 + 3) / 4; ++i) {
+          const float4 z4 = *reinterpret_cast<const float4*>(zcol + m * B::KP16 + part * KQ + 4 * i);
+          zz[4 * i] = z4.x; zz[4 * i + 1] = z4.y; zz[4 * i + 2] = z4.z; zz[4 * i + 3] = z4.w;
+        }
         float t = 0.f;
 #pragma unroll
-        for (int k4 = 0; k4 < (FK + 3) / 4; ++k4) {
+        for (int k4 = 0; k4 < K4; ++k4) {
           const int k = 4 * k4 + part;
-          if (k < FK) t = __builtin_fmaf((float)hs[k], zz[k], t);
+          if (k < FK) t = __builtin_fmaf((float)hs[k], zz[k4], t);
         }
         t += __shfl_xor(t, 1, 64);
         t += __shfl_xor(t, 2, 64);
         t *= kMixScale;                                  // (G8: the 1 / sqrt 8 of H_8 inside the 56 x 56 factor; else 1)
-        // row k' goes to row owner k' / RPO.  This workgroup's 2 RPO granules per owner are a cache line of its own, written
-        // as 16-byte stores of the rows (k', k' + 1), k' even (the odd row's value comes over from the next quad)
+        // row k' goes to row owner k' / RPO, into the row's own line of its matrix: inbox[owner][row][matrix][column], so that
+        // an owner lane reads four consecutive columns of one row as 32 consecutive bytes.  This workgroup's two columns of a
+        // row are ONE 16-byte store (the second column's value comes over from the next quad)
         const float tn = __shfl_down(t, 4, 64);
-        if (live && part == 0 && (kq & 1) == 0) {
-          uint64_t* dst = inbox + (((size_t)(kq / RPO) * FL + (2 * (w & 127) + m)) * (2 * RPO) + mgu * RPO + (kq % RPO));
-          if (kq + 1 < FK) esync::st_granule2(dst, as_u32(t), as_u32(tn), tag1);
-          else esync::st_granule(dst, as_u32(t), tag1);
-        }
+        if (live && part == 0 && m == 0)
+          esync::st_granule2(inbox + (((size_t)kq * 2 + mgu) * FL + 2 * (w & 127)), as_u32(t), as_u32(tn), tag1);
       }
       ++hop;                                           // hand-off: rows -> everybody
       const uint32_t tag2 = ebase | hop;
@@ -1656,86 +1667,75 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       }
 #endif
       if (w < NRO) {
-        // the owner's inbox = 256 columns x (2 matrices x RPO rows) granules, swept by all 512 threads (coalesced 16-byte
-        // pieces); piece p = column p / RPO, matrix (p / (RPO / 2)) & 1, rows 2 (p % (RPO / 2)) and + 1
-        {
-          constexpr int NPC = FL * RPO / kThreads;       // pieces per thread
-          u32x4_t pc[NPC];
-          uint32_t spins = 0;
-          for (;;) {
-#pragma unroll
-            for (int jj = 0; jj < NPC; ++jj) esync::ld16(pc[jj], inbox + ((size_t)w * FL * 2 * RPO + 2 * (tid + kThreads * jj)));
-            esync::drain();
-            bool ok = true;
-#pragma unroll
-            for (int jj = 0; jj < NPC; ++jj) {
-              esync::own(pc[jj]);
-              const int kl = 2 * ((tid + kThreads * jj) % (RPO / 2));
-              ok = ok && (RPO * w + kl >= FK || pc[jj].y == tag1) && (RPO * w + kl + 1 >= FK || pc[jj].w == tag1);
-            }
-            if (esync::spin_step(ok, spins, ctl + 1, 0x1000u + (uint32_t)w)) break;
-          }
-          if (dbg_on && tid == 0) a.dbg[w * 32 + 25] = __builtin_amdgcn_s_memtime();
-          uint32_t* rowbuf = reinterpret_cast<uint32_t*>(smem + B::kArea);        // [RPO rows][2 matrices][256 columns]
-#pragma unroll
-          for (int jj = 0; jj < NPC; ++jj) {
-            const int pi = tid + kThreads * jj, col = pi / RPO, mm = (pi / (RPO / 2)) & 1, kl = 2 * (pi % (RPO / 2));
-            rowbuf[(kl * 2 + mm) * FL + col] = pc[jj].x;
-            rowbuf[((kl + 1) * 2 + mm) * FL + col] = pc[jj].z;
-          }
-          had::wg_barrier<true>();
-          MSTAMP(4);
-        }
-        // a row on a PAIR of waves: wave rw its gate half, wave 4 + rw its up half, 4 consecutive elements per lane (index bits
-        // 0..1 in registers, 2..7 = lane bits 0..5; ascending bit order: the same additions as fht16_lanes, fht_wg512.hip.h);
-        // the up half crosses to the gate wave through LDS
-        const int rw = wave & (RPO - 1), mh = (wave / RPO) & 1;
-        const bool act = wave < 2 * RPO;                 // (RPO = 2: waves 0..3, one per SIMD)
+        // the owner's inbox = [RPO rows][2 matrices][256 columns] granules.  ONE wave per row (waves 0 .. RPO - 1, one per SIMD)
+        // carries its gate half AND its up half, 4 consecutive columns of each per lane (index bits 0..1 in registers, 2..7 = lane
+        // bits 0..5; ascending bit order: the same additions as fht16_lanes, fht_wg512.hip.h): a lane's columns of a matrix are 32
+        // consecutive bytes of the inbox, requested as two 16-byte pieces on the wave's drained queue and checked by the lane
+        // itself, so the rows go from the hand-off straight into the transform's registers -- no sweep by the workgroup, no
+        // transposition through LDS and no barrier in front of the transforms, and the two halves meet in registers.  The row
+        // that does not exist (row 43 of owner 21 at FK = 43) checks no tag and holds zeros.
+        const int rw = wave & (RPO - 1);
+        const bool act = wave < RPO;
         const bool row_ok = RPO * w + rw < FK;
-        auto fht256 = [&](float (&x)[4]) {
+        // 256 points per group of four registers (N / 4 groups side by side: eight independent values per stage instead of four
+        // on a chain that waits for its own results); lane bit 5 on the half swap, as the 4096-point transforms
+        auto fht256 = [&](auto& x) {
 #pragma clang fp contract(off)
-          const float a0 = x[0] + x[1], a1 = x[0] - x[1], a2 = x[2] + x[3], a3 = x[2] - x[3];
-          x[0] = a0 + a2; x[2] = a0 - a2; x[1] = a1 + a3; x[3] = a1 - a3;
-          auto lst = [&](auto sc) {
-            constexpr int S = decltype(sc)::value;
-            const float sg = ((lane >> S) & 1) ? -1.f : 1.f;
+          constexpr int N = sizeof(x) / sizeof(float);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) x[r] = __builtin_fmaf(x[r], sg, had8::lane_partner<S>(x[r], lane));
-          };
-          lst(std::integral_constant<int, 0>{}); lst(std::integral_constant<int, 1>{}); lst(std::integral_constant<int, 2>{});
-          lst(std::integral_constant<int, 3>{}); lst(std::integral_constant<int, 4>{}); lst(std::integral_constant<int, 5>{});
-        };
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        const f16* vecs = reinterpret_cast<const f16*>(smem + B::kStash) + (row_ok ? rw : 0) * 3 * FL;
-        float o[4] = {0.f, 0.f, 0.f, 0.f};
-        if (act) {
-          {
-            const float4 f0 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(smem + B::kArea) +
-                                                              ((row_ok ? rw : 0) * 2 + mh) * FL + lane * 4);
-            v[0] = f0.x; v[1] = f0.y; v[2] = f0.z; v[3] = f0.w;
+          for (int g = 0; g < N; g += 4) {
+            const float a0 = x[g] + x[g + 1], a1 = x[g] - x[g + 1], a2 = x[g + 2] + x[g + 3], a3 = x[g + 2] - x[g + 3];
+            x[g] = a0 + a2; x[g + 2] = a0 - a2; x[g + 1] = a1 + a3; x[g + 3] = a1 - a3;
           }
-          fht256(v);
-          const uint2 svp = *reinterpret_cast<const uint2*>(vecs + mh * FL + lane * 4);
-          const f16x2 s01 = as_f16x2(svp.x), s23 = as_f16x2(svp.y);
-          const float svf[4] = {(float)s01.x, (float)s01.y, (float)s23.x, (float)s23.y};
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = (float)had::out_elem(v[r], 1.f / 16.f, true, svf[r], false, 0.f, false, 0.f);
-        }
-        float* xch = reinterpret_cast<float*>(smem + B::kStage + RPO * FL * 4);     // [RPO][256]: the up halves
-        if (act && mh == 1) *reinterpret_cast<float4*>(xch + rw * FL + lane * 4) = float4{o[0], o[1], o[2], o[3]};
-        MSTAMP(5);
-        had::wg_barrier<true>();
-        MSTAMP(6);
+          hadw::lane_stages<N, 0, 6>(x, lane);
+        };
+        const f16* vecs = reinterpret_cast<const f16*>(smem + B::kStash) + (row_ok ? rw : 0) * 3 * FL;
         uint32_t* stage = reinterpret_cast<uint32_t*>(smem + B::kStage);
-        if (act && mh == 0) {
-          const float4 u4 = *reinterpret_cast<const float4*>(xch + rw * FL + lane * 4);
-          const float u[4] = {u4.x, u4.y, u4.z, u4.w};
+        if (act) {
+          float v[8];                                    // gate's four columns | up's
+          {
+            u32x4_t pc[4];                               // [matrix][half]: {column, tag, column + 1, tag}
+            const uint64_t* src = inbox + (((size_t)(RPO * w + (row_ok ? rw : 0)) * 2) * FL + 4 * lane);
+            uint32_t spins = 0;
+            for (;;) {
+#pragma unroll
+              for (int j = 0; j < 4; ++j) esync::ld16(pc[j], src + (j >> 1) * FL + 2 * (j & 1));
+              esync::drain();
+              bool ok = true;
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                esync::own(pc[j]);
+                ok = ok && (!row_ok || (pc[j].y == tag1 && pc[j].w == tag1));
+              }
+              if (esync::spin_step(ok, spins, ctl + 1, 0x1000u + (uint32_t)w)) break;
+            }
+            if (dbg_on && tid == 0) a.dbg[w * 32 + 25] = __builtin_amdgcn_s_memtime();
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              v[2 * j] = row_ok ? __builtin_bit_cast(float, (uint32_t)pc[j].x) : 0.f;
+              v[2 * j + 1] = row_ok ? __builtin_bit_cast(float, (uint32_t)pc[j].z) : 0.f;
+            }
+          }
+          MSTAMP(4);
+          fht256(v);
+          float svf[8];
+#pragma unroll
+          for (int mh = 0; mh < 2; ++mh) {
+            const uint2 svp = *reinterpret_cast<const uint2*>(vecs + mh * FL + lane * 4);
+            const f16x2 s01 = as_f16x2(svp.x), s23 = as_f16x2(svp.y);
+            svf[4 * mh] = (float)s01.x; svf[4 * mh + 1] = (float)s01.y; svf[4 * mh + 2] = (float)s23.x; svf[4 * mh + 3] = (float)s23.y;
+          }
+          float o[8];
+#pragma unroll
+          for (int r = 0; r < 8; ++r) o[r] = (float)had::out_elem(v[r], 1.f / 16.f, true, svf[r], false, 0.f, false, 0.f);
+          MSTAMP(5);
+          MSTAMP(6);
           const uint2 sup = *reinterpret_cast<const uint2*>(vecs + 2 * FL + lane * 4);
           const f16x2 s01 = as_f16x2(sup.x), s23 = as_f16x2(sup.y);
           const float suf[4] = {(float)s01.x, (float)s01.y, (float)s23.x, (float)s23.y};
           float e[4];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) e[r] = had::fmul(had::fmul(u[r], had::silu(o[r])), suf[r]);
+          for (int r = 0; r < 4; ++r) e[r] = had::fmul(had::fmul(o[4 + r], had::silu(o[r])), suf[r]);
           fht256(e);
           // the row, ROUNDED TO fp16 (round 5; the reference materialises fp16 here too: the transform's output feeds
           // `hadK @ x` as an fp16 tensor, quant.py:72-88), prescaled, next to the owner's other row in LDS ([j][RPO] fp16).

@@ -112,9 +112,9 @@ if mlp_stamps:     # a library built with -DQUIP_MLP_STAMPS=1: the two 4096-wide
     chain("inside 11 -> 12 (the gate / up products; everybody):", [11, M[0], M[1], M[2], M[3], 12],
           ["factor image + owner vectors through registers into LDS", "drain (the codes of gate / up)",
            "the items decoded ahead (7B: three; G8: two)", "the live items", "barrier"], ev)
-    chain("row owners, 13 -> 14 (wave 0: the gate half of the owner's first row):", [13, 25, M[4], M[5], M[6], M[7], 14],
-          ["down's items decoded ahead + inbox complete", "rows in LDS + barrier", "out-transform (256 points, SV), up half to LDS",
-           "crossing (barrier)", "SiLU product, SU, in-transform, rows staged", "barrier + published (+ barrier: parent)"], ro)
+    chain("row owners, 13 -> 14 (wave 0: the owner's first row, gate and up halves):", [13, 25, M[4], M[5], M[6], M[7], 14],
+          ["down's items decoded ahead + inbox complete", "the row's values out of the granules", "out-transform (256 points x 2, SV)",
+           "(two adjacent stamps)", "SiLU product, SU, in-transform, row staged", "barrier + published"], ro)
     chain("inside 15 -> 16 (everybody):", [15, M[8], M[9], M[10], 16],
           ["K-mix (MFMAs)", "norm bound + barrier", "down's planes", "barrier"], ev)
 wait_stamps = int(os.environ.get("QUIP_WAIT_STAMPS") or 0)
