@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 19
+#define QUIP_ABI_VERSION 20
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -644,6 +644,31 @@ int quip_rope_attn_decode_batched_qknorm_f16(const void* q, const void* k, const
                                              int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim,
                                              int32_t max_len, float scale, int32_t window, void* workspace,
                                              quip_stream_t stream, const void* q_weight, const void* k_weight, float eps);
+
+/* ---- LoRA adapters beside the quantised modules, one adapter index per row (ABI 20; csrc/lora_rows.hip.h) ----
+ * Both calls are row-wise: a row's result depends on that row's inputs, its adapter index a = row_adapter[row] (int32) and
+ * that adapter's weights alone -- not on rows, on the row's place or on its neighbours -- and the order of every addition
+ * is fixed.  An index outside [0, n_adapters) means "no adapter".
+ *
+ * quip_lora_shrink_rows_f16: t[row, r] = sum_k A[a, r, k] xin(row)[k] in fp32; x [rows, in] fp16, A [n_adapters, R, in] fp16,
+ * t [rows, R] fp32.  xin is what the base module's input transform sees, in fp32 with no fp16 rounding in between:
+ *   mode 0  x                                          (aux unused)
+ *   mode 1  (x * (1 / sqrt(sum x^2 / in + eps))) * aux   aux [in] fp16, the RMSNorm weight
+ *   mode 2  x * silu(aux[row])                           aux [rows, in] fp16, the gate
+ * A row without an adapter gets zeros and A is not read.  in % 8 == 0, in >= 8, R % 8 == 0, R >= 8, rows >= 1, mode 0..2
+ * (else QUIP_ERR_BAD_SHAPE); in <= 28672 and R <= 192 (else QUIP_ERR_UNSUPPORTED); x, A, aux 16-byte aligned.
+ *
+ * quip_lora_expand_rows_f16: for the `segments` (1..3) outputs of modules that share the input,
+ *   y_j[row, o] = fp16(fma(scale[a, j], sum_{r < R_j} float(B_j[a, o, r]) t[row, r0_j + r], float(y_j[row, o])))
+ * in place, the sum by fp32 FMA in increasing r.  y / B / out / R / r0: host arrays of `segments` entries; y_j [rows, out_j]
+ * fp16, B_j [n_adapters, out_j, R_j] fp16 (16-byte aligned), t [rows, R_total] fp32, scale [n_adapters, 3] fp32.  A row
+ * without an adapter keeps the bits of its y; a segment with out_j == 0 is skipped (its pointers may be NULL).
+ * out_j % 8 == 0, R_j % 8 == 0, R_j >= 8, r0_j % 8 == 0, r0_j + R_j <= R_total (else QUIP_ERR_BAD_SHAPE); R_total <= 192. */
+int quip_lora_shrink_rows_f16(const void* x, const void* A, const int32_t* row_adapter, float* t, int64_t rows, int32_t in,
+                              int32_t R, int32_t n_adapters, int32_t mode, const void* aux, float eps, quip_stream_t stream);
+int quip_lora_expand_rows_f16(const float* t, const int32_t* row_adapter, const float* scale, int64_t rows, int32_t R_total,
+                              int32_t n_adapters, int32_t segments, void* const* y, const void* const* B, const int32_t* out,
+                              const int32_t* R, const int32_t* r0, quip_stream_t stream);
 
 /* Which kernel a bs=1 E8P12 GEMV launch of `count` matrices (ns[i] rows, common k) is dispatched to by default, without
  * launching anything: 1 = e8p_gemv_mfma_kernel, 2 = e8p_gemv_v2_kernel (needs the workspace of the *_ws entry points when

@@ -181,8 +181,13 @@ def _ragged_passes(dec, slots, toks, chunk, on_pass):
             return dec._attend_ragged(i, q.view(n, s.heads, s.head_dim), k.view(n, s.kv_heads, s.head_dim),
                                       v.view(n, s.kv_heads, s.head_dim), seg_slot, seg_rows).reshape(n, s.q_width)
         h = p.embed[torch.cat([toks[j][a:a + r] for j, a, r in pieces])]      # (n, hidden)
+        rows_adapter = None
+        if p.lora is not None:
+            # every segment's slot adapter over the segment's rows, on the device (nothing read on the host)
+            rows_adapter = torch.repeat_interleave(dec.slot_adapter[torch.tensor(seg_slot, dtype=torch.long, device=dec.dev)],
+                                                   torch.tensor(seg_rows, dtype=torch.long, device=dec.dev), output_size=n)
         for i, L in enumerate(p.layers):
-            h = p._block(L, h, partial(attend, i))
+            h = p._block(L, h, partial(attend, i), adapter=rows_adapter)
         dec.pos.index_add_(0, torch.tensor(seg_slot, dtype=torch.long, device=dec.dev),
                             torch.tensor(seg_rows, dtype=torch.long, device=dec.dev))
         on_pass(pieces, h)
@@ -232,6 +237,17 @@ class BatchDecoder:
         self.graph = None
         self.sampling = None
         self.step_logits = None
+        # LoRA (the parent's enable_lora, before or after this decoder was made): one adapter index per slot, -1 = none,
+        # read in place by the step; the parent drops this decoder's captured step when the launching groups change
+        self.slot_adapter = torch.full((batch,), -1, dtype=torch.int32, device=self.dev)
+        parent._lora_dependents.add(self)
+
+    def set_slot_adapter(self, b, name):
+        """slot b's adapter from now on (a name of the parent's load_adapter; None: none) -- written on the device, a
+        captured step reads it in place.  reset() keeps it."""
+        if not 0 <= int(b) < self.batch:
+            raise ValueError(f"slot {b} of {self.batch} is out of range")
+        self.slot_adapter[int(b):int(b) + 1].fill_(self.parent._need_lora().index(name))
 
     # the cache and the two attention launches on it: what paged_cache.PagedBatchDecoder replaces
     def _alloc_cache(self):
@@ -281,8 +297,9 @@ class BatchDecoder:
             return self._attend_step(i, q.view(B, s.heads, s.head_dim), k.view(B, s.kv_heads, s.head_dim),
                                      v.view(B, s.kv_heads, s.head_dim)).reshape(B, s.q_width)
         fused = self._fuses_norm()
+        adapter = self.slot_adapter if p.lora is not None else None
         for i, L in enumerate(p.layers):
-            h = p._block(L, h, partial(attend, i), norm_in_attend=fused)
+            h = p._block(L, h, partial(attend, i), norm_in_attend=fused, adapter=adapter)
         return self._head(h)
 
     def _head(self, h):
@@ -321,7 +338,8 @@ class BatchDecoder:
         tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
         if not 0 <= b < self.batch or not 1 <= tokens.numel() <= self.max_len:
             raise ValueError(f"slot {b} of {self.batch}, {tokens.numel()} prompt tokens (1 .. {self.max_len})")
-        return self.parent.prefill(tokens, kv=(self.kcache[:, b], self.vcache[:, b]), pos=self.pos[b:b + 1])
+        return self.parent.prefill(tokens, kv=(self.kcache[:, b], self.vcache[:, b]), pos=self.pos[b:b + 1],
+                                   adapter=self.slot_adapter[b:b + 1])
 
     @torch.no_grad()
     def extend_slot(self, b, tokens, chunk=512):
@@ -331,7 +349,8 @@ class BatchDecoder:
         tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
         if not 0 <= b < self.batch or tokens.numel() < 1:
             raise ValueError(f"slot {b} of {self.batch}, {tokens.numel()} tokens to append (>= 1)")
-        return self.parent.extend(tokens, chunk=chunk, kv=(self.kcache[:, b], self.vcache[:, b]), pos=self.pos[b:b + 1])
+        return self.parent.extend(tokens, chunk=chunk, kv=(self.kcache[:, b], self.vcache[:, b]), pos=self.pos[b:b + 1],
+                                  adapter=self.slot_adapter[b:b + 1])
 
     @torch.no_grad()
     def extend_slots(self, slots, token_lists, chunk=512):

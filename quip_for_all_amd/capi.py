@@ -70,6 +70,8 @@ SIGNATURES = {
                                          _P, _P, _F],
     "quip_rope_attn_decode_batched_qknorm_f16": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F,
                                                  _I32, _P, _P, _P, _P, _F],
+    "quip_lora_shrink_rows_f16": [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _F, _P],
+    "quip_lora_expand_rows_f16": [_P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P],
     "quip_block_engine_supported": [_I32, _I32, _I32, _I32, _I32, _I32],
     "quip_block_engine_workspace_bytes": [],
     "quip_block_engine_layer_bytes": [],

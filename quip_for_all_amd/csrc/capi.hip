@@ -915,6 +915,26 @@ int quip_rope_attn_decode_batched_qknorm_f16(const void* q, const void* k, const
                                                 k_weight, eps);
 }
 
+int quip_lora_shrink_rows_f16(const void* x, const void* A, const int32_t* row_adapter, float* t, int64_t rows, int32_t in,
+                              int32_t R, int32_t n_adapters, int32_t mode, const void* aux, float eps, quip_stream_t stream) {
+  if (!x || !A || !row_adapter || !t || (mode != 0 && !aux)) return QUIP_ERR_NULL_POINTER;
+  if (!aligned16(x) || !aligned16(A) || (mode != 0 && !aligned16(aux)) || (reinterpret_cast<uintptr_t>(row_adapter) & 3) ||
+      (reinterpret_cast<uintptr_t>(t) & 3))
+    return QUIP_ERR_MISALIGNED;
+  return lora_shrink_rows_launch(x, A, row_adapter, t, rows, in, R, n_adapters, mode, aux, eps, (hipStream_t)stream);
+}
+
+int quip_lora_expand_rows_f16(const float* t, const int32_t* row_adapter, const float* scale, int64_t rows, int32_t R_total,
+                              int32_t n_adapters, int32_t segments, void* const* y, const void* const* B, const int32_t* out,
+                              const int32_t* R, const int32_t* r0, quip_stream_t stream) {
+  if (!t || !row_adapter || !scale || !y || !B || !out || !R || !r0) return QUIP_ERR_NULL_POINTER;
+  if ((reinterpret_cast<uintptr_t>(t) & 3) || (reinterpret_cast<uintptr_t>(row_adapter) & 3) ||
+      (reinterpret_cast<uintptr_t>(scale) & 3))
+    return QUIP_ERR_MISALIGNED;
+  return lora_expand_rows_launch(t, row_adapter, scale, rows, R_total, n_adapters, segments, y, B, out, R, r0,
+                                 (hipStream_t)stream);
+}
+
 int quip_rope_attn_decode_z_supported(int32_t heads, int32_t kv_heads, int32_t head_dim) {
   return rope_attn_decode_z_supported(heads, kv_heads, head_dim) ? 1 : 0;
 }

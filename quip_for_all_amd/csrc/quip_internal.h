@@ -248,6 +248,13 @@ int nll_rows_launch(const void* logits, int rows, int n, const int64_t* target, 
 int sample_rows_launch(const void* logits, int rows, int n, const float* temperature, const int32_t* top_k,
                        const float* top_p, const int64_t* seed, int64_t* tok, int64_t* pos, int32_t* kept,
                        hipStream_t stream);
+// lora_rows.hip.h (in decode_glue.hip): t = A[row_adapter[row]] xin(row) over (rows, in) fp16 rows (mode 0 x, 1 RMSNorm(x) w with
+// aux = w, 2 x silu(aux row)), and y_j += scale B_j t for up to three segments; rows without an adapter: zeros / untouched
+int lora_shrink_rows_launch(const void* x, const void* A, const int32_t* row_adapter, float* t, int64_t rows, int in, int R,
+                            int n_adapters, int mode, const void* aux, float eps, hipStream_t stream);
+int lora_expand_rows_launch(const float* t, const int32_t* row_adapter, const float* scale, int64_t rows, int Rt, int n_adapters,
+                            int segments, void* const* y, const void* const* B, const int32_t* out, const int32_t* R,
+                            const int32_t* r0, hipStream_t stream);
 // persistent decode engine, stage 1 (decode_engine.hip): GEMV[gate, up] -> output transforms -> SiLU product ->
 // input transform of down -> GEMV[down] of one decoder block in one launch
 struct FfnEngineArgs {

@@ -14,6 +14,7 @@ fast: SURVEY.md 8f rank 1)."""
 import math
 import os
 import warnings
+import weakref
 from contextlib import contextmanager
 from dataclasses import dataclass
 from functools import partial
@@ -23,6 +24,7 @@ import torch
 import torch.nn.functional as F
 
 from . import chunk_attn as _chunk_attn  # noqa: F401  (defines quip_lib::rope_attn_chunk)
+from . import lora as _lora  # (defines quip_lib::lora_shrink_rows / lora_expand_rows)
 from . import qk_norm as _qk_norm  # noqa: F401  (defines quip_lib::qk_norm_rows and the two _qknorm decode launches)
 from . import register_lib as _R
 from . import score as _score  # (defines quip_lib::nll_rows)
@@ -234,10 +236,11 @@ def capture_graph(warmup, body):
     return graph, out
 
 
-def _extend_chunks(dec, what, tokens, chunk, kv, pos, on_chunk):
+def _extend_chunks(dec, what, tokens, chunk, kv, pos, on_chunk, adapter=None):
     """the chunk loop of extend() / score(): `tokens` behind the position in chunks of at most `chunk` rows, every block
     over each chunk, the position advanced on the device; on_chunk(c0, h) gets the hidden rows h (n, hidden) of the
-    chunk that starts at token c0"""
+    chunk that starts at token c0.  `adapter`: the (1,) int32 adapter index of the sequence (enable_lora; default: the
+    bs = 1 decoder's), spread over each chunk's rows on the device"""
     s = dec.s
     tokens = torch.as_tensor(tokens, dtype=torch.long, device=dec.dev).reshape(-1)
     P, chunk = tokens.numel(), int(chunk)
@@ -258,8 +261,9 @@ def _extend_chunks(dec, what, tokens, chunk, kv, pos, on_chunk):
     for c0 in range(0, P, chunk):
         n = min(chunk, P - c0)
         h = dec.embed[tokens[c0:c0 + n]]                           # (n, hidden)
+        rows_adapter = dec._rows_adapter(adapter, n)
         for i, L in enumerate(dec.layers):
-            h = dec._block(L, h, partial(attend, i))
+            h = dec._block(L, h, partial(attend, i), adapter=rows_adapter)
         pos.add_(n)
         on_chunk(c0, h)
 
@@ -486,6 +490,14 @@ class LlamaDecoder:
         # _batched_qknorm); off (QUIP_QK_NORM_FUSED=0, or the attribute with `graph = None`): quip_lib::qk_norm_rows in front of
         # the plain launch, the same bits -- the A/B of tools/qk_norm_bench.py.  Every other route takes the launch in front.
         self.qk_norm = "q_norm" in self.layers[0]
+        # LoRA adapters (enable_lora): the state lives on through a re-run; with it the persistent launches, the _z attention
+        # launch and the token tail stay off, as on a q / k norm model (no adapter branch inside them: not built)
+        self.lora = getattr(self, "lora", None)
+        # bs = 1 with adapters: the chain / prologue route (_step_fused) where the decoder has one, else _block.  Measured on the
+        # 7B shape (tools/lora_bench.py, profiles/lora_bench.txt): _step_fused is 262 us (r 16 on q, v) and 183 us (r 16 on all
+        # seven) per token faster than _block, spreads below 5 us.  False (with `graph = None`): _block, for A/B.
+        self.lora_fused_step = True
+        self._lora_dependents = getattr(self, "_lora_dependents", None) or weakref.WeakSet()    # batched decoders: their captured steps
         self.qk_fused = os.environ.get("QUIP_QK_NORM_FUSED", "1") != "0"
         if self.qk_norm and not self.fused_attention:
             raise NotImplementedError(f"q_norm / k_norm with head_dim {s.head_dim}: the norm launches serve 64 and 128")
@@ -504,6 +516,7 @@ class LlamaDecoder:
         # the MLP half of a block (GEMV[gate, up], two transforms, GEMV[down]) as ONE persistent launch
         # (csrc/decode_engine.hip); QUIP_FFN_ENGINE=0 keeps the four stage-wise launches
         self.ffn_eng = (self.fused_prologue and self.chain and os.environ.get("QUIP_FFN_ENGINE", "1") != "0"
+                        and self.lora is None
                         and all(ffn_engine_ok(L["gate"], L["up"], L["down"]) for L in self.layers))
         self.ffn_ws = _R.ffn_engine_workspace(s.ffn, L0["gate"].K_right, self.dev) if self.ffn_eng else None
         # all blocks of a token as ONE persistent launch (csrc/decode_block.hip); QUIP_BLOCK_ENGINE=0 keeps the stage-wise step
@@ -521,12 +534,14 @@ class LlamaDecoder:
         gqa_shape = self.fused_prologue and self.chain and s.kv_heads != s.heads and s.hidden in (8192, 4096)   # (csrc/decode_block_gqa.hip; decode_block_g8.hip)
         if ((self.ffn_eng or gqa_shape or (d4 and self.fused_prologue and self.chain and os.environ.get("QUIP_FFN_ENGINE", "1") != "0"))
                 and os.environ.get("QUIP_BLOCK_ENGINE", "1") != "0" and not self.window     # (its attention walks [0, pos])
-                and not self.qk_norm):              # (the persistent launches have no q / k norm: not built)
+                and not self.qk_norm                # (the persistent launches have no q / k norm: not built)
+                and self.lora is None):             # (nor an adapter branch)
             self._init_block_engine()
         # q / k / v output transforms inside the attention launch (multi-head attention with a power-of-two hidden <= 4096,
         # or 64 / 32 heads on 8 KV heads -- Llama-2-70B, Llama-3, Mistral-7B; plain SV output side)
         self.attn_z = (self.fused_prologue and self.fused_attention and os.environ.get("QUIP_ATTN_Z", "1") != "0"
                        and not self.qk_norm                 # (the _z launch has no q / k norm: not built)
+                       and self.lora is None                # (adapters add to the materialised q / k / v)
                        and _R.rope_attn_decode_z_supported(s.heads, s.kv_heads, s.head_dim)
                        and all(l.K_right == 1 and not l.per_channel and l.bias is None and l.SV is not None
                                and l.q_out_features == l.out_features == (s.heads if i == 0 else s.kv_heads) * s.head_dim
@@ -747,22 +762,94 @@ class LlamaDecoder:
         torch.ops.quip_lib.qk_norm_rows(q, k, L["q_norm"], L["k_norm"], s.head_dim, self.qk_eps)
         return q, k
 
-    def _block(self, L, h, attend, norm_in_attend=False):
+    def _block(self, L, h, attend, norm_in_attend=False, adapter=None):
         """one decoder block on the rows of `h`, stage by stage; `attend(q, k, v)` -> the attention output, (rows, heads *
         head_dim): the decode step, the prompt passes and BatchDecoder.step differ in nothing else.  A model with q / k norms
         gets them here, behind the projections (quip_lib::qk_norm_rows), unless `norm_in_attend`: that `attend` takes the raw
-        q and k and normalises them itself (the decode launches that fuse the norm)"""
+        q and k and normalises them itself (the decode launches that fuse the norm).
+        `adapter` (enable_lora): the int32 adapter index of every row of `h`, on the device.  q / k / v and gate / up: one
+        shrink over the group's stacked ranks with the norm fused, the base product, one expand over the group's outputs.
+        o and down: their input shrunk (down's with the gate) and the delta expanded INTO THE RESIDUAL (h, in place) in
+        front of the module's output launch, which adds the residual as ever -- the same sum, and nothing has to follow
+        the output-side launch.  A group no loaded adapter targets launches nothing."""
         s = self.s
+        lo = L["lora"] if adapter is not None and self.lora is not None else None
         with self._row_major(L):
             # q / k / v (and gate / up below): one launch per stage for the whole group; RMSNorm rides on
             # the input-side Hadamard launch
+            t = lo.shrink("qkv", h, adapter, rms_weight=L["ln1"], rms_eps=s.rms_eps) if lo else None
             q, k, v = forward_group([L["q"], L["k"], L["v"]], h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
+            if t is not None:
+                lo.expand("qkv", t, [q, k, v], adapter)
             if self.qk_norm and not norm_in_attend:
                 q, k = self._qk_norm_rows(L, q, k)
             # residual adds ride on the output-side Hadamard launch, SiLU(gate)*up on down's input side
-            h = L["o"].forward_fused(attend(q, k, v), residual=h)
+            a = attend(q, k, v)
+            t = lo.shrink("o", a, adapter) if lo else None
+            if t is not None:
+                lo.expand("o", t, [h], adapter)
+            h = L["o"].forward_fused(a, residual=h)
+            t = lo.shrink("gu", h, adapter, rms_weight=L["ln2"], rms_eps=s.rms_eps) if lo else None
             g, u = forward_group([L["gate"], L["up"]], h, rms_weight=L["ln2"], rms_eps=s.rms_eps)
+            if t is not None:
+                lo.expand("gu", t, [g, u], adapter)
+            t = lo.shrink("down", u, adapter, gate=g) if lo else None
+            if t is not None:
+                lo.expand("down", t, [h], adapter)
             return L["down"].forward_fused(u, gate=g, residual=h)
+
+    # ---- LoRA adapters (lora.py) ---------------------------------------------------------------------------------------------
+    def enable_lora(self, max_adapters=4, max_rank=16):
+        """Adapter slots beside every QuantLinear of every block: the stacked A / B / scale tensors of `max_adapters`
+        adapters of rank <= `max_rank` (padded to a multiple of 8), allocated once, zero-filled, at fixed addresses -- a
+        captured step survives load_adapter / unload_adapter / set_adapter.  From here on the persistent launches, the
+        _z attention launch and the token tail are off and the captured steps are dropped.  Without this call nothing
+        changes; with it and no adapter selected, every result keeps its bits."""
+        if self.lora is not None:
+            raise RuntimeError("enable_lora: already enabled")
+        lora = _lora.LoraState(self, max_adapters, max_rank)
+        for L, lay in zip(self.layers, lora.layers):
+            L["lora"] = lay
+        lora.on_launches_changed = self._drop_graphs
+        self.lora = lora
+        self.block_eng = self.ffn_eng = self.attn_z = False
+        self.eng_layers = self._eng_keep = None
+        self._drop_graphs()
+
+    def _drop_graphs(self):
+        """captured steps and passes hold launch lists: gone when the groups that launch change"""
+        self.graph = None
+        self._prefill_graphs, self._extend_graphs = {}, {}
+        for d in list(self._lora_dependents):
+            d.graph = None
+
+    def _need_lora(self):
+        if self.lora is None:
+            raise RuntimeError("no adapter slots: call enable_lora() first")
+        return self.lora
+
+    def load_adapter(self, name, tensors, config):
+        """an adapter in PEFT's key scheme (lora.read_peft_dir; lora.check_config says what is served) into a slot -> the
+        slot's index.  A loaded name is replaced in its slot.  Captured steps are kept unless the adapter targets a module
+        group no loaded adapter targeted before (that group's launches join the step)."""
+        return self._need_lora().load(name, tensors, config)
+
+    def unload_adapter(self, name):
+        """zero the adapter's stack entry and free its slot"""
+        self._need_lora().unload(name)
+
+    def set_adapter(self, name):
+        """the bs = 1 decoder's adapter from now on (None: none): an int32 on the device that step(), captured or not, and
+        the prompt passes read in place"""
+        self._need_lora().idx.fill_(self.lora.index(name))
+
+    def _rows_adapter(self, adapter, n):
+        """the per-row adapter index _block wants for n rows of one sequence, from its (1,) index tensor (default: the
+        bs = 1 decoder's); None without enable_lora.  Nothing is read on the host."""
+        if self.lora is None:
+            return None
+        adapter = self.lora.idx if adapter is None else adapter
+        return adapter if n == 1 else adapter.expand(n).contiguous()
 
     def _engine_args(self):
         """the arguments quip_lib::block_engine and quip_lib::block_engine_token share: everything behind their own I/O"""
@@ -793,13 +880,14 @@ class LlamaDecoder:
         if self.block_eng:
             h = torch.ops.quip_lib.block_engine(self.eng_layers, h.reshape(-1), self.pos, *self._engine_args())
             return self._head(h.reshape(1, -1))
-        if self.fused_prologue:
+        if self.fused_prologue and (self.lora is None or self.lora_fused_step):
             return self._step_fused(h, cos, sin, mask)
 
         def attend(i, q, k, v):
             return self._attention(i, q, k, v, cos, sin, mask).reshape(1, s.q_width)
         for i, L in enumerate(self.layers):
-            h = self._block(L, h, partial(attend, i), norm_in_attend=True)     # (_attention: fused, or the launch in front)
+            h = self._block(L, h, partial(attend, i), norm_in_attend=True,     # (_attention: fused, or the launch in front)
+                            adapter=self._rows_adapter(None, 1))
         return self._head(h)
 
     def _token_tail_on(self):
@@ -816,10 +904,15 @@ class LlamaDecoder:
     def _step_fused(self, h, cos, sin, mask):
         """8 launches per block: the GEMV launches of q/k/v, o and gate/up compute their own input
         transform (RMSNorm, SU, Hadamard) and the output transform + residual of the module before
-        them (down of the previous block, o) in their prologue."""
+        them (down of the previous block, o) in their prologue.
+        With adapters (enable_lora and lora_fused_step; ffn_eng and attn_z are off then) the hooks of _block: the shrink on
+        the h a launch returns or takes, the expand on the materialised q / k / v and gate / up, o's and down's delta into
+        the residual h (in place) in front of the launch that adds it."""
         s = self.s
         zd = prev_down = None
+        ad = self.lora.idx if self.lora is not None else None
         for i, L in enumerate(self.layers):
+            lo = L["lora"] if ad is not None else None
             with self._row_major(L):
                 qkv = [L["q"], L["k"], L["v"]]
                 if zd is None and self.qkv_fused:
@@ -828,6 +921,7 @@ class LlamaDecoder:
                     zs = gemv_group_unfused(qkv, h, rms_weight=L["ln1"], rms_eps=s.rms_eps)
                 else:   # finishes the previous block: h += down(...)
                     h, zs = self._zx(qkv, prev_down, zd, h, L["ln1"])
+                t = lo.shrink("qkv", h, ad, rms_weight=L["ln1"], rms_eps=s.rms_eps) if lo else None
                 if self.attn_z:
                     # the K = 1 output transforms of q / k / v in the attention launch's prologue: 9 launches per block
                     a = torch.ops.quip_lib.rope_attn_decode_z(
@@ -835,7 +929,12 @@ class LlamaDecoder:
                         self.cos, self.sin, self.pos, self.kcache[i], self.vcache[i], self.attn_ws, self.window)
                 else:
                     q, k, v = out_transform_group(qkv, zs)
+                    if t is not None:
+                        lo.expand("qkv", t, [q, k, v], ad)
                     a = self._attention(i, q, k, v, cos, sin, mask)
+                t = lo.shrink("o", a.reshape(1, s.q_width), ad) if lo else None
+                if t is not None:
+                    lo.expand("o", t, [h], ad)
                 if self.o_fused:
                     _, (zo,) = gemv_fused([L["o"]], x=a.reshape(1, s.q_width))
                 else:
@@ -846,7 +945,13 @@ class LlamaDecoder:
                     zd = ffn_engine(L["gate"], L["up"], L["down"], planes, self.ffn_ws)
                 else:
                     h, zgu = self._zx([L["gate"], L["up"]], L["o"], zo, h, L["ln2"])
+                    t = lo.shrink("gu", h, ad, rms_weight=L["ln2"], rms_eps=s.rms_eps) if lo else None
                     g, u = out_transform_group([L["gate"], L["up"]], zgu)
+                    if t is not None:
+                        lo.expand("gu", t, [g, u], ad)
+                    t = lo.shrink("down", u, ad, gate=g) if lo else None
+                    if t is not None:
+                        lo.expand("down", t, [h], ad)
                     zd = gemv_unfused(L["down"], u, gate=g)
                 prev_down = L["down"]
         (h,) = out_transform_group([prev_down], [zd], residual=[h])
@@ -935,13 +1040,14 @@ class LlamaDecoder:
         tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
         return self._replay_per_length(self._prefill_graphs, tokens, self.prefill, self.prefill)
 
-    def prefill(self, tokens, kv=None, pos=None):
+    def prefill(self, tokens, kv=None, pos=None, adapter=None):
         """Batched prompt pass (the reference demo's prefill, example_generate.py:36-47): all `tokens` (1-D ids) go
         through every block at once -- QuantLinear on (P, hidden) rows (M >= 32: skinny chunks or decompress + dense GEMM, fewer
         rows: the skinny paths), rotary embedding for positions 0..P-1, causal attention, K / V written to rows 0..P-1
         of the static cache -- and the position counter is left at P.  Returns the logits of the last token (1, vocab).
         `kv` = (keys, values): per-layer (kv_heads, >= P, head_dim) tensors to write instead of this decoder's cache, and
-        `pos`: the counter to leave at P instead of self.pos (BatchDecoder.prefill_slot: one slot of a batched cache)."""
+        `pos`: the counter to leave at P instead of self.pos (BatchDecoder.prefill_slot: one slot of a batched cache);
+        `adapter`: that slot's (1,) adapter index (enable_lora; default: set_adapter's)."""
         s = self.s
         tokens = torch.as_tensor(tokens, dtype=torch.long, device=self.dev).reshape(-1)
         P = tokens.numel()
@@ -964,13 +1070,14 @@ class LlamaDecoder:
                 a = F.scaled_dot_product_attention(q[None], k[None], v[None], is_causal=True,
                                                    enable_gqa=(s.kv_heads != s.heads))[0]     # (heads, P, hd)
             return a.transpose(0, 1).reshape(P, s.q_width)
+        rows_adapter = self._rows_adapter(adapter, P)
         for i, L in enumerate(self.layers):
-            h = self._block(L, h, partial(attend, i))
+            h = self._block(L, h, partial(attend, i), adapter=rows_adapter)
         (self.pos if pos is None else pos).fill_(P)
         return F.rms_norm(h[-1:], (s.hidden,), self.final_norm, s.rms_eps) @ self.lm_head.T
 
     @torch.no_grad()
-    def extend(self, tokens, chunk=512, kv=None, pos=None):
+    def extend(self, tokens, chunk=512, kv=None, pos=None, adapter=None):
         """Append `tokens` (1-D ids, >= 1) behind the current position: the prompt pass for a cache that already holds a
         conversation (a second turn, a prompt too long for one pass, a slot of a batched cache).  The tokens run in chunks
         of at most `chunk` rows -- bounded activations whatever the prompt length -- and per block and chunk the
@@ -979,16 +1086,16 @@ class LlamaDecoder:
         position is read by that launch and advanced on the device by each chunk's length: nothing here reads it on the
         host, so the pass can be captured once and replayed at any position (extend_graph).  Tokens that do not fit
         (position + rows > max_len) write nothing and give NaN logits -- the launch's range rule is the guard.
-        Returns the logits of the last token (1, vocab).  `kv` / `pos`: as in prefill()."""
+        Returns the logits of the last token (1, vocab).  `kv` / `pos` / `adapter`: as in prefill()."""
         last = [None]
 
         def keep(c0, h):
             last[0] = h
-        _extend_chunks(self, "extend", tokens, chunk, kv, pos, keep)
+        _extend_chunks(self, "extend", tokens, chunk, kv, pos, keep, adapter)
         return F.rms_norm(last[0][-1:], (self.s.hidden,), self.final_norm, self.s.rms_eps) @ self.lm_head.T
 
     @torch.no_grad()
-    def score(self, tokens, targets=None, chunk=512, kv=None, pos=None):
+    def score(self, tokens, targets=None, chunk=512, kv=None, pos=None, adapter=None):
         """extend() that scores its tokens: `tokens` go behind the current position exactly as extend() sends them (same
         chunks, same launches, same cache rows and counter, `kv` / `pos` as there -- a cached context conditions the
         scores), and after each chunk ALL its rows take the final norm, the lm_head product and the scoring tail
@@ -1013,7 +1120,7 @@ class LlamaDecoder:
             lp, am = _score.score_tail(logits, targets[c0:c0 + h.shape[0]])
             lps.append(lp)
             ams.append(am)
-        _extend_chunks(self, "score", tokens, chunk, kv, pos, tail)
+        _extend_chunks(self, "score", tokens, chunk, kv, pos, tail, adapter)
         return torch.cat(lps), torch.cat(ams)
 
     @torch.no_grad()

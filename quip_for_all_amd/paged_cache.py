@@ -307,6 +307,7 @@ class PagedBatchDecoder(BatchDecoder):
         """release slot b's pages; the slot idles (NaN logits, no writes) until it is filled, extended or forked onto"""
         self.pool.release(b)
         self.live[int(b)] = False
+        self.slot_adapter[int(b):int(b) + 1].fill_(-1)
         self._push_table()
 
     @torch.no_grad()
@@ -321,6 +322,7 @@ class PagedBatchDecoder(BatchDecoder):
             self.vpool[:, dp].copy_(self.vpool[:, sp])
         self.tok[dst:dst + 1].copy_(self.tok[src:src + 1])
         self.pos[dst:dst + 1].copy_(self.pos[src:src + 1])
+        self.slot_adapter[dst:dst + 1].copy_(self.slot_adapter[src:src + 1])
 
     def capture(self):
         """BatchDecoder.capture(); the warm-up steps write rows 0 and 1 of every slot, into one page per slot borrowed
