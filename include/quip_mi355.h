@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 20
+#define QUIP_ABI_VERSION 21
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -310,6 +310,20 @@ int quip_e8p_gemv_planes_rows(const void* planes, const void* qidxs, const void*
  * fp32 rounding of the score (ties / near-ties may resolve to a different, equally near codeword). */
 int quip_e8p_quantize_f32(const void* x, int64_t nvec, const void* grid_packed_abs, void* vals, void* idx,
                           quip_stream_t stream);
+
+/* ---- one LDLQ panel in one launch (ABI 21; quant.py:105-228 of the reference, one panel of its buffered loop) ------
+ * For each of m rows independently, over the c / 8 column groups k of the panel from the rightmost to the leftmost:
+ *     target_k = A_k + ( B_k + sum_{j > k} (A_j - hat_j) M[j, k] ) P_k,    (hat_k, idx_k) = nearest E8P12 codeword of target_k
+ * with the search of quip_e8p_quantize_f32 (the same codeword for the same fp32 target).  A, B, hat: fp32 (m, c) row major;
+ * M: fp32 (c, c) row major, only rows below a group's own 8 x 8 block are used; P: fp32 (c / 8, 8, 8), or NULL for the
+ * identity; idx: int64 (m, c / 8).  The sums are fp32 FMAs in increasing j, so a row's result depends on that row, M and P
+ * alone.  LDLQ pass: A = the panel of W, B = the feedback of the columns right of the panel, M = the panel's block of the
+ * block-LDL factor, P = NULL.  Tune sweep: A = the panel of the old hatW, B = (W - hatW) H[:, panel] at the start of the
+ * panel, M = H[panel, panel], P_k = inv(H[k, k]).
+ * c % 8 == 0, c >= 8 (else QUIP_ERR_BAD_SHAPE), c <= 128 (else QUIP_ERR_UNSUPPORTED); m == 0 is ok and launches nothing;
+ * A, B, M, P, hat 16-byte aligned, idx 8-byte aligned. */
+int quip_ldlq_panel_f32(const void* A, const void* B, const void* M, const void* P, int64_t m, int32_t c,
+                        const void* grid_packed_abs, void* hat, void* idx, quip_stream_t stream);
 
 /* Rows mode for the other table modes of the same kernel.  mode 0: E8P12 (== quip_e8p_gemv_planes_rows);
  * mode 64: D4 (qidxs uint8 (n, k/4), grid = fp16 (256, 4) table; HI through its virtual 2k layout, see

@@ -21,6 +21,10 @@
 // lowest (e, par, column) in scan order, which need not be the lowest code; near-ties inside fp32
 // rounding of the score may resolve differently from a GEMM-based arg max.  Either way the returned point
 // is a nearest codeword to within that rounding (tests/test_gpu_quantize.py states the bound).
+//
+// Second kernel, further down: ldlq_panel_kernel runs the LDLQ recursion over a whole panel of <= 128 columns in one
+// launch, with this search in place at every column group (the scan and the winner's reconstruction are device
+// functions that both kernels call).
 #include <hip/hip_runtime.h>
 
 #include "quip_device.hip.h"
@@ -30,42 +34,34 @@ namespace quip {
 
 namespace {
 
-template <int kLanes>
-__global__ __launch_bounds__(256) void e8p_quantize_kernel(const float* __restrict__ x, int64_t nvec,
-                                                          const uint64_t* __restrict__ grid_packed_abs,
-                                                          float* __restrict__ vals, int64_t* __restrict__ idx) {
-  __shared__ float tb[256][8];    // |b_e|, natural column order
-  __shared__ float tn[256];       // |b_e|^2
-  __shared__ int tneg[256];       // column 7 of b_e is negative
-  {
-    const int e = threadIdx.x;
-    const uint64_t p = grid_packed_abs[e];
-    float n2 = 0.f;
-    int neg = 0;
+// ---- the search as device functions: e8p_quantize_kernel and ldlq_panel_kernel run the same instructions on the same
+// fp32 target, so both choose the same codeword ------------------------------------------------------------------------
+
+// thread e of 256 builds abs-table row e: |b_e| in natural column order, |b_e|^2, and whether column 7 is negative
+__device__ __forceinline__ void e8p_table_row(int e, const uint64_t* __restrict__ grid_packed_abs, float (*tb)[8],
+                                              float* tn, int* tneg) {
+  const uint64_t p = grid_packed_abs[e];
+  float n2 = 0.f;
+  int neg = 0;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      // byte j of the packed entry = 4 * value of column [0,2,1,3,4,6,5,7][j] (self-inverse permutation)
-      const int col = e8p_byte_of_pos(j);
-      const int v4 = (int)(int8_t)((p >> (8 * j)) & 0xff);
-      const float v = 0.25f * (float)v4;
-      tb[e][col] = fabsf(v);
-      if (col == 7 && v4 < 0) neg = 1;
-      n2 += v * v;
-    }
-    tn[e] = n2;
-    tneg[e] = neg;
+  for (int j = 0; j < 8; ++j) {
+    // byte j of the packed entry = 4 * value of column [0,2,1,3,4,6,5,7][j] (self-inverse permutation)
+    const int col = e8p_byte_of_pos(j);
+    const int v4 = (int)(int8_t)((p >> (8 * j)) & 0xff);
+    const float v = 0.25f * (float)v4;
+    tb[e][col] = fabsf(v);
+    if (col == 7 && v4 < 0) neg = 1;
+    n2 += v * v;
   }
-  __syncthreads();
-  const int sub = threadIdx.x & (kLanes - 1);
-  int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kLanes;
-  const bool valid = i < nvec;
-  i = valid ? i : nvec - 1;     // keep every lane in the shuffles below
-  float xv[8];
-  {
-    const float4 a = reinterpret_cast<const float4*>(x + i * 8)[0];
-    const float4 b = reinterpret_cast<const float4*>(x + i * 8)[1];
-    xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w; xv[4] = b.x; xv[5] = b.y; xv[6] = b.z; xv[7] = b.w;
-  }
+  tn[e] = n2;
+  tneg[e] = neg;
+}
+
+// candidate scan: lane `sub` of the vector's kLanes lanes scans 256 / kLanes table rows x 2 shifts, then the lanes
+// agree on the arg max.  Returns best_e * 2 + best_par on every lane.  All kLanes lanes must call it.
+template <int kLanes>
+__device__ __forceinline__ int e8p_scan(const float (&xv)[8], int sub, const float (*tb)[8], const float* tn,
+                                        const int* tneg) {
   float ay[2][8];     // |x_j - s| for s = +1/4, -1/4
   int ypar[2];        // parity of the number of negative (x_j - s)
   float cs[2];        // 2 s sum x - 8 s^2
@@ -117,10 +113,13 @@ __global__ __launch_bounds__(256) void e8p_quantize_kernel(const float* __restri
     const int ok = __shfl_xor(key, off, 64);
     if (os > best || (os == best && ok < key)) { best = os; key = ok; }
   }
-  best_e = key >> 1;
-  best_p = key & 1;
-  if (!valid || sub != 0) return;
-  // rebuild the winner: signs, the repaired column, the code and the values
+  return key;
+}
+
+// rebuild the winner of e8p_scan: signs, the repaired column, the values; returns the code
+__device__ __forceinline__ int e8p_rebuild(const float (&xv)[8], int key, const float (*tb)[8], const int* tneg,
+                                           float (&out)[8]) {
+  const int best_e = key >> 1, best_p = key & 1;
   const float s = best_p ? -0.25f : 0.25f;
   float b[8];
 #pragma unroll
@@ -145,16 +144,122 @@ __global__ __launch_bounds__(256) void e8p_quantize_kernel(const float* __restri
       if (j == jm) flip[j] ^= 1;
   }
   int sv = 0;
-  float out[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     sv |= flip[j] << (7 - e8p_byte_of_pos(j));   // the sign bit of column j is the one of its packed byte
     const float signed_b = ((j == 7 && neg7) ? -b[j] : b[j]);
     out[j] = (flip[j] ? -signed_b : signed_b) + s;
   }
-  idx[i] = (int64_t)((best_e << 8) | (sv ^ best_p));
+  return (best_e << 8) | (sv ^ best_p);
+}
+
+template <int kLanes>
+__global__ __launch_bounds__(256) void e8p_quantize_kernel(const float* __restrict__ x, int64_t nvec,
+                                                          const uint64_t* __restrict__ grid_packed_abs,
+                                                          float* __restrict__ vals, int64_t* __restrict__ idx) {
+  __shared__ float tb[256][8];    // |b_e|, natural column order
+  __shared__ float tn[256];       // |b_e|^2
+  __shared__ int tneg[256];       // column 7 of b_e is negative
+  e8p_table_row(threadIdx.x, grid_packed_abs, tb, tn, tneg);
+  __syncthreads();
+  const int sub = threadIdx.x & (kLanes - 1);
+  int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kLanes;
+  const bool valid = i < nvec;
+  i = valid ? i : nvec - 1;     // keep every lane in the shuffles below
+  float xv[8];
+  {
+    const float4 a = reinterpret_cast<const float4*>(x + i * 8)[0];
+    const float4 b = reinterpret_cast<const float4*>(x + i * 8)[1];
+    xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w; xv[4] = b.x; xv[5] = b.y; xv[6] = b.z; xv[7] = b.w;
+  }
+  const int key = e8p_scan<kLanes>(xv, sub, tb, tn, tneg);
+  if (!valid || sub != 0) return;
+  float out[8];
+  const int code = e8p_rebuild(xv, key, tb, tneg, out);
+  idx[i] = (int64_t)code;
   reinterpret_cast<float4*>(vals + i * 8)[0] = make_float4(out[0], out[1], out[2], out[3]);
   reinterpret_cast<float4*>(vals + i * 8)[1] = make_float4(out[4], out[5], out[6], out[7]);
+}
+
+// ---- one LDLQ panel in one launch ---------------------------------------------------------------------------
+// For each of m rows independently, over the c / 8 column groups of the panel from the right:
+//     target_k = A_k + ( B_k + sum_{j > k} (A_j - hat_j) M[j, k] ) P_k,   (hat_k, idx_k) = nearest codeword of target_k
+// kPanelLanes = 8 lanes per row (the search's split), 32 rows per workgroup of 256.  Lane `sub` of a row owns column
+// lo + sub of the current group: it sums that column's feedback over the row's running differences E_j = A_j - hat_j in
+// increasing j by fp32 FMA (a fixed order: a row's bits depend on that row alone), the eight lanes exchange the target by
+// shuffles, search together, and each stores its own column of hat and of E.
+// LDS (dynamic): the abs table | M (c, c) | P (c / 8, 8, 8) | E as [column][row of the workgroup] (the 8 rows of a wave on 8
+// banks, the row's 8 lanes on one address).  E of a row is written and read by that row's 8 lanes only; the barrier per group
+// orders the LDS store before the next group's loads.
+constexpr int kPanelRows = 32;
+constexpr int kPanelMaxCols = 128;
+constexpr int kPanelTableFloats = 256 * 8 + 256 + 256;
+
+__host__ __device__ constexpr int ldlq_panel_lds_bytes(int c) {
+  return 4 * (kPanelTableFloats + c * c + 8 * c + kPanelRows * c);
+}
+
+__global__ __launch_bounds__(256) void ldlq_panel_kernel(const float* __restrict__ A, const float* __restrict__ B,
+                                                        const float* __restrict__ M, const float* __restrict__ P,
+                                                        int64_t m, int c, const uint64_t* __restrict__ grid_packed_abs,
+                                                        float* __restrict__ hat, int64_t* __restrict__ idx) {
+  extern __shared__ float panel_lds[];
+  float (*tb)[8] = reinterpret_cast<float (*)[8]>(panel_lds);
+  float* tn = panel_lds + 256 * 8;
+  int* tneg = reinterpret_cast<int*>(panel_lds + 256 * 8 + 256);
+  float* Ms = panel_lds + kPanelTableFloats;
+  float* Ps = Ms + c * c;
+  float* Es = Ps + 8 * c;
+  e8p_table_row(threadIdx.x, grid_packed_abs, tb, tn, tneg);
+  for (int i = threadIdx.x; i < c * c / 4; i += 256)      // c % 8 == 0, M 16-byte aligned
+    reinterpret_cast<float4*>(Ms)[i] = reinterpret_cast<const float4*>(M)[i];
+  if (P != nullptr)
+    for (int i = threadIdx.x; i < 2 * c; i += 256)
+      reinterpret_cast<float4*>(Ps)[i] = reinterpret_cast<const float4*>(P)[i];
+  __syncthreads();
+  const int sub = threadIdx.x & 7, r = threadIdx.x >> 3;
+  int64_t row = (int64_t)blockIdx.x * kPanelRows + r;
+  const bool valid = row < m;
+  row = valid ? row : m - 1;      // rows past the end repeat the last row (they take part in shuffles and barriers) and store nothing
+  const float* __restrict__ a = A + row * c;
+  const float* __restrict__ b = B + row * c;
+  const int groups = c / 8;
+  float a_cur = a[c - 8 + sub], b_cur = b[c - 8 + sub];
+  for (int k = groups - 1; k >= 0; --k) {
+    const int lo = k * 8, hi = lo + 8;
+    float a_nxt = 0.f, b_nxt = 0.f;
+    if (k > 0) { a_nxt = a[lo - 8 + sub]; b_nxt = b[lo - 8 + sub]; }     // the next group's operands, behind this group's search
+    float acc = 0.f;
+#pragma unroll 8
+    for (int j = hi; j < c; ++j) acc = fmaf(Es[j * kPanelRows + r], Ms[j * c + lo + sub], acc);
+    const float t = b_cur + acc;
+    float tgt;
+    if (P != nullptr) {
+      float s = 0.f;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) s = fmaf(__shfl(t, q, 8), Ps[(lo + q) * 8 + sub], s);
+      tgt = a_cur + s;
+    } else {
+      tgt = a_cur + t;
+    }
+    float xv[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) xv[q] = __shfl(tgt, q, 8);
+    const int key = e8p_scan<8>(xv, sub, tb, tn, tneg);
+    float out[8];
+    const int code = e8p_rebuild(xv, key, tb, tneg, out);
+    float mine = out[0];
+#pragma unroll
+    for (int q = 1; q < 8; ++q) mine = (sub == q) ? out[q] : mine;
+    Es[(lo + sub) * kPanelRows + r] = a_cur - mine;
+    if (valid) {
+      hat[row * c + lo + sub] = mine;
+      if (sub == 0) idx[row * groups + k] = (int64_t)code;
+    }
+    __syncthreads();
+    a_cur = a_nxt;
+    b_cur = b_nxt;
+  }
 }
 
 }  // namespace
@@ -175,6 +280,19 @@ int e8p_quantize_launch(const void* x, int64_t nvec, const void* grid_packed_abs
   int64_t* ix = reinterpret_cast<int64_t*>(idx);
   return lanes == 8 ? launch<e8p_quantize_kernel<8>>(grid, block, 0, stream, xf, nvec, tab, v, ix)
                     : launch<e8p_quantize_kernel<1>>(grid, block, 0, stream, xf, nvec, tab, v, ix);
+}
+
+int ldlq_panel_launch(const void* A, const void* B, const void* M, const void* P, int64_t m, int c,
+                      const void* grid_packed_abs, void* hat, void* idx, hipStream_t stream) {
+  if (m <= 0) return QUIP_OK;
+  if (c < 8 || c % 8 != 0 || c > kPanelMaxCols) return QUIP_ERR_BAD_SHAPE;
+  const int64_t blocks = (m + kPanelRows - 1) / kPanelRows;
+  if (blocks > 0x7fffffff) return QUIP_ERR_BAD_SHAPE;
+  return launch<ldlq_panel_kernel>(dim3((unsigned)blocks), dim3(256), ldlq_panel_lds_bytes(c), stream,
+                                   reinterpret_cast<const float*>(A), reinterpret_cast<const float*>(B),
+                                   reinterpret_cast<const float*>(M), reinterpret_cast<const float*>(P), m, c,
+                                   reinterpret_cast<const uint64_t*>(grid_packed_abs), reinterpret_cast<float*>(hat),
+                                   reinterpret_cast<int64_t*>(idx));
 }
 
 }  // namespace quip

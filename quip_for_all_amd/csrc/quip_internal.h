@@ -116,6 +116,10 @@ int had_transform_group_launch(const HadProblem* problems, int count, bool plane
 // quantise-time nearest E8P12 codeword (quantize.hip): x fp32 (nvec, 8) -> vals fp32 (nvec, 8), idx int64 (nvec)
 int e8p_quantize_launch(const void* x, int64_t nvec, const void* grid_packed_abs, void* vals, void* idx,
                         hipStream_t stream);
+// one LDLQ panel of c <= 128 columns (quantize.hip): A, B fp32 (m, c), M fp32 (c, c), P fp32 (c / 8, 8, 8) or null ->
+// hat fp32 (m, c), idx int64 (m, c / 8)
+int ldlq_panel_launch(const void* A, const void* B, const void* M, const void* P, int64_t m, int c,
+                      const void* grid_packed_abs, void* hat, void* idx, hipStream_t stream);
 // rows mode: up to e8p_gemv_mfma_max_rows(n, k) <= 5 activation rows against one matrix in one pass
 int e8p_gemv_mfma_max_rows(int n, int k, int mode = 0);   // mode: 0 E8P12, 64 D4 / HI, 40 E8P12RVQ3B (2k virtual)
 int e8p_gemv_mfma_rows_launch(const void* planes, const void* qidxs, const void* grid, void* y, int mrows, int n,

@@ -131,6 +131,32 @@ def block_LDL(L, b):
     return out
 
 
+PANEL_MAX_COLS = 128          # columns one ldlq_panel launch holds (csrc/quantize.hip: M (c, c) in LDS)
+_LDLQ_FUSED = None
+
+
+def parse_ldlq_fused(value, default=True):
+    """QUIP_LDLQ_FUSED as the other switches are read: unset or empty -> the default, "0" -> off, anything else -> on"""
+    if value is None or value.strip() == "":
+        return default
+    return value.strip() != "0"
+
+
+def ldlq_fused_enabled():
+    """read once per process"""
+    global _LDLQ_FUSED
+    if _LDLQ_FUSED is None:
+        _LDLQ_FUSED = parse_ldlq_fused(os.environ.get("QUIP_LDLQ_FUSED"))
+    return _LDLQ_FUSED
+
+
+def ldlq_route(Wr, cb):
+    """"panels" (one GEMM + one ldlq_panel launch per panel) for the E8P12 codebook on fp32 GPU tensors unless
+    QUIP_LDLQ_FUSED=0; "stepwise" (one chain of launches per column group) for everything else"""
+    fused = getattr(cb, "id", None) == "E8P12" and Wr.is_cuda and Wr.dtype == torch.float32 and ldlq_fused_enabled()
+    return "panels" if fused else "stepwise"
+
+
 def LDLQ(Wr, Hr, L, cb, quip_tune_iters=0, buf_cols=128):
     """Block LDL adaptive rounding (quant.py:105-135): going through the column groups of width cb.codesz
     from the right, group k is rounded to the codebook AFTER the rounding error of the groups to its right has
@@ -138,7 +164,15 @@ def LDLQ(Wr, Hr, L, cb, quip_tune_iters=0, buf_cols=128):
         hatW_k = Q( W_k + (W_{>k} - hatW_{>k}) L_{>k,k} ),
     so that (W - hatW) L stays small.  The feedback of everything right of the current panel of `buf_cols`
     columns is one GEMM per panel (the reference's LDLQ_buffered, quant.py:138-230); `quip_tune_iters` extra
-    sweeps re-round each group against the exact proxy gradient.  Returns (hatWr, Qidxs (m, n / codesz))."""
+    sweeps re-round each group against the exact proxy gradient.  Returns (hatWr, Qidxs (m, n / codesz)).
+    Two routes compute this (ldlq_route): LDLQ_panels for E8P12 on the GPU, LDLQ_stepwise otherwise."""
+    if ldlq_route(Wr, cb) == "panels":
+        return LDLQ_panels(Wr, Hr, L, cb, quip_tune_iters, buf_cols)
+    return LDLQ_stepwise(Wr, Hr, L, cb, quip_tune_iters, buf_cols)
+
+
+def LDLQ_stepwise(Wr, Hr, L, cb, quip_tune_iters=0, buf_cols=128):
+    """LDLQ with one cb.quantize() per column group: any codebook, any device, any float dtype"""
     m, n = Wr.shape
     b = cb.codesz
     assert n % b == 0
@@ -167,6 +201,61 @@ def LDLQ(Wr, Hr, L, cb, quip_tune_iters=0, buf_cols=128):
             vals, idx = cb.quantize(target)
             hatWr[:, lo:hi] = vals
             Qidxs[:, lo // b] = idx
+    return hatWr, Qidxs
+
+
+def panel_bounds(n, b, cols):
+    """[(lo, hi)] of the panels of `cols` columns from the right; the leftmost one may be shorter"""
+    panel = max(b, (min(cols, n) // b) * b)
+    out, hi = [], n
+    while hi > 0:
+        out.append((max(0, hi - panel), hi))
+        hi = out[-1][0]
+    return out
+
+
+def panel_operands(Wr, hatWr, err, Hr, Lb, Pinv, lo, hi, tune):
+    """(A, B, M, P) of one ldlq_panel call.  err = Wr - hatWr of the finished columns (main pass: right of the panel;
+    tune sweep: everywhere, with the panels further right already re-rounded)."""
+    n = Wr.shape[1]
+    if tune:
+        return (hatWr[:, lo:hi].contiguous(), err @ Hr[:, lo:hi], Hr[lo:hi, lo:hi].contiguous(),
+                Pinv[lo // 8:hi // 8])
+    A = Wr[:, lo:hi].contiguous()
+    B = err[:, hi:] @ Lb[hi:, lo:hi] if hi < n else torch.zeros_like(A)
+    return A, B, Lb[lo:hi, lo:hi].contiguous(), None
+
+
+def LDLQ_panels(Wr, Hr, L, cb, quip_tune_iters=0, buf_cols=128, panel_fn=None):
+    """LDLQ for the E8P12 codebook with a whole panel of up to 128 columns rounded in one launch
+    (torch.ops.quip_lib.ldlq_panel): per panel one GEMM for the feedback of everything outside it, then, for every row
+    independently, the recursion over the panel's groups with the panel's (c, c) coupling block in LDS.  The tune
+    sweep has the same shape: with A the old hatW of the panel, B = (W - hatW) H[:, panel] taken once at the start of
+    the panel, M = H[panel, panel] and P_k = inv(H[kk]) (batched once per call), the error of group j inside the panel
+    is its error at panel start plus A_j - hat_j, which is the reference's sweep (quant.py:190-228).
+    panel_fn(A, B, M, P) -> (hat, idx) replaces the launch (the host model in tests/test_quantize_model_host.py)."""
+    m, n = Wr.shape
+    b = cb.codesz
+    assert b == 8 and n % b == 0
+    if panel_fn is None:
+        grid = cb.grid_packed_abs
+        panel_fn = lambda A, B, M, P: torch.ops.quip_lib.ldlq_panel(A, B, M, P, grid)   # noqa: E731
+    Lb = block_LDL(L.clone(), b)
+    hatWr = torch.zeros_like(Wr)
+    err = torch.zeros_like(Wr)
+    Qidxs = torch.zeros(m, n // b, dtype=cb.idx_dtype, device=Wr.device)
+    bounds = panel_bounds(n, b, min(buf_cols, PANEL_MAX_COLS))
+    Pinv = None
+    if quip_tune_iters > 0:
+        g = torch.arange(n // b, device=Wr.device)
+        Pinv = torch.linalg.inv(Hr.reshape(n // b, b, n // b, b)[g, :, g, :]).contiguous()     # (n / 8, 8, 8)
+    for sweep in range(1 + quip_tune_iters):
+        for lo, hi in bounds:
+            A, B, M, P = panel_operands(Wr, hatWr, err, Hr, Lb, Pinv, lo, hi, tune=sweep > 0)
+            hat, idx = panel_fn(A, B, M, P)
+            hatWr[:, lo:hi] = hat
+            err[:, lo:hi] = Wr[:, lo:hi] - hat
+            Qidxs[:, lo // b:hi // b] = idx
     return hatWr, Qidxs
 
 

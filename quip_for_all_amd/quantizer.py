@@ -1,15 +1,18 @@
-"""Inference-side surface of the reference's quantizer.py: `QuipQuantizer.convert_model`,
-`to_dict` / `from_dict`, `save`, and `load_quantized_model` -- what a user needs to run an
-existing QuIP-for-all checkpoint through HF transformers with the MI355X QuantLinear.
+"""The reference's quantizer.py surface: `QuipQuantizer.quantize_model` (calibration data -> per-block
+Hessians -> QUIP.quant -> QuantLinear.pack -> save), `convert_model`, `to_dict` / `from_dict`, `save`, and
+`load_quantized_model` -- what a user needs to quantise a HF causal LM on one MI355X and to run the
+checkpoint through HF transformers with the MI355X QuantLinear.
 
 Same names, arguments, defaults, config-file format and post-load behaviour as the reference
-(quantizer.py:59-178 ctor / to_dict / convert_model, :718-756 save, :779-848
-load_quantized_model); the quantisation algorithm itself (`quantize_model`, quantizer.py:250-715)
-is out of scope (offline, not the hot path) and raises NotImplementedError.
+(quantizer.py:59-178 ctor / to_dict / convert_model, :250-715 quantize_model, :718-756 save, :779-848
+load_quantized_model).  Not built, and refused by name: dataset loaders by name, fine-tuning
+(ft_epochs > 0), merge_suv during quantisation, models dispatched over several devices.
 
 The checkpoint reader is self-contained (torch.load / safetensors, single file or sharded
 index) so that loading does not depend on accelerate's dispatch machinery."""
+import gc
 import json
+import logging
 import os
 from typing import Any, Dict, Iterable, List, Optional, Union
 
@@ -18,6 +21,8 @@ from torch import nn
 
 from .codebook import codebook_id
 from .qlinear import QuantLinear
+
+logger = logging.getLogger(__name__)
 
 QUIP_CONFIG = "quantization_config.json"      # constants.py
 BLOCK_PATTERNS = ["transformer.h", "model.decoder.layers", "gpt_neox.layers", "model.layers"]   # constants.py
@@ -56,6 +61,142 @@ def get_block_name_with_pattern(model: nn.Module) -> str:
         if any(pat in n for n in names):
             return pat
     raise ValueError("Block pattern could not be match. Pass `block_name_to_quantize` argument in `quantize_model`")
+
+
+def get_preceding_modules(model: nn.Module, module_name: str) -> List[str]:
+    """names of the modules that come before `module_name` in registration order (utils.py:96-119): for a HF causal LM
+    the embeddings in front of the block list"""
+    found, names = False, []
+
+    def walk(mod, prefix):
+        nonlocal found
+        for child_name, child in mod.named_children():
+            full = prefix + "." + child_name if prefix else child_name
+            if full == module_name:
+                found = True
+            if found:
+                return
+            if module_name.startswith(full + "."):
+                walk(child, full)
+            else:
+                names.append(full)
+    walk(model, "")
+    return names
+
+
+def _modules_outside(model: nn.Module, module_name: str) -> List[str]:
+    """names of the outermost modules that do not contain `module_name` (everything but the block list)"""
+    names = []
+
+    def walk(mod, prefix):
+        for child_name, child in mod.named_children():
+            full = prefix + "." + child_name if prefix else child_name
+            if full == module_name:
+                continue
+            if module_name.startswith(full + "."):
+                walk(child, full)
+            else:
+                names.append(full)
+    walk(model, "")
+    return names
+
+
+def get_seqlen(model: nn.Module) -> int:
+    """utils.py:128-138"""
+    cfg = model.config.to_dict() if hasattr(model, "config") else {}
+    for key in ("max_position_embeddings", "seq_length", "n_positions"):
+        if key in cfg:
+            return cfg[key]
+    return 2048
+
+
+DATASET_FORMS = ("a list of strings (tokenised with `tokenizer`, packed to model_seqlen)",
+                 "a list of token-id sequences or tensors",
+                 "a list of dicts with `input_ids` (and optionally `attention_mask`)")
+
+
+def _ids_row(ids) -> torch.Tensor:
+    t = torch.as_tensor(ids).detach().to("cpu", torch.long).reshape(-1)
+    if t.numel() == 0:
+        raise ValueError("calibration dataset: an empty token sequence")
+    return t
+
+
+def calibration_samples(dataset, tokenizer=None, seqlen: int = 2048) -> List[Dict[str, torch.Tensor]]:
+    """The constructor's `dataset` as the reference's sample list (data.py: one {"input_ids", "attention_mask"} of shape
+    (1, L <= seqlen) per sample, on the CPU).  Strings are tokenised, joined into one stream and cut into samples of
+    seqlen tokens (a rest shorter than seqlen is dropped unless it is all there is); id sequences and dicts are one
+    sample each, cut to seqlen."""
+    if dataset is None or isinstance(dataset, str):
+        raise NotImplementedError(
+            f"dataset={dataset!r}: dataset loaders by name (wikitext2, c4, ptb, ... of the reference's data.py) are not "
+            "part of this build.  Pass the calibration data itself as " + "; or ".join(DATASET_FORMS) + ".")
+    items = list(dataset)
+    if not items:
+        raise ValueError("calibration dataset is empty; pass " + "; or ".join(DATASET_FORMS))
+    seqlen = int(seqlen)
+    samples = []
+    if all(isinstance(x, str) for x in items):
+        if tokenizer is None:
+            raise ValueError("a dataset of strings needs a tokenizer")
+        stream = []
+        for text in items:
+            enc = tokenizer(text)
+            stream.append(_ids_row(enc["input_ids"] if hasattr(enc, "keys") else enc))
+        stream = torch.cat(stream)
+        cuts = list(range(0, stream.numel() - seqlen + 1, seqlen)) or [0]
+        for lo in cuts:
+            ids = stream[lo:lo + seqlen][None]
+            samples.append({"input_ids": ids, "attention_mask": torch.ones_like(ids)})
+        return samples
+    for x in items:
+        if isinstance(x, str):
+            raise ValueError("calibration dataset mixes strings with other forms")
+        if hasattr(x, "keys"):
+            if "input_ids" not in x:
+                raise ValueError("calibration dataset: a dict without `input_ids`")
+            ids = _ids_row(x["input_ids"])[:seqlen][None]
+            mask = x.get("attention_mask") if hasattr(x, "get") else None
+            mask = torch.ones_like(ids) if mask is None else _ids_row(mask)[:seqlen][None]
+            if mask.shape != ids.shape:
+                raise ValueError("calibration dataset: attention_mask and input_ids differ in length")
+        else:
+            ids = _ids_row(x)[:seqlen][None]
+            mask = torch.ones_like(ids)
+        samples.append({"input_ids": ids, "attention_mask": mask})
+    return samples
+
+
+def calibration_batches(samples, nsamples: int, batch_size: int) -> List[Dict[str, torch.Tensor]]:
+    """the first `nsamples` samples in batches of `batch_size` (data.py:27-82); a shorter last batch is kept"""
+    if batch_size < 1 or nsamples < 1:
+        raise ValueError("nsamples and batch_size must be positive")
+    samples = samples[:nsamples]
+    batches = []
+    for lo in range(0, len(samples), batch_size):
+        part = samples[lo:lo + batch_size]
+        if len({s["input_ids"].shape[1] for s in part}) != 1:
+            raise ValueError(f"calibration samples {lo} .. {lo + len(part) - 1} differ in length: one batch needs "
+                             "sequences of one length (pad or cut them, or use batch_size=1)")
+        batches.append({k: torch.cat([s[k] for s in part], dim=0) for k in ("input_ids", "attention_mask")})
+    return batches
+
+
+def _to_device(obj, device):
+    """tensors inside (nested) tuples / lists / dicts to `device`; everything else as it is"""
+    if isinstance(obj, torch.Tensor):
+        return obj.to(device)
+    if isinstance(obj, tuple):
+        return tuple(_to_device(o, device) for o in obj)
+    if isinstance(obj, list):
+        return [_to_device(o, device) for o in obj]
+    if isinstance(obj, dict):
+        return {k: _to_device(v, device) for k, v in obj.items()}
+    return obj
+
+
+class _FirstBlockReached(Exception):
+    pass
 
 
 def recurse_getattr(obj, attr: str):
@@ -107,12 +248,155 @@ class QuipQuantizer:
     def from_dict(cls, config_dict: Dict[str, Any]):
         return cls(**config_dict)                                                      # quantizer.py:150-163
 
-    def quantize_model(self, *args, **kwargs):
-        raise NotImplementedError("The model-level calibration pipeline (dataset, per-block Hessians, fine-tuning; "
-                                  "quantizer.py:250-715) is outside the scope of the MI355X inference path: quantise "
-                                  "with the reference and load the result with load_quantized_model().  The "
-                                  "layer-level pieces are here: quip_for_all_amd.quip.QUIP (Hessian, incoherence "
-                                  "processing, LDLQ on the HIP codebook search) -> QuantLinear.pack().")
+    def _refuse_unbuilt(self, model):
+        """everything this build does not do, by name, before the model is touched"""
+        if self.dataset is None or isinstance(self.dataset, str):
+            calibration_samples(self.dataset)                     # raises NotImplementedError naming the accepted forms
+        if self.ft_epochs > 0:
+            raise NotImplementedError(
+                f"ft_epochs={self.ft_epochs}: block-wise and end-to-end fine-tuning (quantizer.py:500-560, 597-702) are "
+                "not part of this build; pass ft_epochs=0")
+        if self.merge_suv:
+            raise NotImplementedError("merge_suv=True during quantisation (quantizer.py:413-424, 579-595) is not part of "
+                                      "this build; pass merge_suv=False (merge_suv checkpoints of the reference still load)")
+        if getattr(model, "hf_device_map", None) is not None:
+            raise NotImplementedError("the model has an hf_device_map (dispatched over devices / offloaded): quantisation "
+                                      "here runs on a single device; load the model without a device_map")
+
+    def capture_first_block_inputs(self, model: nn.Module, batches, device):
+        """Run the model on every batch up to its first block and keep what that block is called with: the hidden
+        states and every keyword argument (position ids / embeddings, masks, ...), with a forward pre-hook that ends the
+        forward there (quantizer.py:325-395).  Kept on the CPU unless cache_on_gpu."""
+        if self.block_name_to_quantize is None:
+            self.block_name_to_quantize = get_block_name_with_pattern(model)
+        if self.module_name_preceding_first_block is None:
+            self.module_name_preceding_first_block = get_preceding_modules(model, self.block_name_to_quantize)
+        blocks = recurse_getattr(model, self.block_name_to_quantize)
+        origin_dtype, origin_device = model.dtype, next(model.parameters()).device
+        keep = (lambda t: t) if self.cache_on_gpu else (lambda t: _to_device(t, "cpu"))
+        preceding = set(self.module_name_preceding_first_block)
+        outside = _modules_outside(model, self.block_name_to_quantize)
+        for name in preceding:
+            if recurse_getattr(model, name) is None:
+                raise ValueError(f"Module {name} was not found in model")
+        for name in list(preceding) + [n for n in outside if n not in preceding]:
+            mod = recurse_getattr(model, name).to(device)
+            if name in preceding:
+                mod.float()                # the blocks run in fp32: their input must be fp32
+        blocks[0].to(device).float()
+        inputs, kwargs_list = [], []
+
+        def store(_, args, kwargs):
+            hidden = args[0] if args else kwargs.get("hidden_states")
+            if hidden is None:
+                raise ValueError("No input value found in the forward pass of the first block")
+            inputs.append(keep(hidden))
+            kwargs_list.append({k: keep(v) for k, v in kwargs.items() if k != "hidden_states"})
+            raise _FirstBlockReached
+
+        handle = blocks[0].register_forward_pre_hook(store, with_kwargs=True)
+        try:
+            for batch in batches:
+                try:
+                    model(**{k: v.to(device) for k, v in batch.items()})
+                except _FirstBlockReached:
+                    pass
+        finally:
+            handle.remove()
+            for name in outside:
+                mod = recurse_getattr(model, name)
+                if name in preceding:
+                    mod.to(origin_dtype)
+                mod.to(origin_device)
+            blocks[0].to(origin_dtype).to(origin_device)
+        if len(inputs) != len(batches):
+            raise RuntimeError("the first block was not reached on every calibration batch")
+        return inputs, kwargs_list
+
+    @torch.no_grad()
+    def quantize_model(self, model: nn.Module, tokenizer: Any = None, save_dir: str = ""):
+        """Quantise every linear layer inside the transformer blocks of `model` with the calibration data given to the
+        constructor, block by block on one device (quantizer.py:250-715 without fine-tuning):
+        capture the first block's inputs; per block, in fp32 on the device: Hessians of every linear from forward hooks
+        (QUIP.add_batch), the block's outputs -- taken BEFORE it is quantised -- become the next block's inputs,
+        QUIP.quant per linear, the linear replaced by a packed QuantLinear, the block back to the model's dtype and
+        device.  Then model.config.quantization_config, `is_quantized`, and `save` / `tokenizer.save_pretrained` when
+        save_dir is given.  The returned model runs as load_quantized_model(save_dir) does (same post-load step).
+        `dataset`: see calibration_samples; model_seqlen=None takes the model's."""
+        from .quip import QUIP
+        self._refuse_unbuilt(model)
+        if isinstance(tokenizer, str):
+            from transformers import AutoTokenizer
+            tokenizer = AutoTokenizer.from_pretrained(tokenizer)
+        seqlen = self.model_seqlen if self.model_seqlen is not None else get_seqlen(model)
+        samples = calibration_samples(self.dataset, tokenizer, seqlen)
+        batches = calibration_batches(samples, self.nsamples, self.batch_size)
+        if not torch.cuda.is_available():
+            raise RuntimeError("No GPU found. A GPU is needed to quantize model.")            # quantizer.py:799-801 likewise
+        self.model_seqlen = seqlen
+        model.eval()
+        has_config = hasattr(model, "config")
+        if has_config:
+            use_cache = getattr(model.config, "use_cache", None)
+            model.config.use_cache = False
+        origin_dtype, origin_device = model.dtype, next(model.parameters()).device
+        device = origin_device if origin_device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+        layer_inputs, layer_kwargs = self.capture_first_block_inputs(model, batches, device)
+        blocks = recurse_getattr(model, self.block_name_to_quantize)
+        torch.cuda.empty_cache()
+        for i, block in enumerate(blocks):
+            logger.info("quantizing block %s %d/%d", self.block_name_to_quantize, i + 1, len(blocks))
+            block = block.to(device).float()
+            layers = get_layers(block, skip=self.modules_to_not_convert)
+            quant_method = {name: QUIP(layer, self.codebook) for name, layer in layers.items()}
+            handles = [layer.register_forward_hook(
+                lambda _, inp, out, name=name: quant_method[name].add_batch(inp[0].data, out.data))
+                for name, layer in layers.items()]
+            layer_outputs = []
+            try:
+                for hidden, kwargs in zip(layer_inputs, layer_kwargs):
+                    out = block(_to_device(hidden, device), **_to_device(kwargs, device))
+                    out = out[0] if isinstance(out, (tuple, list)) else out
+                    layer_outputs.append(out if self.cache_on_gpu else out.cpu())
+            finally:
+                for h in handles:
+                    h.remove()
+            attrs = {}
+            for name in layers:
+                attrs[name] = quant_method[name].quant(
+                    rescale_WH=self.rescale_WH, sigma_reg=self.sigma_reg, quip_tune_iters=self.quip_tune_iters,
+                    scale_override=self.scale_override, use_rand=self.use_rand, per_channel=self.per_channel)
+                quant_method[name].free()
+            self._replace_by_quant_layers(block, set(layers))
+            for name, layer in layers.items():
+                quant_layer = recurse_getattr(block, name)
+                quant_layer.pack(layer, attrs[name])
+                quant_layer.train(block.training)        # a new module starts in training mode; the model is in eval()
+                layer.to("cpu")
+                quant_layer.to(device)
+            blocks[i] = block.to(origin_dtype).to(origin_device)
+            for name in layers:
+                quant_layer = recurse_getattr(blocks[i], name)
+                quant_layer.weight_dtype = origin_dtype
+                if not self.per_channel:      # the scalar scale stays fp32, as in a loaded checkpoint
+                    quant_layer.Wscale = attrs[name]["w_scale"].to(torch.float32).reshape(()).to(origin_device)
+            del layers, quant_method, attrs
+            layer_inputs, layer_outputs = layer_outputs, []
+            gc.collect()
+            torch.cuda.empty_cache()
+        del layer_inputs, layer_kwargs
+        model.is_quantized = True
+        if has_config:
+            model.config.use_cache = use_cache
+            model.config.quantization_config = self.to_dict()
+        if save_dir:
+            self.save(model, save_dir)
+            if tokenizer is not None:
+                tokenizer.save_pretrained(save_dir)
+        # what load_quantized_model does after filling the layers (the saved tensors are the un-finalised ones)
+        finalize_quant_layers(model, merge_suv=False)
+        torch.cuda.empty_cache()
+        return model
 
     def convert_model(self, model: nn.Module) -> nn.Module:
         """replace every linear layer inside the transformer blocks by an (empty) QuantLinear

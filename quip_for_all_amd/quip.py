@@ -1,8 +1,8 @@
 """Layer-level quantiser with the reference's class name and attr contract (quip.py:17-200): accumulate
 the proxy Hessian of one nn.Linear from calibration inputs, incoherence-process (random signs + randomised
 Hadamard on both sides), LDLQ-round against a codebook, and hand back what QuantLinear.pack() consumes.
-Host logic in torch; the codebook search inside LDLQ is the HIP kernel behind cb.quantize().  The model-level
-calibration pipeline of the reference (quantizer.py:250-715) stays out of scope."""
+Host logic in torch; LDLQ for E8P12 rounds a panel of 128 columns per launch (quant.LDLQ_panels, csrc/quantize.hip), the
+other codebooks go through cb.quantize() per column group.  QuipQuantizer.quantize_model drives this class over a model."""
 import math
 
 import torch

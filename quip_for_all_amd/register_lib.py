@@ -1067,3 +1067,41 @@ for _cb_name, _cb in _CODEBOOKS.items():
         _reg_fake(_cb_name + _n, lambda x, Q, *tables: x.new_empty((x.shape[0], Q.shape[0]), dtype=torch.float16))
     _reg_fake(f"decompress_{_cb_name}_origorder", lambda Q, *tables, _c=_cb.cols:
               Q.new_empty((Q.shape[0], Q.shape[1] * _c[0] // _c[1]), dtype=torch.float16))
+
+
+# ---- quantise-time: one LDLQ panel in one launch (csrc/quantize.hip) ------------------------------------
+# Defined beside the table above like the ops of lora.py / score.py (_SCHEMAS is the reference's op surface plus the
+# inference path's; tests/test_fakes_meta.py pins exactly that set).
+LDLQ_PANEL_MAX_COLS = 128
+
+
+def _ldlq_panel_cuda(A, B, M, P, grid):
+    """A, B (m, c) fp32; M (c, c) fp32; P (c / 8, 8, 8) fp32 or None -> (hat (m, c) fp32, idx (m, c / 8) int64)"""
+    _need(A.is_cuda and A.dim() == 2 and A.dtype == torch.float32 and A.is_contiguous(),
+          "ldlq_panel: A must be a contiguous float32 (m, c) CUDA tensor")
+    m, c = A.shape
+    _need(c >= 8 and c % 8 == 0 and c <= LDLQ_PANEL_MAX_COLS,
+          f"ldlq_panel: c = {c} (a multiple of 8 in 8 .. {LDLQ_PANEL_MAX_COLS})")
+    _need(B.dtype == torch.float32 and B.is_contiguous() and B.device == A.device and tuple(B.shape) == (m, c),
+          "ldlq_panel: B must be contiguous float32 with A's shape on A's device")
+    _need(M.dtype == torch.float32 and M.is_contiguous() and M.device == A.device and tuple(M.shape) == (c, c),
+          "ldlq_panel: M must be contiguous float32 (c, c) on A's device")
+    _need(P is None or (P.dtype == torch.float32 and P.is_contiguous() and P.device == A.device
+                        and tuple(P.shape) == (c // 8, 8, 8)),
+          "ldlq_panel: P must be contiguous float32 (c / 8, 8, 8) on A's device, or None")
+    g = _grid_i64(grid, A)
+    hat = torch.empty_like(A)
+    idx = _empty((m, c // 8), dtype=torch.int64, device=A.device)
+    with torch.cuda.device(A.device):
+        capi.check(capi.lib().quip_ldlq_panel_f32(A.data_ptr(), B.data_ptr(), M.data_ptr(), _ptr(P), m, c, g.data_ptr(),
+                                                  hat.data_ptr(), idx.data_ptr(), _stream(A)), "quip_ldlq_panel_f32")
+    return hat, idx
+
+
+try:
+    _lib.define("ldlq_panel(Tensor A, Tensor B, Tensor M, Tensor? P, Tensor grid) -> (Tensor, Tensor)")
+    _lib.impl("ldlq_panel", _ldlq_panel_cuda, "CUDA")
+    _reg_fake("ldlq_panel", lambda A, B, M, P, grid:
+              (torch.empty_like(A), A.new_empty((A.shape[0], A.shape[1] // 8), dtype=torch.int64)))
+except RuntimeError:
+    pass
