@@ -221,21 +221,29 @@ struct BLds {
                                                              // of rounds 3-4, 8 KB here, lives in registers now.)
   static constexpr int kQkv = kDescN + 256;                  // fp16 [3][128]: this head's q, k, v; [128] attention output
   static constexpr int kCs = kQkv + 4 * HD * 2;              // float [2][128]: the rotary row of this token (cos | sin), the same for every block
-  // ONE transient area for everything that lives between two products (E8P12: T1 x 32 + T2 x 16 = 96 KB of tables leave 50.3 KB).
+  // ONE transient area for everything that lives between two products (E8P12 on byte tables: T1 x 32 + T2 x 16 = 96 KB of tables leave
+  // 58.1 KB; nibble mode and D4, 64 KB of tables: 90.1 KB).
   // In time: the transforms' exchange buffers (16.5 KB per transform from the base: 1, 2 or -- attention -- 3) -> digit planes
   // of the consumers (12 / 24 KB from the base, written after the transforms' last reads) | attention partials; for the MLP:
   // planes [0, 24 K) + the K x K factor image [24 K, 36 K) + the row owners' vectors [36 K, 48 K) (both stored while the gate / up
-  // edge's exchange buffer is alive: they lie behind it) -> row owners: rows on the way out [8 K, 9 K) (the inbox rows go from memory into registers) ->
+  // edge's exchange buffer is alive: they lie behind it; kTwoBuf: behind its TWO buffers, at 33 K and 45 K) -> row owners: rows on the way out [8 K, 9 K) (the inbox rows go from memory into registers) ->
   // (the gathered rows never touch LDS: they are the K-mix's A operands) -> down's planes [0, 35.1 K), over the factor image once
   // every wave's K-mix has read it.
   static constexpr int kArea = kCs + 2 * HD * 4;
   static constexpr int kBufBytes = ((had::buf_floats(HID) * 4) + 15) & ~15;
   static constexpr int kAreaBytes = (160 * 1024 - kArea) & ~15;
   static constexpr int kBuf0 = kArea;
+  // A SECOND exchange buffer for the 4096-wide edges (E8P12 / D4 rows of the plain width, shape 0): fwd exchanges through kBuf0, rev
+  // through kBuf1 (one buffer per consumer: two for the straddling workgroups' q / k / v edge), the planes land on kBuf0 -- the
+  // barriers that only ordered the reuse of ONE buffer are gone.  The virtual rows of RVQ / HI (planes of twice the
+  // width) and G8's map (factor image at 32 K, stash at 17 K) have no room for it: kBuf1 == kBuf0 there, and edge() keeps every barrier.
+  static constexpr bool kTwoBuf = !G8 && !RVQ;
+  static constexpr int kBuf1 = kTwoBuf ? kBuf0 + kBufBytes : kBuf0;
   static constexpr int kHadElems = 2 * KKP + KP16 * KPS;
   static constexpr int kStage = kArea + 8 * 1024;            // MLP row owners: their RPO rows as fp16 [column][RPO], on the way out (1 KB)
   // fp16 image of the three K x K factors (12 KB; G8: 20.3 KB), behind the planes of gate / up (G8: at 32 K)
-  static constexpr int kHad = kArea + (G8 ? 32 * 1024 : 2 * 3 * PSH);
+  // (kTwoBuf: behind the gate / up edge's SECOND exchange buffer as well)
+  static constexpr int kHad = kArea + (G8 ? 32 * 1024 : (kTwoBuf && 2 * kBufBytes > 2 * 3 * PSH ? 2 * kBufBytes : 2 * 3 * PSH));
   // MLP row owners: SV_gate / SV_up / SU_down of their rows (3 KB): behind the factor image; G8: at 17 K (free while they are alive:
   // the gate / up edge's exchange buffer ends at 16.5 K, the planes of the ONE consumer at 12.5 K, the owners' staging at 9 K)
   static constexpr int kStash = G8 ? kArea + 17 * 1024 : kHad + 12 * 1024;
@@ -253,6 +261,12 @@ struct BLds {
                 "transient area");
   // (both are written while the gate / up edge's ONE exchange buffer is alive, in front of its planes)
   static_assert(kHad >= kBuf0 + kBufBytes && kStash >= kBuf0 + kBufBytes && kStash >= kArea + 3 * PSH, "factor image and owner vectors: clear of the gate / up edge");
+  // the second buffer: behind the first and behind ONE consumer's planes (which land while rev's reads of it may still be on their
+  // way); two of them (the straddlers' q / k / v edge) inside the area; the factor image and the owner vectors behind the gate / up
+  // edge's one
+  static_assert(!kTwoBuf || (kBuf1 % 16 == 0 && kBuf1 >= kBuf0 + kBufBytes && kBuf1 >= kArea + 3 * PSH && kBuf1 + 2 * kBufBytes <= kArea + kAreaBytes &&
+                             kHad >= kBuf1 + kBufBytes && kStash >= kBuf1 + kBufBytes),
+                "second exchange buffer of the 4096-wide edges");
 };
 #if QUIP_BLOCK_G8
 static_assert(BLds<24>::kBytes <= 160 * 1024 && BLds<4>::kBytes <= 160 * 1024, "LDS budget");
@@ -630,7 +644,22 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
   // sv_prev, ln, su0, su1: vectors PERMUTED by the host to the strided layout, p[8 t + k] = v[t + 512 k].
   // `rev` adds in another order than the stand-alone kernels: the launch is no longer bit identical to the stage-wise step
   // (tests/test_gpu_block_engine.py states the bound, tests/test_gpu_decode.py the distance to the float64 model).
+  // Barriers of an edge (DESIGN 4.11 has the table).  With ONE exchange buffer (E2 false: RVQ / HI, G8) an edge executes six; two of
+  // them order data that crosses waves -- the one between the exchange's write and its reads, in fwd and in rev.  E2: fwd exchanges
+  // through kBuf0, rev through kBuf1, the planes land on kBuf0, and
+  //   fwd's leading barrier goes: everything that read or wrote [kBuf0, kBuf1 + 2 buffers) before this edge did so in front of a
+  //     barrier every wave has passed (the producer's pre-publish barrier; block 0: the one behind the descriptor's copy);
+  //   rev's leading barrier goes: it kept rev's writes off fwd's strided reads of the SAME buffer;
+  //   rev's barrier behind its reads goes where the planes stay clear of kBuf1 -- ONE consumer (3 PSH <= kBufBytes).  Two consumers'
+  //     planes (the straddling workgroups 85 / 170, 6 PSH) reach into kBuf1: they keep it (a workgroup-uniform branch);
+  //   the barrier behind the planes becomes the wave's own LDS wait: thread t writes dword t (byte tables: bytes [8 t, 8 t + 8)) of
+  //     each (half-)plane, wave W therefore bytes [256 W, +256) ([512 W, +512)) -- and xlane + the offsets of nib_fragments
+  //     (16 (s & 1) + 128 (s >> 1) + 32 q, 16 bytes) / item_fragments (16 t | 256 + 16 (t - 4), + 64 q) stay inside exactly that
+  //     range of the same rows, for both plane sets.  The products behind the edge write nothing into the area, and meet at their
+  //     pre-publish barrier, behind which shs[] is read; red[] is read behind rev's inner barrier and next written behind that one.
+  constexpr bool E2 = B::kTwoBuf;
   float* xbuf = reinterpret_cast<float*>(smem + B::kBuf0);
+  float* xbuf1 = reinterpret_cast<float*>(smem + B::kBuf1);
   auto planes_nat = [&](const float (&v)[8], float scale, int sh, uint32_t base) {
 #pragma clang fp contract(off)
     const float p2 = as_f32((uint32_t)(sh + 127) << 23);
@@ -712,7 +741,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
       if constexpr (NC > 0) asm volatile("" : "+v"(pln), "+v"(psu0), "+v"(psu1));
       after_gather();
       ESTAMP(0);
-      hadw::fwd<12, 1, true>(v, xbuf, tid);
+      hadw::fwd<12, 1, true, !E2>(v, xbuf, tid);
       ESTAMP(1);
       float svf[8];
       had::unpack8(u4(psv), svf);
@@ -760,7 +789,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         n1 = had::wave_reduce_to_lane63<false>(n1);
         if (lane_ == 63) { red[wave] = ssw; red[8 + wave] = n0; red[16 + wave] = n1; }
         ESTAMP(2);
-        hadw::rev<12, 2, true, true>(v, xbuf, tid);
+        hadw::rev<12, 2, true, true, !E2>(v, xbuf1, tid);      // (two consumers' planes reach into kBuf1: the barrier behind the reads stays)
         ESTAMP(3);
         drip2();
         const float tot = red_sum8(0);
@@ -784,7 +813,7 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         n0 = had::wave_reduce_to_lane63<false>(n0);
         if (lane_ == 63) { red[wave] = ssw; red[8 + wave] = n0; }
         ESTAMP(2);
-        hadw::rev<12, 1, true, true>(v, xbuf, tid);
+        hadw::rev<12, 1, true, !E2, !E2>(v, xbuf1, tid);
         ESTAMP(3);
         drip2();
         const float tot = red_sum8(0);
@@ -793,7 +822,9 @@ __global__ __launch_bounds__(kThreads) void decode_block_kernel(BlockArgs a) {
         planes_nat(v[0], s0, sh0, (uint32_t)B::kArea);
         if (tid == 0) shs[0] = sh0;
       }
-      had::wg_barrier<true>();
+      // E2: a wave multiplies against the plane bytes it wrote itself (above) -- its own LDS counter orders that
+      if constexpr (E2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      else had::wg_barrier<true>();
       ESTAMP(4);
     }
     // (opaque from here on: otherwise the fp32 images of h made above stay alive until the next edge's update)

@@ -116,8 +116,10 @@ struct Geo {
   __device__ static __forceinline__ int str(int t) { return t + (t >> 5); }
 };
 
-// natural -> strided (ascending index bits)
-template <int LOGN, int NT, bool RAW>
+// natural -> strided (ascending index bits).  LEAD: the barrier in front of the exchange write ("the buffer's earlier readers
+// are done").  A caller whose buffer nobody has read or written since a barrier that every wave has passed (decode_block.hip's
+// edge(): DESIGN 4.11's table) does without it.
+template <int LOGN, int NT, bool RAW, bool LEAD = true>
 __device__ __forceinline__ void fwd(float (&v)[NT][Geo<LOGN>::EPT], float* xbuf, int tid) {
   using G = Geo<LOGN>;
   constexpr int E = G::EPT;
@@ -126,7 +128,7 @@ __device__ __forceinline__ void fwd(float (&v)[NT][Geo<LOGN>::EPT], float* xbuf,
   for (int i = 0; i < NT; ++i) reg_stages<E, 1>(v[i]);
 #pragma unroll
   for (int i = 0; i < NT; ++i) lane_stages<E, 0, 6>(v[i], lane);          // index bits RB .. RB + 5
-  had::wg_barrier<RAW>();
+  if constexpr (LEAD) had::wg_barrier<RAW>();
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
     float* b = xbuf + i * G::kBufFloats + G::nat(tid);
@@ -145,15 +147,18 @@ __device__ __forceinline__ void fwd(float (&v)[NT][Geo<LOGN>::EPT], float* xbuf,
 }
 
 // strided -> natural.  SYNC_AFTER_READ: one more barrier right behind the LDS reads -- the caller writes over the exchange
-// buffer as soon as rev returns (digit planes), and the barrier's skew hides under the stages that follow it here
-template <int LOGN, int NT, bool RAW, bool SYNC_AFTER_READ = false>
+// buffer as soon as rev returns (digit planes), and the barrier's skew hides under the stages that follow it here.
+// LEAD: as fwd's -- a caller that hands rev a buffer of its own (not the one fwd's strided reads may still be on) passes false,
+// and one whose next writes stay clear of that buffer leaves SYNC_AFTER_READ off as well: ONE barrier, the one between the
+// exchange's write and its read.
+template <int LOGN, int NT, bool RAW, bool SYNC_AFTER_READ = false, bool LEAD = true>
 __device__ __forceinline__ void rev(float (&v)[NT][Geo<LOGN>::EPT], float* xbuf, int tid) {
   using G = Geo<LOGN>;
   constexpr int E = G::EPT;
   const int lane = tid & 63;
 #pragma unroll
   for (int i = 0; i < NT; ++i) reg_stages<E, 1>(v[i]);                      // index bits 9 .. LOGN - 1 (all bits of k)
-  had::wg_barrier<RAW>();
+  if constexpr (LEAD) had::wg_barrier<RAW>();
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
     float* b = xbuf + i * G::kBufFloats + G::str(tid);
