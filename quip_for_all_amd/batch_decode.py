@@ -44,53 +44,27 @@ def rope_attn_batched_workspace(batch, heads, head_dim, device):
                        device=device)
 
 
-def _check_batched_operands(q, k, v, cos, sin, pos, kcache, vcache, workspace):
-    """the operand checks of both batched decode launches -> (B, heads, kv_heads, hd, max_len)"""
-    need = _R._need
-    for t in (q, k, v, kcache, vcache):
-        need(t.dtype == torch.float16 and t.is_contiguous() and t.is_cuda and t.device == q.device,
-             "rope_attn_decode_batched: fp16 contiguous tensors on one CUDA device")
-    need(cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
-         and cos.device == q.device and sin.device == q.device, "cos / sin must be contiguous float32 on q's device")
-    need(q.dim() == 3 and kcache.dim() == 4, "rope_attn_decode_batched: q (B, heads, hd), caches (B, kv_heads, max_len, hd)")
-    B, heads, hd = q.shape
-    kvh, max_len = kcache.shape[1], kcache.shape[2]
-    need(pos.dtype == torch.int64 and tuple(pos.shape) == (B,) and pos.is_contiguous() and pos.device == q.device,
-         "pos must be a contiguous int64 (B,) tensor on q's device")
-    need(tuple(k.shape) == (B, kvh, hd) and tuple(v.shape) == (B, kvh, hd) and tuple(kcache.shape) == (B, kvh, max_len, hd)
-         and tuple(vcache.shape) == tuple(kcache.shape) and tuple(cos.shape) == (max_len, hd)
-         and tuple(sin.shape) == (max_len, hd), "rope_attn_decode_batched: shape mismatch")
-    if workspace is not None:
-        need(workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == q.device
-             and workspace.numel() >= capi.lib().quip_rope_attn_batched_workspace_bytes(B, heads, hd),
-             "workspace: use rope_attn_batched_workspace(batch, heads, head_dim, device)")
-    return B, heads, kvh, hd, max_len
+def _decode_batched(entry, q, k, v, cos, sin, pos, kcache, vcache, workspace, window, *more):
+    """the checks and the call of the contiguous batched decode launches; more: what an entry takes behind the stream"""
+    B, heads, kvh, hd, max_len, _ = _R._check_attn("rope_attn_decode_batched", "batched", q, k, v, cos, sin, pos, kcache, vcache)
+    _R._check_attn_workspace(workspace, q, B, heads, hd)
+    out = torch.empty_like(q)
+    _R._attn_call(entry, q, *_R._ptrs(q, k, v, cos, sin, pos, kcache, vcache, out), B, heads, kvh, hd, max_len,
+                  1.0 / math.sqrt(hd), int(window), _R._ptr(workspace), _R._stream(q), *more)
+    return out
 
 
 def _rope_attn_decode_batched_cuda(q, k, v, cos, sin, pos, kcache, vcache, workspace=None, window=0):
-    B, heads, kvh, hd, max_len = _check_batched_operands(q, k, v, cos, sin, pos, kcache, vcache, workspace)
-    out = torch.empty_like(q)
-    with torch.cuda.device(q.device):
-        capi.check(capi.lib().quip_rope_attn_decode_batched_f16(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
-            kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), B, heads, kvh, hd, max_len, 1.0 / math.sqrt(hd),
-            int(window), _R._ptr(workspace), _R._stream(q)), "quip_rope_attn_decode_batched_f16")
-    return out
+    return _decode_batched("quip_rope_attn_decode_batched_f16", q, k, v, cos, sin, pos, kcache, vcache, workspace, window)
 
 
 def _rope_attn_decode_batched_start_cuda(q, k, v, cos, sin, pos, start, kcache, vcache, workspace=None, window=0):
     """rope_attn_decode_batched for sequences whose tokens are cache rows start[b] .. pos[b] (csrc/decode_glue.hip,
     StartAttnArgs): rotary position of row t is t - start[b], rows below start[b] are never read"""
-    B, heads, kvh, hd, max_len = _check_batched_operands(q, k, v, cos, sin, pos, kcache, vcache, workspace)
-    _R._need(start.dtype == torch.int64 and tuple(start.shape) == (B,) and start.is_contiguous() and start.device == q.device,
-             "start must be a contiguous int64 (B,) tensor on q's device")
-    out = torch.empty_like(q)
-    with torch.cuda.device(q.device):
-        capi.check(capi.lib().quip_rope_attn_decode_batched_start_f16(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
-            kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), B, heads, kvh, hd, max_len, 1.0 / math.sqrt(hd),
-            int(window), _R._ptr(workspace), _R._stream(q), start.data_ptr()), "quip_rope_attn_decode_batched_start_f16")
-    return out
+    _R._need(start.dtype == torch.int64 and tuple(start.shape) == tuple(pos.shape) and start.is_contiguous()
+             and start.device == q.device, "start must be a contiguous int64 (B,) tensor on q's device")      # (pos: checked below)
+    return _decode_batched("quip_rope_attn_decode_batched_start_f16", q, k, v, cos, sin, pos, kcache, vcache, workspace, window,
+                           start.data_ptr())
 
 
 def _argmax_step_batched_cuda(logits, tok, pos):

@@ -704,6 +704,34 @@ int quip_block_engine_g8_supported(int32_t hidden, int32_t heads, int32_t kv_hea
 }
 size_t quip_block_engine_g8_workspace_bytes(void) { return block_engine_g8_workspace_bytes(); }
 
+// ---- the attention entry points ------------------------------------------------------------------------------------------
+// Each one is its own pointer lists and one call.  attn_refusal answers what is wrong with the pointers and the window in
+// the order the ABI promises: NULL (the nine operands of AttnIO and `more`), then MISALIGNED (the 16-, 8- and 4-byte lists;
+// the optional workspace: 16), then a negative window (BAD_SHAPE).  The launcher (quip_internal.h) answers the sizes,
+// BAD_SHAPE before UNSUPPORTED.  The lists differ from entry to entry and are part of the ABI as they are: the bs = 1
+// entries do not look at the alignment of pos, only the prompt-side entries at that of out / cos / sin, and those leave
+// the window to their launcher.
+namespace {
+using Ptrs = std::initializer_list<const void*>;
+bool any_null(Ptrs ps) {
+  for (const void* p : ps)
+    if (!p) return true;
+  return false;
+}
+bool any_off(Ptrs ps, uintptr_t mask) {
+  for (const void* p : ps)
+    if (reinterpret_cast<uintptr_t>(p) & mask) return true;
+  return false;
+}
+int attn_refusal(const AttnIO& io, Ptrs more, Ptrs a16, Ptrs a8 = {}, Ptrs a4 = {}, const void* workspace = nullptr,
+                 int window = 0) {
+  if (any_null({io.q, io.k, io.v, io.cos, io.sin, io.pos, io.kcache, io.vcache, io.out}) || any_null(more))
+    return QUIP_ERR_NULL_POINTER;
+  if (any_off(a16, 15) || any_off(a8, 7) || any_off(a4, 3) || any_off({workspace}, 15)) return QUIP_ERR_MISALIGNED;
+  return window < 0 ? QUIP_ERR_BAD_SHAPE : QUIP_OK;
+}
+}  // namespace
+
 size_t quip_rope_attn_workspace_bytes(int32_t heads, int32_t head_dim) {
   return heads > 0 && head_dim > 0 ? rope_attn_workspace_bytes(heads, head_dim) : 0;
 }
@@ -721,13 +749,10 @@ int quip_rope_attn_decode_window_f16(const void* q, const void* k, const void* v
                                      void* out, int32_t heads, int32_t kv_heads, int32_t head_dim,
                                      int32_t max_len, float scale, int32_t window, void* workspace,
                                      quip_stream_t stream) {
-  if (!q || !k || !v || !cos || !sin || !pos || !kcache || !vcache || !out) return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kcache) || !aligned16(vcache))
-    return QUIP_ERR_MISALIGNED;
-  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
-  if (window < 0) return QUIP_ERR_BAD_SHAPE;
-  return rope_attn_decode_launch(q, k, v, cos, sin, pos, kcache, vcache, out, heads, kv_heads, head_dim,
-                                 max_len, scale, (hipStream_t)stream, workspace, window);
+  const AttnIO io{q, k, v, cos, sin, pos, kcache, vcache, out};
+  const AttnShape s{1, heads, kv_heads, head_dim, max_len, window, scale};
+  if (int rc = attn_refusal(io, {}, {q, k, v, kcache, vcache}, {}, {}, workspace, window)) return rc;
+  return rope_attn_decode_launch(io, s, (hipStream_t)stream, workspace);
 }
 
 size_t quip_rope_attn_batched_workspace_bytes(int32_t batch, int32_t heads, int32_t head_dim) {
@@ -739,14 +764,10 @@ int quip_rope_attn_decode_batched_f16(const void* q, const void* k, const void* 
                                       void* out, int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim,
                                       int32_t max_len, float scale, int32_t window, void* workspace,
                                       quip_stream_t stream) {
-  if (!q || !k || !v || !cos || !sin || !pos || !kcache || !vcache || !out) return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kcache) || !aligned16(vcache) ||
-      (reinterpret_cast<uintptr_t>(pos) & 7))
-    return QUIP_ERR_MISALIGNED;
-  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
-  if (window < 0) return QUIP_ERR_BAD_SHAPE;
-  return rope_attn_decode_batched_launch(q, k, v, cos, sin, pos, kcache, vcache, out, batch, heads, kv_heads, head_dim,
-                                         max_len, scale, (hipStream_t)stream, workspace, window);
+  const AttnIO io{q, k, v, cos, sin, pos, kcache, vcache, out};
+  const AttnShape s{batch, heads, kv_heads, head_dim, max_len, window, scale};
+  if (int rc = attn_refusal(io, {}, {q, k, v, kcache, vcache}, {pos}, {}, workspace, window)) return rc;
+  return rope_attn_decode_batched_launch(io, s, (hipStream_t)stream, workspace);
 }
 
 int quip_rope_attn_decode_batched_start_f16(const void* q, const void* k, const void* v, const float* cos,
@@ -754,27 +775,21 @@ int quip_rope_attn_decode_batched_start_f16(const void* q, const void* k, const 
                                             void* out, int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim,
                                             int32_t max_len, float scale, int32_t window, void* workspace,
                                             quip_stream_t stream, const void* start) {
-  if (!q || !k || !v || !cos || !sin || !pos || !kcache || !vcache || !out || !start) return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kcache) || !aligned16(vcache) ||
-      (reinterpret_cast<uintptr_t>(pos) & 7) || (reinterpret_cast<uintptr_t>(start) & 7))
-    return QUIP_ERR_MISALIGNED;
-  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
-  if (window < 0) return QUIP_ERR_BAD_SHAPE;
-  return rope_attn_decode_batched_start_launch(q, k, v, cos, sin, pos, reinterpret_cast<const int64_t*>(start), kcache,
-                                               vcache, out, batch, heads, kv_heads, head_dim, max_len, scale,
-                                               (hipStream_t)stream, workspace, window);
+  const AttnIO io{q, k, v, cos, sin, pos, kcache, vcache, out};
+  const AttnShape s{batch, heads, kv_heads, head_dim, max_len, window, scale};
+  if (int rc = attn_refusal(io, {start}, {q, k, v, kcache, vcache}, {pos, start}, {}, workspace, window)) return rc;
+  return rope_attn_decode_batched_start_launch(io, reinterpret_cast<const int64_t*>(start), s, (hipStream_t)stream,
+                                               workspace);
 }
 
 int quip_rope_attn_chunk_f16(const void* q, const void* k, const void* v, const float* cos, const float* sin,
                              const int64_t* pos, void* kcache, void* vcache, void* out, int32_t rows, int32_t heads,
                              int32_t kv_heads, int32_t head_dim, int32_t max_len, float scale, int32_t window,
                              quip_stream_t stream) {
-  if (!q || !k || !v || !cos || !sin || !pos || !kcache || !vcache || !out) return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kcache) || !aligned16(vcache) || !aligned16(out) ||
-      !aligned16(cos) || !aligned16(sin) || (reinterpret_cast<uintptr_t>(pos) & 7))
-    return QUIP_ERR_MISALIGNED;
-  return rope_attn_chunk_launch(q, k, v, cos, sin, pos, kcache, vcache, out, rows, heads, kv_heads, head_dim, max_len,
-                                scale, window, (hipStream_t)stream);
+  const AttnIO io{q, k, v, cos, sin, pos, kcache, vcache, out};
+  const AttnShape s{1, heads, kv_heads, head_dim, max_len, window, scale};
+  if (int rc = attn_refusal(io, {}, {q, k, v, kcache, vcache, out, cos, sin}, {pos})) return rc;
+  return rope_attn_chunk_launch(io, s, rows, (hipStream_t)stream);
 }
 
 int quip_rope_attn_ragged_f16(const void* q, const void* k, const void* v, const float* cos, const float* sin,
@@ -782,13 +797,10 @@ int quip_rope_attn_ragged_f16(const void* q, const void* k, const void* v, const
                               int32_t kv_heads, int32_t head_dim, int32_t max_len, int32_t batch,
                               const int32_t* seg_slot, const int32_t* seg_rows, int32_t nseg, float scale,
                               int32_t window, quip_stream_t stream) {
-  if (!q || !k || !v || !cos || !sin || !pos || !kcache || !vcache || !out || !seg_slot || !seg_rows)
-    return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kcache) || !aligned16(vcache) || !aligned16(out) ||
-      !aligned16(cos) || !aligned16(sin) || (reinterpret_cast<uintptr_t>(pos) & 7))
-    return QUIP_ERR_MISALIGNED;
-  return rope_attn_ragged_launch(q, k, v, cos, sin, pos, kcache, vcache, out, rows, heads, kv_heads, head_dim, max_len,
-                                 batch, seg_slot, seg_rows, nseg, scale, window, (hipStream_t)stream);
+  const AttnIO io{q, k, v, cos, sin, pos, kcache, vcache, out};
+  const AttnShape s{batch, heads, kv_heads, head_dim, max_len, window, scale};
+  if (int rc = attn_refusal(io, {seg_slot, seg_rows}, {q, k, v, kcache, vcache, out, cos, sin}, {pos})) return rc;
+  return rope_attn_ragged_launch(io, s, rows, {seg_slot, seg_rows, nseg}, (hipStream_t)stream);
 }
 
 int quip_rope_attn_decode_paged_f16(const void* q, const void* k, const void* v, const float* cos, const float* sin,
@@ -796,15 +808,10 @@ int quip_rope_attn_decode_paged_f16(const void* q, const void* k, const void* v,
                                     int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t max_len,
                                     int32_t n_pages, int32_t max_pages, float scale, int32_t window, void* workspace,
                                     quip_stream_t stream) {
-  if (!q || !k || !v || !cos || !sin || !pos || !table || !kpool || !vpool || !out) return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kpool) || !aligned16(vpool) ||
-      (reinterpret_cast<uintptr_t>(pos) & 7) || (reinterpret_cast<uintptr_t>(table) & 3))
-    return QUIP_ERR_MISALIGNED;
-  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
-  if (window < 0) return QUIP_ERR_BAD_SHAPE;
-  return rope_attn_decode_paged_launch(q, k, v, cos, sin, pos, table, kpool, vpool, out, batch, heads, kv_heads,
-                                       head_dim, max_len, n_pages, max_pages, scale, (hipStream_t)stream, workspace,
-                                       window);
+  const AttnIO io{q, k, v, cos, sin, pos, kpool, vpool, out};
+  const AttnShape s{batch, heads, kv_heads, head_dim, max_len, window, scale};
+  if (int rc = attn_refusal(io, {table}, {q, k, v, kpool, vpool}, {pos}, {table}, workspace, window)) return rc;
+  return rope_attn_decode_paged_launch(io, {table, n_pages, max_pages, 0, 0}, s, (hipStream_t)stream, workspace);
 }
 
 int quip_rope_attn_ragged_paged_f16(const void* q, const void* k, const void* v, const float* cos, const float* sin,
@@ -813,14 +820,10 @@ int quip_rope_attn_ragged_paged_f16(const void* q, const void* k, const void* v,
                                     int32_t batch, int32_t n_pages, int32_t max_pages, const int32_t* seg_slot,
                                     const int32_t* seg_rows, int32_t nseg, float scale, int32_t window,
                                     quip_stream_t stream) {
-  if (!q || !k || !v || !cos || !sin || !pos || !table || !kpool || !vpool || !out || !seg_slot || !seg_rows)
-    return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kpool) || !aligned16(vpool) || !aligned16(out) ||
-      !aligned16(cos) || !aligned16(sin) || (reinterpret_cast<uintptr_t>(pos) & 7) ||
-      (reinterpret_cast<uintptr_t>(table) & 3))
-    return QUIP_ERR_MISALIGNED;
-  return rope_attn_ragged_paged_launch(q, k, v, cos, sin, pos, table, kpool, vpool, out, rows, heads, kv_heads, head_dim,
-                                       max_len, batch, n_pages, max_pages, seg_slot, seg_rows, nseg, scale, window,
+  const AttnIO io{q, k, v, cos, sin, pos, kpool, vpool, out};
+  const AttnShape s{batch, heads, kv_heads, head_dim, max_len, window, scale};
+  if (int rc = attn_refusal(io, {table, seg_slot, seg_rows}, {q, k, v, kpool, vpool, out, cos, sin}, {pos}, {table})) return rc;
+  return rope_attn_ragged_paged_launch(io, {table, n_pages, max_pages, 0, 0}, s, rows, {seg_slot, seg_rows, nseg},
                                        (hipStream_t)stream);
 }
 
@@ -829,15 +832,10 @@ int quip_rope_attn_decode_paged_f8(const void* q, const void* k, const void* v, 
                                    int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t max_len,
                                    int32_t n_pages, int32_t max_pages, float scale, int32_t window, void* workspace,
                                    quip_stream_t stream, int32_t k_exp, int32_t v_exp) {
-  if (!q || !k || !v || !cos || !sin || !pos || !table || !kpool || !vpool || !out) return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kpool) || !aligned16(vpool) ||
-      (reinterpret_cast<uintptr_t>(pos) & 7) || (reinterpret_cast<uintptr_t>(table) & 3))
-    return QUIP_ERR_MISALIGNED;
-  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
-  if (window < 0) return QUIP_ERR_BAD_SHAPE;
-  return rope_attn_decode_paged_f8_launch(q, k, v, cos, sin, pos, table, kpool, vpool, out, batch, heads, kv_heads,
-                                          head_dim, max_len, n_pages, max_pages, scale, (hipStream_t)stream, workspace,
-                                          window, k_exp, v_exp);
+  const AttnIO io{q, k, v, cos, sin, pos, kpool, vpool, out};
+  const AttnShape s{batch, heads, kv_heads, head_dim, max_len, window, scale};
+  if (int rc = attn_refusal(io, {table}, {q, k, v, kpool, vpool}, {pos}, {table}, workspace, window)) return rc;
+  return rope_attn_decode_paged_f8_launch(io, {table, n_pages, max_pages, k_exp, v_exp}, s, (hipStream_t)stream, workspace);
 }
 
 int quip_rope_attn_ragged_paged_f8(const void* q, const void* k, const void* v, const float* cos, const float* sin,
@@ -846,15 +844,11 @@ int quip_rope_attn_ragged_paged_f8(const void* q, const void* k, const void* v, 
                                    int32_t batch, int32_t n_pages, int32_t max_pages, const int32_t* seg_slot,
                                    const int32_t* seg_rows, int32_t nseg, float scale, int32_t window,
                                    quip_stream_t stream, int32_t k_exp, int32_t v_exp) {
-  if (!q || !k || !v || !cos || !sin || !pos || !table || !kpool || !vpool || !out || !seg_slot || !seg_rows)
-    return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kpool) || !aligned16(vpool) || !aligned16(out) ||
-      !aligned16(cos) || !aligned16(sin) || (reinterpret_cast<uintptr_t>(pos) & 7) ||
-      (reinterpret_cast<uintptr_t>(table) & 3))
-    return QUIP_ERR_MISALIGNED;
-  return rope_attn_ragged_paged_f8_launch(q, k, v, cos, sin, pos, table, kpool, vpool, out, rows, heads, kv_heads,
-                                          head_dim, max_len, batch, n_pages, max_pages, seg_slot, seg_rows, nseg, scale,
-                                          window, (hipStream_t)stream, k_exp, v_exp);
+  const AttnIO io{q, k, v, cos, sin, pos, kpool, vpool, out};
+  const AttnShape s{batch, heads, kv_heads, head_dim, max_len, window, scale};
+  if (int rc = attn_refusal(io, {table, seg_slot, seg_rows}, {q, k, v, kpool, vpool, out, cos, sin}, {pos}, {table})) return rc;
+  return rope_attn_ragged_paged_f8_launch(io, {table, n_pages, max_pages, k_exp, v_exp}, s, rows, {seg_slot, seg_rows, nseg},
+                                          (hipStream_t)stream);
 }
 
 int quip_argmax_step_batched_f16(const void* logits, int32_t batch, int32_t n, void* tok, void* pos,
@@ -889,8 +883,8 @@ int quip_sample_step_f16(const void* logits, int32_t rows, int32_t n, const floa
 
 int quip_qk_norm_rows_f16(void* q, void* k, const void* q_weight, const void* k_weight, int64_t rows, int32_t heads,
                           int32_t kv_heads, int32_t head_dim, float eps, quip_stream_t stream) {
-  if (!q || !k || !q_weight || !k_weight) return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(q_weight) || !aligned16(k_weight)) return QUIP_ERR_MISALIGNED;
+  if (any_null({q, k, q_weight, k_weight})) return QUIP_ERR_NULL_POINTER;
+  if (any_off({q, k, q_weight, k_weight}, 15)) return QUIP_ERR_MISALIGNED;
   return qk_norm_rows_launch(q, k, q_weight, k_weight, rows, heads, kv_heads, head_dim, eps, (hipStream_t)stream);
 }
 
@@ -899,15 +893,11 @@ int quip_rope_attn_decode_qknorm_f16(const void* q, const void* k, const void* v
                                      int32_t kv_heads, int32_t head_dim, int32_t max_len, float scale, int32_t window,
                                      void* workspace, quip_stream_t stream, const void* q_weight, const void* k_weight,
                                      float eps) {
-  if (!q || !k || !v || !cos || !sin || !pos || !kcache || !vcache || !out || !q_weight || !k_weight)
-    return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kcache) || !aligned16(vcache) ||
-      !aligned16(q_weight) || !aligned16(k_weight))
-    return QUIP_ERR_MISALIGNED;
-  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
-  if (window < 0) return QUIP_ERR_BAD_SHAPE;
-  return rope_attn_decode_qknorm_launch(q, k, v, cos, sin, pos, kcache, vcache, out, heads, kv_heads, head_dim, max_len,
-                                        scale, (hipStream_t)stream, workspace, window, q_weight, k_weight, eps);
+  const AttnIO io{q, k, v, cos, sin, pos, kcache, vcache, out};
+  const AttnShape s{1, heads, kv_heads, head_dim, max_len, window, scale};
+  if (int rc = attn_refusal(io, {q_weight, k_weight}, {q, k, v, kcache, vcache, q_weight, k_weight}, {}, {}, workspace, window))
+    return rc;
+  return rope_attn_decode_qknorm_launch(io, s, {q_weight, k_weight, eps}, (hipStream_t)stream, workspace);
 }
 
 int quip_rope_attn_decode_batched_qknorm_f16(const void* q, const void* k, const void* v, const float* cos,
@@ -915,16 +905,11 @@ int quip_rope_attn_decode_batched_qknorm_f16(const void* q, const void* k, const
                                              int32_t batch, int32_t heads, int32_t kv_heads, int32_t head_dim,
                                              int32_t max_len, float scale, int32_t window, void* workspace,
                                              quip_stream_t stream, const void* q_weight, const void* k_weight, float eps) {
-  if (!q || !k || !v || !cos || !sin || !pos || !kcache || !vcache || !out || !q_weight || !k_weight)
-    return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(kcache) || !aligned16(vcache) ||
-      !aligned16(q_weight) || !aligned16(k_weight) || (reinterpret_cast<uintptr_t>(pos) & 7))
-    return QUIP_ERR_MISALIGNED;
-  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
-  if (window < 0) return QUIP_ERR_BAD_SHAPE;
-  return rope_attn_decode_batched_qknorm_launch(q, k, v, cos, sin, pos, kcache, vcache, out, batch, heads, kv_heads,
-                                                head_dim, max_len, scale, (hipStream_t)stream, workspace, window, q_weight,
-                                                k_weight, eps);
+  const AttnIO io{q, k, v, cos, sin, pos, kcache, vcache, out};
+  const AttnShape s{batch, heads, kv_heads, head_dim, max_len, window, scale};
+  if (int rc = attn_refusal(io, {q_weight, k_weight}, {q, k, v, kcache, vcache, q_weight, k_weight}, {pos}, {}, workspace, window))
+    return rc;
+  return rope_attn_decode_batched_qknorm_launch(io, s, {q_weight, k_weight, eps}, (hipStream_t)stream, workspace);
 }
 
 int quip_lora_shrink_rows_f16(const void* x, const void* A, const int32_t* row_adapter, float* t, int64_t rows, int32_t in,
@@ -963,16 +948,15 @@ int quip_rope_attn_decode_z_window_f16(const void* const* z, const void* const* 
                                        const float* cos, const float* sin, const int64_t* pos, void* kcache, void* vcache,
                                        void* out, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t max_len,
                                        float scale, int32_t window, void* workspace, quip_stream_t stream) {
-  if (!z || !post || !scales || !cos || !sin || !pos || !kcache || !vcache || !out) return QUIP_ERR_NULL_POINTER;
-  for (int i = 0; i < 3; ++i) {
-    if (!z[i] || !post[i]) return QUIP_ERR_NULL_POINTER;
-    if (!aligned16(z[i]) || !aligned16(post[i])) return QUIP_ERR_MISALIGNED;
+  if (any_null({z, post, scales, cos, sin, pos, kcache, vcache, out})) return QUIP_ERR_NULL_POINTER;
+  for (int i = 0; i < 3; ++i) {     // (element by element: a misaligned z[0] is answered before a NULL z[1])
+    if (any_null({z[i], post[i]})) return QUIP_ERR_NULL_POINTER;
+    if (any_off({z[i], post[i]}, 15)) return QUIP_ERR_MISALIGNED;
   }
-  if (!aligned16(kcache) || !aligned16(vcache)) return QUIP_ERR_MISALIGNED;
-  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QUIP_ERR_MISALIGNED;
+  if (any_off({kcache, vcache, workspace}, 15)) return QUIP_ERR_MISALIGNED;
   if (window < 0) return QUIP_ERR_BAD_SHAPE;
-  return rope_attn_decode_z_launch(z, post, scales, cos, sin, pos, kcache, vcache, out, heads, kv_heads, head_dim,
-                                   max_len, scale, (hipStream_t)stream, workspace, window);
+  return rope_attn_decode_z_launch(z, post, scales, {nullptr, nullptr, nullptr, cos, sin, pos, kcache, vcache, out},
+                                   {1, heads, kv_heads, head_dim, max_len, window, scale}, (hipStream_t)stream, workspace);
 }
 
 int quip_e8p_mm_origorder(const void* x, const void* qidxs, const void* grid, void* y, int32_t m,

@@ -330,17 +330,24 @@ __global__ __launch_bounds__(kChunkThreads) void rope_attn_chunk_kernel(ChunkArg
   chunk_tile_body<HD>(a, a.tile0 + (int)blockIdx.y);
 }
 
+// the kernel arguments of the prompt-side launches from AttnIO / AttnShape (quip_internal.h); rows: of the whole chunk,
+// 0 where the kernel takes them per segment (the ragged launches)
+ChunkArgs make_chunk_args(const AttnIO& io, const AttnShape& s, int rows) {
+  return ChunkArgs{reinterpret_cast<const f16*>(io.q), reinterpret_cast<const f16*>(io.k), reinterpret_cast<const f16*>(io.v),
+                   io.cos, io.sin, io.pos, reinterpret_cast<f16*>(io.kcache), reinterpret_cast<f16*>(io.vcache),
+                   reinterpret_cast<f16*>(io.out), rows, 0, s.heads, s.kv_heads, s.max_len, s.window, s.scale};
+}
+
+// what the prompt-side launches ask of their sizes (attn_shape_ok: decode_glue.hip)
+bool chunk_shape_ok(const AttnShape& s, int rows) { return rows >= 1 && attn_shape_ok(s) && s.window >= 0; }
+
 }  // namespace
 
-int rope_attn_chunk_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                           const int64_t* pos, void* kcache, void* vcache, void* out, int rows, int heads, int kv_heads,
-                           int head_dim, int max_len, float scale, int window, hipStream_t stream) {
-  if (rows < 1 || max_len < 1 || heads < 1 || kv_heads < 1 || heads % kv_heads != 0 || window < 0)
-    return QUIP_ERR_BAD_SHAPE;
+int rope_attn_chunk_launch(const AttnIO& io, const AttnShape& s, int rows, hipStream_t stream) {
+  if (!chunk_shape_ok(s, rows)) return QUIP_ERR_BAD_SHAPE;
+  const int heads = s.heads, head_dim = s.head_dim;
   if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
-  ChunkArgs a{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
-              cos, sin, pos, reinterpret_cast<f16*>(kcache), reinterpret_cast<f16*>(vcache),
-              reinterpret_cast<f16*>(out), rows, 0, heads, kv_heads, max_len, window, scale};
+  ChunkArgs a = make_chunk_args(io, s, rows);
   // query tiles on grid.y: more of them than one grid holds go out as slices of the same chunk (workgroups of a
   // launch never depend on each other, so neither do the slices)
   const int tiles = (rows - 1) / kChunkTile + 1;

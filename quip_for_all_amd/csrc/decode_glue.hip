@@ -427,103 +427,65 @@ void rope_attn_decode_kernel(Args a, AttnZ zz) {
 
 }  // namespace
 
+// ---- the host path of every attention launch of this translation unit ---------------------------------------------------
+// Operands and sizes arrive as AttnIO / AttnShape (quip_internal.h).  make_attn_args / make_chunk_args are the one place
+// where they become kernel arguments, place_workspace the one place of the split rule and of the workspace layout,
+// decode_launch the one launch of the decode-side kernels without _z input.  A launcher is its shape checks (BAD_SHAPE
+// before UNSUPPORTED), what its argument type adds, and one call.
+namespace {
+
+AttnArgs make_attn_args(const AttnIO& io, const AttnShape& s) {
+  return AttnArgs{reinterpret_cast<const f16*>(io.q), reinterpret_cast<const f16*>(io.k), reinterpret_cast<const f16*>(io.v),
+                  io.cos, io.sin, io.pos, reinterpret_cast<f16*>(io.kcache), reinterpret_cast<f16*>(io.vcache),
+                  reinterpret_cast<f16*>(io.out), s.heads, s.kv_heads, s.max_len, s.scale, nullptr, nullptr, s.window};
+}
+
+// one of the types derived from AttnArgs with its base filled; the caller sets what the type adds
+template <class Args>
+Args make_attn_args_as(const AttnIO& io, const AttnShape& s) {
+  Args a{};
+  static_cast<AttnArgs&>(a) = make_attn_args(io, s);
+  return a;
+}
+
+// what every launch asks of its sizes; the batched ones add batch_ok, the paged ones paged_shape_ok (paged_attn.hip.h)
+bool attn_shape_ok(const AttnShape& s) {
+  return s.heads >= 1 && s.kv_heads >= 1 && s.heads % s.kv_heads == 0 && s.max_len >= 1;
+}
+bool batch_ok(int batch) { return batch >= 1 && batch <= 65535; }       // grid.z
+
+// Split mode: a workspace is given and the cache can hold a context beyond kSplitFromPos (`len`: max_len, or what the
+// block table can address).  The workspace: partial states of every (sequence, head, split), then the arrival counters
+// of every (sequence, head).  -> whether the launch is split (grid.y = kSplits)
+bool place_workspace(AttnArgs& a, int batch, int head_dim, long long len, void* workspace) {
+  if (workspace == nullptr || len <= kSplitFromPos) return false;
+  a.ws = reinterpret_cast<float*>(workspace);
+  a.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) +
+                                           (size_t)batch * a.heads * kSplits * (head_dim + 4) * sizeof(float));
+  return true;
+}
+
+// The decode-side launch on filled arguments: SEQ false is the bs = 1 kernel (batch 1), true the batched one.
+template <bool SEQ, class Args>
+int decode_launch(Args a, int batch, int head_dim, long long split_len, int lds, hipStream_t stream, void* workspace) {
+  const bool split = place_workspace(a, batch, head_dim, split_len, workspace);
+  const dim3 grid(a.heads, split ? kSplits : 1, batch);
+  const AttnZ none{};
+  if (head_dim == 128)
+    return launch<rope_attn_decode_kernel<128, false, 0, 0, SEQ, Args>>(grid, dim3(256), lds, stream, a, none);
+  if (head_dim == 64)
+    return launch<rope_attn_decode_kernel<64, false, 0, 0, SEQ, Args>>(grid, dim3(256), lds, stream, a, none);
+  return QUIP_ERR_UNSUPPORTED;
+}
+
+}  // namespace
+
 size_t rope_attn_workspace_bytes(int heads, int head_dim) {
   return (size_t)heads * kSplits * (head_dim + 4) * sizeof(float) + (size_t)heads * sizeof(unsigned);
 }
 
-static int rope_attn_launch_common(AttnArgs a, const AttnZ* zz, int head_dim, int max_len, hipStream_t stream,
-                                   void* workspace) {
-  const int heads = a.heads;
-  const bool split = workspace != nullptr && max_len > kSplitFromPos;
-  if (split) {
-    a.ws = reinterpret_cast<float*>(workspace);
-    a.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) +
-                                             (size_t)heads * kSplits * (head_dim + 4) * sizeof(float));
-  }
-  const dim3 grid(heads, split ? kSplits : 1);
-  if (zz && a.heads != a.kv_heads) {
-    const int nq = a.heads * head_dim, nkv = a.kv_heads * head_dim;
-    const size_t lds = ((size_t)had::buf_floats(nq) + 2 * (size_t)had::buf_floats(nkv)) * sizeof(float);
-    if (head_dim == 128 && nq == 8192 && nkv == 1024)
-      return launch<rope_attn_decode_kernel<128, true, 13, 10>>(grid, dim3(512 + 128), (int)lds, stream, a, *zz);
-    if (head_dim == 128 && nq == 4096 && nkv == 1024)
-      return launch<rope_attn_decode_kernel<128, true, 12, 10>>(grid, dim3(256 + 128), (int)lds, stream, a, *zz);
-  } else if (zz) {
-    const size_t lds = 3 * (size_t)had::buf_floats(zz->n) * sizeof(float);
-    if (head_dim == 128) return launch<rope_attn_decode_kernel<128, true>>(grid, dim3(768), (int)lds, stream, a, *zz);
-    if (head_dim == 64) return launch<rope_attn_decode_kernel<64, true>>(grid, dim3(768), (int)lds, stream, a, *zz);
-  } else {
-    const AttnZ none{};
-    if (head_dim == 128) return launch<rope_attn_decode_kernel<128, false>>(grid, dim3(256), 0, stream, a, none);
-    if (head_dim == 64) return launch<rope_attn_decode_kernel<64, false>>(grid, dim3(256), 0, stream, a, none);
-  }
-  return QUIP_ERR_UNSUPPORTED;
-}
-
-int rope_attn_decode_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                            const int64_t* pos, void* kcache, void* vcache, void* out, int heads, int kv_heads,
-                            int head_dim, int max_len, float scale, hipStream_t stream, void* workspace, int window) {
-  if (heads < 1 || kv_heads < 1 || heads % kv_heads != 0 || max_len < 1) return QUIP_ERR_BAD_SHAPE;
-  AttnArgs a{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
-             cos, sin, pos, reinterpret_cast<f16*>(kcache), reinterpret_cast<f16*>(vcache),
-             reinterpret_cast<f16*>(out), heads, kv_heads, max_len, scale, nullptr, nullptr, window};
-  return rope_attn_launch_common(a, nullptr, head_dim, max_len, stream, workspace);
-}
-
-// partial states of every (sequence, head, split), then the arrival counters of every (sequence, head): batch 1 is the
-// bs=1 workspace
 size_t rope_attn_batched_workspace_bytes(int batch, int heads, int head_dim) {
   return (size_t)batch * rope_attn_workspace_bytes(heads, head_dim);
-}
-
-int rope_attn_decode_batched_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                    const int64_t* pos, void* kcache, void* vcache, void* out, int batch, int heads,
-                                    int kv_heads, int head_dim, int max_len, float scale, hipStream_t stream,
-                                    void* workspace, int window) {
-  if (batch < 1 || batch > 65535 || heads < 1 || kv_heads < 1 || heads % kv_heads != 0 || max_len < 1)
-    return QUIP_ERR_BAD_SHAPE;
-  if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
-  AttnArgs a{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
-             cos, sin, pos, reinterpret_cast<f16*>(kcache), reinterpret_cast<f16*>(vcache),
-             reinterpret_cast<f16*>(out), heads, kv_heads, max_len, scale, nullptr, nullptr, window};
-  // the grid rule of rope_attn_launch_common, per sequence
-  const bool split = workspace != nullptr && max_len > kSplitFromPos;
-  if (split) {
-    a.ws = reinterpret_cast<float*>(workspace);
-    a.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) +
-                                             (size_t)batch * heads * kSplits * (head_dim + 4) * sizeof(float));
-  }
-  const dim3 grid(heads, split ? kSplits : 1, batch);
-  const AttnZ none{};
-  if (head_dim == 128) return launch<rope_attn_decode_kernel<128, false, 0, 0, true>>(grid, dim3(256), 0, stream, a, none);
-  return launch<rope_attn_decode_kernel<64, false, 0, 0, true>>(grid, dim3(256), 0, stream, a, none);
-}
-
-// rope_attn_decode_batched_launch with a first cache row per sequence (StartAttnArgs): same grid, same workspace
-int rope_attn_decode_batched_start_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                          const int64_t* pos, const int64_t* start, void* kcache, void* vcache, void* out,
-                                          int batch, int heads, int kv_heads, int head_dim, int max_len, float scale,
-                                          hipStream_t stream, void* workspace, int window) {
-  if (batch < 1 || batch > 65535 || heads < 1 || kv_heads < 1 || heads % kv_heads != 0 || max_len < 1)
-    return QUIP_ERR_BAD_SHAPE;
-  if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
-  StartAttnArgs a{};
-  static_cast<AttnArgs&>(a) =
-      AttnArgs{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
-               cos, sin, pos, reinterpret_cast<f16*>(kcache), reinterpret_cast<f16*>(vcache),
-               reinterpret_cast<f16*>(out), heads, kv_heads, max_len, scale, nullptr, nullptr, window};
-  a.start = start;
-  const bool split = workspace != nullptr && max_len > kSplitFromPos;
-  if (split) {
-    a.ws = reinterpret_cast<float*>(workspace);
-    a.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) +
-                                             (size_t)batch * heads * kSplits * (head_dim + 4) * sizeof(float));
-  }
-  const dim3 grid(heads, split ? kSplits : 1, batch);
-  const AttnZ none{};
-  if (head_dim == 128)
-    return launch<rope_attn_decode_kernel<128, false, 0, 0, true, StartAttnArgs>>(grid, dim3(256), 0, stream, a, none);
-  return launch<rope_attn_decode_kernel<64, false, 0, 0, true, StartAttnArgs>>(grid, dim3(256), 0, stream, a, none);
 }
 
 bool rope_attn_decode_z_supported(int heads, int kv_heads, int head_dim) {
@@ -533,25 +495,52 @@ bool rope_attn_decode_z_supported(int heads, int kv_heads, int head_dim) {
   return heads >= 1 && (head_dim == 64 || head_dim == 128) && n >= 256 && n <= 4096 && (n & (n - 1)) == 0;
 }
 
-int rope_attn_decode_z_launch(const void* const* z, const void* const* post, const float* scales, const float* cos,
-                              const float* sin, const int64_t* pos, void* kcache, void* vcache, void* out, int heads,
-                              int kv_heads, int head_dim, int max_len, float scale, hipStream_t stream,
-                              void* workspace, int window) {
-  if (heads < 1 || kv_heads < 1 || max_len < 1) return QUIP_ERR_BAD_SHAPE;
-  if (!rope_attn_decode_z_supported(heads, kv_heads, head_dim)) return QUIP_ERR_UNSUPPORTED;
-  AttnArgs a{nullptr, nullptr, nullptr, cos, sin, pos, reinterpret_cast<f16*>(kcache),
-             reinterpret_cast<f16*>(vcache), reinterpret_cast<f16*>(out), heads, kv_heads, max_len, scale, nullptr,
-             nullptr, window};
+// The _z launch chooses its own instance (transform widths, block size, LDS); workspace and grid are the bs = 1 launch's.
+int rope_attn_decode_z_launch(const void* const* z, const void* const* post, const float* scales, const AttnIO& io,
+                              const AttnShape& s, hipStream_t stream, void* workspace) {
+  if (s.heads < 1 || s.kv_heads < 1 || s.max_len < 1) return QUIP_ERR_BAD_SHAPE;
+  if (!rope_attn_decode_z_supported(s.heads, s.kv_heads, s.head_dim)) return QUIP_ERR_UNSUPPORTED;
+  AttnArgs a = make_attn_args(io, s);
   AttnZ zz{};
-  const int n = heads * head_dim;
+  const int head_dim = s.head_dim, nq = s.heads * head_dim, nkv = s.kv_heads * head_dim;
   for (int i = 0; i < 3; ++i) {
     zz.z[i] = reinterpret_cast<const f16*>(z[i]);
     zz.post[i] = reinterpret_cast<const f16*>(post[i]);
     zz.scale[i] = scales[i];
   }
-  zz.n = n;
-  zz.logL = 31 - __builtin_clz((unsigned)n);
-  return rope_attn_launch_common(a, &zz, head_dim, max_len, stream, workspace);
+  zz.n = nq;
+  zz.logL = 31 - __builtin_clz((unsigned)nq);
+  const dim3 grid(s.heads, place_workspace(a, 1, head_dim, s.max_len, workspace) ? kSplits : 1);
+  if (s.heads != s.kv_heads) {
+    const size_t lds = ((size_t)had::buf_floats(nq) + 2 * (size_t)had::buf_floats(nkv)) * sizeof(float);
+    if (head_dim == 128 && nq == 8192 && nkv == 1024)
+      return launch<rope_attn_decode_kernel<128, true, 13, 10>>(grid, dim3(512 + 128), (int)lds, stream, a, zz);
+    if (head_dim == 128 && nq == 4096 && nkv == 1024)
+      return launch<rope_attn_decode_kernel<128, true, 12, 10>>(grid, dim3(256 + 128), (int)lds, stream, a, zz);
+    return QUIP_ERR_UNSUPPORTED;
+  }
+  const size_t lds = 3 * (size_t)had::buf_floats(nq) * sizeof(float);
+  if (head_dim == 128) return launch<rope_attn_decode_kernel<128, true>>(grid, dim3(768), (int)lds, stream, a, zz);
+  if (head_dim == 64) return launch<rope_attn_decode_kernel<64, true>>(grid, dim3(768), (int)lds, stream, a, zz);
+  return QUIP_ERR_UNSUPPORTED;
+}
+
+int rope_attn_decode_launch(const AttnIO& io, const AttnShape& s, hipStream_t stream, void* workspace) {
+  if (!attn_shape_ok(s)) return QUIP_ERR_BAD_SHAPE;
+  return decode_launch<false>(make_attn_args(io, s), 1, s.head_dim, s.max_len, 0, stream, workspace);
+}
+
+int rope_attn_decode_batched_launch(const AttnIO& io, const AttnShape& s, hipStream_t stream, void* workspace) {
+  if (!batch_ok(s.batch) || !attn_shape_ok(s)) return QUIP_ERR_BAD_SHAPE;
+  return decode_launch<true>(make_attn_args(io, s), s.batch, s.head_dim, s.max_len, 0, stream, workspace);
+}
+
+int rope_attn_decode_batched_start_launch(const AttnIO& io, const int64_t* start, const AttnShape& s, hipStream_t stream,
+                                          void* workspace) {
+  if (!batch_ok(s.batch) || !attn_shape_ok(s)) return QUIP_ERR_BAD_SHAPE;
+  auto a = make_attn_args_as<StartAttnArgs>(io, s);
+  a.start = start;
+  return decode_launch<true>(a, s.batch, s.head_dim, s.max_len, 0, stream, workspace);
 }
 
 // Greedy tail of the decode step (example_generate.py's argmax sampling with temperature 0): next token =

@@ -108,154 +108,70 @@ __global__ __launch_bounds__(kChunkThreads) void rope_attn_paged_ragged_f8_kerne
 
 bool fp8_exp_ok(int e) { return e >= -8 && e <= 7; }
 
-bool paged_shape_ok(int max_len, int n_pages, int max_pages) {
-  return n_pages >= 1 && max_pages >= 1 && max_len >= 1 && (long long)max_len <= (long long)max_pages * kPage;
+// what the paged launches ask beyond attn_shape_ok (the launches on fp16 pools carry exponents 0)
+bool paged_shape_ok(int max_len, const AttnPages& p) {
+  return p.n_pages >= 1 && p.max_pages >= 1 && max_len >= 1 && (long long)max_len <= (long long)p.max_pages * kPage &&
+         fp8_exp_ok(p.k_exp) && fp8_exp_ok(p.v_exp);
+}
+
+// what PagedAttnArgs / PagedChunkArgs and their F8 types add to their base
+template <class Args>
+void set_pages(Args& a, const AttnPages& p) {
+  a.table = p.table;
+  a.n_pages = p.n_pages;
+  a.max_pages = p.max_pages;
+  if constexpr (Args::kFp8) {     // (kcache / vcache carry the byte pools: the fp8 code addresses them as bytes)
+    a.k_exp = p.k_exp;
+    a.v_exp = p.v_exp;
+  }
+}
+
+// rope_attn_decode_batched_launch on Args = PagedAttnArgs / PagedAttnArgsF8: the sequence's table row in dynamic LDS, and
+// the split rule on what the table can address in place of max_len
+template <class Args>
+int decode_paged_launch(const AttnIO& io, const AttnPages& pages, const AttnShape& s, hipStream_t stream, void* workspace) {
+  if (!batch_ok(s.batch) || !attn_shape_ok(s) || !paged_shape_ok(s.max_len, pages)) return QUIP_ERR_BAD_SHAPE;
+  if ((s.head_dim != 64 && s.head_dim != 128) || pages.max_pages > kPagedMaxPages) return QUIP_ERR_UNSUPPORTED;
+  auto a = make_attn_args_as<Args>(io, s);
+  set_pages(a, pages);
+  return decode_launch<true>(a, s.batch, s.head_dim, (long long)pages.max_pages * kPage,
+                             pages.max_pages * (int)sizeof(int32_t), stream, workspace);
+}
+
+// rope_attn_ragged_launch on RA = PagedRaggedArgs / PagedRaggedArgsF8 and its kernels
+template <auto K128, auto K64, class RA>
+int ragged_paged_launch(const AttnIO& io, const AttnPages& pages, const AttnShape& s, int rows, const AttnSegments& segs,
+                        hipStream_t stream) {
+  if (!ragged_shape_ok(s, rows, segs.nseg) || !paged_shape_ok(s.max_len, pages)) return QUIP_ERR_BAD_SHAPE;
+  RA ra{};
+  static_cast<ChunkArgs&>(ra.c) = make_chunk_args(io, s, 0);
+  set_pages(ra.c, pages);
+  return ragged_launch<K128, K64>(ra, segs, s, rows, stream);
 }
 
 }  // namespace
 
-int rope_attn_decode_paged_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                  const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
-                                  int batch, int heads, int kv_heads, int head_dim, int max_len, int n_pages,
-                                  int max_pages, float scale, hipStream_t stream, void* workspace, int window) {
-  if (batch < 1 || batch > 65535 || heads < 1 || kv_heads < 1 || heads % kv_heads != 0 ||
-      !paged_shape_ok(max_len, n_pages, max_pages))
-    return QUIP_ERR_BAD_SHAPE;
-  if ((head_dim != 64 && head_dim != 128) || max_pages > kPagedMaxPages) return QUIP_ERR_UNSUPPORTED;
-  PagedAttnArgs a{};
-  static_cast<AttnArgs&>(a) =
-      AttnArgs{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
-               cos, sin, pos, reinterpret_cast<f16*>(kpool), reinterpret_cast<f16*>(vpool),
-               reinterpret_cast<f16*>(out), heads, kv_heads, max_len, scale, nullptr, nullptr, window};
-  a.table = table;
-  a.n_pages = n_pages;
-  a.max_pages = max_pages;
-  // the grid rule of rope_attn_decode_batched_launch with the table's capacity for max_len
-  const bool split = workspace != nullptr && (long long)max_pages * kPage > kSplitFromPos;
-  if (split) {
-    a.ws = reinterpret_cast<float*>(workspace);
-    a.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) +
-                                             (size_t)batch * heads * kSplits * (head_dim + 4) * sizeof(float));
-  }
-  const dim3 grid(heads, split ? kSplits : 1, batch);
-  const int lds = max_pages * (int)sizeof(int32_t);
-  const AttnZ none{};
-  if (head_dim == 128)
-    return launch<rope_attn_decode_kernel<128, false, 0, 0, true, PagedAttnArgs>>(grid, dim3(256), lds, stream, a, none);
-  return launch<rope_attn_decode_kernel<64, false, 0, 0, true, PagedAttnArgs>>(grid, dim3(256), lds, stream, a, none);
+int rope_attn_decode_paged_launch(const AttnIO& io, const AttnPages& pages, const AttnShape& s, hipStream_t stream,
+                                  void* workspace) {
+  return decode_paged_launch<PagedAttnArgs>(io, pages, s, stream, workspace);
 }
 
-int rope_attn_ragged_paged_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                  const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
-                                  int rows, int heads, int kv_heads, int head_dim, int max_len, int batch, int n_pages,
-                                  int max_pages, const int32_t* seg_slot, const int32_t* seg_rows, int nseg,
-                                  float scale, int window, hipStream_t stream) {
-  if (nseg < 1 || nseg > kRaggedMaxSegments || rows < 1 || batch < 1 || heads < 1 || kv_heads < 1 ||
-      heads % kv_heads != 0 || window < 0 || !paged_shape_ok(max_len, n_pages, max_pages))
-    return QUIP_ERR_BAD_SHAPE;
-  PagedRaggedArgs ra{};
-  long long total = 0, tiles = 0;
-  for (int s = 0; s < nseg; ++s) {
-    if (seg_rows[s] < 1 || seg_slot[s] < 0 || seg_slot[s] >= batch) return QUIP_ERR_BAD_SHAPE;
-    for (int t = 0; t < s; ++t)
-      if (seg_slot[t] == seg_slot[s]) return QUIP_ERR_BAD_SHAPE;     // rule (1) needs distinct slots
-    if (total + seg_rows[s] > rows) return QUIP_ERR_BAD_SHAPE;
-    ra.slot[s] = seg_slot[s];
-    ra.row0[s] = (int)total;
-    ra.rows[s] = seg_rows[s];
-    total += seg_rows[s];
-    tiles += (seg_rows[s] - 1) / kChunkTile + 1;
-  }
-  if (total != rows) return QUIP_ERR_BAD_SHAPE;
-  if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
-  if (tiles > kChunkMaxTilesY) return QUIP_ERR_UNSUPPORTED;           // callers chunk their passes
-  static_cast<ChunkArgs&>(ra.c) =
-      ChunkArgs{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
-                cos, sin, pos, reinterpret_cast<f16*>(kpool), reinterpret_cast<f16*>(vpool),
-                reinterpret_cast<f16*>(out), 0, 0, heads, kv_heads, max_len, window, scale};
-  ra.c.table = table;
-  ra.c.n_pages = n_pages;
-  ra.c.max_pages = max_pages;
-  ra.nseg = nseg;
-  const dim3 grid(heads, (unsigned)tiles);
-  return head_dim == 128 ? launch<rope_attn_paged_ragged_kernel<128>>(grid, dim3(kChunkThreads), 0, stream, ra)
-                         : launch<rope_attn_paged_ragged_kernel<64>>(grid, dim3(kChunkThreads), 0, stream, ra);
+int rope_attn_ragged_paged_launch(const AttnIO& io, const AttnPages& pages, const AttnShape& s, int rows,
+                                  const AttnSegments& segs, hipStream_t stream) {
+  return ragged_paged_launch<rope_attn_paged_ragged_kernel<128>, rope_attn_paged_ragged_kernel<64>, PagedRaggedArgs>(
+      io, pages, s, rows, segs, stream);
 }
 
 // ---- the same two launches on fp8 pools (see the header of this file) ----------------------------------------------------
-int rope_attn_decode_paged_f8_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                     const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
-                                     int batch, int heads, int kv_heads, int head_dim, int max_len, int n_pages,
-                                     int max_pages, float scale, hipStream_t stream, void* workspace, int window,
-                                     int k_exp, int v_exp) {
-  if (batch < 1 || batch > 65535 || heads < 1 || kv_heads < 1 || heads % kv_heads != 0 ||
-      !paged_shape_ok(max_len, n_pages, max_pages) || !fp8_exp_ok(k_exp) || !fp8_exp_ok(v_exp))
-    return QUIP_ERR_BAD_SHAPE;
-  if ((head_dim != 64 && head_dim != 128) || max_pages > kPagedMaxPages) return QUIP_ERR_UNSUPPORTED;
-  PagedAttnArgsF8 a{};
-  // (kcache / vcache carry the byte pools: the fp8 code addresses them as bytes)
-  static_cast<AttnArgs&>(a) =
-      AttnArgs{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
-               cos, sin, pos, reinterpret_cast<f16*>(kpool), reinterpret_cast<f16*>(vpool),
-               reinterpret_cast<f16*>(out), heads, kv_heads, max_len, scale, nullptr, nullptr, window};
-  a.table = table;
-  a.n_pages = n_pages;
-  a.max_pages = max_pages;
-  a.k_exp = k_exp;
-  a.v_exp = v_exp;
-  // the grid rule of rope_attn_decode_paged_launch
-  const bool split = workspace != nullptr && (long long)max_pages * kPage > kSplitFromPos;
-  if (split) {
-    a.ws = reinterpret_cast<float*>(workspace);
-    a.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) +
-                                             (size_t)batch * heads * kSplits * (head_dim + 4) * sizeof(float));
-  }
-  const dim3 grid(heads, split ? kSplits : 1, batch);
-  const int lds = max_pages * (int)sizeof(int32_t);
-  const AttnZ none{};
-  if (head_dim == 128)
-    return launch<rope_attn_decode_kernel<128, false, 0, 0, true, PagedAttnArgsF8>>(grid, dim3(256), lds, stream, a, none);
-  return launch<rope_attn_decode_kernel<64, false, 0, 0, true, PagedAttnArgsF8>>(grid, dim3(256), lds, stream, a, none);
+int rope_attn_decode_paged_f8_launch(const AttnIO& io, const AttnPages& pages, const AttnShape& s, hipStream_t stream,
+                                     void* workspace) {
+  return decode_paged_launch<PagedAttnArgsF8>(io, pages, s, stream, workspace);
 }
 
-int rope_attn_ragged_paged_f8_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                     const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
-                                     int rows, int heads, int kv_heads, int head_dim, int max_len, int batch,
-                                     int n_pages, int max_pages, const int32_t* seg_slot, const int32_t* seg_rows,
-                                     int nseg, float scale, int window, hipStream_t stream, int k_exp, int v_exp) {
-  if (nseg < 1 || nseg > kRaggedMaxSegments || rows < 1 || batch < 1 || heads < 1 || kv_heads < 1 ||
-      heads % kv_heads != 0 || window < 0 || !paged_shape_ok(max_len, n_pages, max_pages) || !fp8_exp_ok(k_exp) ||
-      !fp8_exp_ok(v_exp))
-    return QUIP_ERR_BAD_SHAPE;
-  PagedRaggedArgsF8 ra{};
-  long long total = 0, tiles = 0;
-  for (int s = 0; s < nseg; ++s) {
-    if (seg_rows[s] < 1 || seg_slot[s] < 0 || seg_slot[s] >= batch) return QUIP_ERR_BAD_SHAPE;
-    for (int t = 0; t < s; ++t)
-      if (seg_slot[t] == seg_slot[s]) return QUIP_ERR_BAD_SHAPE;     // rule (1) needs distinct slots
-    if (total + seg_rows[s] > rows) return QUIP_ERR_BAD_SHAPE;
-    ra.slot[s] = seg_slot[s];
-    ra.row0[s] = (int)total;
-    ra.rows[s] = seg_rows[s];
-    total += seg_rows[s];
-    tiles += (seg_rows[s] - 1) / kChunkTile + 1;
-  }
-  if (total != rows) return QUIP_ERR_BAD_SHAPE;
-  if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
-  if (tiles > kChunkMaxTilesY) return QUIP_ERR_UNSUPPORTED;
-  static_cast<ChunkArgs&>(ra.c) =
-      ChunkArgs{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
-                cos, sin, pos, reinterpret_cast<f16*>(kpool), reinterpret_cast<f16*>(vpool),
-                reinterpret_cast<f16*>(out), 0, 0, heads, kv_heads, max_len, window, scale};
-  ra.c.table = table;
-  ra.c.n_pages = n_pages;
-  ra.c.max_pages = max_pages;
-  ra.c.k_exp = k_exp;
-  ra.c.v_exp = v_exp;
-  ra.nseg = nseg;
-  const dim3 grid(heads, (unsigned)tiles);
-  return head_dim == 128 ? launch<rope_attn_paged_ragged_f8_kernel<128>>(grid, dim3(kChunkThreads), 0, stream, ra)
-                         : launch<rope_attn_paged_ragged_f8_kernel<64>>(grid, dim3(kChunkThreads), 0, stream, ra);
+int rope_attn_ragged_paged_f8_launch(const AttnIO& io, const AttnPages& pages, const AttnShape& s, int rows,
+                                     const AttnSegments& segs, hipStream_t stream) {
+  return ragged_paged_launch<rope_attn_paged_ragged_f8_kernel<128>, rope_attn_paged_ragged_f8_kernel<64>, PagedRaggedArgsF8>(
+      io, pages, s, rows, segs, stream);
 }
 
 }  // namespace quip

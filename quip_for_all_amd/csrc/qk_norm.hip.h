@@ -48,14 +48,16 @@ __global__ __launch_bounds__(256) void qk_norm_rows_kernel(f16* __restrict__ q, 
   }
 }
 
-template <class Base>
-QkNormArgs<Base> with_qk_norm(const Base& base, const void* qw, const void* kw, float eps) {
-  QkNormArgs<Base> a{};
-  static_cast<Base&>(a) = base;
-  a.qw = reinterpret_cast<const f16*>(qw);
-  a.kw = reinterpret_cast<const f16*>(kw);
-  a.eps = eps;
-  return a;
+// decode_launch (decode_glue.hip) on QkNormArgs<AttnArgs>: the grid rule and the workspace of the launch without the norm
+template <bool SEQ>
+int decode_qknorm_launch(const AttnIO& io, const AttnShape& s, const AttnQkNorm& norm, int batch, hipStream_t stream,
+                         void* workspace) {
+  if ((SEQ && !batch_ok(batch)) || !attn_shape_ok(s)) return QUIP_ERR_BAD_SHAPE;
+  auto a = make_attn_args_as<QkNormArgs<AttnArgs>>(io, s);
+  a.qw = reinterpret_cast<const f16*>(norm.qw);
+  a.kw = reinterpret_cast<const f16*>(norm.kw);
+  a.eps = norm.eps;
+  return decode_launch<SEQ>(a, batch, s.head_dim, s.max_len, 0, stream, workspace);
 }
 
 }  // namespace
@@ -79,53 +81,14 @@ int qk_norm_rows_launch(void* q, void* k, const void* qw, const void* kw, int64_
                                          eps);
 }
 
-// rope_attn_decode_launch (no _z input) on QkNormArgs<AttnArgs>: its grid rule, its workspace
-int rope_attn_decode_qknorm_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                   const int64_t* pos, void* kcache, void* vcache, void* out, int heads, int kv_heads,
-                                   int head_dim, int max_len, float scale, hipStream_t stream, void* workspace, int window,
-                                   const void* qw, const void* kw, float eps) {
-  if (heads < 1 || kv_heads < 1 || heads % kv_heads != 0 || max_len < 1) return QUIP_ERR_BAD_SHAPE;
-  if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
-  AttnArgs base{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
-                cos, sin, pos, reinterpret_cast<f16*>(kcache), reinterpret_cast<f16*>(vcache),
-                reinterpret_cast<f16*>(out), heads, kv_heads, max_len, scale, nullptr, nullptr, window};
-  const bool split = workspace != nullptr && max_len > kSplitFromPos;
-  if (split) {
-    base.ws = reinterpret_cast<float*>(workspace);
-    base.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) +
-                                                (size_t)heads * kSplits * (head_dim + 4) * sizeof(float));
-  }
-  const auto a = with_qk_norm(base, qw, kw, eps);
-  const dim3 grid(heads, split ? kSplits : 1);
-  const AttnZ none{};
-  if (head_dim == 128)
-    return launch<rope_attn_decode_kernel<128, false, 0, 0, false, QkNormArgs<AttnArgs>>>(grid, dim3(256), 0, stream, a, none);
-  return launch<rope_attn_decode_kernel<64, false, 0, 0, false, QkNormArgs<AttnArgs>>>(grid, dim3(256), 0, stream, a, none);
+int rope_attn_decode_qknorm_launch(const AttnIO& io, const AttnShape& s, const AttnQkNorm& norm, hipStream_t stream,
+                                   void* workspace) {
+  return decode_qknorm_launch<false>(io, s, norm, 1, stream, workspace);
 }
 
-// rope_attn_decode_batched_launch on QkNormArgs<AttnArgs>: its grid rule, its workspace
-int rope_attn_decode_batched_qknorm_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                           const int64_t* pos, void* kcache, void* vcache, void* out, int batch, int heads,
-                                           int kv_heads, int head_dim, int max_len, float scale, hipStream_t stream,
-                                           void* workspace, int window, const void* qw, const void* kw, float eps) {
-  if (batch < 1 || batch > 65535 || heads < 1 || kv_heads < 1 || heads % kv_heads != 0 || max_len < 1)
-    return QUIP_ERR_BAD_SHAPE;
-  if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
-  AttnArgs base{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
-                cos, sin, pos, reinterpret_cast<f16*>(kcache), reinterpret_cast<f16*>(vcache),
-                reinterpret_cast<f16*>(out), heads, kv_heads, max_len, scale, nullptr, nullptr, window};
-  const bool split = workspace != nullptr && max_len > kSplitFromPos;
-  if (split) {
-    base.ws = reinterpret_cast<float*>(workspace);
-    base.counters = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) +
-                                                (size_t)batch * heads * kSplits * (head_dim + 4) * sizeof(float));
-  }
-  const auto a = with_qk_norm(base, qw, kw, eps);
-  const dim3 grid(heads, split ? kSplits : 1, batch);
-  const AttnZ none{};
-  if (head_dim == 128)
-    return launch<rope_attn_decode_kernel<128, false, 0, 0, true, QkNormArgs<AttnArgs>>>(grid, dim3(256), 0, stream, a, none);
-  return launch<rope_attn_decode_kernel<64, false, 0, 0, true, QkNormArgs<AttnArgs>>>(grid, dim3(256), 0, stream, a, none);
+int rope_attn_decode_batched_qknorm_launch(const AttnIO& io, const AttnShape& s, const AttnQkNorm& norm, hipStream_t stream,
+                                           void* workspace) {
+  return decode_qknorm_launch<true>(io, s, norm, s.batch, stream, workspace);
 }
 
 }  // namespace quip

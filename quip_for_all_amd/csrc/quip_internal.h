@@ -175,74 +175,75 @@ int had_transform_launch(const void* x, void* y, int64_t rows, int in_features, 
                          int n, int K, const void* had, int transpose, const void* pre,
                          const void* pre2, const void* post, const void* bias, float scale,
                          hipStream_t stream, const HadFusion* fuse = nullptr);
-int rope_attn_decode_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                            const int64_t* pos, void* kcache, void* vcache, void* out, int heads, int kv_heads,
-                            int head_dim, int max_len, float scale, hipStream_t stream, void* workspace = nullptr,
-                            int window = 0);
+// The attention launches (decode_glue.hip and the headers it includes).  They share their operands: q, k (before the
+// rotation) and v of the new token(s), the rotary tables (max_len, head_dim), the position(s) on the device, the cache
+// (or, paged, the two pools) and out -- AttnIO -- and their sizes -- AttnShape; what a variant adds comes beside them.
+// Every launcher answers BAD_SHAPE before UNSUPPORTED; pointers are the C entry points' business (capi.hip).
+struct AttnIO {
+  const void *q, *k, *v;
+  const float *cos, *sin;
+  const int64_t* pos;
+  void *kcache, *vcache, *out;
+};
+struct AttnShape {
+  int batch;                   // sequences (cache slots); 1: the bs = 1 launches and the chunk launch
+  int heads, kv_heads, head_dim, max_len;
+  int window;                  // sliding window, 0: none
+  float scale;
+};
+// a paged cache: kcache / vcache of AttnIO are pools (n_pages, kv_heads, 64, head_dim), table (batch, max_pages) int32 on the
+// device.  The _f8 launches: pools of e4m3fn bytes, a byte c means e4m3fn(c) * 2^k_exp / 2^v_exp, exponents in [-8, 7];
+// the launches on fp16 pools take 0, 0
+struct AttnPages {
+  const int32_t* table;
+  int n_pages, max_pages;
+  int k_exp, v_exp;
+};
+// the segments of a ragged launch (host arrays): segment s is seg_rows[s] rows that continue slot seg_slot[s]
+struct AttnSegments {
+  const int32_t *slot, *rows;
+  int nseg;
+};
+// per-head RMSNorm of q and of the new k row in front of the rotation (qk_norm.hip.h)
+struct AttnQkNorm {
+  const void *qw, *kw;
+  float eps;
+};
 size_t rope_attn_workspace_bytes(int heads, int head_dim);
-bool rope_attn_decode_z_supported(int heads, int kv_heads, int head_dim);
-int rope_attn_decode_z_launch(const void* const* z, const void* const* post, const float* scales, const float* cos,
-                              const float* sin, const int64_t* pos, void* kcache, void* vcache, void* out, int heads,
-                              int kv_heads, int head_dim, int max_len, float scale, hipStream_t stream,
-                              void* workspace, int window = 0);
-int argmax_step_launch(const void* logits, int n, void* tok, void* pos, hipStream_t stream);
-// batched decode (decode_glue.hip): B sequences, each at its own position, in one launch
 size_t rope_attn_batched_workspace_bytes(int batch, int heads, int head_dim);
-int rope_attn_decode_batched_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                    const int64_t* pos, void* kcache, void* vcache, void* out, int batch, int heads,
-                                    int kv_heads, int head_dim, int max_len, float scale, hipStream_t stream,
-                                    void* workspace, int window);
-// the same for sequences that begin at cache row start[b] (left-padded batches): row t has rotary position t - start[b]
-int rope_attn_decode_batched_start_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                          const int64_t* pos, const int64_t* start, void* kcache, void* vcache, void* out,
-                                          int batch, int heads, int kv_heads, int head_dim, int max_len, float scale,
-                                          hipStream_t stream, void* workspace, int window);
-int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, void* pos, hipStream_t stream);
-// chunk_attn.hip.h (in decode_glue.hip): rows queries at positions [*pos, *pos + rows) against cache rows [0, *pos + rows)
-int rope_attn_chunk_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                           const int64_t* pos, void* kcache, void* vcache, void* out, int rows, int heads, int kv_heads,
-                           int head_dim, int max_len, float scale, int window, hipStream_t stream);
-// ragged_attn.hip.h (in decode_glue.hip): the same for nseg segments of the rows, segment s continuing slot seg_slot[s] of a
-// batched cache at pos[seg_slot[s]]; seg_slot / seg_rows are host arrays
-int rope_attn_ragged_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                            const int64_t* pos, void* kcache, void* vcache, void* out, int rows, int heads, int kv_heads,
-                            int head_dim, int max_len, int batch, const int32_t* seg_slot, const int32_t* seg_rows,
-                            int nseg, float scale, int window, hipStream_t stream);
-// paged_attn.hip.h (in decode_glue.hip): the batched decode launch and the ragged launch on a paged cache -- kpool / vpool
-// (n_pages, kv_heads, 64, head_dim), table (batch, max_pages) int32 on the device; max_len: rows of cos / sin
-int rope_attn_decode_paged_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                  const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
-                                  int batch, int heads, int kv_heads, int head_dim, int max_len, int n_pages,
-                                  int max_pages, float scale, hipStream_t stream, void* workspace, int window);
-int rope_attn_ragged_paged_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                  const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
-                                  int rows, int heads, int kv_heads, int head_dim, int max_len, int batch, int n_pages,
-                                  int max_pages, const int32_t* seg_slot, const int32_t* seg_rows, int nseg,
-                                  float scale, int window, hipStream_t stream);
-// the same two on fp8 pools: uint8 (n_pages, kv_heads, 64, head_dim), a byte c means e4m3fn(c) * 2^k_exp / 2^v_exp;
-// exponents in [-8, 7]
-int rope_attn_decode_paged_f8_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                     const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
-                                     int batch, int heads, int kv_heads, int head_dim, int max_len, int n_pages,
-                                     int max_pages, float scale, hipStream_t stream, void* workspace, int window,
-                                     int k_exp, int v_exp);
-int rope_attn_ragged_paged_f8_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                     const int64_t* pos, const int32_t* table, void* kpool, void* vpool, void* out,
-                                     int rows, int heads, int kv_heads, int head_dim, int max_len, int batch,
-                                     int n_pages, int max_pages, const int32_t* seg_slot, const int32_t* seg_rows,
-                                     int nseg, float scale, int window, hipStream_t stream, int k_exp, int v_exp);
-// qk_norm.hip.h (in decode_glue.hip): per-head RMSNorm of q (rows, heads * head_dim) and k (rows, kv_heads * head_dim) in
-// place, and the bs = 1 / contiguous batched decode launches with that norm on q and the new k row in registers
+// bs = 1: one token against the cache (kv_heads, max_len, head_dim)
+int rope_attn_decode_launch(const AttnIO& io, const AttnShape& s, hipStream_t stream, void* workspace);
+int rope_attn_decode_qknorm_launch(const AttnIO& io, const AttnShape& s, const AttnQkNorm& norm, hipStream_t stream,
+                                   void* workspace);
+// the same from the raw GEMV outputs z[3] of q / k / v_proj and their SV vectors post[3] (io.q / k / v unused)
+bool rope_attn_decode_z_supported(int heads, int kv_heads, int head_dim);
+int rope_attn_decode_z_launch(const void* const* z, const void* const* post, const float* scales, const AttnIO& io,
+                              const AttnShape& s, hipStream_t stream, void* workspace);
+// batched decode: s.batch sequences, each at its own position, in one launch; start: sequences that begin at cache row
+// start[b] (left-padded batches), row t has rotary position t - start[b]
+int rope_attn_decode_batched_launch(const AttnIO& io, const AttnShape& s, hipStream_t stream, void* workspace);
+int rope_attn_decode_batched_start_launch(const AttnIO& io, const int64_t* start, const AttnShape& s, hipStream_t stream,
+                                          void* workspace);
+int rope_attn_decode_batched_qknorm_launch(const AttnIO& io, const AttnShape& s, const AttnQkNorm& norm, hipStream_t stream,
+                                           void* workspace);
+int rope_attn_decode_paged_launch(const AttnIO& io, const AttnPages& pages, const AttnShape& s, hipStream_t stream,
+                                  void* workspace);
+int rope_attn_decode_paged_f8_launch(const AttnIO& io, const AttnPages& pages, const AttnShape& s, hipStream_t stream,
+                                     void* workspace);
+// chunk_attn.hip.h: rows queries at positions [*pos, *pos + rows) against cache rows [0, *pos + rows); ragged_attn.hip.h /
+// paged_attn.hip.h: the same for segments of the rows, each continuing one slot of a batched (paged) cache at pos[slot]
+int rope_attn_chunk_launch(const AttnIO& io, const AttnShape& s, int rows, hipStream_t stream);
+int rope_attn_ragged_launch(const AttnIO& io, const AttnShape& s, int rows, const AttnSegments& segs, hipStream_t stream);
+int rope_attn_ragged_paged_launch(const AttnIO& io, const AttnPages& pages, const AttnShape& s, int rows,
+                                  const AttnSegments& segs, hipStream_t stream);
+int rope_attn_ragged_paged_f8_launch(const AttnIO& io, const AttnPages& pages, const AttnShape& s, int rows,
+                                     const AttnSegments& segs, hipStream_t stream);
+// qk_norm.hip.h: per-head RMSNorm of q (rows, heads * head_dim) and k (rows, kv_heads * head_dim) in place
 int qk_norm_rows_launch(void* q, void* k, const void* qw, const void* kw, int64_t rows, int heads, int kv_heads,
                         int head_dim, float eps, hipStream_t stream);
-int rope_attn_decode_qknorm_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                   const int64_t* pos, void* kcache, void* vcache, void* out, int heads, int kv_heads,
-                                   int head_dim, int max_len, float scale, hipStream_t stream, void* workspace, int window,
-                                   const void* qw, const void* kw, float eps);
-int rope_attn_decode_batched_qknorm_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                                           const int64_t* pos, void* kcache, void* vcache, void* out, int batch, int heads,
-                                           int kv_heads, int head_dim, int max_len, float scale, hipStream_t stream,
-                                           void* workspace, int window, const void* qw, const void* kw, float eps);
+// the greedy tail (decode_glue.hip): tok <- arg-max of the logits (of every row), pos += 1
+int argmax_step_launch(const void* logits, int n, void* tok, void* pos, hipStream_t stream);
+int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, void* pos, hipStream_t stream);
 // nll_rows.hip.h (in decode_glue.hip): per row of (rows, n) fp16 logits the log-sum-exp, the log-probability of target[row] and
 // the arg-max; lse / argmax may be null
 int nll_rows_launch(const void* logits, int rows, int n, const int64_t* target, float* logprob, float* lse,

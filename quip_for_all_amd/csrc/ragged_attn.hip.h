@@ -59,38 +59,44 @@ __global__ __launch_bounds__(kChunkThreads) void rope_attn_ragged_kernel(RaggedA
   chunk_tile_body<HD>(a, (int)blockIdx.y - t0);
 }
 
-}  // namespace
-
-int rope_attn_ragged_launch(const void* q, const void* k, const void* v, const float* cos, const float* sin,
-                            const int64_t* pos, void* kcache, void* vcache, void* out, int rows, int heads, int kv_heads,
-                            int head_dim, int max_len, int batch, const int32_t* seg_slot, const int32_t* seg_rows,
-                            int nseg, float scale, int window, hipStream_t stream) {
-  if (nseg < 1 || nseg > kRaggedMaxSegments || rows < 1 || max_len < 1 || batch < 1 || heads < 1 || kv_heads < 1 ||
-      heads % kv_heads != 0 || window < 0)
-    return QUIP_ERR_BAD_SHAPE;
-  RaggedArgs ra{};
+// The host side of a ragged launch on RA (RaggedArgs, or one of the paged ones of paged_attn.hip.h; ra.c is filled): the
+// segment table -- distinct slots in [0, batch), every segment's first row, rows that sum to `rows` -- the grid of all
+// segments' query tiles, and the launch of K128 / K64, the kernel over RA.
+template <auto K128, auto K64, class RA>
+int ragged_launch(RA& ra, const AttnSegments& g, const AttnShape& s, int rows, hipStream_t stream) {
   long long total = 0, tiles = 0;
-  for (int s = 0; s < nseg; ++s) {
-    if (seg_rows[s] < 1 || seg_slot[s] < 0 || seg_slot[s] >= batch) return QUIP_ERR_BAD_SHAPE;
-    for (int t = 0; t < s; ++t)
-      if (seg_slot[t] == seg_slot[s]) return QUIP_ERR_BAD_SHAPE;     // rule (1) needs distinct slots
-    if (total + seg_rows[s] > rows) return QUIP_ERR_BAD_SHAPE;
-    ra.slot[s] = seg_slot[s];
-    ra.row0[s] = (int)total;
-    ra.rows[s] = seg_rows[s];
-    total += seg_rows[s];
-    tiles += (seg_rows[s] - 1) / kChunkTile + 1;
+  for (int i = 0; i < g.nseg; ++i) {
+    if (g.rows[i] < 1 || g.slot[i] < 0 || g.slot[i] >= s.batch) return QUIP_ERR_BAD_SHAPE;
+    for (int t = 0; t < i; ++t)
+      if (g.slot[t] == g.slot[i]) return QUIP_ERR_BAD_SHAPE;     // rule (1) needs distinct slots
+    if (total + g.rows[i] > rows) return QUIP_ERR_BAD_SHAPE;
+    ra.slot[i] = g.slot[i];
+    ra.row0[i] = (int)total;
+    ra.rows[i] = g.rows[i];
+    total += g.rows[i];
+    tiles += (g.rows[i] - 1) / kChunkTile + 1;
   }
   if (total != rows) return QUIP_ERR_BAD_SHAPE;
-  if (head_dim != 64 && head_dim != 128) return QUIP_ERR_UNSUPPORTED;
+  if (s.head_dim != 64 && s.head_dim != 128) return QUIP_ERR_UNSUPPORTED;
   if (tiles > kChunkMaxTilesY) return QUIP_ERR_UNSUPPORTED;           // callers chunk their passes
-  ra.c = ChunkArgs{reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(v),
-                   cos, sin, pos, reinterpret_cast<f16*>(kcache), reinterpret_cast<f16*>(vcache),
-                   reinterpret_cast<f16*>(out), 0, 0, heads, kv_heads, max_len, window, scale};
-  ra.nseg = nseg;
-  const dim3 grid(heads, (unsigned)tiles);
-  return head_dim == 128 ? launch<rope_attn_ragged_kernel<128>>(grid, dim3(kChunkThreads), 0, stream, ra)
-                         : launch<rope_attn_ragged_kernel<64>>(grid, dim3(kChunkThreads), 0, stream, ra);
+  ra.nseg = g.nseg;
+  const dim3 grid(s.heads, (unsigned)tiles);
+  return s.head_dim == 128 ? launch<K128>(grid, dim3(kChunkThreads), 0, stream, ra)
+                           : launch<K64>(grid, dim3(kChunkThreads), 0, stream, ra);
+}
+
+// what the ragged launches ask of their sizes before the segments are looked at
+bool ragged_shape_ok(const AttnShape& s, int rows, int nseg) {
+  return nseg >= 1 && nseg <= kRaggedMaxSegments && s.batch >= 1 && chunk_shape_ok(s, rows);
+}
+
+}  // namespace
+
+int rope_attn_ragged_launch(const AttnIO& io, const AttnShape& s, int rows, const AttnSegments& segs, hipStream_t stream) {
+  if (!ragged_shape_ok(s, rows, segs.nseg)) return QUIP_ERR_BAD_SHAPE;
+  RaggedArgs ra{};
+  ra.c = make_chunk_args(io, s, 0);
+  return ragged_launch<rope_attn_ragged_kernel<128>, rope_attn_ragged_kernel<64>>(ra, segs, s, rows, stream);
 }
 
 }  // namespace quip

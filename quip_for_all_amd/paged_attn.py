@@ -20,11 +20,9 @@ import math
 
 import torch
 
-from . import capi
 from . import register_lib as _R
-from .ragged_attn import MAX_SEGMENTS
 
-PAGE = 64          # kPage == kChunkTile
+PAGE = _R._PAGE          # kPage == kChunkTile
 F8_EXP_MIN, F8_EXP_MAX = -8, 7
 
 try:
@@ -60,77 +58,6 @@ def dequant_f8(b, e):
     return (b.view(torch.float8_e4m3fn).float() * 2.0 ** int(e)).to(torch.float16)
 
 
-def _check_paged(what, q, k, v, cos, sin, pos, table, kpool, vpool, rows_are_slots, pool_dtype=torch.float16):
-    """dtype, shape, contiguity and device of everything both ops take -> (heads, hd, kvh, max_len, B, n_pages, max_pages)"""
-    need = _R._need
-    need(kpool.dtype == pool_dtype and vpool.dtype == pool_dtype,
-         f"{what}: the pools must be {'fp16' if pool_dtype == torch.float16 else 'uint8 (e4m3fn bytes)'}")
-    for t in (q, k, v):
-        need(t.dtype == torch.float16, f"{what}: q, k, v must be fp16")
-    for t in (q, k, v, kpool, vpool):
-        need(t.is_contiguous() and t.is_cuda and t.device == q.device, f"{what}: contiguous tensors on one CUDA device")
-    need(cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
-         and cos.device == q.device and sin.device == q.device, "cos / sin must be contiguous float32 on q's device")
-    need(q.dim() == 3 and kpool.dim() == 4 and table.dim() == 2,
-         f"{what}: q (rows, heads, hd), pools (n_pages, kv_heads, {PAGE}, hd), table (B, max_pages)")
-    rows, heads, hd = q.shape
-    n_pages, kvh = kpool.shape[0], kpool.shape[1]
-    B, max_pages = table.shape
-    max_len = cos.shape[0]
-    need(table.dtype == torch.int32 and table.is_contiguous() and table.device == q.device,
-         "table must be a contiguous int32 (B, max_pages) tensor on q's device")
-    need(pos.dtype == torch.int64 and tuple(pos.shape) == (B,) and pos.is_contiguous() and pos.device == q.device,
-         "pos must be a contiguous int64 (B,) tensor on q's device")
-    need(not rows_are_slots or rows == B, f"{what}: one q row per table row")
-    need(tuple(k.shape) == (rows, kvh, hd) and tuple(v.shape) == (rows, kvh, hd)
-         and tuple(kpool.shape) == (n_pages, kvh, PAGE, hd) and tuple(vpool.shape) == tuple(kpool.shape)
-         and n_pages >= 1 and max_pages >= 1 and tuple(cos.shape) == (max_len, hd) and tuple(sin.shape) == (max_len, hd)
-         and 1 <= max_len <= max_pages * PAGE, f"{what}: shape mismatch")
-    return heads, hd, kvh, max_len, B, n_pages, max_pages
-
-
-def _rope_attn_decode_paged_cuda(q, k, v, cos, sin, pos, table, kpool, vpool, workspace=None, window=0):
-    """rope_attn_decode_batched with q (B, heads, hd), k / v (B, kv_heads, hd), pos (B,) and the caches behind `table`;
-    row pos[b] of slot b is written -> (B, heads, hd) fp16"""
-    heads, hd, kvh, max_len, B, n_pages, max_pages = _check_paged("rope_attn_decode_paged", q, k, v, cos, sin, pos, table,
-                                                                  kpool, vpool, True)
-    if workspace is not None:
-        _R._need(workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == q.device
-                 and workspace.numel() >= capi.lib().quip_rope_attn_batched_workspace_bytes(B, heads, hd),
-                 "workspace: use rope_attn_batched_workspace(batch, heads, head_dim, device)")
-    out = torch.empty_like(q)
-    with torch.cuda.device(q.device):
-        capi.check(capi.lib().quip_rope_attn_decode_paged_f16(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), table.data_ptr(),
-            kpool.data_ptr(), vpool.data_ptr(), out.data_ptr(), B, heads, kvh, hd, max_len, n_pages, max_pages,
-            1.0 / math.sqrt(hd), int(window), _R._ptr(workspace), _R._stream(q)), "quip_rope_attn_decode_paged_f16")
-    return out
-
-
-def _rope_attn_ragged_paged_cuda(q, k, v, cos, sin, pos, seg_slot, seg_rows, table, kpool, vpool, window=0):
-    """rope_attn_ragged with the caches behind `table`: rows [pos[slot], pos[slot] + seg_rows[s]) of every named slot are
-    written -> (rows, heads, hd) fp16"""
-    need = _R._need
-    heads, hd, kvh, max_len, B, n_pages, max_pages = _check_paged("rope_attn_ragged_paged", q, k, v, cos, sin, pos, table,
-                                                                  kpool, vpool, False)
-    rows = q.shape[0]
-    seg_slot, seg_rows = [int(x) for x in seg_slot], [int(x) for x in seg_rows]
-    n = len(seg_slot)
-    need(1 <= n <= MAX_SEGMENTS and len(seg_rows) == n,
-         f"rope_attn_ragged_paged: 1 .. {MAX_SEGMENTS} segments, one slot and one row count each")
-    need(all(r >= 1 for r in seg_rows) and sum(seg_rows) == rows, "rope_attn_ragged_paged: seg_rows >= 1 that sum to q's rows")
-    need(all(0 <= b < B for b in seg_slot) and len(set(seg_slot)) == n, "rope_attn_ragged_paged: distinct slots in [0, B)")
-    slots, counts = (ctypes.c_int32 * n)(*seg_slot), (ctypes.c_int32 * n)(*seg_rows)
-    out = torch.empty_like(q)
-    with torch.cuda.device(q.device):
-        capi.check(capi.lib().quip_rope_attn_ragged_paged_f16(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), table.data_ptr(),
-            kpool.data_ptr(), vpool.data_ptr(), out.data_ptr(), rows, heads, kvh, hd, max_len, B, n_pages, max_pages,
-            ctypes.addressof(slots), ctypes.addressof(counts), n, 1.0 / math.sqrt(hd), int(window), _R._stream(q)),
-            "quip_rope_attn_ragged_paged_f16")
-    return out
-
-
 def _check_exps(what, k_exp, v_exp):
     k_exp, v_exp = int(k_exp), int(v_exp)
     _R._need(F8_EXP_MIN <= k_exp <= F8_EXP_MAX and F8_EXP_MIN <= v_exp <= F8_EXP_MAX,
@@ -138,48 +65,55 @@ def _check_exps(what, k_exp, v_exp):
     return k_exp, v_exp
 
 
+def _decode_paged(op, q, k, v, cos, sin, pos, table, kpool, vpool, workspace, window, exps=None):
+    """both paged decode ops; exps (k_exp, v_exp): the one on uint8 pools, its entry takes them behind the stream"""
+    B, heads, kvh, hd, max_len, _ = _R._check_attn(op, "batched", q, k, v, cos, sin, pos, kpool, vpool, table,
+                                                   torch.float16 if exps is None else torch.uint8)
+    more = () if exps is None else _check_exps(op, *exps)
+    _R._check_attn_workspace(workspace, q, B, heads, hd)
+    out = torch.empty_like(q)
+    _R._attn_call("quip_" + op + ("_f16" if exps is None else ""), q, *_R._ptrs(q, k, v, cos, sin, pos, table, kpool, vpool, out),
+                  B, heads, kvh, hd, max_len, kpool.shape[0], table.shape[1], 1.0 / math.sqrt(hd), int(window),
+                  _R._ptr(workspace), _R._stream(q), *more)
+    return out
+
+
+def _ragged_paged(op, q, k, v, cos, sin, pos, seg_slot, seg_rows, table, kpool, vpool, window, exps=None):
+    """both paged ragged ops; exps as in _decode_paged"""
+    rows, heads, kvh, hd, max_len, B = _R._check_attn(op, "ragged", q, k, v, cos, sin, pos, kpool, vpool, table,
+                                                      torch.float16 if exps is None else torch.uint8)
+    more = () if exps is None else _check_exps(op, *exps)
+    n, slots, counts = _R._pack_segments(op, seg_slot, seg_rows, rows, B)
+    out = torch.empty_like(q)
+    _R._attn_call("quip_" + op + ("_f16" if exps is None else ""), q, *_R._ptrs(q, k, v, cos, sin, pos, table, kpool, vpool, out),
+                  rows, heads, kvh, hd, max_len, B, kpool.shape[0], table.shape[1], ctypes.addressof(slots),
+                  ctypes.addressof(counts), n, 1.0 / math.sqrt(hd), int(window), _R._stream(q), *more)
+    return out
+
+
+def _rope_attn_decode_paged_cuda(q, k, v, cos, sin, pos, table, kpool, vpool, workspace=None, window=0):
+    """rope_attn_decode_batched with q (B, heads, hd), k / v (B, kv_heads, hd), pos (B,) and the caches behind `table`;
+    row pos[b] of slot b is written -> (B, heads, hd) fp16"""
+    return _decode_paged("rope_attn_decode_paged", q, k, v, cos, sin, pos, table, kpool, vpool, workspace, window)
+
+
+def _rope_attn_ragged_paged_cuda(q, k, v, cos, sin, pos, seg_slot, seg_rows, table, kpool, vpool, window=0):
+    """rope_attn_ragged with the caches behind `table`: rows [pos[slot], pos[slot] + seg_rows[s]) of every named slot are
+    written -> (rows, heads, hd) fp16"""
+    return _ragged_paged("rope_attn_ragged_paged", q, k, v, cos, sin, pos, seg_slot, seg_rows, table, kpool, vpool, window)
+
+
 def _rope_attn_decode_paged_f8_cuda(q, k, v, cos, sin, pos, table, kpool, vpool, workspace=None, window=0, k_exp=0, v_exp=0):
     """rope_attn_decode_paged on uint8 pools of e4m3fn bytes at exponents (k_exp, v_exp) -> (B, heads, hd) fp16"""
-    heads, hd, kvh, max_len, B, n_pages, max_pages = _check_paged("rope_attn_decode_paged_f8", q, k, v, cos, sin, pos, table,
-                                                                  kpool, vpool, True, torch.uint8)
-    k_exp, v_exp = _check_exps("rope_attn_decode_paged_f8", k_exp, v_exp)
-    if workspace is not None:
-        _R._need(workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == q.device
-                 and workspace.numel() >= capi.lib().quip_rope_attn_batched_workspace_bytes(B, heads, hd),
-                 "workspace: use rope_attn_batched_workspace(batch, heads, head_dim, device)")
-    out = torch.empty_like(q)
-    with torch.cuda.device(q.device):
-        capi.check(capi.lib().quip_rope_attn_decode_paged_f8(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), table.data_ptr(),
-            kpool.data_ptr(), vpool.data_ptr(), out.data_ptr(), B, heads, kvh, hd, max_len, n_pages, max_pages,
-            1.0 / math.sqrt(hd), int(window), _R._ptr(workspace), _R._stream(q), k_exp, v_exp),
-            "quip_rope_attn_decode_paged_f8")
-    return out
+    return _decode_paged("rope_attn_decode_paged_f8", q, k, v, cos, sin, pos, table, kpool, vpool, workspace, window,
+                         (k_exp, v_exp))
 
 
 def _rope_attn_ragged_paged_f8_cuda(q, k, v, cos, sin, pos, seg_slot, seg_rows, table, kpool, vpool, window=0, k_exp=0,
                                     v_exp=0):
     """rope_attn_ragged_paged on uint8 pools of e4m3fn bytes at exponents (k_exp, v_exp) -> (rows, heads, hd) fp16"""
-    need = _R._need
-    heads, hd, kvh, max_len, B, n_pages, max_pages = _check_paged("rope_attn_ragged_paged_f8", q, k, v, cos, sin, pos, table,
-                                                                  kpool, vpool, False, torch.uint8)
-    k_exp, v_exp = _check_exps("rope_attn_ragged_paged_f8", k_exp, v_exp)
-    rows = q.shape[0]
-    seg_slot, seg_rows = [int(x) for x in seg_slot], [int(x) for x in seg_rows]
-    n = len(seg_slot)
-    need(1 <= n <= MAX_SEGMENTS and len(seg_rows) == n,
-         f"rope_attn_ragged_paged_f8: 1 .. {MAX_SEGMENTS} segments, one slot and one row count each")
-    need(all(r >= 1 for r in seg_rows) and sum(seg_rows) == rows, "rope_attn_ragged_paged_f8: seg_rows >= 1 that sum to q's rows")
-    need(all(0 <= b < B for b in seg_slot) and len(set(seg_slot)) == n, "rope_attn_ragged_paged_f8: distinct slots in [0, B)")
-    slots, counts = (ctypes.c_int32 * n)(*seg_slot), (ctypes.c_int32 * n)(*seg_rows)
-    out = torch.empty_like(q)
-    with torch.cuda.device(q.device):
-        capi.check(capi.lib().quip_rope_attn_ragged_paged_f8(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), table.data_ptr(),
-            kpool.data_ptr(), vpool.data_ptr(), out.data_ptr(), rows, heads, kvh, hd, max_len, B, n_pages, max_pages,
-            ctypes.addressof(slots), ctypes.addressof(counts), n, 1.0 / math.sqrt(hd), int(window), _R._stream(q),
-            k_exp, v_exp), "quip_rope_attn_ragged_paged_f8")
-    return out
+    return _ragged_paged("rope_attn_ragged_paged_f8", q, k, v, cos, sin, pos, seg_slot, seg_rows, table, kpool, vpool, window,
+                         (k_exp, v_exp))
 
 
 try:

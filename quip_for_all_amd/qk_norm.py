@@ -54,31 +54,26 @@ def _qk_norm_rows_cuda(q, k, q_weight, k_weight, head_dim, eps):
 
 def _rope_attn_decode_qknorm_cuda(q, k, v, cos, sin, pos, kcache, vcache, workspace, window, q_weight, k_weight, eps):
     """quip_lib::rope_attn_decode with the norm on q and the new k row"""
-    heads, kvh, hd, max_len = _R._check_rope_attn_decode(q, k, v, cos, sin, pos, kcache, vcache, workspace)
+    _, heads, kvh, hd, max_len, _ = _R._check_attn("rope_attn_decode", "bs1", q, k, v, cos, sin, pos, kcache, vcache)
+    _R._check_attn_workspace(workspace, q, None, heads, hd)
     _check_weights("rope_attn_decode_qknorm", q, hd, q_weight, k_weight)
     out = torch.empty_like(q)
-    with torch.cuda.device(q.device):
-        capi.check(capi.lib().quip_rope_attn_decode_qknorm_f16(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
-            kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), heads, kvh, hd, max_len, 1.0 / math.sqrt(hd),
-            int(window), _R._ptr(workspace), _R._stream(q), q_weight.data_ptr(), k_weight.data_ptr(), float(eps)),
-            "quip_rope_attn_decode_qknorm_f16")
+    _R._attn_call("quip_rope_attn_decode_qknorm_f16", q, *_R._ptrs(q, k, v, cos, sin, pos, kcache, vcache, out), heads, kvh, hd,
+                  max_len, 1.0 / math.sqrt(hd), int(window), _R._ptr(workspace), _R._stream(q), q_weight.data_ptr(),
+                  k_weight.data_ptr(), float(eps))
     return out
 
 
 def _rope_attn_decode_batched_qknorm_cuda(q, k, v, cos, sin, pos, kcache, vcache, workspace, window, q_weight, k_weight,
                                           eps):
     """quip_lib::rope_attn_decode_batched with the norm on q and the new k rows"""
-    from .batch_decode import _check_batched_operands
-    B, heads, kvh, hd, max_len = _check_batched_operands(q, k, v, cos, sin, pos, kcache, vcache, workspace)
+    B, heads, kvh, hd, max_len, _ = _R._check_attn("rope_attn_decode_batched", "batched", q, k, v, cos, sin, pos, kcache, vcache)
+    _R._check_attn_workspace(workspace, q, B, heads, hd)
     _check_weights("rope_attn_decode_batched_qknorm", q, hd, q_weight, k_weight)
     out = torch.empty_like(q)
-    with torch.cuda.device(q.device):
-        capi.check(capi.lib().quip_rope_attn_decode_batched_qknorm_f16(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
-            kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), B, heads, kvh, hd, max_len, 1.0 / math.sqrt(hd),
-            int(window), _R._ptr(workspace), _R._stream(q), q_weight.data_ptr(), k_weight.data_ptr(), float(eps)),
-            "quip_rope_attn_decode_batched_qknorm_f16")
+    _R._attn_call("quip_rope_attn_decode_batched_qknorm_f16", q, *_R._ptrs(q, k, v, cos, sin, pos, kcache, vcache, out), B, heads,
+                  kvh, hd, max_len, 1.0 / math.sqrt(hd), int(window), _R._ptr(workspace), _R._stream(q), q_weight.data_ptr(),
+                  k_weight.data_ptr(), float(eps))
     return out
 
 

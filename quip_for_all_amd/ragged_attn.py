@@ -10,10 +10,9 @@ import math
 
 import torch
 
-from . import capi
 from . import register_lib as _R
 
-MAX_SEGMENTS = 32          # QUIP_RAGGED_MAX_SEGMENTS
+MAX_SEGMENTS = _R._MAX_SEGMENTS          # QUIP_RAGGED_MAX_SEGMENTS
 
 try:
     _R._lib.define("rope_attn_ragged(Tensor q, Tensor k, Tensor v, Tensor cos, Tensor sin, Tensor pos, int[] seg_slot, "
@@ -27,33 +26,12 @@ def _rope_attn_ragged_cuda(q, k, v, cos, sin, pos, seg_slot, seg_rows, kcache, v
     the device; seg_slot / seg_rows: python ints, sum(seg_rows) == rows, distinct slots in [0, B); kcache / vcache
     (B, kv_heads, max_len, hd) fp16, rows [pos[slot], pos[slot] + seg_rows[s]) of every named slot are written
     -> (rows, heads, hd) fp16"""
-    need = _R._need
-    for t in (q, k, v, kcache, vcache):
-        need(t.dtype == torch.float16 and t.is_contiguous() and t.is_cuda and t.device == q.device,
-             "rope_attn_ragged: fp16 contiguous tensors on one CUDA device")
-    need(cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
-         and cos.device == q.device and sin.device == q.device, "cos / sin must be contiguous float32 on q's device")
-    need(q.dim() == 3 and kcache.dim() == 4, "rope_attn_ragged: q (rows, heads, hd), caches (B, kv_heads, max_len, hd)")
-    rows, heads, hd = q.shape
-    B, kvh, max_len = kcache.shape[0], kcache.shape[1], kcache.shape[2]
-    need(pos.dtype == torch.int64 and tuple(pos.shape) == (B,) and pos.is_contiguous() and pos.device == q.device,
-         "pos must be a contiguous int64 (B,) tensor on q's device")
-    need(tuple(k.shape) == (rows, kvh, hd) and tuple(v.shape) == (rows, kvh, hd) and tuple(kcache.shape) == (B, kvh, max_len, hd)
-         and tuple(vcache.shape) == tuple(kcache.shape) and tuple(cos.shape) == (max_len, hd)
-         and tuple(sin.shape) == (max_len, hd), "rope_attn_ragged: shape mismatch")
-    seg_slot, seg_rows = [int(x) for x in seg_slot], [int(x) for x in seg_rows]
-    n = len(seg_slot)
-    need(1 <= n <= MAX_SEGMENTS and len(seg_rows) == n, f"rope_attn_ragged: 1 .. {MAX_SEGMENTS} segments, one slot and one row count each")
-    need(all(r >= 1 for r in seg_rows) and sum(seg_rows) == rows, "rope_attn_ragged: seg_rows >= 1 that sum to q's rows")
-    need(all(0 <= b < B for b in seg_slot) and len(set(seg_slot)) == n, "rope_attn_ragged: distinct slots in [0, B)")
-    slots, counts = (ctypes.c_int32 * n)(*seg_slot), (ctypes.c_int32 * n)(*seg_rows)
+    rows, heads, kvh, hd, max_len, B = _R._check_attn("rope_attn_ragged", "ragged", q, k, v, cos, sin, pos, kcache, vcache)
+    n, slots, counts = _R._pack_segments("rope_attn_ragged", seg_slot, seg_rows, rows, B)
     out = torch.empty_like(q)
-    with torch.cuda.device(q.device):
-        capi.check(capi.lib().quip_rope_attn_ragged_f16(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
-            kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), rows, heads, kvh, hd, max_len, B,
-            ctypes.addressof(slots), ctypes.addressof(counts), n, 1.0 / math.sqrt(hd), int(window), _R._stream(q)),
-            "quip_rope_attn_ragged_f16")
+    _R._attn_call("quip_rope_attn_ragged_f16", q, *_R._ptrs(q, k, v, cos, sin, pos, kcache, vcache, out), rows, heads, kvh, hd,
+                  max_len, B, ctypes.addressof(slots), ctypes.addressof(counts), n, 1.0 / math.sqrt(hd), int(window),
+                  _R._stream(q))
     return out
 
 

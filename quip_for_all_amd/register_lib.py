@@ -147,6 +147,90 @@ def _need(cond, msg):
         raise ValueError("quip_lib: " + msg)
 
 
+# ---- the attention ops (here, batch_decode, chunk_attn, ragged_attn, paged_attn, qk_norm): one set of operand checks ----
+_PAGE = 64              # positions per page of a paged cache (kPage, csrc/decode_glue.hip)
+_MAX_SEGMENTS = 32      # QUIP_RAGGED_MAX_SEGMENTS
+
+
+def _ptrs(*tensors):
+    return [t.data_ptr() for t in tensors]
+
+
+def _attn_call(entry, q, *args):
+    """one attention entry point of the C ABI on q's device; the softmax scale is the caller's argument like every other"""
+    with torch.cuda.device(q.device):
+        capi.check(getattr(capi.lib(), entry)(*args), entry)
+
+
+def _check_attn(what, layout, q, k, v, cos, sin, pos, kcache, vcache, table=None, pool_dtype=torch.float16):
+    """The checks of the q / k / v / cos / sin / pos / cache family: dtype, contiguity, device and shape.  layout:
+        "bs1"      q (heads, hd), k / v (kv_heads, hd), caches (kv_heads, max_len, hd), pos one element
+        "chunk"    q (rows, heads, hd), k / v (rows, kv_heads, hd), caches and pos as bs1
+        "batched"  q (B, heads, hd), k / v (B, kv_heads, hd), caches (B, kv_heads, max_len, hd), pos (B,)
+        "ragged"   q (rows, heads, hd), k / v (rows, kv_heads, hd), caches and pos as batched
+    With `table` (B, max_pages) int32 ("batched" / "ragged") the caches are pools (n_pages, kv_heads, 64, hd) of pool_dtype
+    and max_len is the row count of cos.  -> (q.shape[0] or 1, heads, kv_heads, hd, max_len, B or 1)
+    Two differences between the layouts are kept as they always were.  bs1 asks for CUDA tensors but does not compare
+    their devices (and does not ask where cos / sin live): the bs = 1 decoder is the only caller and allocates all of
+    them together.  Only chunk refuses zero rows itself; the other layouts leave an empty q to the entry point."""
+    f16, bs1, slots, paged = torch.float16, layout == "bs1", layout in ("batched", "ragged"), table is not None
+    if paged:     # (first: a pool of the other dtype is named as such whatever else is wrong)
+        _need(kcache.dtype == pool_dtype and vcache.dtype == pool_dtype,
+              f"{what}: the pools must be {'fp16' if pool_dtype == f16 else 'uint8 (e4m3fn bytes)'}")
+    here = (lambda t: t.is_cuda) if bs1 else (lambda t: t.is_cuda and t.device == q.device)
+    for t in (q, k, v, kcache, vcache):
+        _need(t.dtype == (pool_dtype if t is kcache or t is vcache else f16) and t.is_contiguous() and here(t),
+              f"{what}: fp16 contiguous tensors on one CUDA device")
+    _need(all(t.dtype == torch.float32 and t.is_contiguous() and (bs1 or t.device == q.device) for t in (cos, sin)),
+          "cos / sin must be contiguous float32" + ("" if bs1 else " on q's device"))
+    _need(q.dim() == (2 if bs1 else 3) and kcache.dim() == (4 if slots else 3) and (not paged or table.dim() == 2),
+          f"{what}: q ({'' if bs1 else 'B, ' if layout == 'batched' else 'rows, '}heads, hd), " +
+          (f"pools (n_pages, kv_heads, {_PAGE}, hd), table (B, max_pages)" if paged else
+           f"caches ({'B, ' if slots else ''}kv_heads, max_len, hd)"))
+    lead, (heads, hd) = 1 if bs1 else q.shape[0], q.shape[-2:]
+    if paged:
+        kvh, (B, max_pages), max_len = kcache.shape[1], table.shape, cos.shape[0]
+        cache_shape = (kcache.shape[0], kvh, _PAGE, hd)
+        _need(table.dtype == torch.int32 and table.is_contiguous() and table.device == q.device,
+              "table must be a contiguous int32 (B, max_pages) tensor on q's device")
+    else:
+        B, kvh, max_len = (1,) * (not slots) + tuple(kcache.shape[:-1])
+        cache_shape = tuple(kcache.shape[:-1]) + (hd,)
+    if slots:
+        _need(pos.dtype == torch.int64 and tuple(pos.shape) == (B,) and pos.is_contiguous() and pos.device == q.device,
+              "pos must be a contiguous int64 (B,) tensor on q's device")
+        _need(layout != "batched" or lead == B, f"{what}: one q row per slot")
+    else:
+        _need(pos.dtype == torch.int64 and pos.numel() == 1 and (pos.is_cuda if bs1 else pos.device == q.device),
+              "pos must be an int64 device scalar" + ("" if bs1 else " on q's device"))
+        _need(lead >= 1, f"{what}: at least one row")
+    kv_shape = (kvh, hd) if bs1 else (lead, kvh, hd)
+    _need(tuple(k.shape) == kv_shape and tuple(v.shape) == kv_shape and tuple(kcache.shape) == cache_shape
+          and tuple(vcache.shape) == cache_shape and tuple(cos.shape) == (max_len, hd) and tuple(sin.shape) == (max_len, hd)
+          and (not paged or (cache_shape[0] >= 1 and max_pages >= 1 and 1 <= max_len <= max_pages * _PAGE)),
+          f"{what}: shape mismatch")
+    return lead, heads, kvh, hd, max_len, B
+
+
+def _check_attn_workspace(workspace, q, batch, heads, hd):
+    """the optional split-mode workspace of a decode-side launch: enough zeroed bytes on q's device; batch None: bs = 1"""
+    if workspace is not None:
+        _need(workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == q.device
+              and workspace.numel() >= capi.lib().quip_rope_attn_batched_workspace_bytes(batch or 1, heads, hd),
+              "workspace: use rope_attn_workspace(heads, head_dim, device)" if batch is None else
+              "workspace: use rope_attn_batched_workspace(batch, heads, head_dim, device)")
+
+
+def _pack_segments(what, seg_slot, seg_rows, rows, B):
+    """the segment lists of a ragged launch, checked -> (n, slots, counts), the two as ctypes int32 arrays"""
+    seg_slot, seg_rows = [int(x) for x in seg_slot], [int(x) for x in seg_rows]
+    n = len(seg_slot)
+    _need(1 <= n <= _MAX_SEGMENTS and len(seg_rows) == n, f"{what}: 1 .. {_MAX_SEGMENTS} segments, one slot and one row count each")
+    _need(all(r >= 1 for r in seg_rows) and sum(seg_rows) == rows, f"{what}: seg_rows >= 1 that sum to q's rows")
+    _need(all(0 <= b < B for b in seg_slot) and len(set(seg_slot)) == n, f"{what}: distinct slots in [0, B)")
+    return n, (ctypes.c_int32 * n)(*seg_slot), (ctypes.c_int32 * n)(*seg_rows)
+
+
 def _chk_x(x: Tensor):
     _need(x.dim() == 2, "x must be 2-D (M, in)")
     _need(x.dtype == torch.float16, f"x must be float16, got {x.dtype}")
@@ -262,7 +346,6 @@ def _had_transform_fused_cuda(x, out_features, n, K, had, transpose, pre, pre2, 
     _chk_lens("had_transform_fused", xc.shape[1], out_features, n, K, had, pre, pre2, post, bias, rms_weight)
     y = _empty((xc.shape[0], out_features), dtype=torch.float16, device=x.device)
     f = _fusion(residual, rms_weight, rms_eps, gate, x)
-    import ctypes
     with torch.cuda.device(x.device):
         capi.check(capi.lib().quip_had_transform_fused_f16(
             xc.data_ptr(), y.data_ptr(), xc.shape[0], xc.shape[1], out_features, n, K, _ptr(had),
@@ -285,7 +368,6 @@ def _had_transform_planes_fused_cuda(x, n, K, had, transpose, pre, scale, rms_we
     L = capi.lib()
     planes = _empty(L.quip_e8p_planes_bytes(n), dtype=torch.uint8, device=x.device)
     f = _fusion(None, rms_weight, rms_eps, gate, x)
-    import ctypes
     with torch.cuda.device(x.device):
         capi.check(L.quip_had_transform_planes_fused(xc.data_ptr(), planes.data_ptr(), xc.shape[1], n, K, _ptr(had),
                                                      int(bool(transpose)), _ptr(pre), float(scale), ctypes.byref(f),
@@ -310,7 +392,6 @@ def _had_transform_planes_rows_cuda(x, n, K, had, transpose, pre, scale, rms_wei
     pr = capi.HadProblem(xc.data_ptr(), out.data_ptr(), _vec_ok(had, x.device), _vec_ok(pre, x.device), None, None,
                          None, None, _vec_ok(rms_weight, x.device), _ptr(gate), xc.shape[1], n, float(scale),
                          float(rms_eps), None, None, None, None, 1.0, *_layout(resid_scale))
-    import ctypes
     with torch.cuda.device(x.device):
         capi.check(L.quip_had_transform_planes_rows(ctypes.byref(pr), rows, n, K, int(bool(transpose)), _stream(x)),
                    "quip_had_transform_planes_rows")
@@ -399,7 +480,6 @@ def _gemv_planes_rows_mode_cuda(planes, Qidxs, grid, grid2, mode):
 
 
 def _e8p_mm_planes_rows_cuda(planes, Qidxs, grid):
-    import ctypes
     count = len(planes)
     _need(1 <= count <= capi.MAX_GROUP, "1..3 rows")
     _need(Qidxs.dtype == torch.int16 and Qidxs.is_contiguous(), "Qidxs must be contiguous int16 (n, k/8)")
@@ -519,7 +599,6 @@ class _RawWorkspace:
     _hip = None
 
     def __init__(self, nbytes, dev):
-        import ctypes
         if _RawWorkspace._hip is None:
             _RawWorkspace._hip = ctypes.CDLL("libamdhip64.so")
         hip = _RawWorkspace._hip
@@ -541,7 +620,6 @@ class _RawWorkspace:
 
     def read(self):
         """the contents as an int32 CPU tensor (tests: a launch leaves its workspace zeroed); synchronises the device"""
-        import ctypes
         out = torch.empty(self.nbytes // 4, dtype=torch.int32)
         torch.cuda.synchronize()
         rc = _RawWorkspace._hip.hipMemcpy(ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(self.ptr), ctypes.c_size_t(self.nbytes), 2)
@@ -638,7 +716,6 @@ def _e8p_gemv_planes_cuda(planes, Qidxs, grid):
 
 
 def _e8p_gemv_fused_cuda(x, z, post, residual, rms_weight, rms_eps, z_scale, pre, scale, Qidxs, grid):
-    import ctypes
     count = len(Qidxs)
     _need(1 <= count <= capi.MAX_GROUP and len(pre) == count and len(scale) == count, "group of 1..3 problems")
     k = Qidxs[0].shape[1] * 8
@@ -712,7 +789,6 @@ def _ffn_engine_cuda(planes_gate, planes_up, q_gate, q_up, q_down, had3, sv_gate
                            planes_up.data_ptr(), had3.data_ptr(), sv_gate.data_ptr(), sv_up.data_ptr(),
                            su_down.data_ptr(), out.data_ptr(), g.data_ptr(), workspace.data_ptr(), _ptr(dbg),
                            float(out_scale), float(in_scale), hidden, n_ffn, int(K))
-    import ctypes
     with torch.cuda.device(dev):
         capi.check(capi.lib().quip_ffn_engine(ctypes.byref(a), _stream(planes_gate)), "quip_ffn_engine")
     return out
@@ -769,7 +845,6 @@ def _block_engine_cuda(layers, h_in, pos, cos, sin, grid, workspace, n_layers, m
                              sin.data_ptr(), g.data_ptr(), workspace.data_ptr(), _ptr(dbg), int(n_layers), int(max_len),
                              int(dbg_layer), float(rms_eps), float(attn_scale), int(codebook), float(resid_scale), int(shape),
                              _ptr(grid2) if codebook == 4 else None)
-    import ctypes
     with torch.cuda.device(dev):
         rc = capi.lib().quip_block_engine(ctypes.byref(a), _stream(h_in))
         # (shape 1, dbg_layer == -2: the measurement mode answers QUIP_NO_RESULT = 1 -- the caller asked for exactly that)
@@ -783,37 +858,14 @@ def rope_attn_workspace(heads, head_dim, device):
     return torch.zeros(capi.lib().quip_rope_attn_workspace_bytes(heads, head_dim), dtype=torch.uint8, device=device)
 
 
-def _check_rope_attn_decode(q, k, v, cos, sin, pos, kcache, vcache, workspace):
-    """the operand checks of the bs = 1 decode launch (rope_attn_decode, rope_attn_decode_qknorm) -> (heads, kv_heads, hd,
-    max_len)"""
-    for t in (q, k, v, kcache, vcache):
-        _need(t.dtype == torch.float16 and t.is_contiguous() and t.is_cuda, "rope_attn_decode: fp16 contiguous CUDA tensors")
-    _need(cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous(),
-          "cos / sin must be contiguous float32")
-    _need(pos.dtype == torch.int64 and pos.numel() == 1 and pos.is_cuda, "pos must be an int64 device scalar")
-    heads, hd = q.shape
-    kvh, max_len = kcache.shape[0], kcache.shape[1]
-    _need(tuple(k.shape) == (kvh, hd) and tuple(v.shape) == (kvh, hd) and tuple(vcache.shape) == tuple(kcache.shape)
-          and kcache.shape[2] == hd and tuple(cos.shape) == (max_len, hd) and tuple(sin.shape) == (max_len, hd),
-          "rope_attn_decode: shape mismatch")
-    if workspace is not None:
-        _need(workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == q.device
-              and workspace.numel() >= capi.lib().quip_rope_attn_workspace_bytes(heads, hd),
-              "workspace: use rope_attn_workspace(heads, head_dim, device)")
-    return heads, kvh, hd, max_len
-
-
 def _rope_attn_decode_cuda(q, k, v, cos, sin, pos, kcache, vcache, workspace=None, window=0):
     """q (heads, hd), k / v (kv_heads, hd) fp16; cos / sin (max_len, hd) fp32; pos int64 device scalar;
     kcache / vcache (kv_heads, max_len, hd) fp16 (row pos is written) -> (heads, hd) fp16"""
-    import math
-    heads, kvh, hd, max_len = _check_rope_attn_decode(q, k, v, cos, sin, pos, kcache, vcache, workspace)
+    _, heads, kvh, hd, max_len, _ = _check_attn("rope_attn_decode", "bs1", q, k, v, cos, sin, pos, kcache, vcache)
+    _check_attn_workspace(workspace, q, None, heads, hd)
     out = torch.empty_like(q)
-    with torch.cuda.device(q.device):
-        capi.check(capi.lib().quip_rope_attn_decode_window_f16(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
-            kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), heads, kvh, hd, max_len, 1.0 / math.sqrt(hd),
-            int(window), _ptr(workspace), _stream(q)), "quip_rope_attn_decode_window_f16")
+    _attn_call("quip_rope_attn_decode_window_f16", q, *_ptrs(q, k, v, cos, sin, pos, kcache, vcache, out), heads, kvh, hd,
+               max_len, 1.0 / math.sqrt(hd), int(window), _ptr(workspace), _stream(q))
     return out
 
 
@@ -824,8 +876,6 @@ def rope_attn_decode_z_supported(heads, kv_heads, head_dim):
 def _rope_attn_decode_z_cuda(zs, posts, scales, cos, sin, pos, kcache, vcache, workspace=None, window=0):
     """zs / posts: the raw GEMV outputs (1, n) or (n,) and SV vectors (n,) of q / k / v_proj, fp16; the rest as
     rope_attn_decode -> (heads, hd) fp16"""
-    import ctypes
-    import math
     _need(len(zs) == 3 and len(posts) == 3 and len(scales) == 3, "rope_attn_decode_z: q, k, v")
     kvh, max_len, hd = kcache.shape
     n = zs[0].numel()
@@ -843,18 +893,12 @@ def _rope_attn_decode_z_cuda(zs, posts, scales, cos, sin, pos, kcache, vcache, w
     _need(pos.dtype == torch.int64 and pos.numel() == 1 and pos.is_cuda, "pos must be an int64 device scalar")
     _need(tuple(vcache.shape) == tuple(kcache.shape), "cache shapes differ")
     out = _empty((heads, hd), dtype=torch.float16, device=kcache.device)
-    if workspace is not None:
-        _need(workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == kcache.device
-              and workspace.numel() >= capi.lib().quip_rope_attn_workspace_bytes(heads, hd),
-              "workspace: use rope_attn_workspace(heads, head_dim, device)")
+    _check_attn_workspace(workspace, kcache, None, heads, hd)
     zp = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in zs])
     pp = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in posts])
     sc = (ctypes.c_float * 3)(*[float(x) for x in scales])
-    with torch.cuda.device(kcache.device):
-        capi.check(capi.lib().quip_rope_attn_decode_z_window_f16(
-            zp, pp, sc, cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), kcache.data_ptr(), vcache.data_ptr(),
-            out.data_ptr(), heads, kvh, hd, max_len, 1.0 / math.sqrt(hd), int(window), _ptr(workspace), _stream(kcache)),
-            "quip_rope_attn_decode_z_window_f16")
+    _attn_call("quip_rope_attn_decode_z_window_f16", kcache, zp, pp, sc, *_ptrs(cos, sin, pos, kcache, vcache, out), heads, kvh,
+               hd, max_len, 1.0 / math.sqrt(hd), int(window), _ptr(workspace), _stream(kcache))
     return out
 
 
