@@ -127,6 +127,7 @@ _INTERNAL = {
     "quip_e8p_gemv_v2_workspace_bytes": [_I32],
     "quip_e8p_gemv_v2_plan": [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "quip_e8p_gemv_tuned": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P],
+    "quip_had_plan": [_P, _I32, _I32, _I64, _I32, _I32, _I32, _P],
 }
 
 class HadProblem(_c.Structure):
@@ -195,6 +196,8 @@ def lib():
             fn.restype = _c.c_size_t if name.endswith("_bytes") else _c.c_int
         L.quip_strerror.argtypes = [_c.c_int]
         L.quip_strerror.restype = _c.c_char_p
+        L.quip_had_plan_kind_name.argtypes = [_I32]
+        L.quip_had_plan_kind_name.restype = _c.c_char_p
         _lib = L
     return _lib
 
@@ -218,6 +221,31 @@ def gemv_v2_plan(ns, k, rep=0, slots=0, blocks=0, ksplit=0, max_waves=0, runlen=
     out = (_I32 * len(GEMV_V2_PLAN_FIELDS))()
     lib().quip_e8p_gemv_v2_plan(n, len(ns), k, rep, slots, blocks, ksplit, max_waves, runlen, int(bool(grid2)), int(bool(ws)), out)
     return list(out)
+
+
+HAD_PLAN_FIELDS = ("rc", "kind", "grid_x", "grid_y", "grid_z", "threads", "lds")
+HAD_PLAN_PROBLEM_FIELDS = ("pp", "tgroups", "part_off", "chain_off", "vec", "vec_out")
+
+
+def had_plan(problems, planes, rows, n, K, transpose=0):
+    """The plan of the transform launch that quip_had_transform_group_f16 (planes false) / _planes_group and _planes_rows
+    (planes true) would make for these HadProblems: [rc, kernel instantiation as text or None, grid x, y, z, threads, lds,
+    then one list in the order of HAD_PLAN_PROBLEM_FIELDS per problem].  The entry point's validation runs, nothing is
+    launched and no pointer is dereferenced: host scratch pointers do, no GPU is needed."""
+    arr = (HadProblem * max(len(problems), 1))(*problems)
+    out = (_I32 * (len(HAD_PLAN_FIELDS) + len(HAD_PLAN_PROBLEM_FIELDS) * MAX_GROUP))()
+    lib().quip_had_plan(arr, len(problems), int(bool(planes)), rows, n, K, transpose, out)
+    v, name = list(out), lib().quip_had_plan_kind_name(out[1])
+    per = [v[7 + 6 * i:13 + 6 * i] for i in range(v[4])]
+    return [v[0], name.decode() if name else None] + v[2:7] + per
+
+
+def had_plan_kinds():
+    """every kernel instantiation a transform launch can take, as text, in the order of the library's enum"""
+    names, L = [], lib()
+    while L.quip_had_plan_kind_name(len(names)):
+        names.append(L.quip_had_plan_kind_name(len(names)).decode())
+    return names
 
 
 def check(code, what):

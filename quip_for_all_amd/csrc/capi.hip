@@ -239,104 +239,122 @@ int quip_debug_occupy(int32_t nwg, int32_t lds_bytes, int64_t ticks, void* sink,
   return launch<occupy_kernel>(dim3(nwg), dim3(64), lds_bytes, (hipStream_t)stream, (long long)ticks, reinterpret_cast<unsigned*>(sink));
 }
 
-int quip_hadamard_f16(const void* x, void* y, int64_t rows, int32_t n, float scale,
-                      quip_stream_t stream) {
-  if (!x || !y) return QUIP_ERR_NULL_POINTER;
-  return had_transform_launch(x, y, rows, n, n, n, 1, nullptr, 0, nullptr, nullptr, nullptr,
-                              nullptr, scale, (hipStream_t)stream);
+// pointer lists of an entry point's prologue (the transform entries here, the attention entries below)
+namespace {
+using Ptrs = std::initializer_list<const void*>;
+bool any_null(Ptrs ps) {
+  for (const void* p : ps)
+    if (!p) return true;
+  return false;
+}
+bool any_off(Ptrs ps, uintptr_t mask) {
+  for (const void* p : ps)
+    if (reinterpret_cast<uintptr_t>(p) & mask) return true;
+  return false;
 }
 
-int quip_hadamard(const void* x, void* y, int64_t rows, int32_t n, float scale, int32_t dtype,
-                  quip_stream_t stream) {
+// ---- the Hadamard transform entry points ---------------------------------------------------------------------------------
+// Inside the library a problem is the public quip_had_problem, and every entry ends in had_transform_group_launch
+// (hadamard.hip), which answers the sizes, the chain and the optional pointers.  What an entry looks at first is ABI and
+// stays its own: had_refusal answers its pointer lists, NULL before MISALIGNED -- the loose-argument entries name x and
+// their output (plane images 16-byte aligned), the problem-struct entries every problem's input (x or, chained, z) and
+// output, after `problems` and the count.
+int had_refusal(Ptrs required, Ptrs a16 = {}) {
+  if (any_null(required)) return QUIP_ERR_NULL_POINTER;
+  return any_off(a16, 15) ? QUIP_ERR_MISALIGNED : QUIP_OK;
+}
+int had_group_refusal(const quip_had_problem* problems, int32_t count) {
+  if (!problems) return QUIP_ERR_NULL_POINTER;
+  if (count < 1 || count > QUIP_MAX_GROUP) return QUIP_ERR_BAD_SHAPE;
+  for (int i = 0; i < count; ++i)
+    if (int rc = had_refusal({problems[i].x ? problems[i].x : problems[i].z, problems[i].out})) return rc;
+  return QUIP_OK;
+}
+// a loose-argument entry as one problem of the group launcher; planes: one row, out_features = n, no residual
+int had_single(bool planes, const void* x, void* out, int64_t rows, int32_t in_features, int32_t out_features, int32_t n,
+               int32_t K, const void* had, int32_t transpose, const void* pre_scale, const void* pre_scale2,
+               const void* post_scale, const void* bias, float scale, const quip_had_fusion* fusion, quip_stream_t stream) {
+  quip_had_problem pr{};
+  pr.x = x; pr.out = out; pr.had = had;
+  pr.pre_scale = pre_scale; pr.pre_scale2 = pre_scale2; pr.post_scale = post_scale; pr.bias = bias;
+  pr.in_features = in_features; pr.out_features = out_features;
+  pr.scale = scale; pr.rms_eps = 1e-5f; pr.z_scale = 1.f;
+  if (fusion) {
+    pr.residual = planes ? nullptr : fusion->residual;
+    pr.rms_weight = fusion->rms_weight; pr.gate = fusion->gate; pr.rms_eps = fusion->rms_eps;
+  }
+  return had_transform_group_launch(&pr, 1, planes, rows, n, K, transpose, (hipStream_t)stream);
+}
+}  // namespace
+
+int quip_hadamard_f16(const void* x, void* y, int64_t rows, int32_t n, float scale, quip_stream_t stream) {
+  if (int rc = had_refusal({x, y})) return rc;
+  return had_single(false, x, y, rows, n, n, n, 1, nullptr, 0, nullptr, nullptr, nullptr, nullptr, scale, nullptr, stream);
+}
+
+int quip_hadamard(const void* x, void* y, int64_t rows, int32_t n, float scale, int32_t dtype, quip_stream_t stream) {
   if (!x || !y) return QUIP_ERR_NULL_POINTER;
   if (dtype == QUIP_DTYPE_F16) return quip_hadamard_f16(x, y, rows, n, scale, stream);
   return hadamard_generic_launch(x, y, rows, n, scale, dtype, (hipStream_t)stream);
 }
 
-int quip_had_transform_f16(const void* x, void* y, int64_t rows, int32_t in_features,
-                           int32_t out_features, int32_t n, int32_t K, const void* had,
-                           int32_t transpose, const void* pre_scale, const void* pre_scale2,
-                           const void* post_scale, const void* bias, float scale,
-                           quip_stream_t stream) {
-  if (!x || !y) return QUIP_ERR_NULL_POINTER;
-  return had_transform_launch(x, y, rows, in_features, out_features, n, K, had, transpose,
-                              pre_scale, pre_scale2, post_scale, bias, scale, (hipStream_t)stream);
+int quip_had_transform_f16(const void* x, void* y, int64_t rows, int32_t in_features, int32_t out_features, int32_t n,
+                           int32_t K, const void* had, int32_t transpose, const void* pre_scale, const void* pre_scale2,
+                           const void* post_scale, const void* bias, float scale, quip_stream_t stream) {
+  return quip_had_transform_fused_f16(x, y, rows, in_features, out_features, n, K, had, transpose, pre_scale, pre_scale2,
+                                      post_scale, bias, scale, nullptr, stream);
 }
 
-int quip_had_transform_planes(const void* x, void* planes, int32_t in_features, int32_t n, int32_t K,
-                              const void* had, int32_t transpose, const void* pre_scale, float scale,
-                              quip_stream_t stream) {
-  if (!x || !planes) return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(planes)) return QUIP_ERR_MISALIGNED;
-  return had_transform_planes_launch(x, planes, in_features, n, K, had, transpose, pre_scale, scale,
-                                     (hipStream_t)stream);
+int quip_had_transform_planes(const void* x, void* planes, int32_t in_features, int32_t n, int32_t K, const void* had,
+                              int32_t transpose, const void* pre_scale, float scale, quip_stream_t stream) {
+  return quip_had_transform_planes_fused(x, planes, in_features, n, K, had, transpose, pre_scale, scale, nullptr, stream);
 }
 
-static HadFusion to_fusion(const quip_had_fusion* f) {
-  HadFusion h;
-  if (f) { h.residual = f->residual; h.rms_weight = f->rms_weight; h.gate = f->gate; h.rms_eps = f->rms_eps; }
-  return h;
+int quip_had_transform_fused_f16(const void* x, void* y, int64_t rows, int32_t in_features, int32_t out_features, int32_t n,
+                                 int32_t K, const void* had, int32_t transpose, const void* pre_scale, const void* pre_scale2,
+                                 const void* post_scale, const void* bias, float scale, const quip_had_fusion* fusion,
+                                 quip_stream_t stream) {
+  if (int rc = had_refusal({x, y})) return rc;
+  return had_single(false, x, y, rows, in_features, out_features, n, K, had, transpose, pre_scale, pre_scale2, post_scale,
+                    bias, scale, fusion, stream);
 }
 
-int quip_had_transform_fused_f16(const void* x, void* y, int64_t rows, int32_t in_features,
-                                 int32_t out_features, int32_t n, int32_t K, const void* had,
-                                 int32_t transpose, const void* pre_scale, const void* pre_scale2,
-                                 const void* post_scale, const void* bias, float scale,
-                                 const quip_had_fusion* fusion, quip_stream_t stream) {
-  if (!x || !y) return QUIP_ERR_NULL_POINTER;
-  const HadFusion h = to_fusion(fusion);
-  return had_transform_launch(x, y, rows, in_features, out_features, n, K, had, transpose, pre_scale,
-                              pre_scale2, post_scale, bias, scale, (hipStream_t)stream, &h);
+int quip_had_transform_planes_fused(const void* x, void* planes, int32_t in_features, int32_t n, int32_t K, const void* had,
+                                    int32_t transpose, const void* pre_scale, float scale, const quip_had_fusion* fusion,
+                                    quip_stream_t stream) {
+  if (int rc = had_refusal({x, planes}, {planes})) return rc;
+  return had_single(true, x, planes, 1, in_features, n, n, K, had, transpose, pre_scale, nullptr, nullptr, nullptr, scale,
+                    fusion, stream);
 }
 
-int quip_had_transform_planes_fused(const void* x, void* planes, int32_t in_features, int32_t n,
-                                    int32_t K, const void* had, int32_t transpose,
-                                    const void* pre_scale, float scale,
-                                    const quip_had_fusion* fusion, quip_stream_t stream) {
-  if (!x || !planes) return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(planes)) return QUIP_ERR_MISALIGNED;
-  const HadFusion h = to_fusion(fusion);
-  return had_transform_planes_launch(x, planes, in_features, n, K, had, transpose, pre_scale, scale,
-                                     (hipStream_t)stream, &h);
+int quip_had_transform_group_f16(const quip_had_problem* problems, int32_t count, int64_t rows, int32_t n, int32_t K,
+                                 int32_t transpose, quip_stream_t stream) {
+  if (int rc = had_group_refusal(problems, count)) return rc;
+  return had_transform_group_launch(problems, count, false, rows, n, K, transpose, (hipStream_t)stream);
 }
 
-static int group_had(const quip_had_problem* problems, int32_t count, bool planes, int64_t rows, int32_t n,
-                     int32_t K, int32_t transpose, quip_stream_t stream) {
-  if (!problems) return QUIP_ERR_NULL_POINTER;
-  if (count < 1 || count > QUIP_MAX_GROUP) return QUIP_ERR_BAD_SHAPE;
-  HadProblem pr[QUIP_MAX_GROUP];
-  for (int i = 0; i < count; ++i) {
-    const quip_had_problem& s = problems[i];
-    if ((!s.x && !s.z) || !s.out) return QUIP_ERR_NULL_POINTER;
-    pr[i].z = s.z; pr[i].z_post = s.z_post_scale; pr[i].z_residual = s.z_residual; pr[i].h_out = s.h_out;
-    pr[i].z_scale = s.z_scale;
-    pr[i].resid_scale = s.resid_scale;
-    pr[i].planes_layout = s.planes_layout;
-    pr[i].n = s.n;
-    pr[i].z_had = s.z_had;
-    pr[i].x = s.x; pr[i].out = s.out; pr[i].had = s.had; pr[i].pre = s.pre_scale; pr[i].pre2 = s.pre_scale2;
-    pr[i].post = s.post_scale; pr[i].bias = s.bias; pr[i].residual = s.residual; pr[i].rms_weight = s.rms_weight;
-    pr[i].gate = s.gate; pr[i].in_features = s.in_features; pr[i].out_features = s.out_features;
-    pr[i].scale = s.scale; pr[i].rms_eps = s.rms_eps;
-  }
-  return had_transform_group_launch(pr, count, planes, rows, n, K, transpose, (hipStream_t)stream);
-}
-
-int quip_had_transform_group_f16(const quip_had_problem* problems, int32_t count, int64_t rows,
-                                 int32_t n, int32_t K, int32_t transpose, quip_stream_t stream) {
-  return group_had(problems, count, false, rows, n, K, transpose, stream);
-}
-
-int quip_had_transform_planes_group(const quip_had_problem* problems, int32_t count, int32_t n,
-                                    int32_t K, int32_t transpose, quip_stream_t stream) {
-  return group_had(problems, count, true, 1, n, K, transpose, stream);
+int quip_had_transform_planes_group(const quip_had_problem* problems, int32_t count, int32_t n, int32_t K, int32_t transpose,
+                                    quip_stream_t stream) {
+  if (int rc = had_group_refusal(problems, count)) return rc;
+  return had_transform_group_launch(problems, count, true, 1, n, K, transpose, (hipStream_t)stream);
 }
 
 int quip_had_transform_planes_rows(const quip_had_problem* problem, int64_t rows, int32_t n, int32_t K,
                                    int32_t transpose, quip_stream_t stream) {
   if (rows < 1) return rows == 0 ? QUIP_OK : QUIP_ERR_BAD_SHAPE;
-  return group_had(problem, 1, true, rows, n, K, transpose, stream);
+  if (int rc = had_group_refusal(problem, 1)) return rc;
+  return had_transform_group_launch(problem, 1, true, rows, n, K, transpose, (hipStream_t)stream);
 }
+
+int quip_had_plan(const quip_had_problem* problems, int32_t count, int32_t planes, int64_t rows, int32_t n, int32_t K,
+                  int32_t transpose, int32_t* out) {
+  if (!out) return QUIP_ERR_NULL_POINTER;
+  for (int i = 0; i < kHadPlanInts; ++i) out[i] = 0;
+  out[1] = -1;
+  if ((out[0] = had_group_refusal(problems, count)) != QUIP_OK) return out[0];
+  return had_transform_group_plan(problems, count, planes != 0, rows, n, K, transpose, device_cu_count(), out);
+}
+const char* quip_had_plan_kind_name(int32_t kind) { return had_plan_kind_name(kind); }
 
 int quip_e8p_quantize_f32(const void* x, int64_t nvec, const void* grid_packed_abs, void* vals, void* idx,
                           quip_stream_t stream) {
@@ -712,17 +730,6 @@ size_t quip_block_engine_g8_workspace_bytes(void) { return block_engine_g8_works
 // entries do not look at the alignment of pos, only the prompt-side entries at that of out / cos / sin, and those leave
 // the window to their launcher.
 namespace {
-using Ptrs = std::initializer_list<const void*>;
-bool any_null(Ptrs ps) {
-  for (const void* p : ps)
-    if (!p) return true;
-  return false;
-}
-bool any_off(Ptrs ps, uintptr_t mask) {
-  for (const void* p : ps)
-    if (reinterpret_cast<uintptr_t>(p) & mask) return true;
-  return false;
-}
 int attn_refusal(const AttnIO& io, Ptrs more, Ptrs a16, Ptrs a8 = {}, Ptrs a4 = {}, const void* workspace = nullptr,
                  int window = 0) {
   if (any_null({io.q, io.k, io.v, io.cos, io.sin, io.pos, io.kcache, io.vcache, io.out}) || any_null(more))

@@ -26,6 +26,8 @@
 // between the transform and the GEMV.  The shift comes from a bound every workgroup can
 // compute alone: K == 1: the exact max |v| of the transformed row; K > 1: |v_i| <= ||v||_2 =
 // scale * sqrt(L) * ||H||_2 * ||input||_2 with H ~ orthogonal.
+#include <type_traits>
+
 #include "had_device.hip.h"
 #include "launch.hip.h"
 
@@ -1193,161 +1195,218 @@ __global__ __launch_bounds__(256) void had_small_kernel(HadGroup grp) {
   }
 }
 
-// `count` problems of the same (n, K, L) and kind (planes / fp16) in one launch (grid.z)
+// ---- launch plans ----------------------------------------------------------------------------------------------------------
+// Every instantiation a group launch can take, as X(plan kind, kernel).  The transforms agree across instantiations bit
+// for bit, so a shape on the wrong one shows only as speed (or as a wrong LDS size): tests/golden/had_plans.json pins
+// had_plan()'s answers through quip_had_plan().  The device code of this file comes out in the order the host code first
+// names the instantiations, i.e. in the order of this list: append, do not reorder.
+#define QUIP_HAD_KINDS(X)                                          \
+  X(kTallBatchPairIn, had_tall_batch_kernel<6, 0, 11, true>)       \
+  X(kTallBatchPairOut, had_tall_batch_kernel<6, 1, 11, true>)      \
+  X(kTallBatchOut8, had_tall_batch_kernel<8, 1, 3, false>)         \
+  X(kTallBatchOut7, had_tall_batch_kernel<7, 1, 3, false>)         \
+  X(kTallBatchOut6, had_tall_batch_kernel<6, 1, 3, false>)         \
+  X(kTallBatchIn8, had_tall_batch_kernel<8, 0, 3, false>)          \
+  X(kTallBatchIn7, had_tall_batch_kernel<7, 0, 3, false>)          \
+  X(kTallBatchIn6, had_tall_batch_kernel<6, 0, 3, false>)          \
+  X(kTallPlanes, had_fast_kernel<true, true, 1024, false, 0>)      \
+  X(kTallF16, had_fast_kernel<false, true, 1024, false, 0>)        \
+  X(kKoneF16, had_fast_kernel<false, false, 256, true, 0>)         \
+  X(kWide1024F16, had_fast_kernel<false, false, 1024, false, 0>)   \
+  X(kChain9, had_fast_kernel<true, false, 512, false, 9>)          \
+  X(kChain10, had_fast_kernel<true, false, 512, false, 10>)        \
+  X(kChain11, had_fast_kernel<true, false, 512, false, 11>)        \
+  X(kChain12, had_fast_kernel<true, false, 768, false, 12>)        \
+  X(kWide1024Planes, had_fast_kernel<true, false, 1024, false, 0>) \
+  X(kWideBatch12K3, had_wide_batch_kernel<12, 3>)                  \
+  X(kWideBatch11K3, had_wide_batch_kernel<11, 3>)                  \
+  X(kWideBatch10K3, had_wide_batch_kernel<10, 3>)                  \
+  X(kWideBatch9K3, had_wide_batch_kernel<9, 3>)                    \
+  X(kWideBatch12K5, had_wide_batch_kernel<12, 5>)                  \
+  X(kWideBatch11K5, had_wide_batch_kernel<11, 5>)                  \
+  X(kWideBatch10K5, had_wide_batch_kernel<10, 5>)                  \
+  X(kWideBatch9K5, had_wide_batch_kernel<9, 5>)                    \
+  X(kWideBatch12K7, had_wide_batch_kernel<12, 7>)                  \
+  X(kWideBatch11K7, had_wide_batch_kernel<11, 7>)                  \
+  X(kWideBatch10K7, had_wide_batch_kernel<10, 7>)                  \
+  X(kWideBatch9K7, had_wide_batch_kernel<9, 7>)                    \
+  X(kKoneBatch13, had_kone_batch_kernel<13>)                       \
+  X(kKoneBatch12, had_kone_batch_kernel<12>)                       \
+  X(kKoneBatch11, had_kone_batch_kernel<11>)                       \
+  X(kKoneBatch10, had_kone_batch_kernel<10>)                       \
+  X(kKonePlanes, had_fast_kernel<true, false, 256, true, 0>)       \
+  X(kKone512Planes, had_fast_kernel<true, false, 512, true, 0>)    \
+  X(kKone512F16, had_fast_kernel<false, false, 512, true, 0>)      \
+  X(kWide256Planes, had_fast_kernel<true, false, 256, false, 0>)   \
+  X(kWide256F16, had_fast_kernel<false, false, 256, false, 0>)     \
+  X(kSmallPlanes, had_small_kernel<true>)                          \
+  X(kSmallF16, had_small_kernel<false>)
+
+enum HadKind : int {
+#define X(kind, ...) kind,
+  QUIP_HAD_KINDS(X)
+#undef X
+  kHadKinds
+};
+const char* const kHadKindNames[kHadKinds] = {
+#define X(kind, ...) #__VA_ARGS__,
+  QUIP_HAD_KINDS(X)
+#undef X
+};
+
+// what had_plan() reads of a group: `count` problems of the same (n, K, L) -- K == 1 fp16 groups may mix widths, L is
+// problem 0's -- and kind (planes / fp16)
+struct HadFacts {
+  int K, L, logL, n, count;
+  bool planes;
+  struct {
+    int L;
+    bool vec, vec_out, out8;   // HadArgs::vec, vec_out; out_features % 8 == 0
+    bool rms_w, pre, pre2, gate, post, bias, residual, z;
+  } p[kMaxGroup];
+};
+
+struct HadPlan {
+  int rc = QUIP_OK;
+  HadKind kind = kSmallF16;
+  int gx = 0, gy = 0, gz = 0, threads = 0, lds = 0;
+  struct { int pp = 0, tgroups = 1, part_off = 0, chain_off = 0; } p[kMaxGroup];   // HadArgs' fields of the same names
+};
+
+// Pure host arithmetic.  rows <= 65535 (grid.y); cus: CUs of the device (sizes the grid of the tall batch kernels only)
+HadPlan had_plan(const HadFacts& f, int64_t rows, int cus) {
+  const int K = f.K, L = f.L, logL = f.logL, n = f.n, count = f.count;
+  const bool planes = f.planes;
+  // batches (prefill): throughput, single shuffle buffer so that more rows are resident per CU; else the latency-bound
+  // decode launches: more threads per row, ping-pong shuffle buffer
+  const bool batch = rows > 8;
+  // what every batch kernel asks of every problem: 16-byte vector access on both sides, whole 8-chunks of output, no
+  // RMSNorm statistic, no chain
+  bool vector_rows = true;
+  // element-wise vectors of the input side (gate, pre) / the output side (post, bias, residual) anywhere in the group
+  bool in_side = false, out_side = false, any_pre2 = false;
+  int Lmax = L;   // != L: K == 1 problems of different power-of-two widths (host-checked: fp16, no RMSNorm statistic)
+  for (int i = 0; i < count; ++i) {
+    const auto& p = f.p[i];
+    vector_rows = vector_rows && p.vec && p.vec_out && !p.rms_w && !p.z && p.out8;
+    in_side = in_side || p.gate || p.pre;
+    out_side = out_side || p.post || p.bias || p.residual;
+    any_pre2 = any_pre2 || p.pre2;
+    Lmax = p.L > Lmax ? p.L : Lmax;
+  }
+  bool mixed = false;
+  for (int i = 1; i < count; ++i) mixed = mixed || f.p[i].L != L;
+
+  HadPlan pl;
+  auto launch_as = [&](HadKind kind, int64_t gx, int64_t gy, int threads, int lds) {
+    pl.kind = kind; pl.gx = (int)gx; pl.gy = (int)gy; pl.gz = count; pl.threads = threads; pl.lds = lds;
+    return pl;
+  };
+
+  if (K > 1 && L >= 64 && L <= 256) {   // tall: R = 4096 / L rows of the K-mix per workgroup, on the matrix cores
+    // prefill batches: one workgroup per row at a time (had_tall_batch_kernel), vectors of one side only
+    if (rows >= 32 && (K <= 48 || (K <= 176 && L == 64)) && n <= 12288 && !planes && vector_rows && !any_pre2 &&
+        !(in_side && out_side)) {
+      const int BR = (K + 3) & ~3;
+      const int KP = K <= 48 ? 48 : 176;
+      const bool pair = K > 48;   // two rows in flight in ONE workgroup per CU (they share the 62 KB of H); else two workgroups
+      const int lds = (pair ? 2 : 1) * ((had::buf_floats(BR * L) + 3) & ~3) * 4 + KP * KP * 2;
+      const int64_t want = (pair ? 1 : 2) * (int64_t)cus, units = pair ? (rows + 1) / 2 : rows;
+      const HadKind kind = pair ? (in_side ? kTallBatchPairIn : kTallBatchPairOut)
+                         : in_side ? (logL == 8 ? kTallBatchIn8 : logL == 7 ? kTallBatchIn7 : kTallBatchIn6)
+                                   : (logL == 8 ? kTallBatchOut8 : logL == 7 ? kTallBatchOut7 : kTallBatchOut6);
+      return launch_as(kind, units < want ? units : want, 1, pair ? 512 : 256, lds);
+    }
+    // [shuffle buffer | H tile | x rows | second half of the ping-pong buffer]; decode launches: 1024 threads; batches:
+    // 512 threads, so that two workgroups share a CU (one at a time made prefill throughput = workgroup latency)
+    const int R = 4096 / L;
+    const int pp = had::buf_floats(4096) + ((K + 3) & ~3) * R + K * (L + 8);
+    for (int i = 0; i < count; ++i) pl.p[i].pp = batch ? 0 : pp;
+    return launch_as(planes ? kTallPlanes : kTallF16, (K + R - 1) / R, rows, batch ? 512 : 1024,
+                     (pp + (batch ? 0 : had::buf_floats(4096))) * 4);
+  }
+  if (mixed) {
+    // the workgroup has the threads of the widest problem, a narrower problem keeps its first L / 16 threads active
+    // (thread groups > 0 only take part in the barriers)
+    for (int i = 0; i < count; ++i) {
+      pl.p[i].tgroups = Lmax / f.p[i].L;
+      pl.p[i].pp = batch ? 0 : had::buf_floats(f.p[i].L);
+    }
+    return launch_as(Lmax <= 4096 ? kKoneF16 : kWide1024F16, K, rows, Lmax / 16, (batch ? 1 : 2) * had::buf_floats(Lmax) * 4);
+  }
+  if (L < 256 || L > 16384) return launch_as(planes ? kSmallPlanes : kSmallF16, K, rows, L >= 512 ? 256 : 64, L * 4);
+
+  // the register-blocked kernels, L / 16 threads per thread group
+  const int lds = (batch ? 1 : 2) * had::buf_floats(L) * 4;
+  for (int i = 0; i < count; ++i) pl.p[i].pp = batch ? 0 : had::buf_floats(L);
+  if (L <= 4096 && K > 1 && !batch) {
+    // latency-bound decode launch of a long row (28672 = 7 x 4096): up to 4 thread groups split the k loop
+    int tg = K < 4 ? K : 4;
+    while ((L / 16) * tg > 1024) --tg;
+    if (tg > 1) {
+      const int part = 2 * had::buf_floats(L);
+      for (int i = 0; i < count; ++i) { pl.p[i].tgroups = tg; pl.p[i].part_off = part; pl.p[i].pp = had::buf_floats(L); }
+      if (f.p[0].z) {
+        // chain: a ping-pong shuffle buffer per thread group -- the partial sums reuse the buffers of groups 1..
+        // afterwards -- then the fp16 images of z and h and the producer's factor.  What the kernel's CLOGL branch
+        // relies on, from fill(): K in {3, 5, 7} and 512 <= L <= 4096, hence tg = min(K, 4) here (L / 16 * 4 <= 1024),
+        // K <= 2 tg (two rounds of rows / k terms per thread group), K * K <= 49 <= 64 floats of z_had and <= 96 =
+        // the fewest threads of a launch (tg L / 16 at K = 3, L = 512), and n / 8 <= 4 threads pieces of z
+        if (!(K == 3 || K == 5 || K == 7) || L < 512 || tg != (K < 4 ? K : 4)) { pl.rc = QUIP_ERR_UNSUPPORTED; return pl; }
+        const int chain = tg * part;
+        for (int i = 0; i < count; ++i) pl.p[i].chain_off = chain;
+        return launch_as(HadKind(kChain9 + (logL - 9)), K, rows, (L / 16) * tg, chain * 4 + 2 * n * 2 + 64 * 4);
+      }
+      return launch_as(planes ? kWide1024Planes : kWide1024F16, K, rows, (L / 16) * tg, (part + (tg - 1) * 16 * (L / 16)) * 4);
+    }
+  }
+  if ((K == 3 || K == 5 || K == 7) && !planes && batch && L >= 512 && L <= 4096 && vector_rows)   // batches, small odd K
+    return launch_as(HadKind(kWideBatch12K3 + 4 * ((K - 3) / 2) + (12 - logL)), 1, rows, L / 16, had::buf_floats(L) * 4);
+  if (K == 1 && !planes && rows >= 32 && logL >= 10 && logL <= 13 && vector_rows)   // prefill batches
+    return launch_as(HadKind(kKoneBatch13 + (13 - logL)), K, rows, L / 16, had::buf_floats(L) * 4);
+  if (K == 1 && L <= 4096) return launch_as(planes ? kKonePlanes : kKoneF16, K, rows, L / 16, lds);
+  // Llama-2-70B's hidden size: the K == 1 instantiation (no K-mix code) on 512 threads
+  if (K == 1 && L == 8192) return launch_as(planes ? kKone512Planes : kKone512F16, K, rows, L / 16, lds);
+  if (L <= 4096) return launch_as(planes ? kWide256Planes : kWide256F16, K, rows, L / 16, lds);
+  return launch_as(planes ? kWide1024Planes : kWide1024F16, K, rows, L / 16, lds);
+}
+
+HadFacts had_facts(const HadGroup& g, int count) {
+  HadFacts f{};
+  const HadArgs& a0 = g.p[0];
+  f.K = a0.K; f.L = a0.L; f.logL = a0.logL; f.n = a0.n; f.count = count; f.planes = a0.planes != nullptr;
+  for (int i = 0; i < count; ++i) {
+    const HadArgs& a = g.p[i];
+    f.p[i] = {a.L, a.vec != 0, a.vec_out != 0, a.out_features % 8 == 0, a.rms_w != nullptr, a.pre != nullptr,
+              a.pre2 != nullptr, a.gate != nullptr, a.post != nullptr, a.bias != nullptr, a.residual != nullptr,
+              a.z != nullptr};
+  }
+  return f;
+}
+
+template <auto Kern>
+int launch_planned(const HadPlan& pl, const HadGroup& g, int64_t rows, hipStream_t stream) {
+  const dim3 grid(pl.gx, pl.gy, pl.gz), block(pl.threads);
+  if constexpr (std::is_invocable_v<decltype(Kern), HadGroup, int>)   // had_tall_batch_kernel walks over the rows itself
+    return launch<Kern>(grid, block, pl.lds, stream, g, (int)rows);
+  else
+    return launch<Kern>(grid, block, pl.lds, stream, g);
+}
+
+// the plan's per-launch fields into the group, then the launch (grid.z = the problems)
 int launch_group(HadGroup& g, int count, int64_t rows, hipStream_t stream) {
-  const int L = g.p[0].L, K = g.p[0].K, n = g.p[0].n;
-  const bool planes = g.p[0].planes != nullptr;
+  const HadPlan pl = had_plan(had_facts(g, count), rows, device_cu_count());
+  if (pl.rc != QUIP_OK) return pl.rc;
   for (int i = 0; i < count; ++i) {
     HadArgs& a = g.p[i];
-    a.vec = (a.in_features % 8 == 0) && aligned16(a.x) && aligned16(a.gate) && aligned16(a.rms_w) &&
-            aligned16(a.pre) && aligned16(a.pre2);
-    a.vec_out = (a.out_features % 8 == 0) && aligned16(a.y) && aligned16(a.post) && aligned16(a.bias) &&
-                aligned16(a.residual);
+    a.pp = pl.p[i].pp; a.tgroups = pl.p[i].tgroups; a.part_off = pl.p[i].part_off; a.chain_off = pl.p[i].chain_off;
   }
-  if (K > 1 && L >= 64 && L <= 256) {   // tall: 256 threads, R = 4096 / L rows per workgroup
-    const int R = 4096 / L;
-    // [shuffle buffer | H tile | x rows | second half of the ping-pong buffer]
-    // decode launches: 1024 threads, ping-pong buffer (latency); batches: 512 threads, single buffer, so
-    // that two workgroups share a CU (one at a time made prefill throughput = workgroup latency)
-    const bool batch = rows > 8;
-    {   // prefill batches: one workgroup per row at a time (had_tall_batch_kernel)
-      bool ok = rows >= 32 && (K <= 48 || (K <= 176 && L == 64)) && n <= 12288 && !planes;
-      for (int i = 0; i < count; ++i)
-        ok = ok && g.p[i].vec && g.p[i].vec_out && !g.p[i].rms_w && !g.p[i].pre2 && !g.p[i].z && g.p[i].out_features % 8 == 0;
-      // element-wise vectors of one side only (input: gate, pre; output: post, bias, residual), see the kernel
-      bool in_side = false, out_side = false;
-      for (int i = 0; i < count; ++i) {
-        in_side = in_side || g.p[i].gate || g.p[i].pre;
-        out_side = out_side || g.p[i].post || g.p[i].bias || g.p[i].residual;
-      }
-      ok = ok && !(in_side && out_side);
-      if (ok) {
-        const int BR = (K + 3) & ~3;
-        const int KP = K <= 48 ? 48 : 176;
-        const bool pair = K > 48;   // two rows in flight in ONE workgroup per CU (they share the 62 KB of H); else two workgroups
-        const int lds = (pair ? 2 : 1) * ((had::buf_floats(BR * L) + 3) & ~3) * 4 + KP * KP * 2;
-        const int threads = pair ? 512 : 256;
-        const int64_t want = (pair ? 1 : 2) * (int64_t)device_cu_count(), units = pair ? (rows + 1) / 2 : rows;
-        const dim3 grid((unsigned)(units < want ? units : want), 1, count);
-        auto go = [&](auto kern) { return launch<decltype(kern)::value>(grid, dim3(threads), lds, stream, g, (int)rows); };
-        const int logL = g.p[0].logL;
-        if (K > 48) return in_side ? go(kernel_c<had_tall_batch_kernel<6, 0, 11, true>>) : go(kernel_c<had_tall_batch_kernel<6, 1, 11, true>>);
-        if (!in_side) return logL == 8 ? go(kernel_c<had_tall_batch_kernel<8, 1, 3, false>>) : logL == 7 ? go(kernel_c<had_tall_batch_kernel<7, 1, 3, false>>)
-                                                                                                  : go(kernel_c<had_tall_batch_kernel<6, 1, 3, false>>);
-        return logL == 8 ? go(kernel_c<had_tall_batch_kernel<8, 0, 3, false>>) : logL == 7 ? go(kernel_c<had_tall_batch_kernel<7, 0, 3, false>>)
-                                                                                    : go(kernel_c<had_tall_batch_kernel<6, 0, 3, false>>);
-      }
-    }
-    const int pp = had::buf_floats(4096) + ((K + 3) & ~3) * R + K * (L + 8);
-    const int lds = (pp + (batch ? 0 : had::buf_floats(4096))) * 4;
-    for (int i = 0; i < count; ++i) g.p[i].pp = batch ? 0 : pp;
-    const dim3 grid((K + R - 1) / R, (unsigned)rows, count);
-    const int threads = batch ? 512 : 1024;
-    return planes ? launch<had_fast_kernel<true, true, 1024>>(grid, dim3(threads), lds, stream, g)
-                  : launch<had_fast_kernel<false, true, 1024>>(grid, dim3(threads), lds, stream, g);
+  switch (pl.kind) {
+#define X(kind, ...) case kind: return launch_planned<__VA_ARGS__>(pl, g, rows, stream);
+    QUIP_HAD_KINDS(X)
+#undef X
+    default: return QUIP_ERR_UNSUPPORTED;
   }
-  const dim3 grid(K, (unsigned)rows, count);
-  bool mixed = false;
-  for (int i = 1; i < count; ++i) mixed = mixed || g.p[i].L != L;
-  if (mixed) {
-    // K == 1 problems of different power-of-two widths (host-checked: fp16 output, no RMSNorm statistic) in one
-    // launch: the workgroup has the threads of the widest problem, a narrower problem keeps its first L / 16
-    // threads active (thread groups > 0 only take part in the barriers)
-    int Lmax = L;
-    for (int i = 1; i < count; ++i) Lmax = g.p[i].L > Lmax ? g.p[i].L : Lmax;
-    const bool batch = rows > 8;
-    for (int i = 0; i < count; ++i) {
-      g.p[i].tgroups = Lmax / g.p[i].L;
-      g.p[i].part_off = 0;
-      g.p[i].pp = batch ? 0 : had::buf_floats(g.p[i].L);
-    }
-    const int lds = (batch ? 1 : 2) * had::buf_floats(Lmax) * 4;
-    return Lmax <= 4096 ? launch<had_fast_kernel<false, false, 256, true>>(grid, dim3(Lmax / 16), lds, stream, g)
-                        : launch<had_fast_kernel<false, false, 1024>>(grid, dim3(Lmax / 16), lds, stream, g);
-  }
-  if (L >= 256 && L <= 16384) {
-    // ping-pong shuffle buffer for the latency-bound decode launches; batches (prefill) take the single
-    // buffer so that more rows are resident per CU
-    const bool batch = rows > 8;
-    const int lds = (batch ? 1 : 2) * had::buf_floats(L) * 4;
-    for (int i = 0; i < count; ++i) g.p[i].pp = batch ? 0 : had::buf_floats(L);
-    for (int i = 0; i < count; ++i) { g.p[i].tgroups = 1; g.p[i].part_off = 0; }
-    if (L <= 4096 && K > 1 && rows <= 8) {
-      // latency-bound decode launch of a long row (28672 = 7 x 4096): up to 4 thread groups split the k loop
-      int tg = K < 4 ? K : 4;
-      while ((L / 16) * tg > 1024) --tg;
-      if (tg > 1) {
-        const int part = 2 * had::buf_floats(L);
-        const int lds2 = (part + (tg - 1) * 16 * (L / 16)) * 4;
-        for (int i = 0; i < count; ++i) { g.p[i].tgroups = tg; g.p[i].part_off = part; g.p[i].pp = had::buf_floats(L); }
-        if (g.p[0].z) {
-          // chain: a ping-pong shuffle buffer per thread group -- the partial sums reuse the buffers of groups 1..
-          // afterwards -- then the fp16 images of z and h and the producer's factor.  What the kernel's CLOGL branch
-          // relies on, from fill(): K in {3, 5, 7} and 512 <= L <= 4096, hence tg = min(K, 4) here (L / 16 * 4 <= 1024),
-          // K <= 2 tg (two rounds of rows / k terms per thread group), K * K <= 49 <= 64 floats of z_had and <= 96 =
-          // the fewest threads of a launch (tg L / 16 at K = 3, L = 512), and n / 8 <= 4 threads pieces of z
-          if (!(K == 3 || K == 5 || K == 7) || L < 512 || tg != (K < 4 ? K : 4)) return QUIP_ERR_UNSUPPORTED;
-          const int chain = tg * part;
-          const int lds3 = chain * 4 + 2 * n * 2 + 64 * 4;
-          for (int i = 0; i < count; ++i) g.p[i].chain_off = chain;
-          const int threads = (L / 16) * tg, logL = g.p[0].logL;
-          return logL == 9 ? launch<had_fast_kernel<true, false, 512, false, 9>>(grid, dim3(threads), lds3, stream, g)
-               : logL == 10 ? launch<had_fast_kernel<true, false, 512, false, 10>>(grid, dim3(threads), lds3, stream, g)
-               : logL == 11 ? launch<had_fast_kernel<true, false, 512, false, 11>>(grid, dim3(threads), lds3, stream, g)
-                            : launch<had_fast_kernel<true, false, 768, false, 12>>(grid, dim3(threads), lds3, stream, g);
-        }
-        return planes ? launch<had_fast_kernel<true, false, 1024>>(grid, dim3((L / 16) * tg), lds2, stream, g)
-                      : launch<had_fast_kernel<false, false, 1024>>(grid, dim3((L / 16) * tg), lds2, stream, g);
-      }
-    }
-    if ((K == 3 || K == 5 || K == 7) && !planes && rows > 8 && L >= 512 && L <= 4096) {   // batches, small odd K
-      bool ok = true;
-      for (int i = 0; i < count; ++i)
-        ok = ok && g.p[i].vec && g.p[i].vec_out && !g.p[i].rms_w && !g.p[i].z && g.p[i].out_features % 8 == 0;
-      if (ok) {
-        const int lds1 = had::buf_floats(L) * 4;
-        const dim3 grid1(1, (unsigned)rows, count);
-        const int logL = g.p[0].logL;
-        auto go = [&](auto kern) { return launch<decltype(kern)::value>(grid1, dim3(L / 16), lds1, stream, g); };
-#define QUIP_WIDE_BATCH(KK)                                                                               \
-        return logL == 12 ? go(kernel_c<had_wide_batch_kernel<12, KK>>) : logL == 11 ? go(kernel_c<had_wide_batch_kernel<11, KK>>) \
-             : logL == 10 ? go(kernel_c<had_wide_batch_kernel<10, KK>>) : go(kernel_c<had_wide_batch_kernel<9, KK>>)
-        if (K == 3) { QUIP_WIDE_BATCH(3); }
-        if (K == 5) { QUIP_WIDE_BATCH(5); }
-        QUIP_WIDE_BATCH(7);
-#undef QUIP_WIDE_BATCH
-      }
-    }
-    if (K == 1 && !planes && rows >= 32 && (L == 1024 || L == 2048 || L == 4096 || L == 8192)) {   // prefill batches
-      bool ok = true;
-      for (int i = 0; i < count; ++i)
-        ok = ok && g.p[i].vec && g.p[i].vec_out && !g.p[i].rms_w && !g.p[i].z && g.p[i].out_features % 8 == 0;
-      if (ok) {
-        const int lds1 = had::buf_floats(L) * 4;
-        const dim3 block(L / 16);
-        return L == 8192 ? launch<had_kone_batch_kernel<13>>(grid, block, lds1, stream, g)
-             : L == 4096 ? launch<had_kone_batch_kernel<12>>(grid, block, lds1, stream, g)
-             : L == 2048 ? launch<had_kone_batch_kernel<11>>(grid, block, lds1, stream, g)
-                         : launch<had_kone_batch_kernel<10>>(grid, block, lds1, stream, g);
-      }
-    }
-    if (L <= 4096 && K == 1) {
-      return planes ? launch<had_fast_kernel<true, false, 256, true>>(grid, dim3(L / 16), lds, stream, g)
-                    : launch<had_fast_kernel<false, false, 256, true>>(grid, dim3(L / 16), lds, stream, g);
-    }
-    if (L == 8192 && K == 1) {   // Llama-2-70B's hidden size: the K == 1 instantiation (no K-mix code) on 512 threads
-      return planes ? launch<had_fast_kernel<true, false, 512, true>>(grid, dim3(L / 16), lds, stream, g)
-                    : launch<had_fast_kernel<false, false, 512, true>>(grid, dim3(L / 16), lds, stream, g);
-    }
-    if (L <= 4096)
-      return planes ? launch<had_fast_kernel<true, false, 256>>(grid, dim3(L / 16), lds, stream, g)
-                    : launch<had_fast_kernel<false, false, 256>>(grid, dim3(L / 16), lds, stream, g);
-    return planes ? launch<had_fast_kernel<true, false, 1024>>(grid, dim3(L / 16), lds, stream, g)
-                  : launch<had_fast_kernel<false, false, 1024>>(grid, dim3(L / 16), lds, stream, g);
-  }
-  const int threads = L >= 512 ? 256 : 64;
-  return planes ? launch<had_small_kernel<true>>(grid, dim3(threads), L * 4, stream, g)
-                : launch<had_small_kernel<false>>(grid, dim3(threads), L * 4, stream, g);
 }
 
 int check_shape(int in_features, int out_features, int n, int K, const void* had, int& L, int& logL) {
@@ -1361,43 +1420,41 @@ int check_shape(int in_features, int out_features, int n, int K, const void* had
   return QUIP_OK;
 }
 
-int fill(HadArgs& a, const HadProblem& pr, bool planes, int n, int K, int transpose) {
+// The only place that turns a problem into kernel arguments; pp, tgroups, part_off and chain_off are the plan's.
+int fill(HadArgs& a, const quip_had_problem& pr, bool planes, int n, int K, int transpose) {
   int rc = check_shape(pr.in_features, planes ? n : pr.out_features, n, K, pr.had, a.L, a.logL);
   if (rc != QUIP_OK) return rc;
   if ((!pr.x && !pr.z) || !pr.out) return QUIP_ERR_NULL_POINTER;
   a.x = reinterpret_cast<const f16*>(pr.x ? pr.x : pr.z);
   if (planes) a.planes = reinterpret_cast<uint8_t*>(pr.out); else a.y = reinterpret_cast<f16*>(pr.out);
   a.had = reinterpret_cast<const f16*>(pr.had);
-  a.pre = reinterpret_cast<const f16*>(pr.pre);
-  a.pre2 = reinterpret_cast<const f16*>(pr.pre2);
-  a.post = reinterpret_cast<const f16*>(pr.post);
+  a.pre = reinterpret_cast<const f16*>(pr.pre_scale);
+  a.pre2 = reinterpret_cast<const f16*>(pr.pre_scale2);
+  a.post = reinterpret_cast<const f16*>(pr.post_scale);
   a.bias = reinterpret_cast<const f16*>(pr.bias);
   a.residual = reinterpret_cast<const f16*>(pr.residual);
   a.rms_w = reinterpret_cast<const f16*>(pr.rms_weight);
   a.gate = reinterpret_cast<const f16*>(pr.gate);
   a.rms_eps = pr.rms_eps;
   a.z = reinterpret_cast<const f16*>(pr.z);
-  a.z_post = reinterpret_cast<const f16*>(pr.z_post);
+  a.z_post = reinterpret_cast<const f16*>(pr.z_post_scale);
   a.z_res = reinterpret_cast<const f16*>(pr.z_residual);
   a.h_out = reinterpret_cast<f16*>(pr.h_out);
   a.z_scale = pr.z_scale;
-  a.tgroups = 1;
-  a.part_off = 0;
   a.z_had = reinterpret_cast<const f16*>(pr.z_had);
-  a.chain_off = 0;
   if (pr.z) {   // chain: blocked kernel, vector access
     // K == 1: plain power-of-two width; K > 1: the wide single-row planes launch with K = 3, 5, 7 thread-group
     // rounds (512 <= L <= 4096, n <= 16384) -- the tall shapes (L <= 256, K-mix on the matrix cores) have no chain
     if (pr.in_features != n) return QUIP_ERR_UNSUPPORTED;
     if (K == 1 ? (a.L < 256 || a.L > 16384)
-               : (!(K == 3 || K == 5 || K == 7) || a.L < 512 || a.L > 4096 || n > 16384 || !planes || pr.gate || pr.pre2))
+               : (!(K == 3 || K == 5 || K == 7) || a.L < 512 || a.L > 4096 || n > 16384 || !planes || pr.gate || pr.pre_scale2))
       return QUIP_ERR_UNSUPPORTED;
-    if (!pr.z_post || !pr.h_out || (K > 1 && !pr.z_had)) return QUIP_ERR_NULL_POINTER;
+    if (!pr.z_post_scale || !pr.h_out || (K > 1 && !pr.z_had)) return QUIP_ERR_NULL_POINTER;
     if (pr.h_out == pr.z_residual) return QUIP_ERR_BAD_SHAPE;
     if (K > 1 && pr.h_out == pr.z) return QUIP_ERR_BAD_SHAPE;   // every workgroup rereads all of z while rows of h_out are stored
-    uintptr_t al = reinterpret_cast<uintptr_t>(pr.z) | reinterpret_cast<uintptr_t>(pr.z_post) |
+    uintptr_t al = reinterpret_cast<uintptr_t>(pr.z) | reinterpret_cast<uintptr_t>(pr.z_post_scale) |
                    reinterpret_cast<uintptr_t>(pr.z_residual) | reinterpret_cast<uintptr_t>(pr.h_out);
-    if (K > 1) al |= reinterpret_cast<uintptr_t>(pr.pre) | reinterpret_cast<uintptr_t>(pr.rms_weight);   // its k loop is the vector one
+    if (K > 1) al |= reinterpret_cast<uintptr_t>(pr.pre_scale) | reinterpret_cast<uintptr_t>(pr.rms_weight);   // its k loop is the vector one
     if (al & 15) return QUIP_ERR_MISALIGNED;
   }
   a.in_features = pr.in_features; a.out_features = planes ? n : pr.out_features; a.n = n; a.K = K;
@@ -1411,15 +1468,18 @@ int fill(HadArgs& a, const HadProblem& pr, bool planes, int n, int K, int transp
     a.Kp = (2 * n + 511) & ~511;
   }
   a.transpose = transpose; a.scale = pr.scale;
+  // 16-byte vector access.  The row offsets of a sliced batch keep both: with in_features (out_features) a multiple of 8
+  // every row starts 16-byte aligned where the first one does, and otherwise they are 0 anyway.
+  a.vec = (a.in_features % 8 == 0) && aligned16(a.x) && aligned16(a.gate) && aligned16(a.rms_w) && aligned16(a.pre) &&
+          aligned16(a.pre2);
+  a.vec_out = (a.out_features % 8 == 0) && aligned16(a.y) && aligned16(a.post) && aligned16(a.bias) && aligned16(a.residual);
   return QUIP_OK;
 }
 
-}  // namespace
-
-int had_transform_group_launch(const HadProblem* problems, int count, bool planes, int64_t rows, int n, int K,
-                               int transpose, hipStream_t stream) {
+// everything a group launch refuses, and the group's kernel arguments for the first token row
+int fill_group(HadGroup& g, const quip_had_problem* problems, int count, bool planes, int64_t rows, int n, int K,
+               int transpose) {
   if (count < 1 || count > kMaxGroup || !problems) return QUIP_ERR_BAD_SHAPE;
-  HadGroup g{};
   for (int i = 0; i < count; ++i) {
     const int ni = problems[i].n > 0 ? problems[i].n : n;
     if (ni != n && (planes || K != 1 || problems[i].rms_weight || problems[i].z)) return QUIP_ERR_UNSUPPORTED;
@@ -1434,10 +1494,18 @@ int had_transform_group_launch(const HadProblem* problems, int count, bool plane
     for (int i = 0; i < count; ++i) { any = any || problems[i].z; all = all && problems[i].z; }
     if (any && (!all || rows != 1)) return QUIP_ERR_UNSUPPORTED;
   }
-  if (rows <= 0) return QUIP_OK;
-  // grid.y carries the token rows (<= 65535 per launch): longer batches go out in slices
-  constexpr int64_t kMaxRows = 65535;
-  for (int64_t r0 = 0; r0 < rows; r0 += kMaxRows) {
+  return QUIP_OK;
+}
+
+constexpr int64_t kMaxRows = 65535;   // grid.y carries the token rows: longer batches go out in slices
+
+}  // namespace
+
+int had_transform_group_launch(const quip_had_problem* problems, int count, bool planes, int64_t rows, int n, int K,
+                               int transpose, hipStream_t stream) {
+  HadGroup g{};
+  if (int rc = fill_group(g, problems, count, planes, rows, n, K, transpose)) return rc;
+  for (int64_t r0 = 0; r0 < rows; r0 += kMaxRows) {   // (rows <= 0: shape errors are still reported, nothing is launched)
     const int64_t nr = rows - r0 < kMaxRows ? rows - r0 : kMaxRows;
     HadGroup part = g;
     for (int i = 0; i < count; ++i) {
@@ -1449,35 +1517,33 @@ int had_transform_group_launch(const HadProblem* problems, int count, bool plane
       if (a.residual) a.residual += r0 * a.out_features;
       if (a.z) { a.z += r0 * a.n; a.h_out += r0 * a.n; if (a.z_res) a.z_res += r0 * a.n; }
     }
+    // one plan per slice: only `rows` differs between them
     const int rc = launch_group(part, count, nr, stream);
     if (rc != QUIP_OK) return rc;
   }
   return QUIP_OK;
 }
 
-int had_transform_launch(const void* x, void* y, int64_t rows, int in_features, int out_features,
-                         int n, int K, const void* had, int transpose, const void* pre,
-                         const void* pre2, const void* post, const void* bias, float scale,
-                         hipStream_t stream, const HadFusion* fuse) {
-  HadProblem pr;
-  pr.x = x; pr.out = y; pr.had = had; pr.pre = pre; pr.pre2 = pre2; pr.post = post; pr.bias = bias;
-  pr.in_features = in_features; pr.out_features = out_features; pr.scale = scale;
-  if (fuse) { pr.residual = fuse->residual; pr.rms_weight = fuse->rms_weight; pr.gate = fuse->gate; pr.rms_eps = fuse->rms_eps; }
-  if (rows <= 0) {   // shape errors still reported for empty batches
-    HadArgs a{};
-    return check_shape(in_features, out_features, n, K, had, a.L, a.logL);
+int had_transform_group_plan(const quip_had_problem* problems, int count, bool planes, int64_t rows, int n, int K,
+                             int transpose, int cus, int32_t* out) {
+  for (int i = 0; i < kHadPlanInts; ++i) out[i] = 0;
+  out[1] = -1;
+  HadGroup g{};
+  HadPlan pl;
+  pl.rc = fill_group(g, problems, count, planes, rows, n, K, transpose);
+  const bool planned = pl.rc == QUIP_OK && rows > 0;
+  if (planned) pl = had_plan(had_facts(g, count), rows < kMaxRows ? rows : kMaxRows, cus);
+  out[0] = pl.rc;
+  if (!planned || pl.rc != QUIP_OK) return pl.rc;
+  const int head[7] = {pl.rc, pl.kind, pl.gx, pl.gy, pl.gz, pl.threads, pl.lds};
+  for (int i = 0; i < 7; ++i) out[i] = head[i];
+  for (int i = 0; i < count; ++i) {
+    const int v[6] = {pl.p[i].pp, pl.p[i].tgroups, pl.p[i].part_off, pl.p[i].chain_off, g.p[i].vec, g.p[i].vec_out};
+    for (int j = 0; j < 6; ++j) out[7 + 6 * i + j] = v[j];
   }
-  return had_transform_group_launch(&pr, 1, false, rows, n, K, transpose, stream);
+  return pl.rc;
 }
 
-int had_transform_planes_launch(const void* x, void* planes, int in_features, int n, int K,
-                                const void* had, int transpose, const void* pre, float scale,
-                                hipStream_t stream, const HadFusion* fuse) {
-  HadProblem pr;
-  pr.x = x; pr.out = planes; pr.had = had; pr.pre = pre;
-  pr.in_features = in_features; pr.out_features = n; pr.scale = scale;
-  if (fuse) { pr.rms_weight = fuse->rms_weight; pr.gate = fuse->gate; pr.rms_eps = fuse->rms_eps; }
-  return had_transform_group_launch(&pr, 1, true, 1, n, K, transpose, stream);
-}
+const char* had_plan_kind_name(int kind) { return kind >= 0 && kind < kHadKinds ? kHadKindNames[kind] : nullptr; }
 
 }  // namespace quip

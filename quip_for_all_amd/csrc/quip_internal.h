@@ -78,41 +78,16 @@ int generic_mm_launch(CodebookId cb, const void* x, const void* qidxs, const Cod
                       void* y, int m, int n, int k, hipStream_t stream);
 int decompress_launch(CodebookId cb, const void* qidxs, const CodebookArgs& a, void* w,
                       int64_t rows, int k, hipStream_t stream);
-// optional decoder-block glue fused into the Hadamard kernels (all pointers may be null)
-struct HadFusion {
-  const void* residual = nullptr;    // fp16 [rows, out_features], added to the output
-  const void* rms_weight = nullptr;  // fp16 [in_features]: RMSNorm(x) * weight before everything else
-  const void* gate = nullptr;        // fp16 [rows, in_features]: input is silu(gate) * x
-  float rms_eps = 1e-5f;
-};
-// one Hadamard problem of a grouped launch (same n, K, transpose, kind for the whole group)
-struct HadProblem {
-  const void* x = nullptr;
-  void* out = nullptr;               // fp16 [rows, out_features] or digit planes
-  const void* had = nullptr;
-  const void* pre = nullptr;
-  const void* pre2 = nullptr;
-  const void* post = nullptr;
-  const void* bias = nullptr;
-  const void* residual = nullptr;
-  const void* rms_weight = nullptr;
-  const void* gate = nullptr;
-  int in_features = 0, out_features = 0;
-  float scale = 1.f, rms_eps = 1e-5f;
-  // chain (in_features == n; K == 1, or the wide K = 3, 5, 7 planes launch with z_had): x := z_post (.) (z_scale *
-  // (z_had (x) H_L) z) + z_residual, also stored to h_out
-  const void* z = nullptr;
-  const void* z_post = nullptr;
-  const void* z_residual = nullptr;
-  void* h_out = nullptr;
-  float z_scale = 1.f;
-  float resid_scale = 0.f;   // planes only: != 0 -> planes of the E8P12RVQ4B virtual vector [s * x_g | x_g] (2n digits)
-  int planes_layout = 0;     // planes only: 0 plain (or RVQ4 when resid_scale != 0), 2 = HI virtual vector (2n digits)
-  int n = 0;                 // fp16, K == 1: this problem's own width (0: the launch's n)
-  const void* z_had = nullptr;   // chain, K > 1: the producer's (K, K) fp16 had_right (its K is the launch's K)
-};
-int had_transform_group_launch(const HadProblem* problems, int count, bool planes, int64_t rows, int n, int K,
+// The Hadamard transform launches (hadamard.hip): `count` problems -- the public quip_had_problem is the record inside the
+// library too -- of one n, K, transpose and kind (planes / fp16 rows) in one launch.  Every C entry point ends here.
+int had_transform_group_launch(const quip_had_problem* problems, int count, bool planes, int64_t rows, int n, int K,
                                int transpose, hipStream_t stream);
+// the same validation, then the plan of the launch (of its first 65535 rows) for a device of `cus` CUs instead of the
+// launch; out[kHadPlanInts] as quip_had_plan() documents it
+constexpr int kHadPlanInts = 7 + 6 * QUIP_MAX_GROUP;
+int had_transform_group_plan(const quip_had_problem* problems, int count, bool planes, int64_t rows, int n, int K,
+                             int transpose, int cus, int32_t* out);
+const char* had_plan_kind_name(int kind);   // the instantiation as text, null past the last kind
 // quantise-time nearest E8P12 codeword (quantize.hip): x fp32 (nvec, 8) -> vals fp32 (nvec, 8), idx int64 (nvec)
 int e8p_quantize_launch(const void* x, int64_t nvec, const void* grid_packed_abs, void* vals, void* idx,
                         hipStream_t stream);
@@ -171,10 +146,6 @@ int d4_skinny_gemm_launch(const void* x, const void* qidxs, const void* grid_f16
 int hi_skinny_gemm_launch(const void* x, const void* qidxs, void* y, int m, int n, int k, hipStream_t stream);
 // bf16 / fp32 (and plain fp16) Walsh-Hadamard transform of the last dimension (hadamard_generic.hip)
 int hadamard_generic_launch(const void* x, void* y, int64_t rows, int n, float scale, int dtype, hipStream_t stream);
-int had_transform_launch(const void* x, void* y, int64_t rows, int in_features, int out_features,
-                         int n, int K, const void* had, int transpose, const void* pre,
-                         const void* pre2, const void* post, const void* bias, float scale,
-                         hipStream_t stream, const HadFusion* fuse = nullptr);
 // The attention launches (decode_glue.hip and the headers it includes).  They share their operands: q, k (before the
 // rotation) and v of the new token(s), the rotary tables (max_len, head_dim), the position(s) on the device, the cache
 // (or, paged, the two pools) and out -- AttnIO -- and their sizes -- AttnShape; what a variant adds comes beside them.
@@ -326,9 +297,6 @@ int block_engine_gqa_launch(const BlockEngineArgs& in, hipStream_t stream);
 bool block_engine_g8_supported(int hidden, int heads, int kv_heads, int head_dim, int n_ffn, int K);
 size_t block_engine_g8_workspace_bytes();
 int block_engine_g8_launch(const BlockEngineArgs& in, hipStream_t stream);
-int had_transform_planes_launch(const void* x, void* planes, int in_features, int n, int K,
-                                const void* had, int transpose, const void* pre, float scale,
-                                hipStream_t stream, const HadFusion* fuse = nullptr);
 
 }  // namespace quip
 
@@ -358,6 +326,14 @@ extern "C" size_t quip_e8p_gemv_v2_workspace_bytes(int32_t n);
 extern "C" int quip_e8p_gemv_v2_plan(const int32_t* ns, int32_t count, int32_t k, int32_t rep, int32_t slots,
                                      int32_t blocks, int32_t ksplit, int32_t max_waves, int32_t runlen,
                                      int32_t have_grid2, int32_t have_ws, int32_t* out);
+// the plan quip_had_transform_group_f16 (planes == 0) / quip_had_transform_planes_group and _planes_rows (planes != 0) make
+// for these arguments, without a launch; pointers are looked at (NULL, alignment), never dereferenced.  Returns what the
+// entry point would, up to the launch.  out[25] = rc, kind, grid x / y / z, threads, lds, then per problem pp, tgroups,
+// part_off, chain_off, vec, vec_out; kind -1 and zeros when nothing would be launched.  quip_had_plan_kind_name(kind): the
+// kernel instantiation as text, NULL past the last kind.  Pure host arithmetic: without a GPU the CU count is 256, the MI355X's
+extern "C" int quip_had_plan(const quip_had_problem* problems, int32_t count, int32_t planes, int64_t rows, int32_t n,
+                             int32_t K, int32_t transpose, int32_t* out);
+extern "C" const char* quip_had_plan_kind_name(int32_t kind);
 // kernel 2 in quip_e8p_gemv_tuned = streaming-read probe (y is a 4-byte scratch)
 // lane-ordered digit planes for the VALU integer GEMV (kernel 0); planes: 3*k + 16 bytes
 extern "C" int quip_e8p_x_to_planes_laneorder(const void* x, void* planes, int32_t k, quip_stream_t stream);

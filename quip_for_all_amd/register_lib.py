@@ -297,105 +297,165 @@ def _hadamard_cuda(x: Tensor, scale: float) -> Tensor:
     return y
 
 
+# ---- the transform ops: one problem builder, one operand check, one call --------------------------------------------------
+HI_PLANES = float("inf")     # resid_scale value that selects the HI virtual-vector layout of the planes ops
+
+
+def _layout(resid_scale):
+    """the planes fields of a quip_had_problem from the ops' single float argument"""
+    hi = resid_scale == HI_PLANES
+    return {"resid_scale": 0.0 if hi else float(resid_scale), "planes_layout": 2 if hi else 0}
+
+
+def _planes_numel(n, resid_scale=0.0):
+    """quip_e8p_planes_bytes of the n digits, or of the 2n digits of a virtual-vector layout"""
+    m = 2 * n if resid_scale != 0.0 else n
+    return 3 * ((m + 511) // 512 * 512) + 16
+
+
+_HAD_DEFAULTS = {"scale": 1.0, "rms_eps": 1e-5, "z_scale": 1.0}
+_HAD_FIELDS = frozenset(f[0] for f in capi.HadProblem._fields_)
+
+
+def _had_problem(**fields):
+    """a capi.HadProblem by field name; a tensor stands for its address.  Unnamed fields take the defaults the header
+    documents: scale = 1, rms_eps = 1e-5, z_scale = 1, the rest zero / NULL"""
+    assert set(fields) <= _HAD_FIELDS, sorted(set(fields) - _HAD_FIELDS)
+    return capi.HadProblem(**{**_HAD_DEFAULTS, **{k: _ptr(v) if v is None or isinstance(v, Tensor) else v for k, v in fields.items()}})
+
+
+def _check_had(what, x, out_features, n, K, had=None, pre=None, pre2=None, post=None, bias=None, rms_weight=None,
+               gate=None, residual=None):
+    """The operand check of the family, for one problem on the rows x (from _chk_x): every optional tensor is fp16,
+    contiguous and on x's device; the vectors have the lengths the launch reads (_chk_lens); gate has x's shape and
+    residual the output's.  Before any library call."""
+    for name, t in (("had", had), ("pre", pre), ("pre2", pre2), ("post", post), ("bias", bias), ("rms_weight", rms_weight),
+                    ("gate", gate), ("residual", residual)):
+        _need(t is None or (t.dtype == torch.float16 and t.is_contiguous() and t.device == x.device),
+              f"{what}: {name} must be contiguous float16 on x's device")
+    _need(gate is None or gate.shape == x.shape, f"{what}: gate must have x's shape")
+    _need(residual is None or tuple(residual.shape) == (x.shape[0], out_features), f"{what}: residual must have the output's shape")
+    _chk_lens(what, x.shape[1], out_features, n, K, had, pre, pre2, post, bias, rms_weight)
+
+
+def _had_call(x, problems, planes, n, K, transpose, rows=None):
+    """the problem-struct entry points: fp16 rows; planes of one row per problem (rows None); planes of the rows of one problem"""
+    arr = (capi.HadProblem * len(problems))(*problems)
+    L, tail = capi.lib(), (n, int(K), int(bool(transpose)), _stream(x))
+    with torch.cuda.device(x.device):
+        if not planes:
+            capi.check(L.quip_had_transform_group_f16(arr, len(problems), rows, *tail), "quip_had_transform_group_f16")
+        elif rows is None:
+            capi.check(L.quip_had_transform_planes_group(arr, len(problems), *tail), "quip_had_transform_planes_group")
+        else:
+            capi.check(L.quip_had_transform_planes_rows(arr, rows, *tail), "quip_had_transform_planes_rows")
+
+
+def _group_count(what, count, *lists):
+    _need(1 <= count <= capi.MAX_GROUP and all(len(v) == count for v in lists),
+          f"{what}: a group of 1..{capi.MAX_GROUP} problems, one entry per problem in every list")
+
+
+def _had_transform_fused_cuda(x, out_features, n, K, had, transpose, pre, pre2, post, bias, scale, residual=None,
+                              rms_weight=None, rms_eps=1e-5, gate=None, what="had_transform_fused"):
+    xc = _chk_x(x)
+    _check_had(what, xc, out_features, n, K, had, pre, pre2, post, bias, rms_weight, gate, residual)
+    y = _empty((xc.shape[0], out_features), dtype=torch.float16, device=x.device)
+    pr = _had_problem(x=xc, out=y, had=had, pre_scale=pre, pre_scale2=pre2, post_scale=post, bias=bias, residual=residual,
+                      rms_weight=rms_weight, gate=gate, in_features=xc.shape[1], out_features=out_features,
+                      scale=float(scale), rms_eps=float(rms_eps))
+    _had_call(x, [pr], False, n, K, transpose, xc.shape[0])
+    return y
+
+
 def _had_transform_cuda(x, out_features, n, K, had, transpose, pre, pre2, post, bias, scale):
-    xc = _chk_x(x)
-    for t in (had, pre, pre2, post, bias):
-        _need(t is None or (t.dtype == torch.float16 and t.is_contiguous() and t.device == x.device),
-              "had_transform: vectors must be contiguous float16 on x's device")
-    _chk_lens("had_transform", xc.shape[1], out_features, n, K, had, pre, pre2, post, bias)
-    y = _empty((xc.shape[0], out_features), dtype=torch.float16, device=x.device)
-    with torch.cuda.device(x.device):
-        capi.check(capi.lib().quip_had_transform_f16(
-            xc.data_ptr(), y.data_ptr(), xc.shape[0], xc.shape[1], out_features, n, K, _ptr(had),
-            int(bool(transpose)), _ptr(pre), _ptr(pre2), _ptr(post), _ptr(bias), float(scale),
-            _stream(x)), "quip_had_transform_f16")
-    return y
+    return _had_transform_fused_cuda(x, out_features, n, K, had, transpose, pre, pre2, post, bias, scale, what="had_transform")
 
 
-def _had_transform_planes_cuda(x, n, K, had, transpose, pre, scale):
+def _had_transform_planes_rows_cuda(x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate, resid_scale=0.0,
+                                    what="had_transform_planes_rows", one_row=False):
     xc = _chk_x(x)
-    _need(xc.shape[0] == 1, "had_transform_planes is the bs=1 path (one row)")
-    for t in (had, pre):
-        _need(t is None or (t.dtype == torch.float16 and t.is_contiguous() and t.device == x.device),
-              "had_transform_planes: vectors must be contiguous float16 on x's device")
-    _chk_lens("had_transform_planes", xc.shape[1], n, n, K, had, pre)
-    L = capi.lib()
-    planes = _empty(L.quip_e8p_planes_bytes(n), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        capi.check(L.quip_had_transform_planes(xc.data_ptr(), planes.data_ptr(), xc.shape[1], n, K, _ptr(had),
-                                               int(bool(transpose)), _ptr(pre), float(scale), _stream(x)),
-                   "quip_had_transform_planes")
+    _need(not one_row or xc.shape[0] == 1, f"{what} is the bs=1 path (one row)")
+    _check_had(what, xc, n, n, K, had, pre, rms_weight=rms_weight, gate=gate)
+    planes = _empty((_planes_numel(n, resid_scale),) if one_row else (xc.shape[0], _planes_numel(n, resid_scale)),
+                    dtype=torch.uint8, device=x.device)
+    pr = _had_problem(x=xc, out=planes, had=had, pre_scale=pre, rms_weight=rms_weight, gate=gate, in_features=xc.shape[1],
+                      out_features=n, scale=float(scale), rms_eps=float(rms_eps), **_layout(resid_scale))
+    _had_call(x, [pr], True, n, K, transpose, None if one_row else xc.shape[0])
     return planes
-
-
-def _fusion(residual, rms_weight, rms_eps, gate, x):
-    for t in (residual, rms_weight, gate):
-        _need(t is None or (t.dtype == torch.float16 and t.is_contiguous() and t.device == x.device),
-              "fusion tensors must be contiguous float16 on x's device")
-    return capi.HadFusion(_ptr(residual), _ptr(rms_weight), _ptr(gate), float(rms_eps))
-
-
-def _had_transform_fused_cuda(x, out_features, n, K, had, transpose, pre, pre2, post, bias, scale, residual,
-                              rms_weight, rms_eps, gate):
-    xc = _chk_x(x)
-    for t in (had, pre, pre2, post, bias):
-        _need(t is None or (t.dtype == torch.float16 and t.is_contiguous() and t.device == x.device),
-              "had_transform: vectors must be contiguous float16 on x's device")
-    _need(gate is None or gate.shape == xc.shape, "gate must have x's shape")
-    _need(residual is None or tuple(residual.shape) == (xc.shape[0], out_features), "residual shape")
-    _chk_lens("had_transform_fused", xc.shape[1], out_features, n, K, had, pre, pre2, post, bias, rms_weight)
-    y = _empty((xc.shape[0], out_features), dtype=torch.float16, device=x.device)
-    f = _fusion(residual, rms_weight, rms_eps, gate, x)
-    with torch.cuda.device(x.device):
-        capi.check(capi.lib().quip_had_transform_fused_f16(
-            xc.data_ptr(), y.data_ptr(), xc.shape[0], xc.shape[1], out_features, n, K, _ptr(had),
-            int(bool(transpose)), _ptr(pre), _ptr(pre2), _ptr(post), _ptr(bias), float(scale), ctypes.byref(f),
-            _stream(x)), "quip_had_transform_fused_f16")
-    return y
 
 
 def _had_transform_planes_fused_cuda(x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate, resid_scale=0.0):
-    if resid_scale != 0.0:     # the RVQ4 virtual-vector layout is served by the problem-struct entry point
-        return _had_transform_planes_group_cuda(x, n, K, [had], transpose, [pre], [scale], rms_weight, rms_eps, gate,
-                                                resid_scale)[0]
+    return _had_transform_planes_rows_cuda(x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate, resid_scale,
+                                           what="had_transform_planes_fused", one_row=True)
+
+
+def _had_transform_planes_cuda(x, n, K, had, transpose, pre, scale):
+    return _had_transform_planes_rows_cuda(x, n, K, had, transpose, pre, scale, None, 1e-5, None,
+                                           what="had_transform_planes", one_row=True)
+
+
+def _had_transform_planes_group_cuda(x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate, resid_scale=0.0):
+    what = "had_transform_planes_group"
     xc = _chk_x(x)
-    _need(xc.shape[0] == 1, "had_transform_planes is the bs=1 path (one row)")
-    for t in (had, pre):
-        _need(t is None or (t.dtype == torch.float16 and t.is_contiguous() and t.device == x.device),
-              "had_transform_planes: vectors must be contiguous float16 on x's device")
-    _need(gate is None or gate.shape == xc.shape, "gate must have x's shape")
-    _chk_lens("had_transform_planes_fused", xc.shape[1], n, n, K, had, pre, rms_weight=rms_weight)
-    L = capi.lib()
-    planes = _empty(L.quip_e8p_planes_bytes(n), dtype=torch.uint8, device=x.device)
-    f = _fusion(None, rms_weight, rms_eps, gate, x)
-    with torch.cuda.device(x.device):
-        capi.check(L.quip_had_transform_planes_fused(xc.data_ptr(), planes.data_ptr(), xc.shape[1], n, K, _ptr(had),
-                                                     int(bool(transpose)), _ptr(pre), float(scale), ctypes.byref(f),
-                                                     _stream(x)), "quip_had_transform_planes_fused")
-    return planes
+    count = len(pre)
+    _need(xc.shape[0] in (1, count), f"{what}: x has one row (shared) or one row per problem")
+    _group_count(what, count, had, scale)
+    for i in range(count):
+        _check_had(what, xc, n, n, K, had[i], pre[i], rms_weight=rms_weight, gate=gate)
+    outs = [_empty(_planes_numel(n, resid_scale), dtype=torch.uint8, device=x.device) for _ in range(count)]
+    row = 2 * xc.shape[1] if xc.shape[0] == count and count > 1 else 0      # bytes from one problem's row to the next
+    _had_call(x, [_had_problem(x=xc.data_ptr() + row * i, out=outs[i], had=had[i], pre_scale=pre[i], rms_weight=rms_weight,
+                               gate=None if gate is None else gate.data_ptr() + row * i, in_features=xc.shape[1],
+                               out_features=n, scale=float(scale[i]), rms_eps=float(rms_eps), **_layout(resid_scale))
+                  for i in range(count)], True, n, K, transpose)
+    return outs
 
 
-def _vec_ok(t, dev):
-    _need(t is None or (t.dtype == torch.float16 and t.is_contiguous() and t.device == dev),
-          "vectors must be contiguous float16 on x's device")
-    return _ptr(t)
+def _had_chain_planes_group_cuda(z, z_post, z_residual, z_scale, n, pre, scale, rms_weight, rms_eps, resid_scale=0.0,
+                                 K=1, z_had=None, had=None):
+    """K > 1 (n = K * L): z_had is the producer's (K, K) had_right, had[i] consumer i's had_left (applied transposed);
+    z_scale and scale then carry 1 / sqrt(L)"""
+    what = "had_chain_planes_group"
+    zc = _chk_x(z)
+    count = len(pre)
+    _need(zc.shape == (1, n), f"{what} is the bs=1 path: z must be (1, n)")
+    had = list(had) if had is not None else [None] * count
+    _group_count(what, count, scale, had)
+    _need(K == 1 or z_had is not None, f"{what}: K = {K} needs the producer's (K, K) factor")
+    for i in range(count):
+        _check_had(what, zc, n, n, K, had[i], pre[i], post=z_post, rms_weight=rms_weight, residual=z_residual)
+    _check_had(what + " (producer)", zc, n, n, K, z_had if K > 1 else None)
+    outs = [_empty(_planes_numel(n, resid_scale), dtype=torch.uint8, device=z.device) for _ in range(count)]
+    h = _empty((1, n), dtype=torch.float16, device=z.device)
+    factors = {} if K == 1 else {"z_had": z_had}
+    _had_call(z, [_had_problem(out=outs[i], had=had[i] if K > 1 else None, pre_scale=pre[i], rms_weight=rms_weight,
+                               in_features=n, out_features=n, scale=float(scale[i]), rms_eps=float(rms_eps), z=zc,
+                               z_post_scale=z_post, z_residual=z_residual, h_out=h, z_scale=float(z_scale), **factors,
+                               **_layout(resid_scale)) for i in range(count)], True, n, K, True)
+    return [h] + outs
 
 
-def _had_transform_planes_rows_cuda(x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate, resid_scale=0.0):
-    xc = _chk_x(x)
-    _need(gate is None or (gate.shape == xc.shape and gate.dtype == torch.float16 and gate.is_contiguous()),
-          "gate must be contiguous float16 with x's shape")
-    _chk_lens("had_transform_planes_rows", xc.shape[1], n, n, K, had, pre, rms_weight=rms_weight)
-    L = capi.lib()
-    rows = xc.shape[0]
-    out = _empty((rows, _planes_numel(n, resid_scale)), dtype=torch.uint8, device=x.device)
-    pr = capi.HadProblem(xc.data_ptr(), out.data_ptr(), _vec_ok(had, x.device), _vec_ok(pre, x.device), None, None,
-                         None, None, _vec_ok(rms_weight, x.device), _ptr(gate), xc.shape[1], n, float(scale),
-                         float(rms_eps), None, None, None, None, 1.0, *_layout(resid_scale))
-    with torch.cuda.device(x.device):
-        capi.check(L.quip_had_transform_planes_rows(ctypes.byref(pr), rows, n, K, int(bool(transpose)), _stream(x)),
-                   "quip_had_transform_planes_rows")
-    return out
+def _had_transform_group_cuda(x, out_features, n, K, had, transpose, pre2, post, bias, scale, residual, pre,
+                              rms_weight, rms_eps, ns=None):
+    what = "had_transform_group"
+    count = len(x)
+    _group_count(what, count, out_features, had, pre2, post, bias, scale, residual, pre)
+    xs = [_chk_x(t) for t in x]
+    rows = xs[0].shape[0]
+    _need(all(t.shape[0] == rows and t.device == xs[0].device for t in xs), f"{what}: group inputs must share rows / device")
+    _need(ns is not None or all(t.shape == xs[0].shape for t in xs), f"{what}: group inputs must share a shape (or pass ns)")
+    _need(ns is None or (len(ns) == count and K == 1 and rms_weight is None),
+          f"{what}: ns: one width per problem, K == 1, no rms_weight")
+    for i in range(count):
+        _check_had(what, xs[i], int(out_features[i]), int(ns[i]) if ns is not None else n, K, had[i], pre[i], pre2[i], post[i],
+                   bias[i], rms_weight, residual=residual[i])
+    outs = [_empty((rows, int(o)), dtype=torch.float16, device=xs[0].device) for o in out_features]
+    _had_call(xs[0], [_had_problem(x=xs[i], out=outs[i], had=had[i], pre_scale=pre[i], pre_scale2=pre2[i], post_scale=post[i],
+                                   bias=bias[i], residual=residual[i], rms_weight=rms_weight, in_features=xs[i].shape[1],
+                                   out_features=int(out_features[i]), scale=float(scale[i]), rms_eps=float(rms_eps),
+                                   n=int(ns[i]) if ns is not None else 0) for i in range(count)], False, n, K, transpose, rows)
+    return outs
 
 
 def _argmax_step_cuda(logits, tok, pos):
@@ -495,96 +555,6 @@ def _e8p_mm_planes_rows_cuda(planes, Qidxs, grid):
             vp(*[out.data_ptr() + 2 * n * i for i in range(count)]), ns, count, k, _stream(out)),
             "quip_e8p_gemv_planes_group (rows)")
     return out
-
-
-def _had_transform_planes_group_cuda(x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate, resid_scale=0.0):
-    xc = _chk_x(x)
-    count = len(pre)
-    _need(xc.shape[0] in (1, count), "had_transform_planes_group: x has one row (shared) or one row per problem")
-    _need(1 <= count <= capi.MAX_GROUP and len(had) == count and len(scale) == count, "group of 1..3 problems")
-    _need(gate is None or gate.shape == xc.shape, "gate must have x's shape")
-    for i in range(count):
-        _chk_lens("had_transform_planes_group", xc.shape[1], n, n, K, had[i], pre[i], rms_weight=rms_weight)
-    L = capi.lib()
-    nbytes = L.quip_e8p_planes_bytes(2 * n if resid_scale != 0.0 else n)
-    outs = [_empty(nbytes, dtype=torch.uint8, device=x.device) for _ in range(count)]
-    arr = (capi.HadProblem * count)()
-    per_row = xc.shape[0] == count and count > 1
-    gptr = _vec_ok(gate, x.device)
-    for i in range(count):
-        off = 2 * xc.shape[1] * i if per_row else 0
-        arr[i] = capi.HadProblem(xc.data_ptr() + off, outs[i].data_ptr(), _vec_ok(had[i], x.device),
-                                 _vec_ok(pre[i], x.device), None, None, None, None, _vec_ok(rms_weight, x.device),
-                                 None if gptr is None else gptr + off, xc.shape[1], n, float(scale[i]), float(rms_eps),
-                                 None, None, None, None, 1.0, *_layout(resid_scale))
-    with torch.cuda.device(x.device):
-        capi.check(L.quip_had_transform_planes_group(arr, count, n, K, int(bool(transpose)), _stream(x)),
-                   "quip_had_transform_planes_group")
-    return outs
-
-
-def _had_chain_planes_group_cuda(z, z_post, z_residual, z_scale, n, pre, scale, rms_weight, rms_eps, resid_scale=0.0,
-                                 K=1, z_had=None, had=None):
-    """K > 1 (n = K * L): z_had is the producer's (K, K) had_right, had[i] consumer i's had_left (applied transposed);
-    z_scale and scale then carry 1 / sqrt(L)"""
-    zc = _chk_x(z)
-    count = len(pre)
-    _need(zc.shape == (1, n), "had_chain_planes_group is the bs=1 path: z must be (1, n)")
-    _need(1 <= count <= capi.MAX_GROUP and len(scale) == count, "group of 1..3 problems")
-    _need(z_residual is None or tuple(z_residual.shape) == (1, n), "residual shape")
-    had = list(had) if had is not None else [None] * count
-    _need(len(had) == count, "had: one factor per problem")
-    _need(K == 1 or z_had is not None, f"had_chain_planes_group: K = {K} needs the producer's (K, K) factor")
-    for i in range(count):
-        _chk_lens("had_chain_planes_group", n, n, n, K, had[i], pre[i], post=z_post, rms_weight=rms_weight)
-    _chk_lens("had_chain_planes_group (producer)", n, n, n, K, z_had if K > 1 else None)
-    L = capi.lib()
-    nbytes = L.quip_e8p_planes_bytes(2 * n if resid_scale != 0.0 else n)
-    outs = [_empty(nbytes, dtype=torch.uint8, device=z.device) for _ in range(count)]
-    h = _empty((1, n), dtype=torch.float16, device=z.device)
-    arr = (capi.HadProblem * count)()
-    for i in range(count):
-        arr[i] = capi.HadProblem(None, outs[i].data_ptr(), _vec_ok(had[i], z.device) if K > 1 else None,
-                                 _vec_ok(pre[i], z.device), None, None, None, None,
-                                 _vec_ok(rms_weight, z.device), None, n, n, float(scale[i]), float(rms_eps),
-                                 zc.data_ptr(), _vec_ok(z_post, z.device), _vec_ok(z_residual, z.device),
-                                 h.data_ptr(), float(z_scale), *_layout(resid_scale), 0,
-                                 _vec_ok(z_had, z.device) if K > 1 else None)
-    with torch.cuda.device(z.device):
-        capi.check(L.quip_had_transform_planes_group(arr, count, n, int(K), 1, _stream(z)),
-                   "quip_had_transform_planes_group (chain)")
-    return [h] + outs
-
-
-def _had_transform_group_cuda(x, out_features, n, K, had, transpose, pre2, post, bias, scale, residual, pre,
-                              rms_weight, rms_eps, ns=None):
-    count = len(x)
-    _need(1 <= count <= capi.MAX_GROUP and all(len(v) == count for v in (out_features, had, pre2, post, bias, scale,
-                                                                          residual, pre)), "group of 1..3 problems")
-    xs = [_chk_x(t) for t in x]
-    rows = xs[0].shape[0]
-    _need(all(t.shape[0] == rows and t.device == xs[0].device for t in xs), "group inputs must share rows / device")
-    _need(ns is not None or all(t.shape == xs[0].shape for t in xs), "group inputs must share a shape (or pass ns)")
-    _need(ns is None or (len(ns) == count and K == 1 and rms_weight is None),
-          "ns: one width per problem, K == 1, no rms_weight")
-    dev = xs[0].device
-    outs = [_empty((rows, int(o)), dtype=torch.float16, device=dev) for o in out_features]
-    arr = (capi.HadProblem * count)()
-    for i in range(count):
-        _need(residual[i] is None or tuple(residual[i].shape) == tuple(outs[i].shape), "residual shape")
-        ni = int(ns[i]) if ns is not None else n
-        _chk_lens("had_transform_group", xs[i].shape[1], int(out_features[i]), ni, K, had[i], pre[i], pre2[i], post[i],
-                  bias[i], rms_weight)
-        arr[i] = capi.HadProblem(xs[i].data_ptr(), outs[i].data_ptr(), _vec_ok(had[i], dev), _vec_ok(pre[i], dev),
-                                 _vec_ok(pre2[i], dev), _vec_ok(post[i], dev), _vec_ok(bias[i], dev),
-                                 _vec_ok(residual[i], dev), _vec_ok(rms_weight, dev), None,
-                                 xs[i].shape[1], int(out_features[i]), float(scale[i]), float(rms_eps))
-        if ns is not None:
-            arr[i].n = int(ns[i])
-    with torch.cuda.device(dev):
-        capi.check(capi.lib().quip_had_transform_group_f16(arr, count, rows, n, K, int(bool(transpose)), _stream(xs[0])),
-                   "quip_had_transform_group_f16")
-    return outs
 
 
 _GEMV_WS = {}        # (device type, index, stream handle) -> zeroed int32 workspace
@@ -1056,22 +1026,9 @@ _reg_fake("hadamard", lambda x, scale: torch.empty_like(x, memory_format=torch.c
 _reg_fake("had_transform", lambda x, out_features, n, K, had, transpose, pre, pre2, post, bias, scale:
           x.new_empty((x.shape[0], out_features)))
 _reg_fake("had_transform_planes", lambda x, n, K, had, transpose, pre, scale:
-          x.new_empty((3 * ((n + 511) // 512 * 512) + 16,), dtype=torch.uint8))
+          x.new_empty((_planes_numel(n),), dtype=torch.uint8))
 _reg_fake("had_transform_fused", lambda x, out_features, n, K, had, transpose, pre, pre2, post, bias, scale, residual,
           rms_weight, rms_eps, gate: x.new_empty((x.shape[0], out_features)))
-HI_PLANES = float("inf")     # resid_scale value that selects the HI virtual-vector layout of the planes ops
-
-
-def _layout(resid_scale):
-    """(resid_scale, planes_layout) of a quip_had_problem from the ops' single float argument"""
-    return (0.0, 2) if resid_scale == HI_PLANES else (float(resid_scale), 0)
-
-
-def _planes_numel(n, resid_scale):
-    m = 2 * n if resid_scale != 0.0 else n
-    return 3 * ((m + 511) // 512 * 512) + 16
-
-
 _reg_fake("had_transform_planes_fused", lambda x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate,
           resid_scale=0.0: x.new_empty((_planes_numel(n, resid_scale),), dtype=torch.uint8))
 _reg_fake("had_transform_planes_group", lambda x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate,
