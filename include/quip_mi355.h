@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 21
+#define QUIP_ABI_VERSION 22
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -630,6 +630,39 @@ int quip_nll_rows_f16(const void* logits, int32_t rows, int32_t n, const int64_t
 int quip_sample_step_f16(const void* logits, int32_t rows, int32_t n, const float* temperature, const int32_t* top_k,
                          const float* top_p, const int64_t* seed, int64_t* tok, int64_t* pos, int32_t* kept,
                          quip_stream_t stream);
+
+/* ---- speculative greedy decode (ABI 22): the step between two chunk passes of n = k + 1 rows, one launch, one workgroup --
+ * (csrc/spec_rows.hip.h).  All on the device; token ids, pos, out_len and stats int64, n_draft / n_pred int32:
+ *   rows_tok [n]   the tokens of the pass: row 0 the current token, rows 1 .. n_draft[0] guesses, 0 behind them
+ *   pos [1]        the position counter; for _accept_draft it arrives as p0 + n (the pass advanced it)
+ *   hist [hist_cap]  hist[p] = the token fed at position p, valid on [0, p0], hist[p0] == rows_tok[0]
+ *   pred [pred_cap], n_pred [1]  the caller's prediction, its first n_pred[0] entries (clamped to 0 .. pred_cap); pred may be
+ *                  NULL where pred_cap is 0
+ *   out [cap_out], out_len [1]   the emitted tokens; out may be NULL where cap_out is 0
+ *   stats [4]      passes, drafted, accepted, status
+ *   argmax [n] int64, lse [n] fp32   quip_nll_rows_f16's results for the pass's logits
+ * accept  d = n_draft[0]; a = the largest j in [0, d] with argmax[i] == rows_tok[i + 1] for all i < j and lse[i] finite for
+ *         all i <= j.  Without one (row 0 not finite): status |= 1, pos = p0, nothing else is written.  Else, t = argmax[a]:
+ *         out gets rows_tok[1 .. a] and t at out_len (entries at or past cap_out are dropped), out_len += a + 1,
+ *         hist[p0 + 1 .. p0 + a] = rows_tok[1 .. a], hist[p0 + a + 1] = t, pos = p0 + a + 1, stats += (1, d, a, 0).
+ * draft   corpus C = pred[0 .. n_pred) ++ hist[0 .. pos]; neither a match nor a continuation crosses the seam.  For a match
+ *         length g from gmax down to max(gmin, 1), g <= pos + 1: a candidate is an end index e < len(C) - 1 with
+ *         C[e - g + 1 .. e] equal to the last g tokens of hist[0 .. pos], those g tokens in one segment, and
+ *         avail(e) >= 1 tokens behind e in e's segment.  The winner is the maximum of (g, min(avail, k), e); the guesses are
+ *         C[e + 1 .. e + min(avail, k)], n_draft their count (0 without a candidate), rows_tok = [t, guesses, 0 ...]
+ *         (t = rows_tok[0] for quip_spec_draft_i64).  gmax = 0: no drafting.
+ * quip_spec_draft_i64 drafts only (pos is p0 and stays); quip_spec_accept_draft_i64 accepts, then drafts.  A position that
+ * hist cannot hold (pos outside [0, hist_cap), p0 < 0 or p0 + n >= hist_cap) sets status |= 2 and writes nothing else.
+ * 1 <= k <= 15, 0 <= gmin <= gmax <= 8, hist_cap >= 1, pred_cap, cap_out >= 0, hist_cap + pred_cap <= 2^20 (else
+ * QUIP_ERR_BAD_SHAPE); int64 operands 8-byte, int32 / fp32 operands 4-byte aligned (else QUIP_ERR_MISALIGNED).  Every
+ * operand is checked before any launch. */
+int quip_spec_draft_i64(int64_t* rows_tok, int32_t* n_draft, int64_t* pos, int64_t* hist, int32_t hist_cap,
+                        const int64_t* pred, const int32_t* n_pred, int32_t pred_cap, int64_t* stats, int32_t k,
+                        int32_t gmin, int32_t gmax, quip_stream_t stream);
+int quip_spec_accept_draft_i64(const int64_t* argmax, const float* lse, int64_t* rows_tok, int32_t* n_draft, int64_t* pos,
+                               int64_t* hist, int32_t hist_cap, const int64_t* pred, const int32_t* n_pred,
+                               int32_t pred_cap, int64_t* out, int64_t* out_len, int32_t cap_out, int64_t* stats,
+                               int32_t k, int32_t gmin, int32_t gmax, quip_stream_t stream);
 
 /* ---- per-head RMSNorm of q and k in front of the rotary embedding (ABI 19; Qwen3's q_norm / k_norm) ---------------------
  * For one head vector x[0..HD) (fp16), weight w[0..HD) (fp16) and eps (fp32), HD = head_dim (csrc/attn_query.hip.h):

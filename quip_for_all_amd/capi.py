@@ -66,6 +66,8 @@ SIGNATURES = {
                                        _I32, _P, _P, _I32, _F, _I32, _P, _I32, _I32],
     "quip_nll_rows_f16": [_P, _I32, _I32, _P, _P, _P, _P, _P],
     "quip_sample_step_f16": [_P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
+    "quip_spec_draft_i64": [_P, _P, _P, _P, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _P],
+    "quip_spec_accept_draft_i64": [_P, _P, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _P],
     "quip_qk_norm_rows_f16": [_P, _P, _P, _P, _I64, _I32, _I32, _I32, _F, _P],
     "quip_rope_attn_decode_qknorm_f16": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F, _I32, _P, _P,
                                          _P, _P, _F],

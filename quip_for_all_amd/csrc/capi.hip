@@ -888,6 +888,28 @@ int quip_sample_step_f16(const void* logits, int32_t rows, int32_t n, const floa
   return sample_rows_launch(logits, rows, n, temperature, top_k, top_p, seed, tok, pos, kept, (hipStream_t)stream);
 }
 
+int quip_spec_draft_i64(int64_t* rows_tok, int32_t* n_draft, int64_t* pos, int64_t* hist, int32_t hist_cap,
+                        const int64_t* pred, const int32_t* n_pred, int32_t pred_cap, int64_t* stats, int32_t k,
+                        int32_t gmin, int32_t gmax, quip_stream_t stream) {
+  if (any_null({rows_tok, n_draft, pos, hist, n_pred, stats}) || (!pred && pred_cap != 0)) return QUIP_ERR_NULL_POINTER;
+  if (any_off({rows_tok, pos, hist, pred, stats}, 7) || any_off({n_draft, n_pred}, 3)) return QUIP_ERR_MISALIGNED;
+  return spec_draft_launch(rows_tok, n_draft, pos, hist, hist_cap, pred, n_pred, pred_cap, stats, k, gmin, gmax,
+                           (hipStream_t)stream);
+}
+
+int quip_spec_accept_draft_i64(const int64_t* argmax, const float* lse, int64_t* rows_tok, int32_t* n_draft, int64_t* pos,
+                               int64_t* hist, int32_t hist_cap, const int64_t* pred, const int32_t* n_pred,
+                               int32_t pred_cap, int64_t* out, int64_t* out_len, int32_t cap_out, int64_t* stats,
+                               int32_t k, int32_t gmin, int32_t gmax, quip_stream_t stream) {
+  if (any_null({argmax, lse, rows_tok, n_draft, pos, hist, n_pred, out_len, stats}) || (!pred && pred_cap != 0) ||
+      (!out && cap_out != 0))
+    return QUIP_ERR_NULL_POINTER;
+  if (any_off({argmax, rows_tok, pos, hist, pred, out, out_len, stats}, 7) || any_off({lse, n_draft, n_pred}, 3))
+    return QUIP_ERR_MISALIGNED;
+  return spec_accept_draft_launch(argmax, lse, rows_tok, n_draft, pos, hist, hist_cap, pred, n_pred, pred_cap, out, out_len,
+                                  cap_out, stats, k, gmin, gmax, (hipStream_t)stream);
+}
+
 int quip_qk_norm_rows_f16(void* q, void* k, const void* q_weight, const void* k_weight, int64_t rows, int32_t heads,
                           int32_t kv_heads, int32_t head_dim, float eps, quip_stream_t stream) {
   if (any_null({q, k, q_weight, k_weight})) return QUIP_ERR_NULL_POINTER;

@@ -622,5 +622,7 @@ int argmax_step_batched_launch(const void* logits, int batch, int n, void* tok, 
 #include "nll_rows.hip.h"
 // the sampling tail: one token per row, every row with its own temperature, top-k, top-p and seed
 #include "sample_rows.hip.h"
+// speculative greedy decode: accept the confirmed guesses of a chunk pass, emit, rewind, draft the next ones by prompt lookup
+#include "spec_rows.hip.h"
 // LoRA adapters beside the quantised modules, one adapter index per row: the shrink and the expand launch
 #include "lora_rows.hip.h"

@@ -224,6 +224,15 @@ int nll_rows_launch(const void* logits, int rows, int n, const int64_t* target, 
 int sample_rows_launch(const void* logits, int rows, int n, const float* temperature, const int32_t* top_k,
                        const float* top_p, const int64_t* seed, int64_t* tok, int64_t* pos, int32_t* kept,
                        hipStream_t stream);
+// spec_rows.hip.h (in decode_glue.hip): the step of a speculative greedy decode between two chunk passes of k + 1 rows, one
+// workgroup.  _draft: the guesses behind rows_tok[0] at pos (the first pass of a call); _accept_draft: accept the guesses
+// that nll_rows' arg-max confirmed, emit, rewind pos, then the same draft.  pred may be null where pred_cap is 0
+int spec_draft_launch(int64_t* rows_tok, int32_t* n_draft, int64_t* pos, int64_t* hist, int hist_cap, const int64_t* pred,
+                      const int32_t* n_pred, int pred_cap, int64_t* stats, int k, int gmin, int gmax, hipStream_t stream);
+int spec_accept_draft_launch(const int64_t* argmax, const float* lse, int64_t* rows_tok, int32_t* n_draft, int64_t* pos,
+                             int64_t* hist, int hist_cap, const int64_t* pred, const int32_t* n_pred, int pred_cap,
+                             int64_t* out, int64_t* out_len, int cap_out, int64_t* stats, int k, int gmin, int gmax,
+                             hipStream_t stream);
 // lora_rows.hip.h (in decode_glue.hip): t = A[row_adapter[row]] xin(row) over (rows, in) fp16 rows (mode 0 x, 1 RMSNorm(x) w with
 // aux = w, 2 x silu(aux row)), and y_j += scale B_j t for up to three segments; rows without an adapter: zeros / untouched
 int lora_shrink_rows_launch(const void* x, const void* A, const int32_t* row_adapter, float* t, int64_t rows, int in, int R,

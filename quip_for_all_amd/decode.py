@@ -28,6 +28,7 @@ from . import lora as _lora  # (defines quip_lib::lora_shrink_rows / lora_expand
 from . import qk_norm as _qk_norm  # noqa: F401  (defines quip_lib::qk_norm_rows and the two _qknorm decode launches)
 from . import register_lib as _R
 from . import score as _score  # (defines quip_lib::nll_rows)
+from . import spec as _spec  # (defines quip_lib::spec_draft / spec_accept_draft)
 from . import token_tail as _token_tail  # noqa: F401  (defines quip_lib::block_engine_token)
 from .codebook import codebook_id
 from .qlinear import (QuantLinear, _engine_had3, chain_planes, chain_supported, ffn_engine, ffn_engine_ok, forward_group,
@@ -483,6 +484,9 @@ class LlamaDecoder:
         self._fed = None                    # host-side count of the tokens generate() fed (generate(append=True))
         self._tail_logits = None            # the whole-token launch's one logits row (step())
         self._prefill_graphs, self._extend_graphs = {}, {}      # length -> (graph, logits, static tokens)
+        self._spec = None                   # device state of generate_speculative (_spec_state)
+        self._spec_graphs = {}              # (k, gmin, gmax, adapter) -> the captured pass
+        self.spec_stats = None              # what the last generate_speculative call did
         self._rm_scratch = {}               # projection name -> row-major scratch (_row_major)
         self.fused_attention = s.head_dim in (64, 128)
         # per-head RMSNorm of q / k in front of the rotation (Qwen3): the layer dicts carry q_norm / k_norm.  qk_fused: the bs = 1
@@ -819,7 +823,7 @@ class LlamaDecoder:
     def _drop_graphs(self):
         """captured steps and passes hold launch lists: gone when the groups that launch change"""
         self.graph = None
-        self._prefill_graphs, self._extend_graphs = {}, {}
+        self._prefill_graphs, self._extend_graphs, self._spec_graphs = {}, {}, {}
         for d in list(self._lora_dependents):
             d.graph = None
 
@@ -1163,6 +1167,129 @@ class LlamaDecoder:
             self.extend(static_tok)
             self.pos.copy_(pos0)
         return self._replay_per_length(self._extend_graphs, tokens, warmup, self.extend)
+
+    # ---- speculative greedy decode (spec.py) ------------------------------------------------------------------
+    def _spec_state(self):
+        """the device state of a speculative decode at fixed addresses (a captured pass reads and writes it in place):
+        the pass's rows, hist, the prediction buffer, the emitted tokens and the counters (csrc/spec_rows.hip.h)"""
+        if self._spec is None:
+            def z(n, dt=torch.long):
+                return torch.zeros(n, dtype=dt, device=self.dev)
+            cap = min(max(4096, 4 * self.max_len), _spec.MAX_CORPUS - (self.max_len + 1))
+            self._spec = dict(rows=z(_spec.MAX_K + 1), neg=z(_spec.MAX_K + 1) - 1, hist=z(self.max_len + 1), pred=z(cap),
+                              out=z(self.max_len + _spec.MAX_K + 1), out_len=z(1), stats=z(4), n_draft=z(1, torch.int32),
+                              n_pred=z(1, torch.int32))
+        return self._spec
+
+    def _spec_pass(self, k, gmin, gmax, adapter=None):
+        """one pass of generate_speculative: the k + 1 rows (current token, guesses) behind the position through every block
+        on the chunk route, final norm and lm_head on all rows, the scoring tail (targets -1: lse and arg-max), then accept /
+        emit / rewind / draft in one launch.  Nothing is read on the host."""
+        S, s = self._spec_state(), self.s
+        rows = S["rows"][:k + 1]
+
+        def tail(c0, h):
+            logits = F.rms_norm(h, (s.hidden,), self.final_norm, s.rms_eps) @ self.lm_head.T
+            _, lse, am = torch.ops.quip_lib.nll_rows(logits, S["neg"][:k + 1])
+            torch.ops.quip_lib.spec_accept_draft(am, lse, rows, S["n_draft"], self.pos, S["hist"], S["pred"], S["n_pred"],
+                                                 S["out"], S["out_len"], S["stats"], gmin, gmax)
+        _extend_chunks(self, "generate_speculative", rows, k + 1, None, None, tail, adapter)
+
+    def _spec_graph(self, k, gmin, gmax, adapter):
+        """the captured pass for (k, ngram, adapter tensor), captured at first use with prefill_graph's cache-size rule.  The
+        warm-up runs on the live state and puts it back: the cache rows it appends are the ones the replay writes again."""
+        key = (k, gmin, gmax, None if adapter is None else adapter.data_ptr())
+        if key not in self._spec_graphs:
+            if len(self._spec_graphs) >= self.prefill_graph_cache_size:
+                self._spec_graphs.pop(next(iter(self._spec_graphs)))
+            S = self._spec_state()
+            live = [self.pos, S["hist"], S["rows"], S["n_draft"], S["out"], S["out_len"], S["stats"]]
+
+            def warmup():
+                saved = [t.clone() for t in live]
+                self._spec_pass(k, gmin, gmax, adapter)
+                for t, t0 in zip(live, saved):
+                    t.copy_(t0)
+            self._spec_graphs[key] = capture_graph(warmup, lambda: self._spec_pass(k, gmin, gmax, adapter))[0]
+        return self._spec_graphs[key]
+
+    @torch.no_grad()
+    def generate_speculative(self, n_tokens, prompt, k=4, ngram=(1, 3), prediction=None, use_graph=True, adapter=None):
+        """generate(n_tokens, prompt=prompt) for greedy decoding, the same tokens, with up to `k` guessed tokens verified per
+        pass: the current token and the guesses go through the blocks as ONE chunk pass of k + 1 rows (the codes are read once
+        for all of them), the longest prefix of guesses that the model's own arg-max confirms is accepted with the model's
+        next token behind it, and the cache is taken back behind the rest by moving the position.  Guesses need no second
+        model: they are the continuation of the most recent place where the last ngram = (gmin, gmax) tokens -- the longest
+        match first -- already occurred, in `prediction` (1-D ids: what the caller expects the output to look like, as in
+        editing and retrieval workloads) or in the prompt and the text generated so far; ngram = (0, 0) guesses nothing.
+        quip_lib::spec_accept_draft does all of that on the device; after a pass the host reads the count of emitted tokens,
+        nothing else.  use_graph: the pass is captured once per (k, ngram) and replayed at every position, whatever the
+        prompt and the prediction.  Returns the (n_tokens,) ids on the device; leaves the position, the current token and
+        the fed count as generate() does (generate(append=True) continues) and self.spec_stats = {passes, drafted, accepted,
+        emitted}: emitted = passes + accepted >= n_tokens, the surplus of the last pass is dropped.  `adapter`: as in
+        prefill().  A pass whose first row has no finite logits raises RuntimeError; nothing retries."""
+        what = "generate_speculative"
+        prompt = torch.as_tensor(prompt, dtype=torch.long, device=self.dev).reshape(-1)
+        P, n_tokens = prompt.numel(), int(n_tokens)
+        if P < 1 or n_tokens < 1:
+            raise ValueError(f"{what}: prompt needs at least one token and n_tokens must be >= 1")
+        if not isinstance(k, int) or not 1 <= k <= _spec.MAX_K:
+            raise ValueError(f"{what}: k = {k!r} outside 1 .. {_spec.MAX_K}")
+        try:
+            gmin, gmax = (int(g) for g in ngram)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: ngram = {ngram!r} is not a pair (gmin, gmax)") from None
+        if not 0 <= gmin <= gmax <= _spec.MAX_G:
+            raise ValueError(f"{what}: ngram = {ngram!r}: need 0 <= gmin <= gmax <= {_spec.MAX_G}")
+        if self.sampling is not None:
+            raise ValueError(f"{what}: greedy only, but a temperature is set (set_sampling(None) first)")
+        if self.s.head_dim not in (64, 128):
+            raise ValueError(f"{what}: head_dim {self.s.head_dim}: the chunk attention launch serves 64 and 128")
+        if P - 1 + n_tokens + k > self.max_len:
+            raise ValueError(f"{what}: {P} prompt tokens - 1 + n_tokens {n_tokens} + k {k} > max_len {self.max_len}: "
+                             f"the last pass would not fit the cache")
+        S = self._spec_state()
+        n_pred = 0
+        if prediction is not None:
+            prediction = torch.as_tensor(prediction, dtype=torch.long, device=self.dev).reshape(-1)
+            n_pred = prediction.numel()
+            if n_pred > S["pred"].numel():
+                raise ValueError(f"{what}: prediction of {n_pred} tokens > the buffer's {S['pred'].numel()}")
+            if n_pred and not (0 <= int(prediction.min()) and int(prediction.max()) < self.s.vocab):
+                raise ValueError(f"{what}: prediction holds ids outside the vocabulary 0 .. {self.s.vocab - 1}")
+        self.reset()
+        if P > 1:
+            self.prefill(prompt[:-1], adapter=adapter)
+        self.tok.copy_(prompt[-1:].view_as(self.tok))
+        S["hist"][:P].copy_(prompt)
+        S["rows"].zero_()
+        S["rows"][:1].copy_(prompt[-1:])
+        S["pred"][:n_pred].copy_(prediction if n_pred else S["pred"][:0])
+        S["n_pred"].fill_(n_pred)
+        for name in ("n_draft", "out_len", "stats"):
+            S[name].zero_()
+        torch.ops.quip_lib.spec_draft(S["rows"][:k + 1], S["n_draft"], self.pos, S["hist"], S["pred"], S["n_pred"],
+                                      S["stats"], gmin, gmax)
+        graph = self._spec_graph(k, gmin, gmax, adapter) if use_graph else None
+        emitted = 0
+        while emitted < n_tokens:
+            if graph is not None:
+                graph.replay()
+            else:
+                self._spec_pass(k, gmin, gmax, adapter)
+            before, emitted = emitted, int(S["out_len"])           # the one host read of a pass
+            if emitted <= before:
+                break                                               # (a status bit: the pass emitted nothing)
+        passes, drafted, accepted, status = S["stats"].tolist()
+        if status or emitted < n_tokens:
+            raise RuntimeError(f"{what}: status {status} after {passes} passes and {emitted} tokens"
+                               + (": a pass gave no finite logits" if status & _spec.STATUS_NONFINITE else ""))
+        out = S["out"][:n_tokens].clone()
+        self.tok.copy_(out[-1:].view_as(self.tok))
+        self.pos.fill_(P - 1 + n_tokens)
+        self._fed = P - 1 + n_tokens
+        self.spec_stats = {"passes": passes, "drafted": drafted, "accepted": accepted, "emitted": emitted}
+        return out
 
     def reset(self, first_token=1):
         if self.block_eng and self._eng_sig != self._engine_signature():
