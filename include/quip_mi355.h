@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 22
+#define QUIP_ABI_VERSION 23
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -324,6 +324,19 @@ int quip_e8p_quantize_f32(const void* x, int64_t nvec, const void* grid_packed_a
  * A, B, M, P, hat 16-byte aligned, idx 8-byte aligned. */
 int quip_ldlq_panel_f32(const void* A, const void* B, const void* M, const void* P, int64_t m, int32_t c,
                         const void* grid_packed_abs, void* hat, void* idx, quip_stream_t stream);
+
+/* ---- the same panel for the two residual codebooks (ABI 23; e8p12_rvq4.py:37-45, e8p12_rvq3.py:81-92) ---------------------
+ * The recursion, operands, fixed summation order and refusals of quip_ldlq_panel_f32; the rounding of a group's fp32
+ * target t has two stages, with s = resid_scale as fp32 and every operation rounded to fp32 on its own (an IEEE division,
+ * a multiplication and an addition that do not contract into an FMA):
+ *     a = nearest E8P12 codeword of t,   r = (t - a) / s,   b = Q2(r),   hat = a + b * s
+ * resid_grid == NULL (E8P12RVQ4B): Q2 = the E8P12 search again,                             idx = code_a << 16 | code_b;
+ * resid_grid = fp32 (256, 8), 16-byte aligned (E8P12RVQ3B): Q2 = arg max_c 2 r . g_c - |g_c|^2 over its 256 rows, the
+ * dot product summed left to right, the lowest index on equal scores,                       idx = code_a << 8 | c.
+ * resid_scale must be finite and non-zero (else QUIP_ERR_BAD_SHAPE); it may be negative. */
+int quip_ldlq_panel_rvq_f32(const void* A, const void* B, const void* M, const void* P, int64_t m, int32_t c,
+                            const void* grid_packed_abs, const void* resid_grid, float resid_scale, void* hat, void* idx,
+                            quip_stream_t stream);
 
 /* Rows mode for the other table modes of the same kernel.  mode 0: E8P12 (== quip_e8p_gemv_planes_rows);
  * mode 64: D4 (qidxs uint8 (n, k/4), grid = fp16 (256, 4) table; HI through its virtual 2k layout, see

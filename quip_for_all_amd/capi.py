@@ -30,6 +30,7 @@ SIGNATURES = {
     "quip_e8p_gemv_max_rows": [_I32, _I32],
     "quip_e8p_quantize_f32": [_P, _I64, _P, _P, _P, _P],
     "quip_ldlq_panel_f32": [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P],
+    "quip_ldlq_panel_rvq_f32": [_P, _P, _P, _P, _I64, _I32, _P, _P, _F, _P, _P, _P],
     "quip_gemv_max_rows_mode": [_I32, _I32, _I32],
     "quip_gemv_planes_rows_mode": [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P],
     "quip_e8p_gemv_planes_rows": [_P, _P, _P, _P, _I32, _I32, _I32, _P],

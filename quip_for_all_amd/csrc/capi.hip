@@ -377,6 +377,20 @@ int quip_ldlq_panel_f32(const void* A, const void* B, const void* M, const void*
   return ldlq_panel_launch(A, B, M, P, m, c, grid_packed_abs, hat, idx, (hipStream_t)stream);
 }
 
+int quip_ldlq_panel_rvq_f32(const void* A, const void* B, const void* M, const void* P, int64_t m, int32_t c,
+                            const void* grid_packed_abs, const void* resid_grid, float resid_scale, void* hat, void* idx,
+                            quip_stream_t stream) {
+  if (m < 0 || c < 8 || c % 8 != 0) return QUIP_ERR_BAD_SHAPE;
+  if (c > 128) return QUIP_ERR_UNSUPPORTED;
+  if (!(resid_scale != 0.f) || !(resid_scale - resid_scale == 0.f)) return QUIP_ERR_BAD_SHAPE;     // 0 | nan, +-inf
+  if (m == 0) return QUIP_OK;
+  if (!A || !B || !M || !grid_packed_abs || !hat || !idx) return QUIP_ERR_NULL_POINTER;
+  if (!aligned16(A) || !aligned16(B) || !aligned16(M) || !aligned16(P) || !aligned16(resid_grid) || !aligned16(hat) ||
+      (reinterpret_cast<uintptr_t>(idx) & 7) != 0)
+    return QUIP_ERR_MISALIGNED;
+  return ldlq_panel_rvq_launch(A, B, M, P, m, c, grid_packed_abs, resid_grid, resid_scale, hat, idx, (hipStream_t)stream);
+}
+
 int32_t quip_e8p_gemv_max_rows(int32_t n, int32_t k) { return (n > 0 && k > 0) ? e8p_gemv_mfma_max_rows(n, k) : 0; }
 
 int quip_e8p_gemv_planes_rows(const void* planes, const void* qidxs, const void* grid_packed_abs, void* y,

@@ -24,7 +24,8 @@
 //
 // Second kernel, further down: ldlq_panel_kernel runs the LDLQ recursion over a whole panel of <= 128 columns in one
 // launch, with this search in place at every column group (the scan and the winner's reconstruction are device
-// functions that both kernels call).
+// functions that both kernels call).  The kernel is a template over the rounding step of a group: E8P12 (one search), or the
+// two residual codebooks E8P12RVQ4B / E8P12RVQ3B (a second search on the scaled residual of the first, same launch).
 #include <hip/hip_runtime.h>
 
 #include "quip_device.hip.h"
@@ -181,6 +182,67 @@ __global__ __launch_bounds__(256) void e8p_quantize_kernel(const float* __restri
   reinterpret_cast<float4*>(vals + i * 8)[1] = make_float4(out[4], out[5], out[6], out[7]);
 }
 
+// ---- the second stage of the residual codebooks (e8p12_rvq4.py:37-45, e8p12_rvq3.py:81-92) ----------------------------------
+//     r = (t - a) / s,   b = Q2(r),   hat = a + b * s
+// with every operation rounded to fp32 on its own: the stepwise route and the decoders form hat by a multiplication and
+// an addition, so neither may contract into an FMA, and the division is the IEEE one (not a reciprocal).
+__device__ __forceinline__ float rvq_residual(float t, float a, float s) {
+#pragma clang fp contract(off)
+  return (t - a) / s;
+}
+__device__ __forceinline__ float rvq_combine(float a, float b, float s) {
+#pragma clang fp contract(off)
+  const float bs = b * s;
+  return a + bs;
+}
+
+// E81B (256 entries) in LDS: entry e at slot (e % 32) * 8 + e / 32, so that the 8 lanes of a row, which scan entries
+// sub * 32 + i at the same i, read 64 consecutive floats (no bank conflict) instead of 8 addresses 1 KB apart.
+__device__ __forceinline__ int e81b_slot(int e) { return (e & 31) * 8 + (e >> 5); }
+
+// thread e of 256 loads entry e and its squared norm (entries are multiples of 1/2: the norm is exact in any order)
+__device__ __forceinline__ void e81b_table_row(int e, const float* __restrict__ resid_grid, float (*eb)[8], float* en) {
+  const float4 lo = reinterpret_cast<const float4*>(resid_grid + e * 8)[0];
+  const float4 hi = reinterpret_cast<const float4*>(resid_grid + e * 8)[1];
+  const float g[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  const int slot = e81b_slot(e);
+  float n2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    eb[slot][j] = g[j];
+    n2 += g[j] * g[j];
+  }
+  en[slot] = n2;
+}
+
+// dense arg max_c 2 r . g_c - |g_c|^2 over the 256 entries: lane `sub` of the row's 8 lanes scans entries sub * 32 ..
+// sub * 32 + 31 in increasing order, then the lanes agree.  The dot product is eight products summed left to right, each
+// rounded to fp32 (no FMA: the score is then the one an elementwise fp32 evaluation gives, which the tests write out);
+// equal scores resolve to the lowest index inside a lane (strict >) and across lanes.  Returns the index on every lane.
+__device__ __forceinline__ int e81b_scan(const float (&rv)[8], int sub, const float (*eb)[8], const float* en) {
+#pragma clang fp contract(off)
+  float best = -3.0e38f;
+  int key = sub * 32;
+  for (int i = 0; i < 32; ++i) {
+    const int slot = i * 8 + sub;
+    float dot = rv[0] * eb[slot][0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) {
+      const float pj = rv[j] * eb[slot][j];
+      dot = dot + pj;
+    }
+    const float score = 2.f * dot - en[slot];      // 2 * dot is exact: one rounding
+    if (score > best) { best = score; key = sub * 32 + i; }
+  }
+#pragma unroll
+  for (int off = 1; off < 8; off <<= 1) {
+    const float os = __shfl_xor(best, off, 64);
+    const int ok = __shfl_xor(key, off, 64);
+    if (os > best || (os == best && ok < key)) { best = os; key = ok; }
+  }
+  return key;
+}
+
 // ---- one LDLQ panel in one launch ---------------------------------------------------------------------------
 // For each of m rows independently, over the c / 8 column groups of the panel from the right:
 //     target_k = A_k + ( B_k + sum_{j > k} (A_j - hat_j) M[j, k] ) P_k,   (hat_k, idx_k) = nearest codeword of target_k
@@ -189,19 +251,28 @@ __global__ __launch_bounds__(256) void e8p_quantize_kernel(const float* __restri
 // increasing j by fp32 FMA (a fixed order: a row's bits depend on that row alone), the eight lanes exchange the target by
 // shuffles, search together, and each stores its own column of hat and of E.
 // LDS (dynamic): the abs table | M (c, c) | P (c / 8, 8, 8) | E as [column][row of the workgroup] (the 8 rows of a wave on 8
-// banks, the row's 8 lanes on one address).  E of a row is written and read by that row's 8 lanes only; the barrier per group
-// orders the LDS store before the next group's loads.
+// banks, the row's 8 lanes on one address) | for kStepRVQ3 the E81B entries and norms.  E of a row is written and read by that
+// row's 8 lanes only; the barrier per group orders the LDS store before the next group's loads.
+// kStep is the rounding of one group's fp32 target t (already on the row's 8 lanes):
+//   kStepE8P   hat = a = nearest E8P12 codeword of t,                                   code = code_a
+//   kStepRVQ4  r = (t - a) / s, b = nearest E8P12 codeword of r, hat = a + b * s,       code = code_a << 16 | code_b
+//   kStepRVQ3  the same with b = the dense arg max over the 256 E81B entries,           code = code_a <<  8 | idx_b
+// (s = resid_scale, a kernel argument).  kStepRVQ3 keeps the E81B table and its norms in LDS behind E (+9 KB).
 constexpr int kPanelRows = 32;
 constexpr int kPanelMaxCols = 128;
 constexpr int kPanelTableFloats = 256 * 8 + 256 + 256;
+constexpr int kResidTableFloats = 256 * 8 + 256;
+constexpr int kStepE8P = 0, kStepRVQ4 = 1, kStepRVQ3 = 2;
 
-__host__ __device__ constexpr int ldlq_panel_lds_bytes(int c) {
-  return 4 * (kPanelTableFloats + c * c + 8 * c + kPanelRows * c);
+__host__ __device__ constexpr int ldlq_panel_lds_bytes(int c, int step = kStepE8P) {
+  return 4 * (kPanelTableFloats + c * c + 8 * c + kPanelRows * c + (step == kStepRVQ3 ? kResidTableFloats : 0));
 }
 
+template <int kStep>
 __global__ __launch_bounds__(256) void ldlq_panel_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                         const float* __restrict__ M, const float* __restrict__ P,
                                                         int64_t m, int c, const uint64_t* __restrict__ grid_packed_abs,
+                                                        const float* __restrict__ resid_grid, float resid_scale,
                                                         float* __restrict__ hat, int64_t* __restrict__ idx) {
   extern __shared__ float panel_lds[];
   float (*tb)[8] = reinterpret_cast<float (*)[8]>(panel_lds);
@@ -210,7 +281,10 @@ __global__ __launch_bounds__(256) void ldlq_panel_kernel(const float* __restrict
   float* Ms = panel_lds + kPanelTableFloats;
   float* Ps = Ms + c * c;
   float* Es = Ps + 8 * c;
+  float (*eb)[8] = reinterpret_cast<float (*)[8]>(Es + kPanelRows * c);      // kStepRVQ3 only
+  float* en = Es + kPanelRows * c + 256 * 8;
   e8p_table_row(threadIdx.x, grid_packed_abs, tb, tn, tneg);
+  if constexpr (kStep == kStepRVQ3) e81b_table_row(threadIdx.x, resid_grid, eb, en);
   for (int i = threadIdx.x; i < c * c / 4; i += 256)      // c % 8 == 0, M 16-byte aligned
     reinterpret_cast<float4*>(Ms)[i] = reinterpret_cast<const float4*>(M)[i];
   if (P != nullptr)
@@ -247,14 +321,31 @@ __global__ __launch_bounds__(256) void ldlq_panel_kernel(const float* __restrict
     for (int q = 0; q < 8; ++q) xv[q] = __shfl(tgt, q, 8);
     const int key = e8p_scan<8>(xv, sub, tb, tn, tneg);
     float out[8];
-    const int code = e8p_rebuild(xv, key, tb, tneg, out);
+    int64_t code = e8p_rebuild(xv, key, tb, tneg, out);
+    if constexpr (kStep != kStepE8P) {
+      float rv[8], res[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) rv[q] = rvq_residual(xv[q], out[q], resid_scale);
+      if constexpr (kStep == kStepRVQ4) {
+        const int key_b = e8p_scan<8>(rv, sub, tb, tn, tneg);
+        code = (code << 16) | (int64_t)e8p_rebuild(rv, key_b, tb, tneg, res);
+      } else {
+        const int idx_b = e81b_scan(rv, sub, eb, en);
+        const int slot = e81b_slot(idx_b);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) res[q] = eb[slot][q];
+        code = (code << 8) | (int64_t)idx_b;
+      }
+#pragma unroll
+      for (int q = 0; q < 8; ++q) out[q] = rvq_combine(out[q], res[q], resid_scale);
+    }
     float mine = out[0];
 #pragma unroll
     for (int q = 1; q < 8; ++q) mine = (sub == q) ? out[q] : mine;
     Es[(lo + sub) * kPanelRows + r] = a_cur - mine;
     if (valid) {
       hat[row * c + lo + sub] = mine;
-      if (sub == 0) idx[row * groups + k] = (int64_t)code;
+      if (sub == 0) idx[row * groups + k] = code;
     }
     __syncthreads();
     a_cur = a_nxt;
@@ -288,11 +379,32 @@ int ldlq_panel_launch(const void* A, const void* B, const void* M, const void* P
   if (c < 8 || c % 8 != 0 || c > kPanelMaxCols) return QUIP_ERR_BAD_SHAPE;
   const int64_t blocks = (m + kPanelRows - 1) / kPanelRows;
   if (blocks > 0x7fffffff) return QUIP_ERR_BAD_SHAPE;
-  return launch<ldlq_panel_kernel>(dim3((unsigned)blocks), dim3(256), ldlq_panel_lds_bytes(c), stream,
-                                   reinterpret_cast<const float*>(A), reinterpret_cast<const float*>(B),
-                                   reinterpret_cast<const float*>(M), reinterpret_cast<const float*>(P), m, c,
-                                   reinterpret_cast<const uint64_t*>(grid_packed_abs), reinterpret_cast<float*>(hat),
-                                   reinterpret_cast<int64_t*>(idx));
+  return launch<ldlq_panel_kernel<kStepE8P>>(dim3((unsigned)blocks), dim3(256), ldlq_panel_lds_bytes(c), stream,
+                                             reinterpret_cast<const float*>(A), reinterpret_cast<const float*>(B),
+                                             reinterpret_cast<const float*>(M), reinterpret_cast<const float*>(P), m, c,
+                                             reinterpret_cast<const uint64_t*>(grid_packed_abs),
+                                             static_cast<const float*>(nullptr), 0.f, reinterpret_cast<float*>(hat),
+                                             reinterpret_cast<int64_t*>(idx));
+}
+
+// resid_grid == nullptr: the E8P12RVQ4B step; else (256, 8) fp32 E81B entries: the E8P12RVQ3B step
+int ldlq_panel_rvq_launch(const void* A, const void* B, const void* M, const void* P, int64_t m, int c,
+                          const void* grid_packed_abs, const void* resid_grid, float resid_scale, void* hat, void* idx,
+                          hipStream_t stream) {
+  if (m <= 0) return QUIP_OK;
+  if (c < 8 || c % 8 != 0 || c > kPanelMaxCols) return QUIP_ERR_BAD_SHAPE;
+  const int64_t blocks = (m + kPanelRows - 1) / kPanelRows;
+  if (blocks > 0x7fffffff) return QUIP_ERR_BAD_SHAPE;
+  auto go = [&](auto k, int step) {
+    return launch<decltype(k)::value>(dim3((unsigned)blocks), dim3(256), ldlq_panel_lds_bytes(c, step), stream,
+                                      reinterpret_cast<const float*>(A), reinterpret_cast<const float*>(B),
+                                      reinterpret_cast<const float*>(M), reinterpret_cast<const float*>(P), m, c,
+                                      reinterpret_cast<const uint64_t*>(grid_packed_abs),
+                                      reinterpret_cast<const float*>(resid_grid), resid_scale,
+                                      reinterpret_cast<float*>(hat), reinterpret_cast<int64_t*>(idx));
+  };
+  return resid_grid == nullptr ? go(kernel_c<ldlq_panel_kernel<kStepRVQ4>>, kStepRVQ4)
+                               : go(kernel_c<ldlq_panel_kernel<kStepRVQ3>>, kStepRVQ3);
 }
 
 }  // namespace quip

@@ -95,6 +95,11 @@ int e8p_quantize_launch(const void* x, int64_t nvec, const void* grid_packed_abs
 // hat fp32 (m, c), idx int64 (m, c / 8)
 int ldlq_panel_launch(const void* A, const void* B, const void* M, const void* P, int64_t m, int c,
                       const void* grid_packed_abs, void* hat, void* idx, hipStream_t stream);
+// the same with the two-stage step of the residual codebooks: resid_grid null = E8P12RVQ4B (idx = a << 16 | b), fp32 (256, 8)
+// = E8P12RVQ3B (idx = a << 8 | b); hat = a + b * resid_scale
+int ldlq_panel_rvq_launch(const void* A, const void* B, const void* M, const void* P, int64_t m, int c,
+                          const void* grid_packed_abs, const void* resid_grid, float resid_scale, void* hat, void* idx,
+                          hipStream_t stream);
 // rows mode: up to e8p_gemv_mfma_max_rows(n, k) <= 5 activation rows against one matrix in one pass
 int e8p_gemv_mfma_max_rows(int n, int k, int mode = 0);   // mode: 0 E8P12, 64 D4 / HI, 40 E8P12RVQ3B (2k virtual)
 int e8p_gemv_mfma_rows_launch(const void* planes, const void* qidxs, const void* grid, void* y, int mrows, int n,

@@ -150,10 +150,25 @@ def ldlq_fused_enabled():
     return _LDLQ_FUSED
 
 
+_LDLQ_FUSED_RVQ = None
+RVQ_PANEL_CODEBOOKS = ("E8P12RVQ4B", "E8P12RVQ3B")
+
+
+def ldlq_fused_rvq_enabled():
+    """QUIP_LDLQ_FUSED_RVQ, off unless set; read once per process"""
+    global _LDLQ_FUSED_RVQ
+    if _LDLQ_FUSED_RVQ is None:
+        _LDLQ_FUSED_RVQ = parse_ldlq_fused(os.environ.get("QUIP_LDLQ_FUSED_RVQ"), default=False)
+    return _LDLQ_FUSED_RVQ
+
+
 def ldlq_route(Wr, cb):
-    """"panels" (one GEMM + one ldlq_panel launch per panel) for the E8P12 codebook on fp32 GPU tensors unless
-    QUIP_LDLQ_FUSED=0; "stepwise" (one chain of launches per column group) for everything else"""
-    fused = getattr(cb, "id", None) == "E8P12" and Wr.is_cuda and Wr.dtype == torch.float32 and ldlq_fused_enabled()
+    """"panels" (one GEMM + one ldlq_panel launch per panel) on fp32 GPU tensors for the E8P12 codebook unless
+    QUIP_LDLQ_FUSED=0, and for E8P12RVQ4B / E8P12RVQ3B when QUIP_LDLQ_FUSED_RVQ is set as well; "stepwise" (one chain
+    of launches per column group) for everything else"""
+    cbid = getattr(cb, "id", None)
+    fused = Wr.is_cuda and Wr.dtype == torch.float32 and ldlq_fused_enabled() and (
+        cbid == "E8P12" or (cbid in RVQ_PANEL_CODEBOOKS and ldlq_fused_rvq_enabled()))
     return "panels" if fused else "stepwise"
 
 
@@ -165,7 +180,8 @@ def LDLQ(Wr, Hr, L, cb, quip_tune_iters=0, buf_cols=128):
     so that (W - hatW) L stays small.  The feedback of everything right of the current panel of `buf_cols`
     columns is one GEMM per panel (the reference's LDLQ_buffered, quant.py:138-230); `quip_tune_iters` extra
     sweeps re-round each group against the exact proxy gradient.  Returns (hatWr, Qidxs (m, n / codesz)).
-    Two routes compute this (ldlq_route): LDLQ_panels for E8P12 on the GPU, LDLQ_stepwise otherwise."""
+    Two routes compute this (ldlq_route): LDLQ_panels for E8P12 (and, behind QUIP_LDLQ_FUSED_RVQ, the two residual
+    codebooks) on the GPU, LDLQ_stepwise otherwise."""
     if ldlq_route(Wr, cb) == "panels":
         return LDLQ_panels(Wr, Hr, L, cb, quip_tune_iters, buf_cols)
     return LDLQ_stepwise(Wr, Hr, L, cb, quip_tune_iters, buf_cols)
@@ -226,9 +242,24 @@ def panel_operands(Wr, hatWr, err, Hr, Lb, Pinv, lo, hi, tune):
     return A, B, Lb[lo:hi, lo:hi].contiguous(), None
 
 
+def panel_launch(cb, device):
+    """panel_fn(A, B, M, P) -> (hat, idx int64) of the codebook's fused launch: ldlq_panel for E8P12, ldlq_panel_rvq with
+    the codebook's residual scale (and, for E8P12RVQ3B, its E81B entries as fp32) for the two residual codebooks"""
+    grid = cb.grid_packed_abs
+    if cb.id == "E8P12":
+        return lambda A, B, M, P: torch.ops.quip_lib.ldlq_panel(A, B, M, P, grid)
+    if cb.id not in RVQ_PANEL_CODEBOOKS:
+        raise ValueError(f"LDLQ_panels: no fused panel launch for codebook {cb.id}")
+    scale = float(cb.opt_resid_scale)
+    resid = None
+    if cb.id == "E8P12RVQ3B":
+        resid = cb.e81b_grid.to(device=device, dtype=torch.float32).contiguous()
+    return lambda A, B, M, P: torch.ops.quip_lib.ldlq_panel_rvq(A, B, M, P, grid, resid, scale)
+
+
 def LDLQ_panels(Wr, Hr, L, cb, quip_tune_iters=0, buf_cols=128, panel_fn=None):
-    """LDLQ for the E8P12 codebook with a whole panel of up to 128 columns rounded in one launch
-    (torch.ops.quip_lib.ldlq_panel): per panel one GEMM for the feedback of everything outside it, then, for every row
+    """LDLQ for the E8P12, E8P12RVQ4B and E8P12RVQ3B codebooks with a whole panel of up to 128 columns rounded in one
+    launch (torch.ops.quip_lib.ldlq_panel / ldlq_panel_rvq, panel_launch): per panel one GEMM for the feedback of everything outside it, then, for every row
     independently, the recursion over the panel's groups with the panel's (c, c) coupling block in LDS.  The tune
     sweep has the same shape: with A the old hatW of the panel, B = (W - hatW) H[:, panel] taken once at the start of
     the panel, M = H[panel, panel] and P_k = inv(H[kk]) (batched once per call), the error of group j inside the panel
@@ -238,8 +269,7 @@ def LDLQ_panels(Wr, Hr, L, cb, quip_tune_iters=0, buf_cols=128, panel_fn=None):
     b = cb.codesz
     assert b == 8 and n % b == 0
     if panel_fn is None:
-        grid = cb.grid_packed_abs
-        panel_fn = lambda A, B, M, P: torch.ops.quip_lib.ldlq_panel(A, B, M, P, grid)   # noqa: E731
+        panel_fn = panel_launch(cb, Wr.device)
     Lb = block_LDL(L.clone(), b)
     hatWr = torch.zeros_like(Wr)
     err = torch.zeros_like(Wr)

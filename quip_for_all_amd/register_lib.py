@@ -1099,6 +1099,46 @@ def _ldlq_panel_cuda(A, B, M, P, grid):
     return hat, idx
 
 
+def _ldlq_panel_rvq_cuda(A, B, M, P, grid, resid_grid, resid_scale):
+    """ldlq_panel with the two-stage step of the residual codebooks: resid_grid None -> E8P12RVQ4B (idx = a << 16 | b),
+    the fp32 (256, 8) E81B entries -> E8P12RVQ3B (idx = a << 8 | b); hat = a + b * fp32(resid_scale)"""
+    _need(A.is_cuda and A.dim() == 2 and A.dtype == torch.float32 and A.is_contiguous(),
+          "ldlq_panel_rvq: A must be a contiguous float32 (m, c) CUDA tensor")
+    m, c = A.shape
+    _need(c >= 8 and c % 8 == 0 and c <= LDLQ_PANEL_MAX_COLS,
+          f"ldlq_panel_rvq: c = {c} (a multiple of 8 in 8 .. {LDLQ_PANEL_MAX_COLS})")
+    _need(B.dtype == torch.float32 and B.is_contiguous() and B.device == A.device and tuple(B.shape) == (m, c),
+          "ldlq_panel_rvq: B must be contiguous float32 with A's shape on A's device")
+    _need(M.dtype == torch.float32 and M.is_contiguous() and M.device == A.device and tuple(M.shape) == (c, c),
+          "ldlq_panel_rvq: M must be contiguous float32 (c, c) on A's device")
+    _need(P is None or (P.dtype == torch.float32 and P.is_contiguous() and P.device == A.device
+                        and tuple(P.shape) == (c // 8, 8, 8)),
+          "ldlq_panel_rvq: P must be contiguous float32 (c / 8, 8, 8) on A's device, or None")
+    _need(resid_grid is None or (resid_grid.dtype == torch.float32 and resid_grid.is_contiguous()
+                                 and resid_grid.device == A.device and tuple(resid_grid.shape) == (256, 8)),
+          "ldlq_panel_rvq: resid_grid must be contiguous float32 (256, 8) on A's device, or None")
+    s = float(resid_scale)
+    _need(math.isfinite(s) and s != 0.0 and math.isfinite(ctypes.c_float(s).value) and ctypes.c_float(s).value != 0.0,
+          f"ldlq_panel_rvq: resid_scale = {resid_scale} must be finite and non-zero in float32")
+    g = _grid_i64(grid, A)
+    hat = torch.empty_like(A)
+    idx = _empty((m, c // 8), dtype=torch.int64, device=A.device)
+    with torch.cuda.device(A.device):
+        capi.check(capi.lib().quip_ldlq_panel_rvq_f32(A.data_ptr(), B.data_ptr(), M.data_ptr(), _ptr(P), m, c, g.data_ptr(),
+                                                      _ptr(resid_grid), s, hat.data_ptr(), idx.data_ptr(), _stream(A)),
+                   "quip_ldlq_panel_rvq_f32")
+    return hat, idx
+
+
+try:
+    _lib.define("ldlq_panel_rvq(Tensor A, Tensor B, Tensor M, Tensor? P, Tensor grid, Tensor? resid_grid, "
+                "float resid_scale) -> (Tensor hat, Tensor idx)")
+    _lib.impl("ldlq_panel_rvq", _ldlq_panel_rvq_cuda, "CUDA")
+    _reg_fake("ldlq_panel_rvq", lambda A, B, M, P, grid, resid_grid, resid_scale:
+              (torch.empty_like(A), A.new_empty((A.shape[0], A.shape[1] // 8), dtype=torch.int64)))
+except RuntimeError:
+    pass
+
 try:
     _lib.define("ldlq_panel(Tensor A, Tensor B, Tensor M, Tensor? P, Tensor grid) -> (Tensor, Tensor)")
     _lib.impl("ldlq_panel", _ldlq_panel_cuda, "CUDA")

@@ -3,8 +3,10 @@
 per panel) and the stepwise route (QUIP_LDLQ_FUSED=0: one chain of launches per 8 columns) alternating in one process; wall
 time of the whole call and of LDLQ inside it, medians of `--rounds` rounds with their spreads.  Then one 7B-shaped decoder
 block (random fp16 weights) through QuipQuantizer.quantize_model on both routes.  One JSON line per measurement.
+--codebook E8P12RVQ4B / E8P12RVQ3B measures the same for a residual codebook, whose fused route (ldlq_panel_rvq) sits behind
+QUIP_LDLQ_FUSED_RVQ: the tool sets the route per call, so the stepwise route it alternates with is what LDLQ does by default.
 
-    python tools/ldlq_bench.py [--rounds 3] [--tokens 2048] [--block-iters 10] [--skip-block] [--out FILE]"""
+    python tools/ldlq_bench.py [--codebook E8P12] [--rounds 3] [--tokens 2048] [--block-iters 10] [--skip-block] [--out FILE]"""
 import argparse
 import json
 import os
@@ -19,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--codebook", default="E8P12", choices=["E8P12", "E8P12RVQ4B", "E8P12RVQ3B"])
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--tokens", type=int, default=2048)
     ap.add_argument("--block-iters", type=int, default=10)
@@ -52,9 +55,16 @@ def main():
         ldlq_s.append(time.perf_counter() - t0)
         return r
     quip.LDLQ = timed_ldlq
-    emit(dict(device=torch.cuda.get_device_name(0), codebook="E8P12", calibration_tokens=args.tokens, rounds=args.rounds,
+
+    def set_route(route):
+        """the process-wide switches quant.ldlq_route reads, set as their environment variables would set them"""
+        if args.codebook == "E8P12":
+            quant._LDLQ_FUSED = route == "fused"
+        else:
+            quant._LDLQ_FUSED, quant._LDLQ_FUSED_RVQ = True, route == "fused"
+    emit(dict(device=torch.cuda.get_device_name(0), codebook=args.codebook, calibration_tokens=args.tokens, rounds=args.rounds,
               timing="host wall clock around synchronised calls; routes alternate inside every round"))
-    cb = Q.codebook.codebook_id["E8P12"](inference=False).to(dev)
+    cb = Q.codebook.codebook_id[args.codebook](inference=False).to(dev)
     for shape in args.shapes.split(","):
         fin, fout = (int(v) for v in shape.split("x"))
         torch.manual_seed(fin + fout)
@@ -71,7 +81,8 @@ def main():
             rel = {}
             for rnd in range(args.rounds + 1):                       # round 0 warms both routes up and is dropped
                 for route in ("fused", "stepwise"):
-                    quant._LDLQ_FUSED = route == "fused"
+                    set_route(route)
+                    assert quant.ldlq_route(W0.float(), cb) == ("panels" if route == "fused" else "stepwise")
                     lin.weight.data.copy_(W0)
                     torch.manual_seed(7)
                     del ldlq_s[:]
@@ -109,9 +120,9 @@ def main():
         rec = dict(block="Llama-2-7B-shaped, 1 layer, random fp16 weights", calibration="8 x 512 random tokens, batch_size 4",
                    quip_tune_iters=args.block_iters, what="QuipQuantizer.quantize_model, whole call, once per route")
         for route in ("fused", "stepwise"):
-            quant._LDLQ_FUSED = route == "fused"
+            set_route(route)
             model = copy.deepcopy(base)
-            qz = QuipQuantizer(codebook="E8P12", dataset=data, nsamples=8, model_seqlen=512, batch_size=4,
+            qz = QuipQuantizer(codebook=args.codebook, dataset=data, nsamples=8, model_seqlen=512, batch_size=4,
                                quip_tune_iters=args.block_iters, ft_epochs=0)
             del ldlq_s[:]
             torch.cuda.synchronize()
@@ -126,7 +137,7 @@ def main():
         rec["quantize_model_speedup"] = round(rec["stepwise"]["quantize_model_s"] / rec["fused"]["quantize_model_s"], 2)
         emit(rec)
     quip.LDLQ = ldlq0
-    quant._LDLQ_FUSED = None
+    quant._LDLQ_FUSED = quant._LDLQ_FUSED_RVQ = None
     if out:
         out.close()
 
