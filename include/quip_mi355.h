@@ -76,8 +76,11 @@ int quip_hadamard(const void* x, void* y, int64_t rows, int32_t n, float scale, 
  * Replace quiptools_cuda.{e8p,e8prvq3,e8prvq4,d4,hi}_mm_origorder
  * (quiptools_wrapper.cpp:88-92; origin_order.cu:557-788).  The reference
  * allocates and returns C; here the caller passes y (m, n) fp16.
- * Requirements: k % 8 == 0 (E8P*, HI), k % 32 == 0 (E8P12RVQ3B), k % 4 == 0 (D4);
- * m >= 1 (any m is accepted; the codebook modules call this for m < 32). */
+ * Requirements: k % 8 == 0 (E8P12, E8P12RVQ4B, D4, HI), k % 32 == 0 (E8P12RVQ3B);
+ * m >= 1 (any m is accepted; the codebook modules call this for m < 32).
+ * Checked in this order by all five: the tables, x, qidxs and y are there (QUIP_ERR_NULL_POINTER); m >= 0, n >= 0, k > 0
+ * and k's multiple (QUIP_ERR_BAD_SHAPE); m == 0 or n == 0: QUIP_OK, nothing is launched; x 16-byte aligned
+ * (QUIP_ERR_MISALIGNED; no other pointer's alignment is looked at). */
 int quip_e8p_mm_origorder(const void* x, const void* qidxs /* int16 (n, k/8) */,
                           const void* grid_packed_abs /* int64[256] */, void* y,
                           int32_t m, int32_t n, int32_t k, quip_stream_t stream);
@@ -87,7 +90,10 @@ int quip_e8p_mm_origorder(const void* x, const void* qidxs /* int16 (n, k/8) */,
  * rows in the same launch (one pass over the codes per chunk; faster than quip_e8p_mm_batched up to m * n of about
  * 1.8e6).  Not bit identical to the exact integer path of quip_e8p_mm_origorder_ws / quip_e8p_gemv_planes_rows (which
  * stays available); a row's result does not depend on the other rows of the batch.  k % 128 == 0, n % 2 == 0, else
- * QUIP_ERR_UNSUPPORTED. */
+ * QUIP_ERR_UNSUPPORTED.
+ * Checked in this order by all five skinny entries: x, qidxs, y and the tables are there (QUIP_ERR_NULL_POINTER); m >= 0,
+ * n >= 1, k >= 8 (QUIP_ERR_BAD_SHAPE); m == 0: QUIP_OK before any alignment is looked at; x and the codes 16-byte aligned
+ * (E8P12RVQ3B's 3-byte codes: 4), y 4-byte, every table 8-byte (QUIP_ERR_MISALIGNED); then the shape rules. */
 int quip_e8p_mm_skinny(const void* x, const void* qidxs /* int16 (n, k/8) */, const void* grid_packed_abs, void* y,
                        int32_t m, int32_t n, int32_t k, quip_stream_t stream);
 /* The same for E8P12RVQ4B (replaces the 1 < M < 32 use of tinygemm_m16n8k16_chunk_kernel<.., BLayout_E8RVQ4, ..>,
@@ -116,7 +122,10 @@ int quip_e8p_mm_batched(const void* x, const void* qidxs /* int16 (n, k/8) */, c
  * decompress_* + `x @ W.T` (e8p12_rvq4.py:50-67, e8p12_rvq3.py:109-129, d4.py:128-139, hi.py:52-63), computed on the
  * exact fp16 weights those decompress ops write (E8P12RVQ4B / 3B: fma(resid_scale, w_residual, w_main), one fp16 rounding
  * per weight, origin_order.cu:330-331,378-380), without materialising W.  Code layouts and tables as for the *_mm_skinny
- * entry points above; same shape rules as quip_e8p_mm_batched. */
+ * entry points above; same shape rules as quip_e8p_mm_batched.
+ * Checked in this order by the five batched entries: NULL pointers; m >= 0, n >= 1, k >= 8 (QUIP_ERR_BAD_SHAPE); x, the
+ * codes and y 16-byte aligned, grid_packed_abs / grid_f16 8-byte, e81b_packed 4-byte (QUIP_ERR_MISALIGNED); m == 0: QUIP_OK;
+ * then the shape rules.  quip_e8p_mm_batched alone accepts m == 0 before it looks at the alignment. */
 int quip_e8prvq4_mm_batched(const void* x, const void* qidxs /* int32 (n, k/8) */, const void* grid_packed_abs,
                             float resid_scale, void* y, int64_t m, int32_t n, int32_t k, quip_stream_t stream);
 int quip_e8prvq3_mm_batched(const void* x, const void* qidxs /* 3 k / 8 bytes per row */, const void* grid_packed_abs,
@@ -141,7 +150,9 @@ int quip_e8p_mm_origorder_ws(const void* x, const void* qidxs, const void* grid_
                              size_t workspace_bytes, quip_stream_t stream);
 /* The two halves of the above, for callers that produce the planes themselves (the fused
  * Hadamard kernel does): planes buffer = quip_e8p_planes_bytes(k) bytes, 16-byte aligned;
- * layout documented in csrc/e8p_gemv_i8.hip.  k % 64 == 0. */
+ * layout documented in csrc/e8p_gemv_i8.hip.  k % 64 == 0.  quip_e8p_gemv_planes: planes and codes 16-byte,
+ * grid_packed_abs 64-byte aligned, answered before k is looked at; n == 0 is QUIP_OK once no pointer is NULL
+ * (quip_e8p_gemv_planes_ws answers n == 0 before it looks at anything else). */
 size_t quip_e8p_planes_bytes(int32_t k);
 int quip_e8p_x_to_planes(const void* x /* fp16[k] */, void* planes, int32_t k, quip_stream_t stream);
 int quip_e8p_gemv_planes(const void* planes, const void* qidxs, const void* grid_packed_abs,
@@ -165,7 +176,8 @@ int quip_hi_mm_origorder(const void* x, const void* qidxs /* int32 (n, k/8) */, 
  * Replace quiptools_cuda.decompress_{e8p,e8prvq3,e8prvq4,d4,hi}_origorder
  * (quiptools_wrapper.cpp:93-97; origin_order.cu:794-1074): dense fp16
  * W (rows, cols_out) written into caller-allocated `w`, `cols_out` = number of
- * weights per row (k). */
+ * weights per row (k).  Checked in this order: the tables, qidxs and w are there; rows >= 0, k > 0, k % 8 == 0
+ * (E8P12RVQ3B: k % 32 == 0); rows == 0: QUIP_OK, nothing is launched; w 16-byte aligned. */
 int quip_decompress_e8p_origorder(const void* qidxs, const void* grid_packed_abs, void* w,
                                   int64_t rows, int32_t k, quip_stream_t stream);
 int quip_decompress_e8prvq3_origorder(const void* qidxs, const void* grid_packed_abs,
@@ -338,7 +350,7 @@ int quip_ldlq_panel_rvq_f32(const void* A, const void* B, const void* M, const v
                             const void* grid_packed_abs, const void* resid_grid, float resid_scale, void* hat, void* idx,
                             quip_stream_t stream);
 
-/* Rows mode for the other table modes of the same kernel.  mode 0: E8P12 (== quip_e8p_gemv_planes_rows);
+/* Rows mode for the other table modes of the same kernel.  mode 0: E8P12 (quip_e8p_gemv_planes_rows is this call);
  * mode 64: D4 (qidxs uint8 (n, k/4), grid = fp16 (256, 4) table; HI through its virtual 2k layout, see
  * quip_had_problem.planes_layout); mode 40: E8P12RVQ3B (qidxs = the checkpoint's 3-byte codes, read as 2k virtual
  * weights -- pass k = 2 * in features --, grid = grid_packed_abs, grid2 = e81b_i8, see
@@ -374,7 +386,8 @@ int quip_d4_gemv_planes_group(const void* const* planes, const void* const* qidx
                               quip_stream_t stream);
 /* ... with the zeroed workspace of quip_e8p_gemv_workspace_bytes(sum of ns): rows longer than 28672 (HI's virtual rows at the
  * Llama-2-70B down_proj width, 2 k = 57344) go to the K-splitting kernel in its D4 table mode; grid_f16 64-byte aligned there. */
-/* (the K-splitting kernel's D4 table mode on any shape it takes, k % 128 == 0: for A/B tests against the first kernel) */
+/* (the K-splitting kernel's D4 table mode on any shape it takes, k % 128 == 0: for A/B tests against the first kernel; it
+ * answers n and k before the alignment of planes, codes and workspace, where the entries above answer the alignment first) */
 int quip_d4_gemv_planes_v2(const void* planes, const void* qidxs, const void* grid_f16, void* y, int32_t n, int32_t k,
                            void* workspace, size_t workspace_bytes, quip_stream_t stream);
 int quip_d4_gemv_planes_group_ws(const void* const* planes, const void* const* qidxs, const void* grid_f16,

@@ -63,14 +63,91 @@ int env_int(const char* name, int dflt) {
 
 static inline bool aligned64(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 63u) == 0; }
 
-static int mm_common(CodebookId cb, const void* x, const void* q, const CodebookArgs& a, void* y,
-                     int m, int n, int k, int kdiv, hipStream_t s) {
-  if (!x || !q || !y) return QUIP_ERR_NULL_POINTER;
-  if (m < 0 || n < 0 || k <= 0 || k % kdiv != 0 || k % 8 != 0) return QUIP_ERR_BAD_SHAPE;
+// pointer lists of an entry point's prologue
+namespace {
+using Ptrs = std::initializer_list<const void*>;
+bool any_null(Ptrs ps) {
+  for (const void* p : ps)
+    if (!p) return true;
+  return false;
+}
+bool any_off(Ptrs ps, uintptr_t mask) {
+  for (const void* p : ps)
+    if (reinterpret_cast<uintptr_t>(p) & mask) return true;
+  return false;
+}
+
+// ---- the products of the five codebooks ----------------------------------------------------------------------------------
+// Four families serve the 20 per-codebook entries: original order (generic_mm_launch), skinny (skinny_gemm_launch), batched
+// (prefill_gemm_launch) and decompress (decompress_launch).  An entry fills CodebookArgs and calls its family with its
+// CodebookId; what a family asks of a codebook stands in this table, indexed by CodebookId.  What the families answer, and
+// in which order, is pinned row by row in tests/golden/product_refusals.json.
+struct ProductChecks {
+  bool grid, grid2;             // the tables the codebook needs (NULL: QUIP_ERR_NULL_POINTER)
+  int kdiv;                     // original order and decompress: k % kdiv (E8P12RVQ3B: rows of 3 k / 8 bytes, dword aligned)
+  uintptr_t skinny_q_mask;      // skinny: alignment - 1 of the codes (the 3-byte codes: 4 bytes, else 16)
+  // The packed E81B table is asked to be 8-byte aligned by the skinny family (as every table there) and 4-byte aligned by
+  // the batched one (uint32 entries).  Both are ABI as recorded; DESIGN 9 item 12.
+  uintptr_t skinny_grid2_mask, batched_grid2_mask;
+  // quip_e8p_mm_batched accepts m == 0 before it looks at any alignment, as the skinny family does; the other four batched
+  // entries look at the alignment first and accept m == 0 last.  ABI as recorded; DESIGN 9 item 12.
+  bool batched_empty_first;
+};
+constexpr ProductChecks kProduct[5] = {
+    /* kE8P     */ {true, false, 8, 15, 0, 0, true},
+    /* kE8PRVQ3 */ {true, true, 32, 3, 7, 3, false},
+    /* kE8PRVQ4 */ {true, false, 8, 15, 0, 0, false},
+    /* kD4      */ {true, false, 8, 15, 0, 0, false},
+    /* kHI      */ {false, false, 8, 15, 0, 0, false},
+};
+bool tables_null(const ProductChecks& c, const CodebookArgs& a) { return (c.grid && !a.grid) || (c.grid2 && !a.grid2); }
+
+// original order: the tables, then x / qidxs / y, the shape, the empty product, x 16-byte aligned (nobody looks at the rest)
+int mm_origorder(CodebookId cb, const void* x, const void* q, const CodebookArgs& a, void* y, int m, int n, int k,
+                 quip_stream_t s) {
+  const ProductChecks& c = kProduct[cb];
+  if (tables_null(c, a) || any_null({x, q, y})) return QUIP_ERR_NULL_POINTER;
+  if (m < 0 || n < 0 || k <= 0 || k % c.kdiv != 0 || k % 8 != 0) return QUIP_ERR_BAD_SHAPE;
   if (m == 0 || n == 0) return QUIP_OK;
   if (!aligned16(x)) return QUIP_ERR_MISALIGNED;
-  return generic_mm_launch(cb, x, q, a, y, m, n, k, s);
+  return generic_mm_launch(cb, x, q, a, y, m, n, k, (hipStream_t)s);
 }
+
+int decompress_origorder(CodebookId cb, const void* q, const CodebookArgs& a, void* w, int64_t rows, int k, quip_stream_t s) {
+  const ProductChecks& c = kProduct[cb];
+  if (tables_null(c, a) || any_null({q, w})) return QUIP_ERR_NULL_POINTER;
+  if (rows < 0 || k <= 0 || k % c.kdiv != 0 || k % 8 != 0) return QUIP_ERR_BAD_SHAPE;
+  if (rows == 0) return QUIP_OK;
+  if (!aligned16(w)) return QUIP_ERR_MISALIGNED;
+  return decompress_launch(cb, q, a, w, rows, k, (hipStream_t)s);
+}
+
+// skinny (e8p_skinny_gemm.hip): x and the codes 16-byte aligned (the 3-byte codes: 4), y 4-byte, every table 8-byte; m == 0
+// is accepted before the alignment is looked at (the caller returns, no launch)
+int mm_skinny(CodebookId cb, const void* x, const void* q, const CodebookArgs& a, void* y, int m, int n, int k,
+              quip_stream_t s) {
+  const ProductChecks& c = kProduct[cb];
+  if (any_null({x, q, y}) || tables_null(c, a)) return QUIP_ERR_NULL_POINTER;
+  if (m < 0 || n < 1 || k < 8) return QUIP_ERR_BAD_SHAPE;
+  if (m == 0) return QUIP_OK;
+  if (any_off({x}, 15) || any_off({q}, c.skinny_q_mask) || any_off({y}, 3) || any_off({a.grid}, 7) ||
+      any_off({a.grid2}, c.skinny_grid2_mask))
+    return QUIP_ERR_MISALIGNED;
+  return skinny_gemm_launch(cb, x, q, a, y, m, n, k, (hipStream_t)s);
+}
+
+// batched (e8p_prefill_gemm.hip): x, the codes and y 16-byte aligned, the E8P / D4 table 8-byte
+int mm_batched(CodebookId cb, const void* x, const void* q, const CodebookArgs& a, void* y, int64_t m, int n, int k,
+               quip_stream_t s) {
+  const ProductChecks& c = kProduct[cb];
+  if (tables_null(c, a) || any_null({x, q, y})) return QUIP_ERR_NULL_POINTER;
+  if (m < 0 || n < 1 || k < 8) return QUIP_ERR_BAD_SHAPE;
+  if (c.batched_empty_first && m == 0) return QUIP_OK;
+  if (any_off({x, q, y}, 15) || any_off({a.grid}, 7) || any_off({a.grid2}, c.batched_grid2_mask)) return QUIP_ERR_MISALIGNED;
+  if (m == 0) return QUIP_OK;
+  return prefill_gemm_launch(cb, x, q, a, y, m, n, k, (hipStream_t)s);
+}
+}  // namespace
 
 // ---- the stand-alone bs=1 GEMV -----------------------------------------------------------------------------------------
 // Three kernels serve it: the first (e8p_gemv_mfma.hip: one-shot loads on 8 waves) and the K-splitting kernel
@@ -195,6 +272,25 @@ int gemv_launch(const GemvMode& mode, const void* const* planes, const void* con
   }
   return rc;
 }
+
+// the tuning hooks' loose arguments (0: automatic) as the launchers' record
+GemvTune tune_of(int rep, int rows, int blocks, int waves_g, int max_waves, int digits, void* dbg) {
+  GemvTune t;
+  t.rep = rep; t.rows = rows; t.blocks = blocks; t.waves_g = waves_g; t.max_waves = max_waves; t.digits = digits; t.dbg = dbg;
+  return t;
+}
+
+// the public record of a fused GEMV's input side as the launcher's, the per-problem members for `count` problems
+GemvFusedIn fused_in_of(const quip_gemv_fused_in* in, int count) {
+  GemvFusedIn f;
+  f.x = in->x; f.z = in->z; f.post = in->post_scale; f.residual = in->residual; f.h_out = in->h_out;
+  f.rms_w = in->rms_weight; f.z_scale = in->z_scale; f.rms_eps = in->rms_eps;
+  for (int i = 0; i < count && i < QUIP_MAX_GROUP; ++i) {
+    f.pre[i] = in->pre_scale[i];
+    f.scale[i] = in->scale[i];
+  }
+  return f;
+}
 }  // namespace
 
 }  // namespace quip
@@ -239,20 +335,7 @@ int quip_debug_occupy(int32_t nwg, int32_t lds_bytes, int64_t ticks, void* sink,
   return launch<occupy_kernel>(dim3(nwg), dim3(64), lds_bytes, (hipStream_t)stream, (long long)ticks, reinterpret_cast<unsigned*>(sink));
 }
 
-// pointer lists of an entry point's prologue (the transform entries here, the attention entries below)
 namespace {
-using Ptrs = std::initializer_list<const void*>;
-bool any_null(Ptrs ps) {
-  for (const void* p : ps)
-    if (!p) return true;
-  return false;
-}
-bool any_off(Ptrs ps, uintptr_t mask) {
-  for (const void* p : ps)
-    if (reinterpret_cast<uintptr_t>(p) & mask) return true;
-  return false;
-}
-
 // ---- the Hadamard transform entry points ---------------------------------------------------------------------------------
 // Inside the library a problem is the public quip_had_problem, and every entry ends in had_transform_group_launch
 // (hadamard.hip), which answers the sizes, the chain and the optional pointers.  What an entry looks at first is ABI and
@@ -395,10 +478,7 @@ int32_t quip_e8p_gemv_max_rows(int32_t n, int32_t k) { return (n > 0 && k > 0) ?
 
 int quip_e8p_gemv_planes_rows(const void* planes, const void* qidxs, const void* grid_packed_abs, void* y,
                               int32_t rows, int32_t n, int32_t k, quip_stream_t stream) {
-  if (!planes || !qidxs || !grid_packed_abs || !y) return QUIP_ERR_NULL_POINTER;
-  if (rows < 1 || n < 1 || k < 1 || k % 8 != 0) return QUIP_ERR_BAD_SHAPE;
-  if (!aligned16(planes) || !aligned16(qidxs)) return QUIP_ERR_MISALIGNED;
-  return e8p_gemv_mfma_rows_launch(planes, qidxs, grid_packed_abs, y, rows, n, k, GemvTune{}, (hipStream_t)stream);
+  return quip_gemv_planes_rows_mode(planes, qidxs, grid_packed_abs, nullptr, y, rows, n, k, 0, stream);
 }
 
 // rows mode with another table mode: 64 = D4 table (fp16 (256, 4) grid; HI through its virtual layout),
@@ -409,11 +489,11 @@ int32_t quip_gemv_max_rows_mode(int32_t n, int32_t k, int32_t mode) {
 
 int quip_gemv_planes_rows_mode(const void* planes, const void* qidxs, const void* grid, const void* grid2, void* y,
                                int32_t rows, int32_t n, int32_t k, int32_t mode, quip_stream_t stream) {
-  if (!planes || !qidxs || !grid || !y) return QUIP_ERR_NULL_POINTER;
+  if (any_null({planes, qidxs, grid, y})) return QUIP_ERR_NULL_POINTER;
   if (rows < 1 || n < 1 || k < 1 || k % 8 != 0) return QUIP_ERR_BAD_SHAPE;
   if (mode != 0 && mode != 64 && mode != 40) return QUIP_ERR_BAD_SHAPE;
   if (mode == 40 && k % 64 != 0) return QUIP_ERR_BAD_SHAPE;   // rows of 3 (k / 2) / 8 bytes, dword aligned
-  if (!aligned16(planes) || !aligned16(qidxs)) return QUIP_ERR_MISALIGNED;
+  if (any_off({planes, qidxs}, 15)) return QUIP_ERR_MISALIGNED;
   GemvTune t;
   t.rep = mode;
   t.grid2 = grid2;
@@ -489,12 +569,15 @@ int quip_d4_gemv_planes_group(const void* const* planes, const void* const* qidx
 
 int quip_d4_gemv_planes_v2(const void* planes, const void* qidxs, const void* grid_f16, void* y, int32_t n, int32_t k,
                            void* workspace, size_t workspace_bytes, quip_stream_t stream) {
-  if (!planes || !qidxs || !grid_f16 || !y) return QUIP_ERR_NULL_POINTER;
-  if (n < 1 || k < 1 || k % 8 != 0) return QUIP_ERR_BAD_SHAPE;
-  if (!aligned16(planes) || !aligned16(qidxs) || (workspace && !aligned16(workspace))) return QUIP_ERR_MISALIGNED;
-  if (workspace && workspace_bytes < e8p_gemv_v2_workspace_words(n) * 4) workspace = nullptr;
+  // The K-splitting kernel whatever gemv_plan would choose, so not through gemv_launch; its checks are gemv_launch's for
+  // one problem in another order -- the shape before the alignment (gemv_launch: per problem the alignment, then n, then
+  // k) -- and the table's alignment is the kernel's business.  ABI as recorded; DESIGN 9 item 12.
+  if (any_null({planes, qidxs, grid_f16, y})) return QUIP_ERR_NULL_POINTER;
+  if (n < 1 || k < 1 || k % kGemvD4.k_multiple != 0) return QUIP_ERR_BAD_SHAPE;
+  if (any_off({planes, workspace}, 15) || any_off({qidxs}, kGemvD4.q_mask)) return QUIP_ERR_MISALIGNED;
+  if (workspace_bytes < e8p_gemv_v2_workspace_words(n) * 4) workspace = nullptr;
   GemvTune t;
-  t.rep = 64;
+  t.rep = kGemvD4.rep;
   return e8p_gemv_v2_group_launch(&planes, &qidxs, grid_f16, &y, workspace, &n, 1, k, t, (hipStream_t)stream);
 }
 
@@ -509,22 +592,16 @@ int quip_e8p_gemv_fused(const quip_gemv_fused_in* in, const void* const* qidxs,
                         int32_t count, int32_t k, quip_stream_t stream) {
   if (!in || !qidxs || !grid_packed_abs || !ys || !ns) return QUIP_ERR_NULL_POINTER;
   if (count < 1 || count > QUIP_MAX_GROUP) return QUIP_ERR_BAD_SHAPE;
-  GemvFusedIn f;
-  f.x = in->x; f.z = in->z; f.post = in->post_scale; f.residual = in->residual; f.h_out = in->h_out;
-  f.rms_w = in->rms_weight; f.z_scale = in->z_scale; f.rms_eps = in->rms_eps;
+  const GemvFusedIn f = fused_in_of(in, count);
   if (!f.z && !f.x) return QUIP_ERR_NULL_POINTER;
   if (f.z && (!f.post || !f.h_out)) return QUIP_ERR_NULL_POINTER;
   if (f.z && f.h_out == f.residual) return QUIP_ERR_BAD_SHAPE;
-  if (!aligned16(f.x) || !aligned16(f.z) || !aligned16(f.post) || !aligned16(f.residual) || !aligned16(f.h_out) ||
-      !aligned16(f.rms_w))
-    return QUIP_ERR_MISALIGNED;
+  if (any_off({f.x, f.z, f.post, f.residual, f.h_out, f.rms_w}, 15)) return QUIP_ERR_MISALIGNED;
   int n32[QUIP_MAX_GROUP];
   for (int i = 0; i < count; ++i) {
-    if (!qidxs[i] || !ys[i] || !in->pre_scale[i]) return QUIP_ERR_NULL_POINTER;
-    if (!aligned16(qidxs[i]) || !aligned16(in->pre_scale[i])) return QUIP_ERR_MISALIGNED;
+    if (any_null({qidxs[i], ys[i], f.pre[i]})) return QUIP_ERR_NULL_POINTER;
+    if (any_off({qidxs[i], f.pre[i]}, 15)) return QUIP_ERR_MISALIGNED;
     if (ns[i] < 1) return QUIP_ERR_BAD_SHAPE;
-    f.pre[i] = in->pre_scale[i];
-    f.scale[i] = in->scale[i];
     n32[i] = ns[i];
   }
   return e8p_gemv_mfma_fused_launch(f, qidxs, grid_packed_abs, ys, n32, count, k, GemvTune{}, (hipStream_t)stream);
@@ -1002,17 +1079,16 @@ int quip_rope_attn_decode_z_window_f16(const void* const* z, const void* const* 
                                    {1, heads, kv_heads, head_dim, max_len, window, scale}, (hipStream_t)stream, workspace);
 }
 
+// ---- the products: an entry is its argument list, its CodebookArgs and one call of its family ---------------------------
+// E8P12 has two fast paths above the original-order family: one row on the VALU integer GEMV, and (_ws) fewer than 32 rows
+// through digit planes and rows mode on the matrix cores.  Either is taken only where every argument it needs is there and
+// aligned; everything else, and every refusal, is the family's.
 int quip_e8p_mm_origorder(const void* x, const void* qidxs, const void* grid, void* y, int32_t m,
                           int32_t n, int32_t k, quip_stream_t stream) {
-  if (!grid) return QUIP_ERR_NULL_POINTER;
-  if (x && qidxs && y && m == 1 && n > 0 && e8p_gemv_i8_supported(n, k) && aligned16(x) &&
-      aligned16(qidxs))
+  if (!any_null({grid, x, qidxs, y}) && m == 1 && n > 0 && e8p_gemv_i8_supported(n, k) && !any_off({x, qidxs}, 15))
     return e8p_gemv_i8_launch(x, 1, qidxs, grid, y, n, k, GemvTune{}, (hipStream_t)stream);
-  CodebookArgs a;
-  a.grid = grid;
-  return mm_common(kE8P, x, qidxs, a, y, m, n, k, 8, (hipStream_t)stream);
+  return mm_origorder(kE8P, x, qidxs, {grid}, y, m, n, k, stream);
 }
-
 
 size_t quip_e8p_planes_bytes(int32_t k) { return k > 0 ? e8p_gemv_mfma_planes_bytes(k) : 0; }
 
@@ -1021,121 +1097,75 @@ size_t quip_e8p_mm_workspace_bytes(int32_t m, int32_t n, int32_t k) {
 }
 
 int quip_e8p_x_to_planes(const void* x, void* planes, int32_t k, quip_stream_t stream) {
-  if (!x || !planes) return QUIP_ERR_NULL_POINTER;
-  if (!aligned16(x) || !aligned16(planes)) return QUIP_ERR_MISALIGNED;
+  if (any_null({x, planes})) return QUIP_ERR_NULL_POINTER;
+  if (any_off({x, planes}, 15)) return QUIP_ERR_MISALIGNED;
   return x_to_planes_linear_launch(x, planes, k, (hipStream_t)stream);
 }
 
+// (the one GEMV entry that answers the alignment -- the table's 64 bytes too -- before gemv_launch looks at k, and n == 0
+//  behind the NULL check, where quip_e8p_gemv_planes_ws answers n == 0 before everything: ABI as recorded)
 int quip_e8p_gemv_planes(const void* planes, const void* qidxs, const void* grid, void* y, int32_t n,
                          int32_t k, quip_stream_t stream) {
-  if (!planes || !qidxs || !grid || !y) return QUIP_ERR_NULL_POINTER;
+  if (any_null({planes, qidxs, grid, y})) return QUIP_ERR_NULL_POINTER;
   if (n < 0) return QUIP_ERR_BAD_SHAPE;
   if (n == 0) return QUIP_OK;
-  if (!aligned16(planes) || !aligned16(qidxs) || !aligned64(grid)) return QUIP_ERR_MISALIGNED;
+  if (any_off({planes, qidxs}, 15) || any_off({grid}, kGemvE8P.grid_mask)) return QUIP_ERR_MISALIGNED;
   return gemv_launch(kGemvE8P, &planes, &qidxs, grid, nullptr, &y, &n, 1, k, nullptr, 0, stream);
-}
-
-// the skinny products (e8p_skinny_gemm.hip): x and the codes 16-byte aligned (E8P12RVQ3B's 3-byte codes: 4), y 4-byte, every
-// table 8-byte; m == 0 is accepted before the alignment is looked at (the caller returns, no launch)
-static int skinny_args_ok(const void* x, const void* qidxs, std::initializer_list<const void*> tables, const void* y,
-                          int32_t m, int32_t n, int32_t k, uintptr_t q_mask = 15u) {
-  if (!x || !qidxs || !y) return QUIP_ERR_NULL_POINTER;
-  for (const void* t : tables)
-    if (!t) return QUIP_ERR_NULL_POINTER;
-  if (m < 0 || n < 1 || k < 8) return QUIP_ERR_BAD_SHAPE;
-  if (m == 0) return QUIP_OK;
-  if (!aligned16(x) || (reinterpret_cast<uintptr_t>(qidxs) & q_mask) || (reinterpret_cast<uintptr_t>(y) & 3u))
-    return QUIP_ERR_MISALIGNED;
-  for (const void* t : tables)
-    if (reinterpret_cast<uintptr_t>(t) & 7u) return QUIP_ERR_MISALIGNED;
-  return QUIP_OK;
 }
 
 int quip_e8p_mm_skinny(const void* x, const void* qidxs, const void* grid, void* y, int32_t m, int32_t n, int32_t k,
                        quip_stream_t stream) {
-  if (const int st = skinny_args_ok(x, qidxs, {grid}, y, m, n, k); st != QUIP_OK || m == 0) return st;
-  return e8p_skinny_gemm_launch(x, qidxs, grid, y, m, n, k, (hipStream_t)stream);
+  return mm_skinny(kE8P, x, qidxs, {grid}, y, m, n, k, stream);
 }
 
 int quip_e8prvq4_mm_skinny(const void* x, const void* qidxs, const void* grid, float resid_scale, void* y, int32_t m,
                            int32_t n, int32_t k, quip_stream_t stream) {
-  if (const int st = skinny_args_ok(x, qidxs, {grid}, y, m, n, k); st != QUIP_OK || m == 0) return st;
-  return e8prvq4_skinny_gemm_launch(x, qidxs, grid, resid_scale, y, m, n, k, (hipStream_t)stream);
+  return mm_skinny(kE8PRVQ4, x, qidxs, {grid, nullptr, resid_scale}, y, m, n, k, stream);
 }
 
 int quip_e8prvq3_mm_skinny(const void* x, const void* qidxs, const void* grid, const void* e81b_packed, float resid_scale,
                            void* y, int32_t m, int32_t n, int32_t k, quip_stream_t stream) {
-  if (const int st = skinny_args_ok(x, qidxs, {grid, e81b_packed}, y, m, n, k, 3u); st != QUIP_OK || m == 0) return st;
-  return e8prvq3_skinny_gemm_launch(x, qidxs, grid, e81b_packed, resid_scale, y, m, n, k, (hipStream_t)stream);
+  return mm_skinny(kE8PRVQ3, x, qidxs, {grid, e81b_packed, resid_scale}, y, m, n, k, stream);
 }
 
 int quip_d4_mm_skinny(const void* x, const void* qidxs, const void* grid_f16, void* y, int32_t m, int32_t n, int32_t k,
                       quip_stream_t stream) {
-  if (const int st = skinny_args_ok(x, qidxs, {grid_f16}, y, m, n, k); st != QUIP_OK || m == 0) return st;
-  return d4_skinny_gemm_launch(x, qidxs, grid_f16, y, m, n, k, (hipStream_t)stream);
+  return mm_skinny(kD4, x, qidxs, {grid_f16}, y, m, n, k, stream);
 }
 
 int quip_hi_mm_skinny(const void* x, const void* qidxs, void* y, int32_t m, int32_t n, int32_t k, quip_stream_t stream) {
-  if (const int st = skinny_args_ok(x, qidxs, {}, y, m, n, k); st != QUIP_OK || m == 0) return st;
-  return hi_skinny_gemm_launch(x, qidxs, y, m, n, k, (hipStream_t)stream);
+  return mm_skinny(kHI, x, qidxs, {}, y, m, n, k, stream);
 }
 
 int quip_e8p_mm_batched(const void* x, const void* qidxs, const void* grid, void* y, int64_t m, int32_t n, int32_t k,
                         quip_stream_t stream) {
-  if (!x || !qidxs || !grid || !y) return QUIP_ERR_NULL_POINTER;
-  if (m < 0 || n < 1 || k < 8) return QUIP_ERR_BAD_SHAPE;
-  if (m == 0) return QUIP_OK;
-  if (!aligned16(x) || !aligned16(qidxs) || !aligned16(y) || (reinterpret_cast<uintptr_t>(grid) & 7u)) return QUIP_ERR_MISALIGNED;
-  return e8p_prefill_gemm_launch(x, qidxs, grid, y, m, n, k, (hipStream_t)stream);
-}
-
-// the other codebooks on the fused tile kernel (e8p_prefill_gemm.hip, MODE 1..4)
-static int batched_args_ok(const void* x, const void* qidxs, const void* y, int64_t m, int32_t n, int32_t k) {
-  if (!x || !qidxs || !y) return QUIP_ERR_NULL_POINTER;
-  if (m < 0 || n < 1 || k < 8) return QUIP_ERR_BAD_SHAPE;
-  if (!aligned16(x) || !aligned16(qidxs) || !aligned16(y)) return QUIP_ERR_MISALIGNED;
-  return QUIP_OK;
+  return mm_batched(kE8P, x, qidxs, {grid}, y, m, n, k, stream);
 }
 
 int quip_e8prvq4_mm_batched(const void* x, const void* qidxs, const void* grid, float resid_scale, void* y, int64_t m,
                             int32_t n, int32_t k, quip_stream_t stream) {
-  if (!grid) return QUIP_ERR_NULL_POINTER;
-  if (const int st = batched_args_ok(x, qidxs, y, m, n, k)) return st;
-  if (reinterpret_cast<uintptr_t>(grid) & 7u) return QUIP_ERR_MISALIGNED;
-  if (m == 0) return QUIP_OK;
-  return e8prvq4_prefill_gemm_launch(x, qidxs, grid, resid_scale, y, m, n, k, (hipStream_t)stream);
+  return mm_batched(kE8PRVQ4, x, qidxs, {grid, nullptr, resid_scale}, y, m, n, k, stream);
 }
 
 int quip_e8prvq3_mm_batched(const void* x, const void* qidxs, const void* grid, const void* e81b_packed, float resid_scale,
                             void* y, int64_t m, int32_t n, int32_t k, quip_stream_t stream) {
-  if (!grid || !e81b_packed) return QUIP_ERR_NULL_POINTER;
-  if (const int st = batched_args_ok(x, qidxs, y, m, n, k)) return st;
-  if ((reinterpret_cast<uintptr_t>(grid) & 7u) || (reinterpret_cast<uintptr_t>(e81b_packed) & 3u)) return QUIP_ERR_MISALIGNED;
-  if (m == 0) return QUIP_OK;
-  return e8prvq3_prefill_gemm_launch(x, qidxs, grid, e81b_packed, resid_scale, y, m, n, k, (hipStream_t)stream);
+  return mm_batched(kE8PRVQ3, x, qidxs, {grid, e81b_packed, resid_scale}, y, m, n, k, stream);
 }
 
 int quip_d4_mm_batched(const void* x, const void* qidxs, const void* grid_f16, void* y, int64_t m, int32_t n, int32_t k,
                        quip_stream_t stream) {
-  if (!grid_f16) return QUIP_ERR_NULL_POINTER;
-  if (const int st = batched_args_ok(x, qidxs, y, m, n, k)) return st;
-  if (reinterpret_cast<uintptr_t>(grid_f16) & 7u) return QUIP_ERR_MISALIGNED;
-  if (m == 0) return QUIP_OK;
-  return d4_prefill_gemm_launch(x, qidxs, grid_f16, y, m, n, k, (hipStream_t)stream);
+  return mm_batched(kD4, x, qidxs, {grid_f16}, y, m, n, k, stream);
 }
 
 int quip_hi_mm_batched(const void* x, const void* qidxs, void* y, int64_t m, int32_t n, int32_t k, quip_stream_t stream) {
-  if (const int st = batched_args_ok(x, qidxs, y, m, n, k)) return st;
-  if (m == 0) return QUIP_OK;
-  return hi_prefill_gemm_launch(x, qidxs, y, m, n, k, (hipStream_t)stream);
+  return mm_batched(kHI, x, qidxs, {}, y, m, n, k, stream);
 }
 
 int quip_e8p_mm_origorder_ws(const void* x, const void* qidxs, const void* grid, void* y, int32_t m,
                              int32_t n, int32_t k, void* workspace, size_t workspace_bytes,
                              quip_stream_t stream) {
-  if (x && qidxs && grid && y && workspace && m >= 1 && m < 32 && n > 0 && e8p_gemv_mfma_supported(n, k) &&
-      aligned16(x) && aligned16(qidxs) && aligned16(workspace) && aligned64(grid) &&
-      workspace_bytes >= (size_t)m * e8p_gemv_mfma_planes_bytes(k)) {
+  if (!any_null({x, qidxs, grid, y, workspace}) && m >= 1 && m < 32 && n > 0 && e8p_gemv_mfma_supported(n, k) &&
+      !any_off({x, qidxs, workspace}, 15) && aligned64(grid) && workspace_bytes >= (size_t)m * e8p_gemv_mfma_planes_bytes(k)) {
     // 1 <= M < 32 on the matrix cores: digit planes of every row, then passes of up to
     // e8p_gemv_mfma_max_rows rows over the codes (M == 1: the plain GEMV)
     const int rc = x_to_planes_linear_launch(x, workspace, k, (hipStream_t)stream, m);
@@ -1160,14 +1190,13 @@ int quip_e8p_x_to_planes_laneorder(const void* x, void* planes, int32_t k, quip_
   return x_to_planes_launch(x, planes, k, (hipStream_t)stream);
 }
 
+// ---- the tuning hooks (micro-benchmarks only, not in the public header) ------------------------------------------------
 int quip_e8p_gemv_tuned(const void* x, const void* qidxs, const void* grid, void* y, int32_t n,
                         int32_t k, int32_t kernel, int32_t rep, int32_t rows, int32_t blocks,
                         int32_t waves_g, int32_t max_waves, int32_t digits, void* dbg,
                         quip_stream_t stream) {
-  if (!x || !qidxs || !grid || !y) return QUIP_ERR_NULL_POINTER;
-  GemvTune t;
-  t.rep = rep; t.rows = rows; t.blocks = blocks; t.waves_g = waves_g;
-  t.max_waves = max_waves; t.digits = digits; t.dbg = dbg;
+  if (any_null({x, qidxs, grid, y})) return QUIP_ERR_NULL_POINTER;
+  const GemvTune t = tune_of(rep, rows, blocks, waves_g, max_waves, digits, dbg);
   if (kernel == 2) return stream_probe_launch(qidxs, y, n, k, t, (hipStream_t)stream);
   if (kernel == 5) return pattern_probe_launch(qidxs, y, n, k, t, (hipStream_t)stream);
   if (kernel == 6) return shape_probe_launch(qidxs, y, n, k, t, (hipStream_t)stream);
@@ -1180,25 +1209,19 @@ int quip_e8p_gemv_tuned(const void* x, const void* qidxs, const void* grid, void
 int quip_e8p_gemv_v2_tuned(const void* planes, const void* qidxs, const void* grid, void* y, void* ws, int32_t n,
                            int32_t k, int32_t rep2, int32_t slots, int32_t blocks, int32_t ksplit,
                            int32_t max_waves, int32_t runlen, void* dbg, quip_stream_t stream) {
-  if (!planes || !qidxs || !grid || !y) return QUIP_ERR_NULL_POINTER;
-  GemvTune t;
-  t.rep = rep2; t.rows = slots; t.blocks = blocks; t.waves_g = ksplit; t.max_waves = max_waves; t.dbg = dbg;
-  t.digits = runlen;
-  return gemv_v2_auto(&planes, &qidxs, grid, &y, ws, &n, 1, k, t, (hipStream_t)stream);
+  if (any_null({planes, qidxs, grid, y})) return QUIP_ERR_NULL_POINTER;
+  return gemv_v2_auto(&planes, &qidxs, grid, &y, ws, &n, 1, k, tune_of(rep2, slots, blocks, ksplit, max_waves, runlen, dbg),
+                      (hipStream_t)stream);
 }
 
 int quip_e8p_gemv_v2_group_tuned(const void* const* planes, const void* const* qidxs, const void* grid,
                                  void* const* ys, void* ws, const int32_t* ns, int32_t count, int32_t k, int32_t rep,
                                  int32_t slots, int32_t blocks, int32_t ksplit, int32_t max_waves, int32_t runlen,
                                  void* dbg, quip_stream_t stream) {
-  if (!planes || !qidxs || !grid || !ys || !ns) return QUIP_ERR_NULL_POINTER;
+  if (any_null({planes, qidxs, grid, ys, ns})) return QUIP_ERR_NULL_POINTER;
   if (count < 1 || count > QUIP_MAX_GROUP) return QUIP_ERR_UNSUPPORTED;
-  GemvTune t;
-  t.rep = rep; t.rows = slots; t.blocks = blocks; t.waves_g = ksplit; t.max_waves = max_waves; t.dbg = dbg;
-  t.digits = runlen;
-  int n32[QUIP_MAX_GROUP];
-  for (int i = 0; i < count; ++i) n32[i] = ns[i];
-  return gemv_v2_auto(planes, qidxs, grid, ys, ws, n32, count, k, t, (hipStream_t)stream);
+  return gemv_v2_auto(planes, qidxs, grid, ys, ws, ns, count, k, tune_of(rep, slots, blocks, ksplit, max_waves, runlen, dbg),
+                      (hipStream_t)stream);
 }
 
 size_t quip_e8p_gemv_v2_workspace_bytes(int32_t n) { return e8p_gemv_v2_workspace_words(n) * 4; }
@@ -1206,104 +1229,63 @@ size_t quip_e8p_gemv_v2_workspace_bytes(int32_t n) { return e8p_gemv_v2_workspac
 int quip_e8p_gemv_fused_tuned(const quip_gemv_fused_in* in, const void* const* qidxs, const void* grid,
                               void* const* ys, const int32_t* ns, int32_t count, int32_t k, void* dbg,
                               quip_stream_t stream) {
-  GemvFusedIn f;
-  f.x = in->x; f.z = in->z; f.post = in->post_scale; f.residual = in->residual; f.h_out = in->h_out;
-  f.rms_w = in->rms_weight; f.z_scale = in->z_scale; f.rms_eps = in->rms_eps;
-  int n32[QUIP_MAX_GROUP];
-  for (int i = 0; i < count && i < QUIP_MAX_GROUP; ++i) {
-    f.pre[i] = in->pre_scale[i]; f.scale[i] = in->scale[i]; n32[i] = ns[i];
-  }
-  GemvTune t;
-  t.dbg = dbg;
-  return e8p_gemv_mfma_fused_launch(f, qidxs, grid, ys, n32, count, k, t, (hipStream_t)stream);
+  return e8p_gemv_mfma_fused_launch(fused_in_of(in, count), qidxs, grid, ys, ns, count, k, tune_of(0, 0, 0, 0, 0, 0, dbg),
+                                    (hipStream_t)stream);
 }
 
 int quip_e8p_gemv_group_tuned(const void* const* planes, const void* const* qidxs, const void* grid,
                               void* const* ys, const int32_t* ns, int32_t count, int32_t k, int32_t rep,
                               int32_t rows, int32_t blocks, int32_t max_waves, void* dbg,
                               quip_stream_t stream) {
-  GemvTune t;
-  t.rep = rep; t.rows = rows; t.blocks = blocks; t.max_waves = max_waves; t.dbg = dbg;
-  int n32[QUIP_MAX_GROUP];
-  for (int i = 0; i < count && i < QUIP_MAX_GROUP; ++i) n32[i] = ns[i];
-  return e8p_gemv_mfma_group_launch(planes, qidxs, grid, ys, n32, count, k, t, (hipStream_t)stream);
+  return e8p_gemv_mfma_group_launch(planes, qidxs, grid, ys, ns, count, k, tune_of(rep, rows, blocks, 0, max_waves, 0, dbg),
+                                    (hipStream_t)stream);
 }
 
 int quip_e8prvq3_mm_origorder(const void* x, const void* qidxs, const void* grid,
                               const void* grid2, float scale, void* y, int32_t m, int32_t n,
                               int32_t k, quip_stream_t stream) {
-  if (!grid || !grid2) return QUIP_ERR_NULL_POINTER;
-  CodebookArgs a;
-  a.grid = grid; a.grid2 = grid2; a.scale = scale;
-  return mm_common(kE8PRVQ3, x, qidxs, a, y, m, n, k, 32, (hipStream_t)stream);
+  return mm_origorder(kE8PRVQ3, x, qidxs, {grid, grid2, scale}, y, m, n, k, stream);
 }
 
 int quip_e8prvq4_mm_origorder(const void* x, const void* qidxs, const void* grid, float scale,
                               void* y, int32_t m, int32_t n, int32_t k, quip_stream_t stream) {
-  if (!grid) return QUIP_ERR_NULL_POINTER;
-  CodebookArgs a;
-  a.grid = grid; a.scale = scale;
-  return mm_common(kE8PRVQ4, x, qidxs, a, y, m, n, k, 8, (hipStream_t)stream);
+  return mm_origorder(kE8PRVQ4, x, qidxs, {grid, nullptr, scale}, y, m, n, k, stream);
 }
 
 int quip_d4_mm_origorder(const void* x, const void* qidxs, const void* grid_f16, void* y,
                          int32_t m, int32_t n, int32_t k, quip_stream_t stream) {
-  if (!grid_f16) return QUIP_ERR_NULL_POINTER;
-  CodebookArgs a;
-  a.grid = grid_f16;
-  return mm_common(kD4, x, qidxs, a, y, m, n, k, 8, (hipStream_t)stream);
+  return mm_origorder(kD4, x, qidxs, {grid_f16}, y, m, n, k, stream);
 }
 
 int quip_hi_mm_origorder(const void* x, const void* qidxs, void* y, int32_t m, int32_t n,
                          int32_t k, quip_stream_t stream) {
-  return mm_common(kHI, x, qidxs, CodebookArgs{}, y, m, n, k, 8, (hipStream_t)stream);
-}
-
-static int dec_common(CodebookId cb, const void* q, const CodebookArgs& a, void* w, int64_t rows,
-                      int32_t k, int kdiv, hipStream_t s) {
-  if (!q || !w) return QUIP_ERR_NULL_POINTER;
-  if (rows < 0 || k <= 0 || k % kdiv != 0 || k % 8 != 0) return QUIP_ERR_BAD_SHAPE;
-  if (rows == 0) return QUIP_OK;
-  if (!aligned16(w)) return QUIP_ERR_MISALIGNED;
-  return decompress_launch(cb, q, a, w, rows, k, s);
+  return mm_origorder(kHI, x, qidxs, {}, y, m, n, k, stream);
 }
 
 int quip_decompress_e8p_origorder(const void* qidxs, const void* grid, void* w, int64_t rows,
                                   int32_t k, quip_stream_t stream) {
-  if (!grid) return QUIP_ERR_NULL_POINTER;
-  CodebookArgs a;
-  a.grid = grid;
-  return dec_common(kE8P, qidxs, a, w, rows, k, 8, (hipStream_t)stream);
+  return decompress_origorder(kE8P, qidxs, {grid}, w, rows, k, stream);
 }
 
 int quip_decompress_e8prvq3_origorder(const void* qidxs, const void* grid, const void* grid2,
                                       float scale, void* w, int64_t rows, int32_t k,
                                       quip_stream_t stream) {
-  if (!grid || !grid2) return QUIP_ERR_NULL_POINTER;
-  CodebookArgs a;
-  a.grid = grid; a.grid2 = grid2; a.scale = scale;
-  return dec_common(kE8PRVQ3, qidxs, a, w, rows, k, 32, (hipStream_t)stream);
+  return decompress_origorder(kE8PRVQ3, qidxs, {grid, grid2, scale}, w, rows, k, stream);
 }
 
 int quip_decompress_e8prvq4_origorder(const void* qidxs, const void* grid, float scale, void* w,
                                       int64_t rows, int32_t k, quip_stream_t stream) {
-  if (!grid) return QUIP_ERR_NULL_POINTER;
-  CodebookArgs a;
-  a.grid = grid; a.scale = scale;
-  return dec_common(kE8PRVQ4, qidxs, a, w, rows, k, 8, (hipStream_t)stream);
+  return decompress_origorder(kE8PRVQ4, qidxs, {grid, nullptr, scale}, w, rows, k, stream);
 }
 
 int quip_decompress_d4_origorder(const void* qidxs, const void* grid_f16, void* w, int64_t rows,
                                  int32_t k, quip_stream_t stream) {
-  if (!grid_f16) return QUIP_ERR_NULL_POINTER;
-  CodebookArgs a;
-  a.grid = grid_f16;
-  return dec_common(kD4, qidxs, a, w, rows, k, 8, (hipStream_t)stream);
+  return decompress_origorder(kD4, qidxs, {grid_f16}, w, rows, k, stream);
 }
 
 int quip_decompress_hi_origorder(const void* qidxs, void* w, int64_t rows, int32_t k,
                                  quip_stream_t stream) {
-  return dec_common(kHI, qidxs, CodebookArgs{}, w, rows, k, 8, (hipStream_t)stream);
+  return decompress_origorder(kHI, qidxs, {}, w, rows, k, stream);
 }
 
 }  // extern "C"

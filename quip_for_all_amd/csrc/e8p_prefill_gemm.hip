@@ -524,10 +524,10 @@ bool e8p_prefill_gemm_supported(int64_t m, int n, int k) {
   return m >= 1 && n >= 2 && n % 2 == 0 && k >= kBK && k % kBK == 0 && m < ((int64_t)1 << 31);
 }
 
-// mode 0: E8P12 (int16 codes (n, k/8)), 1: E8P12RVQ4B (int32 codes, resid_scale), 2: D4 (uint8 codes (n, k/4), grid = the fp16
-// (256, 4) table), 3: HI (int32 codes, no table), 4: E8P12RVQ3B (packed 3-byte codes, grid2 = the packed E81B table)
-static int prefill_launch_mode(int mode, const void* x, const void* qidxs, const void* grid, const void* grid2, float resid_scale,
-                               void* y, int64_t m, int n, int k, hipStream_t stream) {
+// the codes and tables per codebook: quip_internal.h.  The branches below name the kernel instantiations: their order is the
+// order of the kernels in the device code
+int prefill_gemm_launch(CodebookId cb, const void* x, const void* qidxs, const CodebookArgs& a, void* y, int64_t m, int n,
+                        int k, hipStream_t stream) {
   if (!e8p_prefill_gemm_supported(m, n, k)) return QUIP_ERR_UNSUPPORTED;
   const int NT = (n + kBN - 1) / kBN;
   // 128-row tiles while 256-row tiles would leave CUs without a workgroup (the K loop of a workgroup takes the same
@@ -537,48 +537,25 @@ static int prefill_launch_mode(int mode, const void* x, const void* qidxs, const
   static const int layout = env_int("QUIP_PREFILL_LAYOUT", 0);   // measured: 0 is the fastest
   // (E8P12RVQ3B: a third table; E8P12RVQ4B: four table entries per fragment in flight, the 256-row tile's 128
   //  accumulator registers would leave it 9 registers short -- 128-row tiles always)
-  const bool half = (mode == 4 || mode == 1) ? true : force ? force == 128 : (m + kBM - 1) / kBM * NT < device_cu_count();
+  const bool half = (cb == kE8PRVQ3 || cb == kE8PRVQ4) ? true : force ? force == 128 : (m + kBM - 1) / kBM * NT < device_cu_count();
   const int bm = half ? kBM / 2 : kBM;
   const int MT = (int)((m + bm - 1) / bm);
   const int64_t blocks = MT >= 8 ? (int64_t)((MT + 7) / 8) * NT * 8 : (int64_t)MT * NT;
   if (blocks > 0x7fffffff) return QUIP_ERR_UNSUPPORTED;
+  const int lds = lds_bytes(bm, cb == kE8PRVQ3 ? 4 : 0);      // (the kernel's MODE 4 keeps a third table in LDS)
   auto go = [&](auto kern, int threads) -> int {
-    return launch<decltype(kern)::value>(dim3((unsigned)blocks), dim3(threads), lds_bytes(bm, mode), stream,
+    return launch<decltype(kern)::value>(dim3((unsigned)blocks), dim3(threads), lds, stream,
                                          reinterpret_cast<const f16*>(x), reinterpret_cast<const uint8_t*>(qidxs),
-                                         reinterpret_cast<const uint64_t*>(grid), reinterpret_cast<f16*>(y), (int)m, n, k, MT,
-                                         NT, resid_scale, reinterpret_cast<const uint32_t*>(grid2));
+                                         reinterpret_cast<const uint64_t*>(a.grid), reinterpret_cast<f16*>(y), (int)m, n, k, MT,
+                                         NT, a.scale, reinterpret_cast<const uint32_t*>(a.grid2));
   };
-  if (mode == 1) return go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8, 1>>, 512);
-  if (mode == 2) return half ? go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8, 2>>, 512) : go(kernel_c<e8p_prefill_gemm_kernel<8, 1, 1, 8, 2>>, 512);
-  if (mode == 3) return half ? go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8, 3>>, 512) : go(kernel_c<e8p_prefill_gemm_kernel<8, 1, 1, 8, 3>>, 512);
-  if (mode == 4) return go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8, 4>>, 512);
+  if (cb == kE8PRVQ4) return go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8, 1>>, 512);
+  if (cb == kD4) return half ? go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8, 2>>, 512) : go(kernel_c<e8p_prefill_gemm_kernel<8, 1, 1, 8, 2>>, 512);
+  if (cb == kHI) return half ? go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8, 3>>, 512) : go(kernel_c<e8p_prefill_gemm_kernel<8, 1, 1, 8, 3>>, 512);
+  if (cb == kE8PRVQ3) return go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8, 4>>, 512);
   if (layout == 2) return half ? go(kernel_c<e8p_prefill_gemm_kernel<4, 2, 1, 4>>, 256) : go(kernel_c<e8p_prefill_gemm_kernel<8, 2, 1, 4>>, 256);
   if (layout == 1) return half ? go(kernel_c<e8p_prefill_gemm_kernel<2, 2, 2, 4>>, 512) : go(kernel_c<e8p_prefill_gemm_kernel<4, 2, 2, 4>>, 512);
   return half ? go(kernel_c<e8p_prefill_gemm_kernel<4, 1, 1, 8>>, 512) : go(kernel_c<e8p_prefill_gemm_kernel<8, 1, 1, 8>>, 512);
-}
-
-int e8p_prefill_gemm_launch(const void* x, const void* qidxs, const void* grid, void* y, int64_t m, int n, int k,
-                            hipStream_t stream) {
-  return prefill_launch_mode(0, x, qidxs, grid, nullptr, 0.f, y, m, n, k, stream);
-}
-
-int e8prvq4_prefill_gemm_launch(const void* x, const void* qidxs, const void* grid, float resid_scale, void* y, int64_t m, int n,
-                                int k, hipStream_t stream) {
-  return prefill_launch_mode(1, x, qidxs, grid, nullptr, resid_scale, y, m, n, k, stream);
-}
-
-int e8prvq3_prefill_gemm_launch(const void* x, const void* qidxs, const void* grid, const void* e81b_packed, float resid_scale,
-                                void* y, int64_t m, int n, int k, hipStream_t stream) {
-  return prefill_launch_mode(4, x, qidxs, grid, e81b_packed, resid_scale, y, m, n, k, stream);
-}
-
-int d4_prefill_gemm_launch(const void* x, const void* qidxs, const void* grid_f16, void* y, int64_t m, int n, int k,
-                           hipStream_t stream) {
-  return prefill_launch_mode(2, x, qidxs, grid_f16, nullptr, 0.f, y, m, n, k, stream);
-}
-
-int hi_prefill_gemm_launch(const void* x, const void* qidxs, void* y, int64_t m, int n, int k, hipStream_t stream) {
-  return prefill_launch_mode(3, x, qidxs, nullptr, nullptr, 0.f, y, m, n, k, stream);
 }
 
 }  // namespace quip

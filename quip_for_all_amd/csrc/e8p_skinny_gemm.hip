@@ -507,10 +507,12 @@ bool e8p_skinny_gemm_supported(int m, int n, int k) {
   return m >= 1 && m <= 32 * 65535 && n >= 2 && n % 2 == 0 && k >= 128 && k % 128 == 0;
 }
 
-// mode 0: E8P12 (16-bit codes), 1: E8P12RVQ4B (32-bit codes, resid_scale = the fp16 residual scale), 2: D4 (grid = the fp16
-// (256, 4) table), 3: HI (no table)
-static int skinny_launch_mode(int mode, const void* x, const void* qidxs, const void* grid, float resid_scale, void* y, int m,
-                              int n, int k, hipStream_t stream, const void* grid2 = nullptr) {
+// a.grid: the packed E8P table (E8P12*), the fp16 (256, 4) table (D4), none (HI); a.scale: the fp16 residual scale (E8P12RVQ*);
+// a.grid2: the packed E81B table (E8P12RVQ3B).  The branches below name the kernel instantiations: their order is the
+// order of the kernels in the device code
+int skinny_gemm_launch(CodebookId cb, const void* x, const void* qidxs, const CodebookArgs& a, void* y, int m, int n, int k,
+                       hipStream_t stream) {
+  if (cb == kE8PRVQ3 && k % 32 != 0) return QUIP_ERR_UNSUPPORTED;      // rows of 3 k / 8 bytes, dword aligned
   if (!e8p_skinny_gemm_supported(m, n, k)) return QUIP_ERR_UNSUPPORTED;
   // few columns: one column block of 32 per workgroup and 16 slices of K (more workgroups, shorter chains per wave);
   // many columns: two column blocks x 8 slices
@@ -520,51 +522,27 @@ static int skinny_launch_mode(int mode, const void* x, const void* qidxs, const 
   auto go = [&](auto kern, int cols) -> int {
     return launch<decltype(kern)::value>(dim3((n + cols - 1) / cols, (m + 31) / 32), dim3(1024), kSLds, stream,
                                          reinterpret_cast<const f16*>(x), reinterpret_cast<const uint16_t*>(qidxs),
-                                         reinterpret_cast<const uint64_t*>(grid), reinterpret_cast<f16*>(y), m, n, k,
-                                         resid_scale, reinterpret_cast<const uint32_t*>(grid2));
+                                         reinterpret_cast<const uint64_t*>(a.grid), reinterpret_cast<f16*>(y), m, n, k,
+                                         a.scale, reinterpret_cast<const uint32_t*>(a.grid2));
   };
-  if (mode == 1) {
+  if (cb == kE8PRVQ4) {
     if (m <= 16) return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 16, 1>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 16, 1>>, 64);
     return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 32, 1>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 32, 1>>, 64);
   }
-  if (mode == 2) {
+  if (cb == kD4) {
     if (m <= 16) return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 16, 2>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 16, 2>>, 64);
     return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 32, 2>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 32, 2>>, 64);
   }
-  if (mode == 4) {
+  if (cb == kE8PRVQ3) {
     if (m <= 16) return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 16, 4>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 16, 4>>, 64);
     return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 32, 4>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 32, 4>>, 64);
   }
-  if (mode == 3) {
+  if (cb == kHI) {
     if (m <= 16) return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 16, 3>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 16, 3>>, 64);
     return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 32, 3>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 32, 3>>, 64);
   }
   if (m <= 16) return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 16>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 16>>, 64);
   return one ? go(kernel_c<e8p_skinny_gemm_kernel<1, 32>>, 32) : go(kernel_c<e8p_skinny_gemm_kernel<2, 32>>, 64);
-}
-
-int e8p_skinny_gemm_launch(const void* x, const void* qidxs, const void* grid, void* y, int m, int n, int k,
-                           hipStream_t stream) {
-  return skinny_launch_mode(0, x, qidxs, grid, 0.f, y, m, n, k, stream);
-}
-
-int e8prvq4_skinny_gemm_launch(const void* x, const void* qidxs, const void* grid, float resid_scale, void* y, int m, int n,
-                               int k, hipStream_t stream) {
-  return skinny_launch_mode(1, x, qidxs, grid, resid_scale, y, m, n, k, stream);
-}
-
-int e8prvq3_skinny_gemm_launch(const void* x, const void* qidxs, const void* grid, const void* e81b_packed, float resid_scale,
-                               void* y, int m, int n, int k, hipStream_t stream) {
-  if (k % 32 != 0) return QUIP_ERR_UNSUPPORTED;
-  return skinny_launch_mode(4, x, qidxs, grid, resid_scale, y, m, n, k, stream, e81b_packed);
-}
-
-int d4_skinny_gemm_launch(const void* x, const void* qidxs, const void* grid_f16, void* y, int m, int n, int k, hipStream_t stream) {
-  return skinny_launch_mode(2, x, qidxs, grid_f16, 0.f, y, m, n, k, stream);
-}
-
-int hi_skinny_gemm_launch(const void* x, const void* qidxs, void* y, int m, int n, int k, hipStream_t stream) {
-  return skinny_launch_mode(3, x, qidxs, nullptr, 0.f, y, m, n, k, stream);
 }
 
 }  // namespace quip

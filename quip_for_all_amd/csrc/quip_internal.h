@@ -66,6 +66,9 @@ int e8p_gemv_v2n_group_launch(const void* const* planes, const void* const* qidx
 int shape_probe_launch(const void* qidxs, void* out, int n, int k, const GemvTune& tune, hipStream_t stream);
 int pattern_probe_launch(const void* qidxs, void* out, int n, int k, const GemvTune& tune, hipStream_t stream);
 
+// The one numbering of the codebooks below the ABI: every product launcher switches on it.  Two kernel-facing numberings
+// stay beside it, each mapped at one place: GemvTune::rep (the GEMV kernels' table mode 0 / 64 / 40: the GemvMode constants
+// of capi.hip) and BlockEngineArgs::codebook (0..5, the public quip_block_engine_args::codebook handed through).
 enum CodebookId { kE8P = 0, kE8PRVQ3 = 1, kE8PRVQ4 = 2, kD4 = 3, kHI = 4 };
 
 struct CodebookArgs {
@@ -124,31 +127,17 @@ bool e8p_gemv_mfma_fused_supported(const int* ns, int count, int k);
 int e8p_gemv_mfma_fused_launch(const GemvFusedIn& in, const void* const* qidxs, const void* grid,
                                void* const* ys, const int* ns, int count, int k, const GemvTune& tune,
                                hipStream_t stream);
-// fused E8P12 dequant + MFMA GEMM for batches (e8p_prefill_gemm.hip): y (m, n) = x (m, k) @ decode(qidxs)^T
+// fused dequant + MFMA GEMM for batches (e8p_prefill_gemm.hip): y (m, n) = x (m, k) @ decode(qidxs)^T.  The codes per
+// codebook: E8P12 int16 (n, k / 8); E8P12RVQ4B int32 (main << 16 | residual), weight = fma(a.scale, w_resid, w_main) in fp16;
+// E8P12RVQ3B 3-byte codes (n, 3 k / 8 bytes), a.grid2 = the packed E81B table, uint32 [256] (eight int4 = 2 x value per
+// entry); D4 one-byte codes (n, k / 4), a.grid = the fp16 (256, 4) table; HI int32 codes of eight nibbles, no table
 bool e8p_prefill_gemm_supported(int64_t m, int n, int k);
-int e8p_prefill_gemm_launch(const void* x, const void* qidxs, const void* grid, void* y, int64_t m, int n, int k,
-                            hipStream_t stream);
-// the same tile kernel with the other codebooks' B-fragment decode (argument meaning as the skinny launchers below)
-int e8prvq4_prefill_gemm_launch(const void* x, const void* qidxs, const void* grid, float resid_scale, void* y, int64_t m, int n,
-                                int k, hipStream_t stream);
-int e8prvq3_prefill_gemm_launch(const void* x, const void* qidxs, const void* grid, const void* e81b_packed, float resid_scale,
-                                void* y, int64_t m, int n, int k, hipStream_t stream);
-int d4_prefill_gemm_launch(const void* x, const void* qidxs, const void* grid_f16, void* y, int64_t m, int n, int k,
-                           hipStream_t stream);
-int hi_prefill_gemm_launch(const void* x, const void* qidxs, void* y, int64_t m, int n, int k, hipStream_t stream);
-// single-pass skinny E8P12 product, 1 <= m <= 32 rows, fp16 MFMA (e8p_skinny_gemm.hip)
+int prefill_gemm_launch(CodebookId cb, const void* x, const void* qidxs, const CodebookArgs& a, void* y, int64_t m, int n,
+                        int k, hipStream_t stream);
+// single-pass skinny product, 1 <= m <= 32 * 65535 rows, fp16 MFMA (e8p_skinny_gemm.hip): the same codes and tables
 bool e8p_skinny_gemm_supported(int m, int n, int k);
-int e8p_skinny_gemm_launch(const void* x, const void* qidxs, const void* grid, void* y, int m, int n, int k,
-                           hipStream_t stream);
-// the same for E8P12RVQ4B: 32-bit codes (main << 16 | residual), weight = fma(resid_scale, w_resid, w_main) in fp16
-int e8prvq4_skinny_gemm_launch(const void* x, const void* qidxs, const void* grid, float resid_scale, void* y, int m, int n,
-                               int k, hipStream_t stream);
-// E8P12RVQ3B: 3-byte codes (n, 3 k / 8 bytes), e81b_packed = uint32 [256] (eight int4 = 2 x value per entry)
-int e8prvq3_skinny_gemm_launch(const void* x, const void* qidxs, const void* grid, const void* e81b_packed, float resid_scale,
-                               void* y, int m, int n, int k, hipStream_t stream);
-// D4: one-byte codes (n, k/4), grid = the fp16 (256, 4) table; HI: 32-bit codes of eight nibbles (n, k/8)
-int d4_skinny_gemm_launch(const void* x, const void* qidxs, const void* grid_f16, void* y, int m, int n, int k, hipStream_t stream);
-int hi_skinny_gemm_launch(const void* x, const void* qidxs, void* y, int m, int n, int k, hipStream_t stream);
+int skinny_gemm_launch(CodebookId cb, const void* x, const void* qidxs, const CodebookArgs& a, void* y, int m, int n, int k,
+                       hipStream_t stream);
 // bf16 / fp32 (and plain fp16) Walsh-Hadamard transform of the last dimension (hadamard_generic.hip)
 int hadamard_generic_launch(const void* x, void* y, int64_t rows, int n, float scale, int dtype, hipStream_t stream);
 // The attention launches (decode_glue.hip and the headers it includes).  They share their operands: q, k (before the

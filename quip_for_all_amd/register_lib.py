@@ -480,65 +480,6 @@ def _e8p_quantize_cuda(X, grid):
     return vals, idx
 
 
-def _e8p_gemv_planes_rows_cuda(planes, Qidxs, grid):
-    _need(Qidxs.dtype == torch.int16 and Qidxs.is_contiguous(), "Qidxs must be contiguous int16 (n, k/8)")
-    n, k = Qidxs.shape[0], Qidxs.shape[1] * 8
-    L = capi.lib()
-    _need(planes.dim() == 2 and planes.dtype == torch.uint8 and planes.is_contiguous()
-          and planes.shape[1] == L.quip_e8p_planes_bytes(k) and planes.device == Qidxs.device,
-          "planes must be the (rows, quip_e8p_planes_bytes(k)) uint8 images of had_transform_planes_rows")
-    rows = planes.shape[0]
-    per = L.quip_e8p_gemv_max_rows(n, k)
-    g = _grid_i64(grid, Qidxs)
-    out = _empty((rows, n), dtype=torch.float16, device=Qidxs.device)
-    if per < 1:
-        # rows longer than rows mode holds in LDS (k > 28672: E8P12RVQ4B's 2k-wide virtual rows at 70B): one bs=1
-        # launch per row through the stand-alone GEMV (the K-splitting kernel) -- the same exact integer sums
-        return torch.cat([_e8p_gemv_planes_cuda(planes[r], Qidxs, grid) for r in range(rows)]) if rows else out
-    with torch.cuda.device(Qidxs.device):
-        for r0 in range(0, rows, per):
-            m = min(per, rows - r0)
-            capi.check(L.quip_e8p_gemv_planes_rows(planes[r0].data_ptr(), Qidxs.data_ptr(), g.data_ptr(),
-                                                   out[r0].data_ptr(), m, n, k, _stream(out)),
-                       "quip_e8p_gemv_planes_rows")
-    return out
-
-
-def _gemv_planes_rows_mode_cuda(planes, Qidxs, grid, grid2, mode):
-    _need(mode in (64, 40), "mode: 64 (D4 table) or 40 (E8P12RVQ3B tables)")
-    _need(Qidxs.is_contiguous() and Qidxs.dtype == (torch.uint8 if mode == 64 else torch.int32),
-          "Qidxs: contiguous uint8 (n, k/4) for mode 64, the checkpoint's int32 (n, 3 k / 32) 3-byte codes for mode 40")
-    n = Qidxs.shape[0]
-    _need(mode == 64 or Qidxs.shape[1] % 3 == 0, "mode 40: Qidxs (n, 3 k / 32)")
-    k = Qidxs.shape[1] * 4 if mode == 64 else Qidxs.shape[1] * 64 // 3   # mode 40: 2 * in features virtual weights
-    L = capi.lib()
-    _need(planes.dim() == 2 and planes.dtype == torch.uint8 and planes.is_contiguous()
-          and planes.shape[1] == L.quip_e8p_planes_bytes(k) and planes.device == Qidxs.device,
-          "planes must be (rows, quip_e8p_planes_bytes(k)) uint8 images")
-    if mode == 64:
-        g = _d4_grid(grid)
-    else:
-        g = _grid_i64(grid, planes)
-        _need(grid2 is not None and grid2.dtype == torch.int8 and tuple(grid2.shape) == (256, 8) and grid2.is_contiguous(),
-              "grid2 must be the contiguous int8 (256, 8) E81B table")
-    rows = planes.shape[0]
-    per = L.quip_gemv_max_rows_mode(n, k, mode)
-    if per < 1:
-        # virtual rows longer than rows mode holds in LDS (70B down_proj; HI's virtual rows in the D4 table mode): one bs=1
-        # launch per row (K-splitting kernel)
-        tables = (grid,) if mode == 64 else (grid, grid2)
-        return torch.cat([_gemv(_GEMV_D4 if mode == 64 else _GEMV_RVQ3, [planes[r]], [Qidxs], *tables)[0]
-                          for r in range(rows)])
-    out = _empty((rows, n), dtype=torch.float16, device=Qidxs.device)
-    with torch.cuda.device(Qidxs.device):
-        for r0 in range(0, rows, per):
-            m = min(per, rows - r0)
-            capi.check(L.quip_gemv_planes_rows_mode(planes[r0].data_ptr(), Qidxs.data_ptr(), g.data_ptr(), _ptr(grid2),
-                                                    out[r0].data_ptr(), m, n, k, mode, _stream(out)),
-                       "quip_gemv_planes_rows_mode")
-    return out
-
-
 def _e8p_mm_planes_rows_cuda(planes, Qidxs, grid):
     count = len(planes)
     _need(1 <= count <= capi.MAX_GROUP, "1..3 rows")
@@ -631,6 +572,7 @@ class _GemvMode(NamedTuple):
     virtual: int              # the planes hold quip_e8p_planes_bytes(virtual * in features)
     qmsg: str
     tables: Callable          # (planes[0], *the op's table arguments) -> the entry point's table arguments
+    rows_mode: int            # the table-mode number of rows mode (quip_gemv_max_rows_mode, quip_gemv_planes_rows_mode)
 
 
 def _e81b_i8(e81b_i8, ref):
@@ -646,13 +588,16 @@ def _d4_grid(grid):
 
 
 _GEMV_E8P = _GemvMode(_Entry("quip_e8p_gemv_planes_group_ws"), torch.int16, (8, 1), 1,
-                      "Qidxs must be contiguous int16 (n, k/8) with a common k", lambda ref, grid: (_grid_i64(grid, ref),))
+                      "Qidxs must be contiguous int16 (n, k/8) with a common k", lambda ref, grid: (_grid_i64(grid, ref),),
+                      0)
 # (HI runs in the D4 table mode through its virtual layout: its uint8 view already counts 2 k weights per row)
 _GEMV_D4 = _GemvMode(_Entry("quip_d4_gemv_planes_group_ws"), torch.uint8, (4, 1), 1,
-                     "Qidxs must be contiguous uint8 (n, k/4) with a common k", lambda ref, grid: (_d4_grid(grid),))
+                     "Qidxs must be contiguous uint8 (n, k/4) with a common k", lambda ref, grid: (_d4_grid(grid),),
+                     64)
 _GEMV_RVQ3 = _GemvMode(_Entry("quip_e8prvq3_gemv_planes_group_ws"), torch.int32, (32, 3), 2,
                        "Qidxs must be the checkpoint's contiguous int32 (n, 3 k / 32) tensors (3-byte codes) with a common k",
-                       lambda ref, grid, e81b_i8: (_grid_i64(grid, ref), _e81b_i8(e81b_i8, ref)))
+                       lambda ref, grid, e81b_i8: (_grid_i64(grid, ref), _e81b_i8(e81b_i8, ref)),
+                       40)
 
 
 def _gemv(mode, planes, Qidxs, *tables):
@@ -676,6 +621,44 @@ def _gemv(mode, planes, Qidxs, *tables):
         mode.entry(vp(*[p.data_ptr() for p in planes]), vp(*[q.data_ptr() for q in Qidxs]), *_args(tabs),
                    vp(*[o.data_ptr() for o in outs]), ns, count, k, ws.data_ptr(), ws.numel() * 4, _stream(planes[0]))
     return outs
+
+
+_GEMV_ROWS = _Entry("quip_gemv_planes_rows_mode")      # (mode 0 is what quip_e8p_gemv_planes_rows forwards to)
+
+
+def _gemv_rows(mode, planes, Qidxs, *tables):
+    """rows mode: the (rows, planes bytes) images of had_transform_planes_rows against one matrix -> (rows, n), in passes of
+    quip_gemv_max_rows_mode(n, k, mode) rows over the codes (k: the weights of a row as the kernel sees them)"""
+    L = capi.lib()
+    num, den = mode.cols
+    _need(Qidxs.dim() == 2 and Qidxs.dtype == mode.qdtype and Qidxs.is_contiguous() and Qidxs.shape[1] * num % den == 0,
+          mode.qmsg)
+    n, k = Qidxs.shape[0], mode.virtual * (Qidxs.shape[1] * num // den)
+    _need(planes.dim() == 2 and planes.dtype == torch.uint8 and planes.is_contiguous()
+          and planes.shape[1] == L.quip_e8p_planes_bytes(k) and planes.device == Qidxs.device,
+          "planes must be the (rows, quip_e8p_planes_bytes(k)) uint8 images of had_transform_planes_rows")
+    tabs = _args(mode.tables(planes, *tables))
+    rows = planes.shape[0]
+    per = L.quip_gemv_max_rows_mode(n, k, mode.rows_mode)
+    out = _empty((rows, n), dtype=torch.float16, device=Qidxs.device)
+    if per < 1:
+        # rows longer than rows mode holds in LDS (k > 28672: the 2k-wide virtual rows at the 70B down_proj width): one
+        # bs=1 launch per row through the stand-alone GEMV (the K-splitting kernel) -- the same exact integer sums
+        if mode is _GEMV_E8P and (rows == 0 or n == 0):     # (E8P12's op takes an empty problem; the other two refuse it)
+            return out
+        return torch.cat([_gemv(mode, [planes[r]], [Qidxs], *tables)[0] for r in range(rows)])
+    grid, grid2 = (tabs + [None])[:2]                       # (grid2: the E81B table of mode 40, else NULL)
+    with torch.cuda.device(Qidxs.device):
+        for r0 in range(0, rows, per):
+            _GEMV_ROWS(planes[r0].data_ptr(), Qidxs.data_ptr(), grid, grid2, out[r0].data_ptr(), min(per, rows - r0), n, k,
+                       mode.rows_mode, _stream(out))
+    return out
+
+
+def _gemv_planes_rows_mode_cuda(planes, Qidxs, grid, grid2, mode):
+    _need(mode in (64, 40), "mode: 64 (D4 table) or 40 (E8P12RVQ3B tables)")
+    _need(mode == 64 or grid2 is not None, "grid2 must be the contiguous int8 (256, 8) E81B table")
+    return _gemv_rows(_GEMV_D4, planes, Qidxs, grid) if mode == 64 else _gemv_rows(_GEMV_RVQ3, planes, Qidxs, grid, grid2)
 
 
 def _e8p_gemv_planes_cuda(planes, Qidxs, grid):
@@ -1000,7 +983,7 @@ _IMPLS = {
     "had_transform_group": _had_transform_group_cuda,
     "e8p_mm_planes_rows": _e8p_mm_planes_rows_cuda,
     "had_transform_planes_rows": _had_transform_planes_rows_cuda,
-    "e8p_gemv_planes_rows": _e8p_gemv_planes_rows_cuda,
+    "e8p_gemv_planes_rows": lambda planes, Qidxs, grid: _gemv_rows(_GEMV_E8P, planes, Qidxs, grid),
     "e8p_quantize": _e8p_quantize_cuda,
     "argmax_step": _argmax_step_cuda,
     "gemv_planes_rows_mode": _gemv_planes_rows_mode_cuda,
