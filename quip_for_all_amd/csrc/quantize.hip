@@ -18,9 +18,14 @@
 // issued thousands of times in sequence) has the latency of 64 candidates, not of a GEMM.
 //
 // Ties (a measure-zero set: some b_j y_j == 0, or two candidates with equal score) resolve to the
-// lowest (e, par, column) in scan order, which need not be the lowest code; near-ties inside fp32
-// rounding of the score may resolve differently from a GEMM-based arg max.  Either way the returned point
-// is a nearest codeword to within that rounding (tests/test_gpu_quantize.py states the bound).
+// lowest (e, par, column) in scan order, which need not be the lowest code: among candidates of equal score
+// the lowest e wins, then par = 0 before par = 1; y_j == 0 counts as positive; an odd flip count is repaired
+// on the first (lowest-index) column among those with the smallest b_j |y_j|.  Every instantiation of the
+// scan and all three panel templates follow this one rule (tests/test_gpu_quantize_hard_cases.py holds them
+// to it by equality on targets that are multiples of 1/8, where no fp32 rounding takes part).  Near-ties inside
+// fp32 rounding of the score may resolve differently from a GEMM-based arg max.  Either way the returned point
+// is a nearest codeword to within that rounding (tests/test_gpu_quantize.py states the bound;
+// tests/quantize_hard_cases.py derives one from the scan's operations).
 //
 // Second kernel, further down: ldlq_panel_kernel runs the LDLQ recursion over a whole panel of <= 128 columns in one
 // launch, with this search in place at every column group (the scan and the winner's reconstruction are device

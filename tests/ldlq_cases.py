@@ -35,8 +35,11 @@ def proxy_loss(W, hat, H):
     return float(np.trace(D @ np.asarray(H, np.float64) @ D.T))
 
 
-def panel_model(A, B, M, P):
-    """the recursion of quip_lib::ldlq_panel in torch, in the operands' dtype, with oracle.quantize as the search"""
+def panel_model(A, B, M, P, quantize=None):
+    """the recursion of quip_lib::ldlq_panel in torch, in the operands' dtype, with oracle.quantize as the search (or
+    quantize(X numpy) -> (vals, idx) in its place)"""
+    if quantize is None:
+        quantize = lambda X: O.quantize("E8P12", X)      # noqa: E731
     m, c = A.shape
     hat, E = torch.zeros_like(A), torch.zeros_like(A)
     idx = torch.zeros(m, c // 8, dtype=torch.int64)
@@ -45,7 +48,7 @@ def panel_model(A, B, M, P):
         t = B[:, lo:hi] + E[:, hi:] @ M[hi:, lo:hi]
         if P is not None:
             t = t @ P[k]
-        vals, ix = O.quantize("E8P12", (A[:, lo:hi] + t).numpy())
+        vals, ix = quantize((A[:, lo:hi] + t).numpy())
         hat[:, lo:hi] = torch.from_numpy(vals).to(A.dtype)
         idx[:, k] = torch.from_numpy(ix)
         E[:, lo:hi] = A[:, lo:hi] - hat[:, lo:hi]
