@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 23
+#define QUIP_ABI_VERSION 24
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -349,6 +349,20 @@ int quip_ldlq_panel_f32(const void* A, const void* B, const void* M, const void*
 int quip_ldlq_panel_rvq_f32(const void* A, const void* B, const void* M, const void* P, int64_t m, int32_t c,
                             const void* grid_packed_abs, const void* resid_grid, float resid_scale, void* hat, void* idx,
                             quip_stream_t stream);
+
+/* ---- the panel for the narrow codebooks D4 and HI (ABI 24; d4.py:116-123, hi.py:30-39) -----------------------------------
+ * The recursion of quip_ldlq_panel_f32 over groups of b = codesz columns, for each of m rows over the c / b groups from the
+ * right:
+ *     t_k = B_k + sum_{j > k} (A_j - hat_j) M[j, k],   target_k = A_k + t_k P_k  (P NULL: A_k + t_k),   hat_k = Q(target_k)
+ * A, B, hat: fp32 (m, c); M: fp32 (c, c); P: fp32 (c / b, b, b) or NULL; idx: int64 (m, c / b).  A column's sum starts from B
+ * and takes its terms by fp32 FMA in decreasing j, ascending inside a group, so a row's result depends on that row, M and P
+ * alone.  Q takes the first maximum of 2 x . g - |g|^2, as torch.argmax does:
+ * codesz 4 (D4): grid = its fp32 (256, 4) entries, 16-byte aligned; the dot product summed left to right, the lowest index
+ *   on equal scores;   codesz 1 (HI): grid is ignored (pass NULL); idx = clamp(ceil(t) + 7, 0, 15), hat = idx - 7.5.
+ * codesz in {1, 4}, c % codesz == 0, c >= codesz (else QUIP_ERR_BAD_SHAPE), c <= 128 (else QUIP_ERR_UNSUPPORTED); m == 0 is
+ * ok and launches nothing; A, B, M, hat 16-byte aligned, P 16-byte (HI: 4-byte) aligned, idx 8-byte aligned. */
+int quip_ldlq_panel_small_f32(const void* A, const void* B, const void* M, const void* P, int64_t m, int32_t c,
+                              const void* grid, int32_t codesz, void* hat, void* idx, quip_stream_t stream);
 
 /* Rows mode for the other table modes of the same kernel.  mode 0: E8P12 (quip_e8p_gemv_planes_rows is this call);
  * mode 64: D4 (qidxs uint8 (n, k/4), grid = fp16 (256, 4) table; HI through its virtual 2k layout, see

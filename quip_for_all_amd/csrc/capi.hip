@@ -474,6 +474,20 @@ int quip_ldlq_panel_rvq_f32(const void* A, const void* B, const void* M, const v
   return ldlq_panel_rvq_launch(A, B, M, P, m, c, grid_packed_abs, resid_grid, resid_scale, hat, idx, (hipStream_t)stream);
 }
 
+int quip_ldlq_panel_small_f32(const void* A, const void* B, const void* M, const void* P, int64_t m, int32_t c,
+                              const void* grid, int32_t codesz, void* hat, void* idx, quip_stream_t stream) {
+  if (codesz != 4 && codesz != 1) return QUIP_ERR_BAD_SHAPE;
+  if (m < 0 || c < codesz || c % codesz != 0) return QUIP_ERR_BAD_SHAPE;
+  if (c > 128) return QUIP_ERR_UNSUPPORTED;
+  if (m == 0) return QUIP_OK;
+  if (!A || !B || !M || !hat || !idx || (codesz == 4 && !grid)) return QUIP_ERR_NULL_POINTER;
+  // HI reads P by the float (its slice of the (n, 1, 1) inverses starts at any column)
+  if (!aligned16(A) || !aligned16(B) || !aligned16(M) || !aligned16(hat) || !aligned16(grid) ||
+      (reinterpret_cast<uintptr_t>(P) & (codesz == 4 ? 15 : 3)) != 0 || (reinterpret_cast<uintptr_t>(idx) & 7) != 0)
+    return QUIP_ERR_MISALIGNED;
+  return ldlq_panel_small_launch(A, B, M, P, m, c, grid, codesz, hat, idx, (hipStream_t)stream);
+}
+
 int32_t quip_e8p_gemv_max_rows(int32_t n, int32_t k) { return (n > 0 && k > 0) ? e8p_gemv_mfma_max_rows(n, k) : 0; }
 
 int quip_e8p_gemv_planes_rows(const void* planes, const void* qidxs, const void* grid_packed_abs, void* y,

@@ -103,6 +103,10 @@ int ldlq_panel_launch(const void* A, const void* B, const void* M, const void* P
 int ldlq_panel_rvq_launch(const void* A, const void* B, const void* M, const void* P, int64_t m, int c,
                           const void* grid_packed_abs, const void* resid_grid, float resid_scale, void* hat, void* idx,
                           hipStream_t stream);
+// the panel over groups of codesz columns for the narrow codebooks: codesz 4 = D4 (grid = fp32 (256, 4) entries), 1 = HI
+// (grid unused); P fp32 (c / codesz, codesz, codesz) or null -> hat fp32 (m, c), idx int64 (m, c / codesz)
+int ldlq_panel_small_launch(const void* A, const void* B, const void* M, const void* P, int64_t m, int c, const void* grid,
+                            int codesz, void* hat, void* idx, hipStream_t stream);
 // rows mode: up to e8p_gemv_mfma_max_rows(n, k) <= 5 activation rows against one matrix in one pass
 int e8p_gemv_mfma_max_rows(int n, int k, int mode = 0);   // mode: 0 E8P12, 64 D4 / HI, 40 E8P12RVQ3B (2k virtual)
 int e8p_gemv_mfma_rows_launch(const void* planes, const void* qidxs, const void* grid, void* y, int mrows, int n,

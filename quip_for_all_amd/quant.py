@@ -162,13 +162,26 @@ def ldlq_fused_rvq_enabled():
     return _LDLQ_FUSED_RVQ
 
 
+_LDLQ_FUSED_SMALL = None
+SMALL_PANEL_CODEBOOKS = ("D4", "HI")
+
+
+def ldlq_fused_small_enabled():
+    """QUIP_LDLQ_FUSED_SMALL, off unless set; read once per process"""
+    global _LDLQ_FUSED_SMALL
+    if _LDLQ_FUSED_SMALL is None:
+        _LDLQ_FUSED_SMALL = parse_ldlq_fused(os.environ.get("QUIP_LDLQ_FUSED_SMALL"), default=False)
+    return _LDLQ_FUSED_SMALL
+
+
 def ldlq_route(Wr, cb):
     """"panels" (one GEMM + one ldlq_panel launch per panel) on fp32 GPU tensors for the E8P12 codebook unless
-    QUIP_LDLQ_FUSED=0, and for E8P12RVQ4B / E8P12RVQ3B when QUIP_LDLQ_FUSED_RVQ is set as well; "stepwise" (one chain
-    of launches per column group) for everything else"""
+    QUIP_LDLQ_FUSED=0, for E8P12RVQ4B / E8P12RVQ3B when QUIP_LDLQ_FUSED_RVQ is set as well, and for D4 / HI when
+    QUIP_LDLQ_FUSED_SMALL is; "stepwise" (one chain of launches per column group) for everything else"""
     cbid = getattr(cb, "id", None)
     fused = Wr.is_cuda and Wr.dtype == torch.float32 and ldlq_fused_enabled() and (
-        cbid == "E8P12" or (cbid in RVQ_PANEL_CODEBOOKS and ldlq_fused_rvq_enabled()))
+        cbid == "E8P12" or (cbid in RVQ_PANEL_CODEBOOKS and ldlq_fused_rvq_enabled())
+        or (cbid in SMALL_PANEL_CODEBOOKS and ldlq_fused_small_enabled()))
     return "panels" if fused else "stepwise"
 
 
@@ -181,9 +194,10 @@ def LDLQ(Wr, Hr, L, cb, quip_tune_iters=0, buf_cols=128):
     columns is one GEMM per panel (the reference's LDLQ_buffered, quant.py:138-230); `quip_tune_iters` extra
     sweeps re-round each group against the exact proxy gradient.  Returns (hatWr, Qidxs (m, n / codesz)).
     Two routes compute this (ldlq_route): LDLQ_panels for E8P12 (and, behind QUIP_LDLQ_FUSED_RVQ, the two residual
-    codebooks) on the GPU, LDLQ_stepwise otherwise."""
+    codebooks; LDLQ_panels_small for D4 / HI behind QUIP_LDLQ_FUSED_SMALL) on the GPU, LDLQ_stepwise otherwise."""
     if ldlq_route(Wr, cb) == "panels":
-        return LDLQ_panels(Wr, Hr, L, cb, quip_tune_iters, buf_cols)
+        run = LDLQ_panels_small if cb.id in SMALL_PANEL_CODEBOOKS else LDLQ_panels
+        return run(Wr, Hr, L, cb, quip_tune_iters, buf_cols)
     return LDLQ_stepwise(Wr, Hr, L, cb, quip_tune_iters, buf_cols)
 
 
@@ -230,13 +244,13 @@ def panel_bounds(n, b, cols):
     return out
 
 
-def panel_operands(Wr, hatWr, err, Hr, Lb, Pinv, lo, hi, tune):
-    """(A, B, M, P) of one ldlq_panel call.  err = Wr - hatWr of the finished columns (main pass: right of the panel;
-    tune sweep: everywhere, with the panels further right already re-rounded)."""
+def panel_operands(Wr, hatWr, err, Hr, Lb, Pinv, lo, hi, tune, b=8):
+    """(A, B, M, P) of one ldlq_panel call over groups of b columns.  err = Wr - hatWr of the finished columns (main pass:
+    right of the panel; tune sweep: everywhere, with the panels further right already re-rounded)."""
     n = Wr.shape[1]
     if tune:
         return (hatWr[:, lo:hi].contiguous(), err @ Hr[:, lo:hi], Hr[lo:hi, lo:hi].contiguous(),
-                Pinv[lo // 8:hi // 8])
+                Pinv[lo // b:hi // b])
     A = Wr[:, lo:hi].contiguous()
     B = err[:, hi:] @ Lb[hi:, lo:hi] if hi < n else torch.zeros_like(A)
     return A, B, Lb[lo:hi, lo:hi].contiguous(), None
@@ -265,11 +279,35 @@ def LDLQ_panels(Wr, Hr, L, cb, quip_tune_iters=0, buf_cols=128, panel_fn=None):
     the panel, M = H[panel, panel] and P_k = inv(H[kk]) (batched once per call), the error of group j inside the panel
     is its error at panel start plus A_j - hat_j, which is the reference's sweep (quant.py:190-228).
     panel_fn(A, B, M, P) -> (hat, idx) replaces the launch (the host model in tests/test_quantize_model_host.py)."""
-    m, n = Wr.shape
-    b = cb.codesz
-    assert b == 8 and n % b == 0
+    assert cb.codesz == 8
     if panel_fn is None:
         panel_fn = panel_launch(cb, Wr.device)
+    return _panel_sweeps(Wr, Hr, L, cb, quip_tune_iters, buf_cols, panel_fn)
+
+
+def small_panel_launch(cb, device):
+    """panel_fn(A, B, M, P) of ldlq_panel_small: D4 with its 256 entries as fp32, HI with no table"""
+    if cb.id not in SMALL_PANEL_CODEBOOKS:
+        raise ValueError(f"LDLQ_panels_small: no fused panel launch for codebook {cb.id}")
+    grid = cb.grid.to(device=device, dtype=torch.float32).contiguous() if cb.id == "D4" else None
+    return lambda A, B, M, P: torch.ops.quip_lib.ldlq_panel_small(A, B, M, P, grid)
+
+
+def LDLQ_panels_small(Wr, Hr, L, cb, quip_tune_iters=0, buf_cols=128, panel_fn=None):
+    """LDLQ_panels over the groups of b = cb.codesz columns of D4 (4) and HI (1): the block-LDL factor of width b, P_k the
+    (b, b) inverses, one torch.ops.quip_lib.ldlq_panel_small launch per panel (csrc/quantize.hip: the recursion
+    right-looking in registers, since a panel holds up to 128 groups here).  panel_fn as in LDLQ_panels."""
+    assert cb.codesz in (4, 1)
+    if panel_fn is None:
+        panel_fn = small_panel_launch(cb, Wr.device)
+    return _panel_sweeps(Wr, Hr, L, cb, quip_tune_iters, buf_cols, panel_fn)
+
+
+def _panel_sweeps(Wr, Hr, L, cb, quip_tune_iters, buf_cols, panel_fn):
+    """the main pass and the tune sweeps of LDLQ_panels / LDLQ_panels_small, panel by panel from the right"""
+    m, n = Wr.shape
+    b = cb.codesz
+    assert n % b == 0
     Lb = block_LDL(L.clone(), b)
     hatWr = torch.zeros_like(Wr)
     err = torch.zeros_like(Wr)
@@ -278,10 +316,10 @@ def LDLQ_panels(Wr, Hr, L, cb, quip_tune_iters=0, buf_cols=128, panel_fn=None):
     Pinv = None
     if quip_tune_iters > 0:
         g = torch.arange(n // b, device=Wr.device)
-        Pinv = torch.linalg.inv(Hr.reshape(n // b, b, n // b, b)[g, :, g, :]).contiguous()     # (n / 8, 8, 8)
+        Pinv = torch.linalg.inv(Hr.reshape(n // b, b, n // b, b)[g, :, g, :]).contiguous()     # (n / b, b, b)
     for sweep in range(1 + quip_tune_iters):
         for lo, hi in bounds:
-            A, B, M, P = panel_operands(Wr, hatWr, err, Hr, Lb, Pinv, lo, hi, tune=sweep > 0)
+            A, B, M, P = panel_operands(Wr, hatWr, err, Hr, Lb, Pinv, lo, hi, tune=sweep > 0, b=b)
             hat, idx = panel_fn(A, B, M, P)
             hatWr[:, lo:hi] = hat
             err[:, lo:hi] = Wr[:, lo:hi] - hat

@@ -1113,6 +1113,42 @@ def _ldlq_panel_rvq_cuda(A, B, M, P, grid, resid_grid, resid_scale):
     return hat, idx
 
 
+def _ldlq_panel_small_cuda(A, B, M, P, grid):
+    """ldlq_panel over the narrow groups of D4 / HI: grid = the fp32 (256, 4) D4 entries -> b = 4 (idx = the entry), grid None
+    -> HI, b = 1 (idx = the level 0 .. 15).  P (c / b, b, b) fp32 or None -> (hat (m, c) fp32, idx (m, c / b) int64)"""
+    _need(A.is_cuda and A.dim() == 2 and A.dtype == torch.float32 and A.is_contiguous(),
+          "ldlq_panel_small: A must be a contiguous float32 (m, c) CUDA tensor")
+    m, c = A.shape
+    _need(grid is None or (grid.dtype == torch.float32 and grid.is_contiguous() and grid.device == A.device
+                           and tuple(grid.shape) == (256, 4)),
+          "ldlq_panel_small: grid must be contiguous float32 (256, 4) on A's device (D4), or None (HI)")
+    b = 1 if grid is None else 4
+    _need(c >= b and c % b == 0 and c <= LDLQ_PANEL_MAX_COLS,
+          f"ldlq_panel_small: c = {c} (a multiple of {b} in {b} .. {LDLQ_PANEL_MAX_COLS})")
+    _need(B.dtype == torch.float32 and B.is_contiguous() and B.device == A.device and tuple(B.shape) == (m, c),
+          "ldlq_panel_small: B must be contiguous float32 with A's shape on A's device")
+    _need(M.dtype == torch.float32 and M.is_contiguous() and M.device == A.device and tuple(M.shape) == (c, c),
+          "ldlq_panel_small: M must be contiguous float32 (c, c) on A's device")
+    _need(P is None or (P.dtype == torch.float32 and P.is_contiguous() and P.device == A.device
+                        and tuple(P.shape) == (c // b, b, b)),
+          f"ldlq_panel_small: P must be contiguous float32 (c / {b}, {b}, {b}) on A's device, or None")
+    hat = torch.empty_like(A)
+    idx = _empty((m, c // b), dtype=torch.int64, device=A.device)
+    with torch.cuda.device(A.device):
+        capi.check(capi.lib().quip_ldlq_panel_small_f32(A.data_ptr(), B.data_ptr(), M.data_ptr(), _ptr(P), m, c, _ptr(grid), b,
+                                                        hat.data_ptr(), idx.data_ptr(), _stream(A)),
+                   "quip_ldlq_panel_small_f32")
+    return hat, idx
+
+
+try:
+    _lib.define("ldlq_panel_small(Tensor A, Tensor B, Tensor M, Tensor? P, Tensor? grid) -> (Tensor hat, Tensor idx)")
+    _lib.impl("ldlq_panel_small", _ldlq_panel_small_cuda, "CUDA")
+    _reg_fake("ldlq_panel_small", lambda A, B, M, P, grid:
+              (torch.empty_like(A), A.new_empty((A.shape[0], A.shape[1] // (1 if grid is None else 4)), dtype=torch.int64)))
+except RuntimeError:
+    pass
+
 try:
     _lib.define("ldlq_panel_rvq(Tensor A, Tensor B, Tensor M, Tensor? P, Tensor grid, Tensor? resid_grid, "
                 "float resid_scale) -> (Tensor hat, Tensor idx)")

@@ -5,6 +5,8 @@ time of the whole call and of LDLQ inside it, medians of `--rounds` rounds with 
 block (random fp16 weights) through QuipQuantizer.quantize_model on both routes.  One JSON line per measurement.
 --codebook E8P12RVQ4B / E8P12RVQ3B measures the same for a residual codebook, whose fused route (ldlq_panel_rvq) sits behind
 QUIP_LDLQ_FUSED_RVQ: the tool sets the route per call, so the stepwise route it alternates with is what LDLQ does by default.
+--codebook D4 / HI: the same behind QUIP_LDLQ_FUSED_SMALL (ldlq_panel_small), preceded by the launch alone on full panels of
+the measured row counts with 8 and 16 lanes per row (QUIP_LDLQ_SMALL_LANES), alternating, main pass and tune operands.
 
     python tools/ldlq_bench.py [--codebook E8P12] [--rounds 3] [--tokens 2048] [--block-iters 10] [--skip-block] [--out FILE]"""
 import argparse
@@ -19,9 +21,37 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def lanes_sweep(cb, rows, rounds, emit):
+    """ldlq_panel_small alone on a full panel of m rows: 8 and 16 lanes per row alternating, 20 launches per timing"""
+    from quip_for_all_amd import quant
+    b, dev = cb.codesz, "cuda:0"
+    fn = quant.small_panel_launch(cb, dev)
+    for m in rows:
+        torch.manual_seed(m)
+        A, B, M = torch.randn(m, 128, device=dev), 0.2 * torch.randn(m, 128, device=dev), 0.1 * torch.randn(128, 128, device=dev)
+        P = (torch.eye(b, device=dev) + 0.1 * torch.randn(128 // b, b, b, device=dev)).contiguous()
+        for tune in (False, True):
+            us, outs = {8: [], 16: []}, {}
+            for rnd in range(rounds + 1):                              # round 0 warms both up and is dropped
+                for lanes in (8, 16):
+                    os.environ["QUIP_LDLQ_SMALL_LANES"] = str(lanes)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(20):
+                        outs[lanes] = fn(A, B, M, P if tune else None)
+                    torch.cuda.synchronize()
+                    if rnd:
+                        us[lanes].append((time.perf_counter() - t0) / 20 * 1e6)
+            assert torch.equal(outs[8][0], outs[16][0]) and torch.equal(outs[8][1], outs[16][1])
+            emit(dict(launch="ldlq_panel_small", codebook=cb.id, rows=m, columns=128, operands="tune" if tune else "main",
+                      **{f"lanes{k}_us": dict(median=round(statistics.median(v), 1), spread=round(max(v) - min(v), 1))
+                         for k, v in us.items()}))
+    del os.environ["QUIP_LDLQ_SMALL_LANES"]
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--codebook", default="E8P12", choices=["E8P12", "E8P12RVQ4B", "E8P12RVQ3B"])
+    ap.add_argument("--codebook", default="E8P12", choices=["E8P12", "E8P12RVQ4B", "E8P12RVQ3B", "D4", "HI"])
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--tokens", type=int, default=2048)
     ap.add_argument("--block-iters", type=int, default=10)
@@ -60,11 +90,15 @@ def main():
         """the process-wide switches quant.ldlq_route reads, set as their environment variables would set them"""
         if args.codebook == "E8P12":
             quant._LDLQ_FUSED = route == "fused"
+        elif args.codebook in quant.SMALL_PANEL_CODEBOOKS:
+            quant._LDLQ_FUSED, quant._LDLQ_FUSED_SMALL = True, route == "fused"
         else:
             quant._LDLQ_FUSED, quant._LDLQ_FUSED_RVQ = True, route == "fused"
     emit(dict(device=torch.cuda.get_device_name(0), codebook=args.codebook, calibration_tokens=args.tokens, rounds=args.rounds,
               timing="host wall clock around synchronised calls; routes alternate inside every round"))
     cb = Q.codebook.codebook_id[args.codebook](inference=False).to(dev)
+    if args.codebook in quant.SMALL_PANEL_CODEBOOKS:
+        lanes_sweep(cb, sorted({int(shape.split("x")[1]) for shape in args.shapes.split(",")}), args.rounds, emit)
     for shape in args.shapes.split(","):
         fin, fout = (int(v) for v in shape.split("x"))
         torch.manual_seed(fin + fout)
@@ -137,7 +171,7 @@ def main():
         rec["quantize_model_speedup"] = round(rec["stepwise"]["quantize_model_s"] / rec["fused"]["quantize_model_s"], 2)
         emit(rec)
     quip.LDLQ = ldlq0
-    quant._LDLQ_FUSED = quant._LDLQ_FUSED_RVQ = None
+    quant._LDLQ_FUSED = quant._LDLQ_FUSED_RVQ = quant._LDLQ_FUSED_SMALL = None
     if out:
         out.close()
 
