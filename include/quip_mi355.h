@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 24
+#define QUIP_ABI_VERSION 25
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -296,6 +296,21 @@ int quip_had_transform_group_f16(const quip_had_problem* problems, int32_t count
                                  int32_t n, int32_t K, int32_t transpose, quip_stream_t stream);
 int quip_had_transform_planes_group(const quip_had_problem* problems, int32_t count, int32_t n,
                                     int32_t K, int32_t transpose, quip_stream_t stream);
+/* ---- prefill transform of K x 512 and K x 1024 rows, any 2 <= K <= 48 (ABI 25) ----------------------------
+ * One problem with the arithmetic of quip_had_transform_fused_f16 on fp16 rows (input-side element work, length-L
+ * transform of the K sub-rows, K x K mix, scale, output-side element work, one rounding), for the batches whose
+ * width no batch kernel of the group launch covers: 13824 = 27 x 512, 18944 = 37 x 512, 17408 = 17 x 1024, ...
+ * The K-mix runs on the matrix cores after the transform, so results differ from quip_had_transform_group_f16 in
+ * the order of the additions (both within the bound tests/test_gpu_had_mix_batch.py states).  A row's bits depend
+ * on that row and the vectors alone.
+ * Checked before the launch, nothing is dereferenced: problem, x, out, had NULL: QUIP_ERR_NULL_POINTER; K < 1,
+ * n % K != 0, L = n / K not a power of two, in_features / out_features outside [1, n]: QUIP_ERR_BAD_SHAPE; everything
+ * else outside the kernel's scope QUIP_ERR_UNSUPPORTED: K < 2 or K > 48, L not 512 or 1024, n > 28672, rows < 32,
+ * rms_weight or a chain (z), vectors of both sides (pre_scale / pre_scale2 / gate next to post_scale / bias /
+ * residual), in_features % 8 or out_features % 8, an operand off 16-byte alignment.  The rows are walked by a
+ * persistent grid, not carried by a grid dimension: any number of rows is one launch. */
+int quip_had_mix_batch_f16(const quip_had_problem* problem, int64_t rows, int32_t n, int32_t K,
+                                     int32_t transpose, quip_stream_t stream);
 /* ---- skinny GEMM on the matrix cores: 2..5 activation rows per pass over the codes ----------------
  * Replaces the 1 < M < 32 use of e8p_mm_origorder (origin_order.cu:388-555, 604-648; e8p12.py:147-150).
  * The MFMA of the bs=1 GEMV has 16 A rows and a single activation row fills 3 of them (its digit

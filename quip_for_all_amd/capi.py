@@ -27,6 +27,7 @@ SIGNATURES = {
     "quip_e8p_gemv_planes_ws": [_P, _P, _P, _P, _I32, _I32, _P, _c.c_size_t, _P],
     "quip_e8p_gemv_planes_group_ws": [_P, _P, _P, _P, _P, _I32, _I32, _P, _c.c_size_t, _P],
     "quip_had_transform_planes_rows": [_P, _I64, _I32, _I32, _I32, _P],
+    "quip_had_mix_batch_f16": [_P, _I64, _I32, _I32, _I32, _P],
     "quip_e8p_gemv_max_rows": [_I32, _I32],
     "quip_e8p_quantize_f32": [_P, _I64, _P, _P, _P, _P],
     "quip_ldlq_panel_f32": [_P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P],

@@ -429,6 +429,12 @@ int quip_had_transform_planes_rows(const quip_had_problem* problem, int64_t rows
   return had_transform_group_launch(problem, 1, true, rows, n, K, transpose, (hipStream_t)stream);
 }
 
+int quip_had_mix_batch_f16(const quip_had_problem* problem, int64_t rows, int32_t n, int32_t K, int32_t transpose,
+                                     quip_stream_t stream) {
+  if (!problem) return QUIP_ERR_NULL_POINTER;
+  return had_mix_batch_launch(problem, rows, n, K, transpose, (hipStream_t)stream);
+}
+
 int quip_had_plan(const quip_had_problem* problems, int32_t count, int32_t planes, int64_t rows, int32_t n, int32_t K,
                   int32_t transpose, int32_t* out) {
   if (!out) return QUIP_ERR_NULL_POINTER;

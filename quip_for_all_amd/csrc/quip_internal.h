@@ -91,6 +91,9 @@ constexpr int kHadPlanInts = 7 + 6 * QUIP_MAX_GROUP;
 int had_transform_group_plan(const quip_had_problem* problems, int count, bool planes, int64_t rows, int n, int K,
                              int transpose, int cus, int32_t* out);
 const char* had_plan_kind_name(int kind);   // the instantiation as text, null past the last kind
+// prefill transform of K x 512 / K x 1024 rows, 2 <= K <= 48 (had_mix_batch.hip): one problem, rows >= 32; every refusal
+// of quip_had_mix_batch_f16 past `problem` itself is answered here, before anything is dereferenced
+int had_mix_batch_launch(const quip_had_problem* problem, int64_t rows, int n, int K, int transpose, hipStream_t stream);
 // quantise-time nearest E8P12 codeword (quantize.hip): x fp32 (nvec, 8) -> vals fp32 (nvec, 8), idx int64 (nvec)
 int e8p_quantize_launch(const void* x, int64_t nvec, const void* grid_packed_abs, void* vals, void* idx,
                         hipStream_t stream);

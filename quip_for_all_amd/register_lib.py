@@ -110,6 +110,11 @@ _SCHEMAS = {
     "had_transform_planes_fused": "(Tensor x, int n, int K, Tensor? had, bool transpose, Tensor? pre, float scale, "
                                   "Tensor? rms_weight, float rms_eps, Tensor? gate, float resid_scale=0.0) -> Tensor",
 }
+# prefill batches (rows >= 32) of K x 512 / K x 1024 rows, 2 <= K <= 48: had_transform_fused without the RMSNorm.  Beside
+# the table: the table is the set of ops the reference's callers and the fakes' pin know
+_MIX_BATCH_SCHEMA = ("had_transform_mix_batch(Tensor x, int out_features, int n, int K, Tensor? had, bool transpose, "
+                     "Tensor? pre, Tensor? pre2, Tensor? post, Tensor? bias, float scale, Tensor? residual=None, "
+                     "Tensor? gate=None) -> Tensor")
 for _name, _schema in _SCHEMAS.items():
     try:
         _lib.define(_name + _schema)
@@ -356,10 +361,55 @@ def _group_count(what, count, *lists):
           f"{what}: a group of 1..{capi.MAX_GROUP} problems, one entry per problem in every list")
 
 
+_HAD_MIX_BATCH = None
+
+
+def had_mix_batch_enabled():
+    """QUIP_HAD_MIX_BATCH, off unless set to something other than "0"; read once per process"""
+    global _HAD_MIX_BATCH
+    if _HAD_MIX_BATCH is None:
+        _HAD_MIX_BATCH = _os.environ.get("QUIP_HAD_MIX_BATCH", "").strip() not in ("", "0")
+    return _HAD_MIX_BATCH
+
+
+def had_mix_batch_route(rows, n, K, out_features, in_vectors=False, out_vectors=False, rms_weight=False, in_features=None):
+    """True where had_transform_mix_batch serves a transform that no batch kernel of the group launch covers: rows >= 32 of
+    K x 512 or K x 1024, 2 <= K <= 48 (K in {3, 5, 7} has its own batch kernel), n <= 28672, whole 8-chunks on both sides,
+    element-wise vectors of one side at most, no RMSNorm.  Pure: shapes and which vectors are present."""
+    if K < 2 or K > 48 or K in (3, 5, 7) or n % K != 0 or n // K not in (512, 1024) or n > 28672:
+        return False
+    in_features = n if in_features is None else in_features
+    return rows >= 32 and out_features % 8 == 0 and in_features % 8 == 0 and not rms_weight and not (in_vectors and out_vectors)
+
+
+def _mix_batch_ok(xc, out_features, n, K, tensors, pre, pre2, gate, post, bias, residual, rms_weight):
+    """the route's predicate on an op's operands, and their 16-byte alignment (the entry refuses what is off it)"""
+    return (had_mix_batch_route(xc.shape[0], n, K, out_features, any(t is not None for t in (pre, pre2, gate)),
+                                any(t is not None for t in (post, bias, residual)), rms_weight is not None, xc.shape[1])
+            and all(t is None or t.data_ptr() % 16 == 0 for t in tensors))
+
+
+def _had_transform_mix_batch_cuda(x, out_features, n, K, had, transpose, pre, pre2, post, bias, scale, residual=None, gate=None):
+    what = "had_transform_mix_batch"
+    xc = _chk_x(x)
+    _check_had(what, xc, out_features, n, K, had, pre, pre2, post, bias, None, gate, residual)
+    y = _empty((xc.shape[0], out_features), dtype=torch.float16, device=x.device)
+    pr = _had_problem(x=xc, out=y, had=had, pre_scale=pre, pre_scale2=pre2, post_scale=post, bias=bias, residual=residual,
+                      gate=gate, in_features=xc.shape[1], out_features=out_features, scale=float(scale))
+    with torch.cuda.device(x.device):
+        capi.check(capi.lib().quip_had_mix_batch_f16(ctypes.byref(pr), xc.shape[0], n, int(K), int(bool(transpose)),
+                                                               _stream(x)), "quip_had_mix_batch_f16")
+    return y
+
+
 def _had_transform_fused_cuda(x, out_features, n, K, had, transpose, pre, pre2, post, bias, scale, residual=None,
                               rms_weight=None, rms_eps=1e-5, gate=None, what="had_transform_fused"):
     xc = _chk_x(x)
     _check_had(what, xc, out_features, n, K, had, pre, pre2, post, bias, rms_weight, gate, residual)
+    if had_mix_batch_enabled() and _mix_batch_ok(xc, out_features, n, K, (xc, pre, pre2, gate, post, bias, residual),
+                                                 pre, pre2, gate, post, bias, residual, rms_weight):
+        return _had_transform_mix_batch_cuda(xc, out_features, n, K, had, transpose, pre, pre2, post, bias,
+                                                          float(scale), residual, gate)
     y = _empty((xc.shape[0], out_features), dtype=torch.float16, device=x.device)
     pr = _had_problem(x=xc, out=y, had=had, pre_scale=pre, pre_scale2=pre2, post_scale=post, bias=bias, residual=residual,
                       rms_weight=rms_weight, gate=gate, in_features=xc.shape[1], out_features=out_features,
@@ -450,6 +500,12 @@ def _had_transform_group_cuda(x, out_features, n, K, had, transpose, pre2, post,
     for i in range(count):
         _check_had(what, xs[i], int(out_features[i]), int(ns[i]) if ns is not None else n, K, had[i], pre[i], pre2[i], post[i],
                    bias[i], rms_weight, residual=residual[i])
+    if ns is None and had_mix_batch_enabled() and all(
+            _mix_batch_ok(xs[i], int(out_features[i]), n, K, (xs[i], pre[i], pre2[i], post[i], bias[i], residual[i]),
+                          pre[i], pre2[i], None, post[i], bias[i], residual[i], rms_weight) for i in range(count)):
+        return [_had_transform_mix_batch_cuda(xs[i], int(out_features[i]), n, K, had[i], transpose, pre[i], pre2[i],
+                                                           post[i], bias[i], float(scale[i]), residual[i], None)
+                for i in range(count)]
     outs = [_empty((rows, int(o)), dtype=torch.float16, device=xs[0].device) for o in out_features]
     _had_call(xs[0], [_had_problem(x=xs[i], out=outs[i], had=had[i], pre_scale=pre[i], pre_scale2=pre2[i], post_scale=post[i],
                                    bias=bias[i], residual=residual[i], rms_weight=rms_weight, in_features=xs[i].shape[1],
@@ -990,6 +1046,11 @@ _IMPLS = {
     "had_transform_fused": _had_transform_fused_cuda,
     "had_transform_planes_fused": _had_transform_planes_fused_cuda,
 }
+try:
+    _lib.define(_MIX_BATCH_SCHEMA)
+except RuntimeError:
+    pass
+_IMPLS["had_transform_mix_batch"] = _had_transform_mix_batch_cuda
 for _cb_name, _cb in _CODEBOOKS.items():
     _IMPLS[f"{_cb_name}_mm_origorder"] = _product(f"{_cb_name}_mm_origorder", _cb)
     _IMPLS[f"{_cb_name}_mm_skinny"] = _product(f"{_cb_name}_mm_skinny", _cb, _SKINNY)
@@ -1012,6 +1073,8 @@ _reg_fake("had_transform_planes", lambda x, n, K, had, transpose, pre, scale:
           x.new_empty((_planes_numel(n),), dtype=torch.uint8))
 _reg_fake("had_transform_fused", lambda x, out_features, n, K, had, transpose, pre, pre2, post, bias, scale, residual,
           rms_weight, rms_eps, gate: x.new_empty((x.shape[0], out_features)))
+_reg_fake("had_transform_mix_batch", lambda x, out_features, n, K, had, transpose, pre, pre2, post, bias, scale, residual,
+          gate: x.new_empty((x.shape[0], out_features)))
 _reg_fake("had_transform_planes_fused", lambda x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate,
           resid_scale=0.0: x.new_empty((_planes_numel(n, resid_scale),), dtype=torch.uint8))
 _reg_fake("had_transform_planes_group", lambda x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate,
