@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 25
+#define QUIP_ABI_VERSION 26
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -111,6 +111,22 @@ int quip_e8prvq3_mm_skinny(const void* x, const void* qidxs, const void* grid_pa
 int quip_d4_mm_skinny(const void* x, const void* qidxs, const void* grid_f16, void* y, int32_t m, int32_t n, int32_t k,
                       quip_stream_t stream);
 int quip_hi_mm_skinny(const void* x, const void* qidxs, void* y, int32_t m, int32_t n, int32_t k, quip_stream_t stream);
+/* ---- 1..3 skinny products in ONE launch (ABI 26) ---------------------------------------------------------------------
+ * ys[g] (m, ns[g]) = xs[g] (m, k) @ decode(qidxs[g])^T for `count` matrices of one codebook and one k: the q / k / v or
+ * gate / up projections of a decoder block at 2..32 rows.  Every ys[g] is bit identical to the codebook's *_mm_skinny entry
+ * on (xs[g], qidxs[g]) alone: a workgroup walks column tiles of all the problems with the single launch's K slicing,
+ * request order and fixed-order reduction, and builds its decode tables once instead of once per tile.
+ * mode: the codebook -- 0 E8P12, 1 E8P12RVQ4B, 2 D4, 3 HI, 4 E8P12RVQ3B; grid / grid2 / resid_scale as the codebook's
+ * *_mm_skinny entry takes them (what a codebook does not read is ignored).  xs[g] may be one pointer or several.
+ * Checked in this order, nothing is launched on a refusal: mode outside 0..4, count outside 1..3, m < 1, k < 8
+ * (QUIP_ERR_BAD_SHAPE); the arrays, any xs[g] / qidxs[g] / ys[g] or a table the codebook needs NULL
+ * (QUIP_ERR_NULL_POINTER); any ns[g] < 1 (QUIP_ERR_BAD_SHAPE); alignment as the *_mm_skinny entries ask it, of every
+ * problem (QUIP_ERR_MISALIGNED); then QUIP_ERR_UNSUPPORTED: m > 32, k % 128, ns[g] % 2, E8P12RVQ3B with k % 32, and
+ * problems that do not agree on the single launch's choice of one or two column blocks per workgroup (a function of
+ * ns[g] alone: callers then launch the problems one by one). */
+int quip_mm_skinny_group_f16(int32_t mode, const void* const* xs, const void* const* qidxs, void* const* ys,
+                             const int32_t* ns, int32_t count, int32_t m, int32_t k, const void* grid, const void* grid2,
+                             float resid_scale, quip_stream_t stream);
 /* Batched E8P12 product for M >= 32 (prompt prefill): fused dequant + MFMA GEMM, y (m, n) = x (m, k) @ W^T with
  * W = decode(qidxs), fp16 in / fp32 accumulation / fp16 out -- the arithmetic of the reference's M >= 32 path
  * (e8p12.py:152-155: decompress_e8p_origorder + `x @ W.T`; origin_order.cu:837-885) without ever materialising W.

@@ -52,7 +52,27 @@ class _Codebook(nn.Module):
         return _Codebook.forward(self, input, Qidxs)
 
 
-class _SkinnyMixin:
+class _SkinnyGroupMixin:
+    """1..3 skinny products of one M <= 32 and k in one launch (csrc/e8p_skinny_group.hip): q / k / v or gate / up of a
+    batched decode step.  Subclasses give mm_skinny_group() with their tables; every result is bit identical to
+    mm_skinny() on the same operands."""
+
+    def skinny_group_supported(self, M, n_list, k):
+        """where mm_skinny_group() is the route: every problem is one mm_skinny() takes, M <= 32, and every problem takes
+        the kernel's tile of ONE column block per workgroup (a function of the width and the device: q / k / v).  The
+        launch itself also takes groups that agree on two column blocks (the Llama gate / up), but measured against the
+        separate launches those stay inside the spread at every M (profiles/skinny_group_bench.txt), so they are not
+        routed to it."""
+        from ..register_lib import mm_skinny_group_supported, skinny_one_block
+        dev = self._skinny_group_device()
+        return (all(self.skinny_supported(M, n, k) for n in n_list)
+                and mm_skinny_group_supported(M, list(n_list), k, dev) and all(skinny_one_block(n, dev) for n in n_list))
+
+    def _skinny_group_device(self):
+        return next((b.device for b in self.buffers() if b.is_cuda), None)
+
+
+class _SkinnyMixin(_SkinnyGroupMixin):
     """2 <= M < 32 beyond one exact rows-mode pass, and M >= mm_threshold up to a few hundred rows: the single-pass fp16
     skinny kernel in the codebook's mode (csrc/e8p_skinny_gemm.hip) -- the reference's arithmetic for this regime
     (origin_order.cu:388-555 with the codebook's BLayout: exact fp16 weights, fp32 accumulation), i.e. x . W of the dense W
@@ -87,7 +107,7 @@ class _SkinnyMixin:
         return _Codebook.forward(self, input, Qidxs)
 
 
-class E8P12_codebook(_Codebook):
+class E8P12_codebook(_SkinnyGroupMixin, _Codebook):
     def __init__(self, inference=False, **kwargs):
         super().__init__()
         self.id = "E8P12"
@@ -198,6 +218,10 @@ class E8P12_codebook(_Codebook):
         """(M <= 32, k) fp16 (already input-transformed) -> (M, n): one pass over the codes, fp16 MFMA"""
         return torch.ops.quip_lib.e8p_mm_skinny(xh, Qidxs, self.grid_packed_abs)
 
+    def mm_skinny_group(self, xs, Qidxs_list):
+        """[mm_skinny(x, Q) for x, Q in zip(xs, Qidxs_list)] -- the same bits -- in one launch"""
+        return list(torch.ops.quip_lib.mm_skinny_group(list(xs), list(Qidxs_list), 0, self.grid_packed_abs, None, 0.0))
+
 
 class E8P12RVQ4B_codebook(_SkinnyMixin, _Codebook):
     def __init__(self, inference=False, opt_resid_scale=None, **kwargs):
@@ -264,6 +288,10 @@ class E8P12RVQ4B_codebook(_SkinnyMixin, _Codebook):
 
     def mm_skinny(self, xh, Qidxs):
         return torch.ops.quip_lib.e8prvq4_mm_skinny(xh, Qidxs, self.grid_packed_abs, self.opt_resid_scale)
+
+    def mm_skinny_group(self, xs, Qidxs_list):
+        return list(torch.ops.quip_lib.mm_skinny_group(list(xs), list(Qidxs_list), 1, self.grid_packed_abs, None,
+                                                       self.opt_resid_scale))
 
     def mm_batched(self, xh, Qidxs):
         return torch.ops.quip_lib.e8prvq4_mm_batched(xh, Qidxs, self.grid_packed_abs, self.opt_resid_scale)
@@ -334,6 +362,10 @@ class E8P12RVQ3B_codebook(_SkinnyMixin, _Codebook):
     def mm_skinny(self, xh, Qidxs):
         return torch.ops.quip_lib.e8prvq3_mm_skinny(xh, Qidxs, self.grid_packed_abs, self.e81b_grid_packed, self.opt_resid_scale)
 
+    def mm_skinny_group(self, xs, Qidxs_list):
+        return list(torch.ops.quip_lib.mm_skinny_group(list(xs), list(Qidxs_list), 4, self.grid_packed_abs,
+                                                       self.e81b_grid_packed, self.opt_resid_scale))
+
     def mm_batched(self, xh, Qidxs):
         return torch.ops.quip_lib.e8prvq3_mm_batched(xh, Qidxs, self.grid_packed_abs, self.e81b_grid_packed, self.opt_resid_scale)
 
@@ -399,6 +431,9 @@ class D4_codebook(_SkinnyMixin, _Codebook):
 
     def mm_skinny(self, xh, Qidxs):
         return torch.ops.quip_lib.d4_mm_skinny(xh, Qidxs, self.grid)
+
+    def mm_skinny_group(self, xs, Qidxs_list):
+        return list(torch.ops.quip_lib.mm_skinny_group(list(xs), list(Qidxs_list), 2, self.grid, None, 0.0))
 
     def mm_batched(self, xh, Qidxs):
         return torch.ops.quip_lib.d4_mm_batched(xh, Qidxs, self.grid)
@@ -472,6 +507,9 @@ class HI4B1C_codebook(_SkinnyMixin, _Codebook):
 
     def mm_skinny(self, xh, Qidxs):
         return torch.ops.quip_lib.hi_mm_skinny(xh, Qidxs)
+
+    def mm_skinny_group(self, xs, Qidxs_list):
+        return list(torch.ops.quip_lib.mm_skinny_group(list(xs), list(Qidxs_list), 3, None, None, 0.0))
 
     def mm_batched(self, xh, Qidxs):
         return torch.ops.quip_lib.hi_mm_batched(xh, Qidxs)

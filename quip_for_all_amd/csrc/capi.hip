@@ -136,6 +136,26 @@ int mm_skinny(CodebookId cb, const void* x, const void* q, const CodebookArgs& a
   return skinny_gemm_launch(cb, x, q, a, y, m, n, k, (hipStream_t)s);
 }
 
+// 1..3 skinny products in one launch (e8p_skinny_group.hip): the checks of mm_skinny on every problem, nothing launched on
+// a refusal.  mode = the kernel's decode mode, mapped to the CodebookId here
+int mm_skinny_group(int mode, const void* const* xs, const void* const* qs, void* const* ys, const int32_t* ns, int count,
+                    int m, int k, const void* grid, const void* grid2, float scale, quip_stream_t s) {
+  constexpr CodebookId kOfMode[5] = {kE8P, kE8PRVQ4, kD4, kHI, kE8PRVQ3};
+  if (mode < 0 || mode > 4 || count < 1 || count > 3 || m < 1 || k < 8) return QUIP_ERR_BAD_SHAPE;
+  const CodebookId cb = kOfMode[mode];
+  const ProductChecks& c = kProduct[cb];
+  const CodebookArgs a{c.grid ? grid : nullptr, c.grid2 ? grid2 : nullptr, scale};
+  if (any_null({xs, qs, ys, ns}) || tables_null(c, a)) return QUIP_ERR_NULL_POINTER;
+  for (int g = 0; g < count; ++g)
+    if (any_null({xs[g], qs[g], ys[g]})) return QUIP_ERR_NULL_POINTER;
+  for (int g = 0; g < count; ++g)
+    if (ns[g] < 1) return QUIP_ERR_BAD_SHAPE;
+  if (any_off({a.grid}, 7) || any_off({a.grid2}, c.skinny_grid2_mask)) return QUIP_ERR_MISALIGNED;
+  for (int g = 0; g < count; ++g)
+    if (any_off({xs[g]}, 15) || any_off({qs[g]}, c.skinny_q_mask) || any_off({ys[g]}, 3)) return QUIP_ERR_MISALIGNED;
+  return skinny_group_launch(cb, xs, qs, a, ys, ns, count, m, k, (hipStream_t)s);
+}
+
 // batched (e8p_prefill_gemm.hip): x, the codes and y 16-byte aligned, the E8P / D4 table 8-byte
 int mm_batched(CodebookId cb, const void* x, const void* q, const CodebookArgs& a, void* y, int64_t m, int n, int k,
                quip_stream_t s) {
@@ -1155,6 +1175,12 @@ int quip_d4_mm_skinny(const void* x, const void* qidxs, const void* grid_f16, vo
 
 int quip_hi_mm_skinny(const void* x, const void* qidxs, void* y, int32_t m, int32_t n, int32_t k, quip_stream_t stream) {
   return mm_skinny(kHI, x, qidxs, {}, y, m, n, k, stream);
+}
+
+int quip_mm_skinny_group_f16(int32_t mode, const void* const* xs, const void* const* qidxs, void* const* ys,
+                             const int32_t* ns, int32_t count, int32_t m, int32_t k, const void* grid, const void* grid2,
+                             float resid_scale, quip_stream_t stream) {
+  return mm_skinny_group(mode, xs, qidxs, ys, ns, count, m, k, grid, grid2, resid_scale, stream);
 }
 
 int quip_e8p_mm_batched(const void* x, const void* qidxs, const void* grid, void* y, int64_t m, int32_t n, int32_t k,

@@ -145,6 +145,11 @@ int prefill_gemm_launch(CodebookId cb, const void* x, const void* qidxs, const C
 bool e8p_skinny_gemm_supported(int m, int n, int k);
 int skinny_gemm_launch(CodebookId cb, const void* x, const void* qidxs, const CodebookArgs& a, void* y, int m, int n, int k,
                        hipStream_t stream);
+// 1..3 skinny products of one codebook, m <= 32 and k in one launch (e8p_skinny_group.hip); every y[g] as skinny_gemm_launch
+// writes it.  QUIP_ERR_UNSUPPORTED: what the single launch refuses, m > 32, problems that disagree on the column blocks
+bool skinny_group_one_block(int n);      // the single launch's rule: one column block of 32 per workgroup (else two)
+int skinny_group_launch(CodebookId cb, const void* const* xs, const void* const* qidxs, const CodebookArgs& a, void* const* ys,
+                        const int* ns, int count, int m, int k, hipStream_t stream);
 // bf16 / fp32 (and plain fp16) Walsh-Hadamard transform of the last dimension (hadamard_generic.hip)
 int hadamard_generic_launch(const void* x, void* y, int64_t rows, int n, float scale, int dtype, hipStream_t stream);
 // The attention launches (decode_glue.hip and the headers it includes).  They share their operands: q, k (before the

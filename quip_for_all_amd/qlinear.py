@@ -296,12 +296,33 @@ def _gemv_planes_grouped(layers, planes):
     return [cb.mm_planes(p, l.Qidxs) for l, p in zip(layers, planes)]
 
 
+def skinny_group_enabled():
+    """QUIP_SKINNY_GROUP, off unless set to something other than "0"; read at every call (a captured step keeps the
+    route it was captured with).  On: forward_group gives the products of a group in the skinny_fp16 regime ONE launch
+    (csrc/e8p_skinny_group.hip) and its transforms the grouped launches, where cb.skinny_group_supported says so -- as
+    measured, q / k / v (profiles/skinny_group_bench.txt)."""
+    return os.environ.get("QUIP_SKINNY_GROUP", "").strip() not in ("", "0")
+
+
+def _skinny_group_ok(layers, M):
+    """the grouped skinny route's predicate for modules that read the same M activation rows"""
+    l0 = layers[0]
+    cb = l0.codebook
+    return (skinny_group_enabled() and 2 <= M <= l0.skinny_max_rows and hasattr(cb, "mm_skinny_group")
+            and all(l.regime(M) == "skinny_fp16" for l in layers)
+            and sum(l.Qidxs.numel() * l.Qidxs.element_size() for l in layers) <= _GROUP_MAX_BYTES
+            and cb.skinny_group_supported(M, [l.q_out_features for l in layers], l0.q_in_features))
+
+
 def forward_group(layers, input, rms_weight=None, rms_eps=1e-5, residual=None):
     """[l(input) for l in layers] for 1..3 QuantLinear modules that read the same bs=1 activation
     (q/k/v_proj, gate/up_proj), each of the three stages issued as ONE launch for the whole group
     instead of one per module; results are identical to calling the modules one by one
     (qlinear.py:87-115 per module).  Falls back to per-module calls whenever the group does not
-    qualify (different input transform shapes, batch > 1, non-E8P12 codebook)."""
+    qualify (different input transform shapes, batch > 1, non-E8P12 codebook).
+    With QUIP_SKINNY_GROUP (skinny_group_enabled) a batch of 2 .. skinny_max_rows rows whose modules are all in the
+    skinny_fp16 regime is grouped as well: one input transform launch, one product launch (mm_skinny_group: the bits of
+    mm_skinny per module), grouped output transforms."""
     x = input.reshape(-1, input.shape[-1])
     l0 = layers[0]
     cb = l0.codebook
@@ -314,7 +335,10 @@ def forward_group(layers, input, rms_weight=None, rms_eps=1e-5, residual=None):
                  and cb.planes_group_supported([l.q_out_features for l in layers], l0.q_in_features))
     skinny = (same_in and 2 <= x.shape[0] <= l0.skinny_max_rows and hasattr(cb, "mm_planes_rows")
               and all(cb.planes_supported(l.q_out_features, l.q_in_features) for l in layers))
-    if not same_in or skinny:   # skinny batches: every module takes its rows-mode path (planes per row)
+    skinny_group = same_in and _skinny_group_ok(layers, x.shape[0])
+    # skinny batches: every module takes its own path (rows mode: planes per row; skinny_fp16: transform, product) --
+    # unless QUIP_SKINNY_GROUP groups the skinny_fp16 regime below
+    if not same_in or (skinny and not skinny_group):
         return [l.forward_fused(input, rms_weight=rms_weight, rms_eps=rms_eps, residual=r)
                 for l, r in zip(layers, residual)]
     L_in = l0.q_in_features // l0.K_left
@@ -331,7 +355,9 @@ def forward_group(layers, input, rms_weight=None, rms_eps=1e-5, residual=None):
             [x] * n, [l0.q_in_features] * n, l0.q_in_features, l0.K_left, [l._had("had_left") for l in layers], True,
             [None] * n, [None] * n, [None] * n, [l.wscale_float / math.sqrt(L_in) for l in layers], [None] * n,
             [l._vec(l.SU) for l in layers], l0._vec(rms_weight), rms_eps)
-        zs = [l.codebook(h, l.Qidxs) for l, h in zip(layers, xh)]
+        # (the skinny_fp16 regime with QUIP_SKINNY_GROUP: the products are one launch too, the bits of mm_skinny)
+        zs = cb.mm_skinny_group(xh, [l.Qidxs for l in layers]) if skinny_group else \
+            [l.codebook(h, l.Qidxs) for l, h in zip(layers, xh)]
     # output transforms: one launch per set of modules with the same (q_out, K_right)
     ys = [None] * len(layers)
     todo = list(range(len(layers)))

@@ -115,6 +115,11 @@ _SCHEMAS = {
 _MIX_BATCH_SCHEMA = ("had_transform_mix_batch(Tensor x, int out_features, int n, int K, Tensor? had, bool transpose, "
                      "Tensor? pre, Tensor? pre2, Tensor? post, Tensor? bias, float scale, Tensor? residual=None, "
                      "Tensor? gate=None) -> Tensor")
+# 1..3 skinny products of one codebook, M <= 32 and k in ONE launch (csrc/e8p_skinny_group.hip): x[g] (M, k) fp16 times
+# the codes Qidxs[g] -> (M, n_g) fp16, every result bit identical to the codebook's *_mm_skinny op on (x[g], Qidxs[g]).
+# mode: 0 e8p, 1 e8prvq4, 2 d4, 3 hi, 4 e8prvq3; grid / grid2 / scale as that op takes them.  Beside the table, as above
+_SKINNY_GROUP_SCHEMA = ("mm_skinny_group(Tensor[] x, Tensor[] Qidxs, int mode, Tensor? grid, Tensor? grid2, float scale) "
+                        "-> Tensor[]")
 for _name, _schema in _SCHEMAS.items():
     try:
         _lib.define(_name + _schema)
@@ -987,6 +992,54 @@ def _product(op, cb, supported=None):
 
 
 _SKINNY = (e8p_mm_skinny_supported, "k % 128 == 0, n % 2 == 0")
+_SKINNY_GROUP_MODES = ("e8p", "e8prvq4", "d4", "hi", "e8prvq3")      # the kernel's decode modes (quip_mm_skinny_group_f16)
+
+
+def skinny_one_block(n, device=None):
+    """the skinny kernel's column tile for an n-column matrix on `device`: True = one column block of 32 per workgroup,
+    False = two (csrc/e8p_skinny_gemm.hip: skinny_group_one_block).  It fixes the order of the fp32 sums, so the grouped
+    launch takes only problems that agree on it."""
+    return (n + 63) // 64 < 2 * torch.cuda.get_device_properties(device).multi_processor_count // 3
+
+
+def mm_skinny_group_supported(m, ns, k, device=None):
+    """shapes quip_mm_skinny_group_f16 takes: 1..3 problems the single launch takes, M <= 32, one column tiling"""
+    return (1 <= len(ns) <= 3 and 1 <= m <= 32 and all(e8p_mm_skinny_supported(m, n, k) for n in ns)
+            and len({skinny_one_block(n, device) for n in ns}) == 1)
+
+
+_SKINNY_GROUP_ENTRY = _Entry("quip_mm_skinny_group_f16")
+
+
+def _mm_skinny_group_cuda(x, Qidxs, mode, grid, grid2, scale):
+    what = "mm_skinny_group"
+    _need(0 <= mode < len(_SKINNY_GROUP_MODES), f"{what}: mode {mode}: 0 e8p, 1 e8prvq4, 2 d4, 3 hi, 4 e8prvq3")
+    name = _SKINNY_GROUP_MODES[mode]
+    cb = _CODEBOOKS[name]
+    _need(1 <= len(x) <= 3 and len(Qidxs) == len(x), f"{what}: x / Qidxs: 1..3 problems, one x per Qidxs, got "
+          f"{len(x)} / {len(Qidxs)}")
+    _need(grid is not None or name == "hi", f"{what}: grid: {name} needs its table")
+    _need(grid2 is not None or name != "e8prvq3", f"{what}: grid2: e8prvq3 needs the packed E81B table")
+    given = {"e8p": (grid,), "e8prvq4": (grid, scale), "d4": (grid,), "hi": (), "e8prvq3": (grid, grid2, scale)}[name]
+    tabs = cb.tables(x[0], *given)
+    ops = [_operands(what, cb, xi, qi) for xi, qi in zip(x, Qidxs)]
+    m, k, ns = ops[0][2], ops[0][4], [o[3] for o in ops]
+    _need(all(o[0].device == x[0].device for o in ops), f"{what}: x: every problem on one device")
+    _need(all(o[2] == m and o[4] == k for o in ops),
+          f"{what}: x: every problem needs the same (M, k), got {[tuple(o[0].shape) for o in ops]}")
+    _need(1 <= m <= 32, f"{what}: x: M = {m} rows, the grouped launch takes 1..32")
+    _need(all(e8p_mm_skinny_supported(m, n, k) for n in ns), f"{what}: Qidxs: shapes ({m}, {ns}, {k}) need {_SKINNY[1]}")
+    _need(name != "e8prvq3" or k % 32 == 0, f"{what}: Qidxs: e8prvq3 needs k % 32 == 0")
+    _need(len({skinny_one_block(n, x[0].device) for n in ns}) == 1,
+          f"{what}: Qidxs: widths {ns} do not share a column tiling (launch them one by one)")
+    ys = [_empty((m, n), dtype=torch.float16, device=x[0].device) for n in ns]
+    arr = ctypes.c_void_p * len(ops)
+    with torch.cuda.device(x[0].device):
+        _SKINNY_GROUP_ENTRY(int(mode), arr(*[o[0].data_ptr() for o in ops]), arr(*[o[1].data_ptr() for o in ops]),
+                            arr(*[y.data_ptr() for y in ys]), (ctypes.c_int32 * len(ops))(*ns), len(ops), m, k,
+                            _ptr(tabs[0]) if name != "hi" else None, _ptr(tabs[1]) if name == "e8prvq3" else None,
+                            float(scale), _stream(x[0]))
+    return ys
 _BATCHED = (lambda m, n, k: e8p_mm_batched_supported(max(m, 1), n, k), "k % 64 == 0 and n % 2 == 0")   # (any M >= 0)
 
 
@@ -1051,6 +1104,11 @@ try:
 except RuntimeError:
     pass
 _IMPLS["had_transform_mix_batch"] = _had_transform_mix_batch_cuda
+try:
+    _lib.define(_SKINNY_GROUP_SCHEMA)
+except RuntimeError:
+    pass
+_IMPLS["mm_skinny_group"] = _mm_skinny_group_cuda
 for _cb_name, _cb in _CODEBOOKS.items():
     _IMPLS[f"{_cb_name}_mm_origorder"] = _product(f"{_cb_name}_mm_origorder", _cb)
     _IMPLS[f"{_cb_name}_mm_skinny"] = _product(f"{_cb_name}_mm_skinny", _cb, _SKINNY)
@@ -1075,6 +1133,8 @@ _reg_fake("had_transform_fused", lambda x, out_features, n, K, had, transpose, p
           rms_weight, rms_eps, gate: x.new_empty((x.shape[0], out_features)))
 _reg_fake("had_transform_mix_batch", lambda x, out_features, n, K, had, transpose, pre, pre2, post, bias, scale, residual,
           gate: x.new_empty((x.shape[0], out_features)))
+_reg_fake("mm_skinny_group", lambda x, Qidxs, mode, grid, grid2, scale:
+          [xi.new_empty((xi.shape[0], q.shape[0]), dtype=torch.float16) for xi, q in zip(x, Qidxs)])
 _reg_fake("had_transform_planes_fused", lambda x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate,
           resid_scale=0.0: x.new_empty((_planes_numel(n, resid_scale),), dtype=torch.uint8))
 _reg_fake("had_transform_planes_group", lambda x, n, K, had, transpose, pre, scale, rms_weight, rms_eps, gate,
