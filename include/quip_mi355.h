@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 26
+#define QUIP_ABI_VERSION 27
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -394,6 +394,22 @@ int quip_ldlq_panel_rvq_f32(const void* A, const void* B, const void* M, const v
  * ok and launches nothing; A, B, M, hat 16-byte aligned, P 16-byte (HI: 4-byte) aligned, idx 8-byte aligned. */
 int quip_ldlq_panel_small_f32(const void* A, const void* B, const void* M, const void* P, int64_t m, int32_t c,
                               const void* grid, int32_t codesz, void* hat, void* idx, quip_stream_t stream);
+
+/* ---- the quantiser's Hessian accumulation in one launch (ABI 27; quip.py:40-69 of the reference, QUIP.add_batch) ---------
+ * A symmetric rank-k update in fp64 on the matrix cores:
+ *     H  <- keep H  + s_h  x^T x        (both triangles written, H == H^T exactly)
+ *     mu <- keep mu + s_mu colsum(x)
+ * x: (rows, n) row major of x_dtype (QUIP_DTYPE_F16 / _BF16 / _F32), read once and widened exactly; H: fp64 (n, n), assumed
+ * symmetric (its lower triangle is what is read); mu: fp64 (n).  The running mean of 2 x x^T over ns_new samples of which
+ * ns_old are in H already: keep = ns_old / ns_new, s_h = 2 / ns_new, s_mu = 1 / ns_new.  Every element of H and mu has one
+ * owner and a fixed order of summation (rows in increasing order, QUIP_HESSIAN_ROW_BLOCK at a time), so the result's bits
+ * depend on the operands alone.  Checked in this order, before any device work: H, mu, x NULL (QUIP_ERR_NULL_POINTER);
+ * n >= 8, n % 8 == 0, rows >= 1 (else QUIP_ERR_BAD_SHAPE); another x_dtype (QUIP_ERR_UNSUPPORTED); x 16-byte, H and mu
+ * 8-byte aligned (else QUIP_ERR_MISALIGNED).  quip_hessian_row_block() returns QUIP_HESSIAN_ROW_BLOCK. */
+#define QUIP_HESSIAN_ROW_BLOCK 32
+int quip_hessian_accumulate_f64(void* H, void* mu, const void* x, int32_t x_dtype, int64_t rows, int32_t n, double keep,
+                                double s_h, double s_mu, quip_stream_t stream);
+int32_t quip_hessian_row_block(void);
 
 /* Rows mode for the other table modes of the same kernel.  mode 0: E8P12 (quip_e8p_gemv_planes_rows is this call);
  * mode 64: D4 (qidxs uint8 (n, k/4), grid = fp16 (256, 4) table; HI through its virtual 2k layout, see

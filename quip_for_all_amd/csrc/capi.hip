@@ -514,6 +514,17 @@ int quip_ldlq_panel_small_f32(const void* A, const void* B, const void* M, const
   return ldlq_panel_small_launch(A, B, M, P, m, c, grid, codesz, hat, idx, (hipStream_t)stream);
 }
 
+int quip_hessian_accumulate_f64(void* H, void* mu, const void* x, int32_t x_dtype, int64_t rows, int32_t n, double keep,
+                                double s_h, double s_mu, quip_stream_t stream) {
+  if (!H || !mu || !x) return QUIP_ERR_NULL_POINTER;
+  if (n < 8 || n % 8 != 0 || rows < 1) return QUIP_ERR_BAD_SHAPE;
+  if (x_dtype != QUIP_DTYPE_F16 && x_dtype != QUIP_DTYPE_BF16 && x_dtype != QUIP_DTYPE_F32) return QUIP_ERR_UNSUPPORTED;
+  if (!aligned16(x) || any_off({H, mu}, 7)) return QUIP_ERR_MISALIGNED;
+  return hessian_accumulate_launch(H, mu, x, x_dtype, rows, n, keep, s_h, s_mu, (hipStream_t)stream);
+}
+
+int32_t quip_hessian_row_block(void) { return hessian_row_block(); }
+
 int32_t quip_e8p_gemv_max_rows(int32_t n, int32_t k) { return (n > 0 && k > 0) ? e8p_gemv_mfma_max_rows(n, k) : 0; }
 
 int quip_e8p_gemv_planes_rows(const void* planes, const void* qidxs, const void* grid_packed_abs, void* y,

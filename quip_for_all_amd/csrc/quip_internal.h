@@ -110,6 +110,11 @@ int ldlq_panel_rvq_launch(const void* A, const void* B, const void* M, const voi
 // (grid unused); P fp32 (c / codesz, codesz, codesz) or null -> hat fp32 (m, c), idx int64 (m, c / codesz)
 int ldlq_panel_small_launch(const void* A, const void* B, const void* M, const void* P, int64_t m, int c, const void* grid,
                             int codesz, void* hat, void* idx, hipStream_t stream);
+// the quantiser's Hessian accumulation (hessian.hip): H (n, n), mu (n) fp64, x (rows, n) of QUIP_DTYPE_*;
+// H <- keep H + s_h x^T x (both triangles), mu <- keep mu + s_mu colsum(x).  n >= 8, n % 8 == 0, rows >= 1
+int hessian_accumulate_launch(void* H, void* mu, const void* x, int dtype, int64_t rows, int n, double keep, double s_h,
+                              double s_mu, hipStream_t stream);
+int hessian_row_block();
 // rows mode: up to e8p_gemv_mfma_max_rows(n, k) <= 5 activation rows against one matrix in one pass
 int e8p_gemv_mfma_max_rows(int n, int k, int mode = 0);   // mode: 0 E8P12, 64 D4 / HI, 40 E8P12RVQ3B (2k virtual)
 int e8p_gemv_mfma_rows_launch(const void* planes, const void* qidxs, const void* grid, void* y, int mrows, int n,

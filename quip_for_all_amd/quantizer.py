@@ -323,7 +323,7 @@ class QuipQuantizer:
         device.  Then model.config.quantization_config, `is_quantized`, and `save` / `tokenizer.save_pretrained` when
         save_dir is given.  The returned model runs as load_quantized_model(save_dir) does (same post-load step).
         `dataset`: see calibration_samples; model_seqlen=None takes the model's."""
-        from .quip import QUIP
+        from .quip import QUIP, SharedHessianInputs, hessian_fused_enabled
         self._refuse_unbuilt(model)
         if isinstance(tokenizer, str):
             from transformers import AutoTokenizer
@@ -349,9 +349,16 @@ class QuipQuantizer:
             block = block.to(device).float()
             layers = get_layers(block, skip=self.modules_to_not_convert)
             quant_method = {name: QUIP(layer, self.codebook) for name, layer in layers.items()}
-            handles = [layer.register_forward_hook(
-                lambda _, inp, out, name=name: quant_method[name].add_batch(inp[0].data, out.data))
-                for name, layer in layers.items()]
+            if hessian_fused_enabled():      # QUIP_HESSIAN_FUSED: q / k / v_proj and gate / up_proj accumulate their input once
+                shared = SharedHessianInputs()
+                handles = [layer.register_forward_hook(
+                    lambda _, inp, out, name=name: shared.add_batch(quant_method[name], inp[0], out.data))
+                    for name, layer in layers.items()]
+            else:
+                shared = None
+                handles = [layer.register_forward_hook(
+                    lambda _, inp, out, name=name: quant_method[name].add_batch(inp[0].data, out.data))
+                    for name, layer in layers.items()]
             layer_outputs = []
             try:
                 for hidden, kwargs in zip(layer_inputs, layer_kwargs):
@@ -361,6 +368,8 @@ class QuipQuantizer:
             finally:
                 for h in handles:
                     h.remove()
+                if shared is not None:
+                    shared.forget()
             attrs = {}
             for name in layers:
                 attrs[name] = quant_method[name].quant(

@@ -3,12 +3,69 @@ the proxy Hessian of one nn.Linear from calibration inputs, incoherence-process 
 Hadamard on both sides), LDLQ-round against a codebook, and hand back what QuantLinear.pack() consumes.
 Host logic in torch; LDLQ for E8P12 rounds a panel of 128 columns per launch (quant.LDLQ_panels, csrc/quantize.hip), the
 other codebooks go through cb.quantize() per column group.  QuipQuantizer.quantize_model drives this class over a model."""
+import itertools
 import math
+import os
 
 import torch
 import torch.nn as nn
 
-from .quant import LDLQ, get_hadK, matmul_hadU, matmul_hadUt
+from .quant import LDLQ, get_hadK, matmul_hadU, matmul_hadUt, parse_ldlq_fused
+
+_HESSIAN_FUSED = None
+HESSIAN_FUSED_DTYPES = (torch.float16, torch.bfloat16, torch.float32)
+
+
+def hessian_fused_enabled():
+    """QUIP_HESSIAN_FUSED, off unless set; read once per process.  On: QUIP.add_batch accumulates CUDA inputs of
+    HESSIAN_FUSED_DTYPES with one torch.ops.quip_lib.hessian_accumulate launch (csrc/hessian.hip), and quantize_model
+    accumulates a tensor that several modules of a block receive once (SharedHessianInputs).  The launch scales the sum
+    X^T X by 2 / nsamples where the torch expression scales x by sqrt(2 / nsamples) first: the two routes agree to
+    rounding, not bit for bit."""
+    global _HESSIAN_FUSED
+    if _HESSIAN_FUSED is None:
+        _HESSIAN_FUSED = parse_ldlq_fused(os.environ.get("QUIP_HESSIAN_FUSED"), default=False)
+    return _HESSIAN_FUSED
+
+
+_history = itertools.count(1)
+
+
+def tensor_identity(t):
+    """what two tensors share when they are the same values at the same place: storage pointer, offset, shape, strides, dtype,
+    device and version counter.  Only meaningful while both tensors are alive: a freed tensor's address is handed out again."""
+    return (t.untyped_storage().data_ptr(), t.storage_offset(), tuple(t.shape), t.stride(), t.dtype, t.device, t._version)
+
+
+class SharedHessianInputs:
+    """The forward hooks of one block: modules that receive the same tensor (q / k / v_proj, gate / up_proj) accumulate it
+    once, the later ones copy H and mu from the module that did the work -- n^2 elements of traffic against n^2 rows
+    operations.  The last input stays referenced until the next one arrives, so its identity cannot be another tensor's; a
+    module copies only from a donor of equal columns whose H, mu and nsamples were its own before the donor's update (the
+    history token of QUIP).  Every QUIP keeps its own H."""
+
+    def __init__(self):
+        self.copies = 0         # accumulations answered by a copy
+        self.forget()
+
+    def forget(self):
+        """drop the reference to the last input"""
+        self._inp = self._key = self._donor = self._before = None
+
+    def add_batch(self, quip, inp, out=None):
+        """quip.add_batch(inp.data, out), or its result copied from the module that has just accumulated the same tensor"""
+        key = tensor_identity(inp)
+        donor = self._donor
+        if (self._inp is not None and key == self._key and donor is not quip and donor.columns == quip.columns
+                and quip.history == self._before):
+            quip.H.copy_(donor.H)
+            quip.mu.copy_(donor.mu)
+            quip.nsamples, quip.history = donor.nsamples, donor.history
+            self.copies += 1
+            return
+        before = quip.history
+        quip.add_batch(inp.data, out)
+        self._inp, self._key, self._donor, self._before = inp, key, quip, before
 
 
 class QUIP:
@@ -20,12 +77,21 @@ class QUIP:
         self.H = torch.zeros((self.columns, self.columns), dtype=torch.float64, device=self.dev)
         self.mu = torch.zeros((self.columns,), dtype=torch.float64, device=self.dev)
         self.nsamples = 0
+        self.history = 0        # equal tokens: equal H, mu and nsamples (0: nothing accumulated; SharedHessianInputs)
         self.cb = cb.to(self.dev)
 
     def add_batch(self, inp, out=None):
         """running mean of 2 x x^T over the calibration rows (quip.py:40-69)"""
-        x = inp.reshape(-1, inp.shape[-1]).to(torch.float64).t()            # (columns, rows)
+        self.history = next(_history)
         batch = 1 if inp.dim() == 2 else inp.shape[0]
+        if hessian_fused_enabled() and inp.is_cuda and inp.dtype in HESSIAN_FUSED_DTYPES:
+            x = inp.reshape(-1, inp.shape[-1])
+            if x.is_contiguous() and x.shape[0] >= 1 and self.columns >= 8 and self.columns % 8 == 0:
+                ns = self.nsamples + batch
+                torch.ops.quip_lib.hessian_accumulate(self.H, self.mu, x, self.nsamples / ns, 2 / ns, 1 / ns)
+                self.nsamples = ns
+                return
+        x = inp.reshape(-1, inp.shape[-1]).to(torch.float64).t()            # (columns, rows)
         keep = self.nsamples / (self.nsamples + batch)
         self.H *= keep
         self.mu *= keep

@@ -1264,6 +1264,38 @@ def _ldlq_panel_small_cuda(A, B, M, P, grid):
     return hat, idx
 
 
+# ---- quantise-time: the Hessian accumulation of QUIP.add_batch in one launch (csrc/hessian.hip) -----------
+HESSIAN_DTYPES = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}      # QUIP_DTYPE_*
+
+
+def hessian_row_block():
+    """rows of x one stage of the kernel's loop takes (QUIP_HESSIAN_ROW_BLOCK)"""
+    return capi.lib().quip_hessian_row_block()
+
+
+def _hessian_accumulate_cuda(H, mu, x, keep, s_h, s_mu):
+    """H (n, n), mu (n) fp64, x (rows, n) fp16 | bf16 | fp32: H <- keep H + s_h x^T x, mu <- keep mu + s_mu colsum(x)"""
+    _need(x.is_cuda and x.dim() == 2 and x.dtype in HESSIAN_DTYPES and x.is_contiguous(),
+          "hessian_accumulate: x must be a contiguous float16, bfloat16 or float32 (rows, n) CUDA tensor")
+    rows, n = x.shape
+    _need(n >= 8 and n % 8 == 0 and rows >= 1, f"hessian_accumulate: x is ({rows}, {n}) (rows >= 1, n a multiple of 8)")
+    _need(H.dtype == torch.float64 and H.is_contiguous() and H.device == x.device and tuple(H.shape) == (n, n),
+          "hessian_accumulate: H must be contiguous float64 (n, n) on x's device")
+    _need(mu.dtype == torch.float64 and mu.is_contiguous() and mu.device == x.device and tuple(mu.shape) == (n,),
+          "hessian_accumulate: mu must be contiguous float64 (n) on x's device")
+    with torch.cuda.device(x.device):
+        capi.check(capi.lib().quip_hessian_accumulate_f64(H.data_ptr(), mu.data_ptr(), x.data_ptr(), HESSIAN_DTYPES[x.dtype],
+                                                          rows, n, float(keep), float(s_h), float(s_mu), _stream(x)),
+                   "quip_hessian_accumulate_f64")
+
+
+try:
+    _lib.define("hessian_accumulate(Tensor(a!) H, Tensor(b!) mu, Tensor x, float keep, float s_h, float s_mu) -> ()")
+    _lib.impl("hessian_accumulate", _hessian_accumulate_cuda, "CUDA")
+    _reg_fake("hessian_accumulate", lambda H, mu, x, keep, s_h, s_mu: None)
+except RuntimeError:
+    pass
+
 try:
     _lib.define("ldlq_panel_small(Tensor A, Tensor B, Tensor M, Tensor? P, Tensor? grid) -> (Tensor hat, Tensor idx)")
     _lib.impl("ldlq_panel_small", _ldlq_panel_small_cuda, "CUDA")
