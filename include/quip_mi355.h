@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 27
+#define QUIP_ABI_VERSION 28
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -68,7 +68,7 @@ int quip_hadamard_f16(const void* x, void* y, int64_t rows, int32_t n, float sca
 /* The same transform for every dtype the reference's op accepts (fast_hadamard_transform takes fp16 / bf16 / fp32,
  * register_lib.py:10-20; fp32 inside, one rounding to the I/O type).  dtype: QUIP_DTYPE_*.  fp16 goes to
  * quip_hadamard_f16's kernels. */
-enum { QUIP_DTYPE_F16 = 0, QUIP_DTYPE_BF16 = 1, QUIP_DTYPE_F32 = 2 };
+enum { QUIP_DTYPE_F16 = 0, QUIP_DTYPE_BF16 = 1, QUIP_DTYPE_F32 = 2, QUIP_DTYPE_F64 = 3 };
 int quip_hadamard(const void* x, void* y, int64_t rows, int32_t n, float scale, int32_t dtype,
                   quip_stream_t stream);
 
@@ -410,6 +410,21 @@ int quip_ldlq_panel_small_f32(const void* A, const void* B, const void* M, const
 int quip_hessian_accumulate_f64(void* H, void* mu, const void* x, int32_t x_dtype, int64_t rows, int32_t n, double keep,
                                 double s_h, double s_mu, quip_stream_t stream);
 int32_t quip_hessian_row_block(void);
+
+/* ---- the quantiser's incoherence transforms in fp32 / fp64 (ABI 28; quip.py:124-128, 162-167 of the reference) -----------
+ * One launch over the rows of x (rows, in_cols) row major of dtype QUIP_DTYPE_F32 / _F64, n = K L, L a power of two:
+ *     y[r, :out_cols] = s_out * ( pad_n(s_in * x[r]) (Hk (x) H_L)^T scale / sqrt(L) )[:out_cols]
+ * on the (K, L) view of a row -- the Sylvester Walsh-Hadamard transform of every segment of L, then the K x K mix Hk = hadK
+ * (hadK_t 0) or its transpose (hadK_t != 0) across the segments.  hadK: fp32 (K, K) row major, ignored when K == 1; s_in
+ * (in_cols), s_out (out_cols): vectors of the dtype or NULL; columns in_cols .. n read as zero, columns out_cols .. n are not
+ * stored.  store_t != 0 stores y transposed, (out_cols, rows) row major.  All arithmetic is in the dtype, in a fixed order: a
+ * row's bits depend on that row, hadK and the scales alone.  Checked in this order, before any device work: y, x NULL, hadK
+ * NULL with K > 1 (QUIP_ERR_NULL_POINTER); rows >= 1, K >= 1, n >= 1, n % K == 0, L a power of two, in_cols and out_cols in
+ * [1, n] (else QUIP_ERR_BAD_SHAPE); x and y 16-byte aligned (else QUIP_ERR_MISALIGNED); y overlapping x
+ * (QUIP_ERR_BAD_SHAPE); another dtype, K > 64, L < 64 or n > 32768 (QUIP_ERR_UNSUPPORTED). */
+int quip_had_wide_rows(void* y, const void* x, int32_t dtype, int64_t rows, int32_t in_cols, int32_t out_cols, int32_t n,
+                       int32_t K, const float* hadK, int32_t hadK_t, const void* s_in, const void* s_out, double scale,
+                       int32_t store_t, quip_stream_t stream);
 
 /* Rows mode for the other table modes of the same kernel.  mode 0: E8P12 (quip_e8p_gemv_planes_rows is this call);
  * mode 64: D4 (qidxs uint8 (n, k/4), grid = fp16 (256, 4) table; HI through its virtual 2k layout, see

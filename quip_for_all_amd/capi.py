@@ -35,6 +35,7 @@ SIGNATURES = {
     "quip_ldlq_panel_small_f32": [_P, _P, _P, _P, _I64, _I32, _P, _I32, _P, _P, _P],
     "quip_hessian_accumulate_f64": [_P, _P, _P, _I32, _I64, _I32, _c.c_double, _c.c_double, _c.c_double, _P],
     "quip_hessian_row_block": [],
+    "quip_had_wide_rows": [_P, _P, _I32, _I64, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _c.c_double, _I32, _P],
     "quip_gemv_max_rows_mode": [_I32, _I32, _I32],
     "quip_gemv_planes_rows_mode": [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P],
     "quip_e8p_gemv_planes_rows": [_P, _P, _P, _P, _I32, _I32, _I32, _P],
@@ -136,6 +137,7 @@ _INTERNAL = {
     "quip_e8p_gemv_v2_plan": [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "quip_e8p_gemv_tuned": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P],
     "quip_had_plan": [_P, _I32, _I32, _I64, _I32, _I32, _I32, _P],
+    "quip_had_wide_rows_tuned": [_P, _P, _I32, _I64, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _c.c_double, _I32, _I32, _P],
 }
 
 class HadProblem(_c.Structure):

@@ -525,6 +525,34 @@ int quip_hessian_accumulate_f64(void* H, void* mu, const void* x, int32_t x_dtyp
 
 int32_t quip_hessian_row_block(void) { return hessian_row_block(); }
 
+static int had_wide_rows_entry(void* y, const void* x, int32_t dtype, int64_t rows, int32_t in_cols, int32_t out_cols,
+                               int32_t n, int32_t K, const float* hadK, int32_t hadK_t, const void* s_in, const void* s_out,
+                               double scale, int32_t store_t, int swizzle, quip_stream_t stream) {
+  if (!y || !x || (K > 1 && !hadK)) return QUIP_ERR_NULL_POINTER;
+  const int rc = had_wide_rows_check(dtype, rows, in_cols, out_cols, n, K);
+  if (rc == QUIP_ERR_BAD_SHAPE) return rc;
+  if (any_off({x, y}, 15)) return QUIP_ERR_MISALIGNED;
+  const uintptr_t elem = dtype == QUIP_DTYPE_F64 ? 8 : 4, xb = reinterpret_cast<uintptr_t>(x), yb = reinterpret_cast<uintptr_t>(y);
+  if (xb < yb + (uintptr_t)rows * out_cols * elem && yb < xb + (uintptr_t)rows * in_cols * elem) return QUIP_ERR_BAD_SHAPE;
+  if (rc != QUIP_OK) return rc;
+  return had_wide_rows_launch(y, x, dtype, rows, in_cols, out_cols, n, K, hadK, hadK_t, s_in, s_out, scale, store_t, swizzle,
+                              (hipStream_t)stream);
+}
+
+int quip_had_wide_rows(void* y, const void* x, int32_t dtype, int64_t rows, int32_t in_cols, int32_t out_cols, int32_t n,
+                       int32_t K, const float* hadK, int32_t hadK_t, const void* s_in, const void* s_out, double scale,
+                       int32_t store_t, quip_stream_t stream) {
+  return had_wide_rows_entry(y, x, dtype, rows, in_cols, out_cols, n, K, hadK, hadK_t, s_in, s_out, scale, store_t, 1, stream);
+}
+
+// not in the header: the same call with the XCD swizzle of the row tiles as an argument (tools/incoherence_bench.py)
+int quip_had_wide_rows_tuned(void* y, const void* x, int32_t dtype, int64_t rows, int32_t in_cols, int32_t out_cols,
+                             int32_t n, int32_t K, const float* hadK, int32_t hadK_t, const void* s_in, const void* s_out,
+                             double scale, int32_t store_t, int32_t swizzle, quip_stream_t stream) {
+  return had_wide_rows_entry(y, x, dtype, rows, in_cols, out_cols, n, K, hadK, hadK_t, s_in, s_out, scale, store_t, swizzle,
+                             stream);
+}
+
 int32_t quip_e8p_gemv_max_rows(int32_t n, int32_t k) { return (n > 0 && k > 0) ? e8p_gemv_mfma_max_rows(n, k) : 0; }
 
 int quip_e8p_gemv_planes_rows(const void* planes, const void* qidxs, const void* grid_packed_abs, void* y,

@@ -115,6 +115,12 @@ int ldlq_panel_small_launch(const void* A, const void* B, const void* M, const v
 int hessian_accumulate_launch(void* H, void* mu, const void* x, int dtype, int64_t rows, int n, double keep, double s_h,
                               double s_mu, hipStream_t stream);
 int hessian_row_block();
+// the quantiser's incoherence transform of fp32 / fp64 rows (had_wide.hip): the shape rules (BAD_SHAPE) and the served range
+// (UNSUPPORTED) of quip_had_wide_rows, and the launch, which asks them again.  swizzle: neighbouring row tiles on one XCD
+int had_wide_rows_check(int dtype, int64_t rows, int in_cols, int out_cols, int n, int K);
+int had_wide_rows_launch(void* y, const void* x, int dtype, int64_t rows, int in_cols, int out_cols, int n, int K,
+                         const float* hadK, int hadK_t, const void* s_in, const void* s_out, double scale, int store_t,
+                         int swizzle, hipStream_t stream);
 // rows mode: up to e8p_gemv_mfma_max_rows(n, k) <= 5 activation rows against one matrix in one pass
 int e8p_gemv_mfma_max_rows(int n, int k, int mode = 0);   // mode: 0 E8P12, 64 D4 / HI, 40 E8P12RVQ3B (2k virtual)
 int e8p_gemv_mfma_rows_launch(const void* planes, const void* qidxs, const void* grid, void* y, int mrows, int n,

@@ -117,6 +117,54 @@ def matmul_hadUt(X, hadK, K, n):
     return matmul_hadU(X, hadK, K, n, transpose=True)
 
 
+_INCOHERENCE_FUSED = None
+INCOHERENCE_FUSED_DTYPES = (torch.float32, torch.float64)
+
+
+def incoherence_fused_enabled():
+    """QUIP_INCOHERENCE_FUSED, off unless set; read once per process.  On: incoherence_in / incoherence_out of fp32 / fp64
+    CUDA tensors are two torch.ops.quip_lib.had_wide_rows launches per matrix (csrc/had_wide.hip) where both sides' (K, L, n)
+    are in the kernel's range.  The two routes agree to rounding, not bit for bit."""
+    global _INCOHERENCE_FUSED
+    if _INCOHERENCE_FUSED is None:
+        _INCOHERENCE_FUSED = parse_ldlq_fused(os.environ.get("QUIP_INCOHERENCE_FUSED"), default=False)
+    return _INCOHERENCE_FUSED
+
+
+def incoherence_route(t, lK, lN, rK, rN):
+    """"fused" or "torch" for a matrix whose columns transform with (lK, lN) and whose rows with (rK, rN)"""
+    if not (incoherence_fused_enabled() and t.is_cuda and t.dtype in INCOHERENCE_FUSED_DTYPES):
+        return "torch"
+    from .register_lib import had_wide_supported
+    return "fused" if had_wide_supported(t.dtype, lN, lK) and had_wide_supported(t.dtype, rN, rK) else "torch"
+
+
+def _had_wide(x, hadK, K, n, transpose, s_in, s_out, out_cols, store_t=True):
+    hk = None if K == 1 else hadK.to(device=x.device, dtype=torch.float32).contiguous()
+    return torch.ops.quip_lib.had_wide_rows(x.contiguous(), n, K, hk, transpose, s_in, s_out, 1.0, out_cols, store_t)
+
+
+def incoherence_in(H, w, SU, SV, lhad, lK, lN, rhad, rK, rN):
+    """H <- U_L (SU H SU) U_L^T,  W <- U_R (SV W SU) U_L^T   (quip.py:124-128): (H, w) in the incoherent basis.  The fused
+    route transforms the rows of a matrix and stores them transposed, once per side; for W that is its columns' side first
+    and its rows' side second, the same function as the torch order to rounding."""
+    if incoherence_route(H, lK, lN, rK, rN) == "fused":
+        H = _had_wide(_had_wide(H, lhad, lK, lN, True, SU, None, lN), lhad, lK, lN, True, SU, None, lN, store_t=False)
+        w = _had_wide(_had_wide(w, lhad, lK, lN, True, SU, None, lN), rhad, rK, rN, True, SV, None, rN)
+        return H, w
+    H = matmul_hadUt(matmul_hadUt(H * SU, lhad, lK, lN).T * SU, lhad, lK, lN)
+    w = matmul_hadUt(matmul_hadUt(w.T * SV, rhad, rK, rN).T * SU, lhad, lK, lN)
+    return H, w
+
+
+def incoherence_out(hat_w, SU, SV, lhad, lK, lN, rhad, rK, rN, columns, rows):
+    """back to the original basis (quip.py:162-167): hat_w (rN, lN) -> (rows, columns)"""
+    if incoherence_route(hat_w, lK, lN, rK, rN) == "fused":
+        return _had_wide(_had_wide(hat_w, lhad, lK, lN, False, None, SU, columns), rhad, rK, rN, False, None, SV, rows)
+    return (matmul_hadU((matmul_hadU(hat_w, lhad, lK, lN)[..., :columns] * SU).T, rhad, rK, rN)
+            [..., :rows] * SV).T
+
+
 def block_LDL(L, b):
     """Cholesky factor L (n, n) -> block-unit-lower factor: every block column i (width b) is multiplied from
     the right by the inverse of its diagonal block, so the diagonal blocks become identities (quant.py:90-102)."""

@@ -10,7 +10,7 @@ import os
 import torch
 import torch.nn as nn
 
-from .quant import LDLQ, get_hadK, matmul_hadU, matmul_hadUt, parse_ldlq_fused
+from .quant import LDLQ, get_hadK, incoherence_in, incoherence_out, parse_ldlq_fused
 
 _HESSIAN_FUSED = None
 HESSIAN_FUSED_DTYPES = (torch.float16, torch.bfloat16, torch.float32)
@@ -127,8 +127,7 @@ class QUIP:
         lhad, lK, lN = get_hadK(self.columns, use_rand=use_rand)
         rhad, rK, rN = get_hadK(self.rows, use_rand=use_rand)
         # incoherence processing: H <- U_L (SU H SU) U_L^T,  W <- U_R (SV W SU) U_L^T   (quip.py:124-128)
-        H = matmul_hadUt(matmul_hadUt(H * SU, lhad, lK, lN).T * SU, lhad, lK, lN)
-        w = matmul_hadUt(matmul_hadUt(w.T * SV, rhad, rK, rN).T * SU, lhad, lK, lN)
+        H, w = incoherence_in(H, w, SU, SV, lhad, lK, lN, rhad, rK, rN)
         diag = torch.arange(H.shape[0], device=self.dev)
         for attempt in range(10):
             H[diag, diag] += sigma_reg
@@ -145,8 +144,7 @@ class QUIP:
         hat_w, Qidxs = LDLQ(w / w_scale, H, L, self.cb, quip_tune_iters, buf_cols=128 if use_buffered else self.cb.codesz)
         hat_w = hat_w * w_scale
         # back to the original basis (quip.py:162-167)
-        deq = (matmul_hadU((matmul_hadU(hat_w, lhad, lK, lN)[..., :self.columns] * SU).T, rhad, rK, rN)
-               [..., :self.rows] * SV).T
+        deq = incoherence_out(hat_w, SU, SV, lhad, lK, lN, rhad, rK, rN, self.columns, self.rows)
         if rescale_WH:
             deq = deq / scaleWH[None, :]
         self.layer.weight.data = deq.reshape(self.layer.weight.shape).to(self.layer.weight.dtype)

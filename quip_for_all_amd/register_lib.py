@@ -1296,6 +1296,62 @@ try:
 except RuntimeError:
     pass
 
+# ---- quantise-time: the incoherence transforms of H and W in fp32 / fp64 (csrc/had_wide.hip) ------------------
+HAD_WIDE_DTYPES = {torch.float32: 2, torch.float64: 3}      # QUIP_DTYPE_*
+HAD_WIDE_MAX_K, HAD_WIDE_MIN_L, HAD_WIDE_MAX_N = 64, 64, 32768
+
+
+def had_wide_supported(dtype, n, K):
+    """the (dtype, K, L, n) range quip_had_wide_rows serves; everything else it answers with UNSUPPORTED"""
+    if dtype not in HAD_WIDE_DTYPES or K < 1 or n < 1 or n % K != 0:
+        return False
+    L = n // K
+    return L & (L - 1) == 0 and L >= HAD_WIDE_MIN_L and K <= HAD_WIDE_MAX_K and n <= HAD_WIDE_MAX_N
+
+
+def had_wide_tile_rows(dtype, n):
+    """R, the rows one workgroup of had_wide_rows_kernel holds: min(8, 32 / CH), CH = the 16-byte pieces per lane and row
+    (512 lanes) rounded up to a power of two"""
+    chunk = 512 * 16 // torch.empty((), dtype=dtype).element_size()
+    ch = 1
+    while ch * chunk < n:
+        ch *= 2
+    return min(8, 32 // ch)
+
+
+def _had_wide_rows_cuda(x, n, K, hadK, hadK_t, s_in, s_out, scale, out_cols, store_t):
+    """x (rows, in_cols) fp32 | fp64 -> s_out * (pad_n(s_in * x) (Hk (x) H_L)^T scale / sqrt(L))[:, :out_cols], transposed to
+    (out_cols, rows) when store_t; quant.matmul_hadU with the scales and the transposition in one launch"""
+    _need(x.is_cuda and x.dim() == 2 and x.dtype in HAD_WIDE_DTYPES and x.is_contiguous(),
+          "had_wide_rows: x must be a contiguous float32 or float64 (rows, in_cols) CUDA tensor")
+    rows, in_cols = x.shape
+    _need(rows >= 1 and 1 <= in_cols <= n and 1 <= out_cols <= n, f"had_wide_rows: x is ({rows}, {in_cols}), n = {n}, "
+          f"out_cols = {out_cols} (rows >= 1, in_cols and out_cols in [1, n])")
+    _need(had_wide_supported(x.dtype, n, K), f"had_wide_rows: n = {n}, K = {K} is outside the kernel's range "
+          f"(L = n / K a power of two >= {HAD_WIDE_MIN_L}, K <= {HAD_WIDE_MAX_K}, n <= {HAD_WIDE_MAX_N})")
+    _need(K == 1 or (hadK is not None and hadK.dtype == torch.float32 and hadK.is_contiguous() and hadK.device == x.device
+                     and tuple(hadK.shape) == (K, K)), "had_wide_rows: hadK must be contiguous float32 (K, K) on x's device")
+    for name, s, cols in (("s_in", s_in, in_cols), ("s_out", s_out, out_cols)):
+        _need(s is None or (s.dtype == x.dtype and s.is_contiguous() and s.device == x.device and tuple(s.shape) == (cols,)),
+              f"had_wide_rows: {name} must be a contiguous ({cols},) vector of x's dtype on x's device, or None")
+    y = _empty((out_cols, rows) if store_t else (rows, out_cols), dtype=x.dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        capi.check(capi.lib().quip_had_wide_rows(y.data_ptr(), x.data_ptr(), HAD_WIDE_DTYPES[x.dtype], rows, in_cols, out_cols,
+                                                 n, K, _ptr(hadK) if K > 1 else None, int(bool(hadK_t)), _ptr(s_in),
+                                                 _ptr(s_out), float(scale), int(bool(store_t)), _stream(x)),
+                   "quip_had_wide_rows")
+    return y
+
+
+try:
+    _lib.define("had_wide_rows(Tensor x, int n, int K, Tensor? hadK, bool hadK_t, Tensor? s_in, Tensor? s_out, float scale, "
+                "int out_cols, bool store_t) -> Tensor")
+    _lib.impl("had_wide_rows", _had_wide_rows_cuda, "CUDA")
+    _reg_fake("had_wide_rows", lambda x, n, K, hadK, hadK_t, s_in, s_out, scale, out_cols, store_t:
+              x.new_empty((out_cols, x.shape[0]) if store_t else (x.shape[0], out_cols)))
+except RuntimeError:
+    pass
+
 try:
     _lib.define("ldlq_panel_small(Tensor A, Tensor B, Tensor M, Tensor? P, Tensor? grid) -> (Tensor hat, Tensor idx)")
     _lib.impl("ldlq_panel_small", _ldlq_panel_small_cuda, "CUDA")
