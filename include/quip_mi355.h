@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define QUIP_ABI_VERSION 28
+#define QUIP_ABI_VERSION 29
 
 typedef void* quip_stream_t; /* hipStream_t */
 
@@ -127,6 +127,42 @@ int quip_hi_mm_skinny(const void* x, const void* qidxs, void* y, int32_t m, int3
 int quip_mm_skinny_group_f16(int32_t mode, const void* const* xs, const void* const* qidxs, void* const* ys,
                              const int32_t* ns, int32_t count, int32_t m, int32_t k, const void* grid, const void* grid2,
                              float resid_scale, quip_stream_t stream);
+/* ---- the MLP half of a sparse-MoE block (Mixtral) at 1..31 rows, experts routed on the device (ABI 29) ----------
+ * Three launches between which the host reads nothing; the Hadamard transforms between them are the transform entries.
+ * P = rows top_k pairs (pair p = row top_k + slot), sorted "by expert, then by row": start [experts + 1] int32 (expert e owns
+ * sorted positions [start[e], start[e + 1])), pair_of [P] int32 (the pair at each position), weight [P] fp32.
+ *
+ * quip_moe_route_rows_f16: per row xn = (h * (1 / sqrt(sum h^2 / hidden + eps))) * ln_weight in fp32; logits
+ * fp16(xn . router_weight[e]) (router_weight [experts, hidden] fp16, fp32 sums); softmax over them in fp32; the top_k
+ * largest logits, the lower index on a tie; the weights divided by their sum when renorm != 0.  Writes start, pair_of, weight
+ * and the signed rows xs [stacks, P, hidden] fp16: xs[g][s] = fp16(xn[row] * su_g[e]) for the pair (row, e) at position s,
+ * su_gate / su_up [experts, hidden] fp16 or NULL (ones); stacks 1..2.  The order is a function of the ids alone.  A row of
+ * NaN / inf yields NaN for its own pairs and in-range indices.  rows >= 1, hidden % 8 == 0, 1 <= top_k <= experts (else
+ * QUIP_ERR_BAD_SHAPE); rows <= 31, experts <= 64, top_k <= 8 (else QUIP_ERR_UNSUPPORTED); fp16 operands 16-byte aligned.
+ *
+ * quip_moe_mm_skinny_f16: y [stacks, P, n] fp16, y[g][s] = fp16(scale[g, e] * fp16(x[g][s] . decode(qidxs[g][e])^T)) for the
+ * expert e that owns s; x [stacks, P, k] fp16, qidxs: host array of `stacks` device pointers to stacked codes
+ * [experts, n, k / 8], scale [stacks, experts] fp32, m = the most rows one expert can own (the token count).  Before the
+ * scale a row is bit identical to quip_e8p_mm_skinny on that expert's rows and codes alone.  Experts without rows stream
+ * no codes.  Whatever start holds, only rows inside [0, P) are read and written.  mode as quip_mm_skinny_group_f16:
+ * 0 E8P12; 1..4 QUIP_ERR_UNSUPPORTED.  m <= 31, experts <= 64, m <= pairs <= 8 m, k % 128 == 0, n % 2 == 0 (else
+ * QUIP_ERR_UNSUPPORTED); x and the codes 16-byte, grid_packed_abs 8-byte aligned.
+ *
+ * quip_moe_combine_rows_f16: mode 0, rows = P / top_k: out[r] = fp16(residual[r] + sum_slots weight[s] * (sv[e(s)] (.) t[s])),
+ * fp32 FMA in ascending slot order, s the position of pair r top_k + slot; t [P, width] fp16, sv [experts, width] fp16 or
+ * NULL, residual [rows, width] fp16 or NULL.  mode 1, rows = P: out[s] = fp16((fp16(t2[s] sv2[e]) * silu(fp16(t[s] sv[e])))
+ * * su[e]) -- gate in t, up in t2, down_proj's sign vectors in su.  width % 8 == 0 (else QUIP_ERR_BAD_SHAPE). */
+int quip_moe_route_rows_f16(const void* h, const void* ln_weight, const void* router_weight, const void* su_gate,
+                            const void* su_up, void* xs, int32_t* start, int32_t* pair_of, float* weight, int32_t rows,
+                            int32_t hidden, int32_t experts, int32_t top_k, int32_t stacks, int32_t renorm, float eps,
+                            quip_stream_t stream);
+int quip_moe_mm_skinny_f16(int32_t mode, const void* x, const void* const* qidxs, const void* grid_packed_abs,
+                           const float* scale, const int32_t* start, void* y, int32_t stacks, int32_t experts, int32_t m,
+                           int32_t pairs, int32_t n, int32_t k, quip_stream_t stream);
+int quip_moe_combine_rows_f16(int32_t mode, const void* t, const void* t2, const void* sv, const void* sv2, const void* su,
+                              const void* residual, void* out, const int32_t* start, const int32_t* pair_of,
+                              const float* weight, int32_t rows, int32_t width, int32_t experts, int32_t top_k, int32_t pairs,
+                              quip_stream_t stream);
 /* Batched E8P12 product for M >= 32 (prompt prefill): fused dequant + MFMA GEMM, y (m, n) = x (m, k) @ W^T with
  * W = decode(qidxs), fp16 in / fp32 accumulation / fp16 out -- the arithmetic of the reference's M >= 32 path
  * (e8p12.py:152-155: decompress_e8p_origorder + `x @ W.T`; origin_order.cu:837-885) without ever materialising W.

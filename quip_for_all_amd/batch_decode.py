@@ -259,7 +259,7 @@ class BatchDecoder:
     def regimes(self):
         """the product path of every module of a block at M = B (QuantLinear.regime)"""
         L0 = self.parent.layers[0]
-        return {k: L0[k].regime(self.batch) for k in PROJECTIONS}
+        return {k: L0[k].regime(self.batch) for k in PROJECTIONS if k in L0}      # (a sparse-MoE model has no gate / up / down)
 
     def step(self):
         """one token for every slot: reads tok / pos, writes the next tokens into tok, advances pos; returns the

@@ -111,6 +111,9 @@ SIGNATURES = {
     "quip_d4_mm_skinny": [_P, _P, _P, _P, _I32, _I32, _I32, _P],
     "quip_hi_mm_skinny": [_P, _P, _P, _I32, _I32, _I32, _P],
     "quip_mm_skinny_group_f16": [_I32, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _F, _P],
+    "quip_moe_route_rows_f16": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P],
+    "quip_moe_mm_skinny_f16": [_I32, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P],
+    "quip_moe_combine_rows_f16": [_I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P],
     "quip_e8p_mm_workspace_bytes": [_I32, _I32, _I32],
     "quip_e8p_mm_origorder_ws": [_P, _P, _P, _P, _I32, _I32, _I32, _P, _c.c_size_t, _P],
     "quip_e8p_planes_bytes": [_I32],

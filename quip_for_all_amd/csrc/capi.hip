@@ -1222,6 +1222,44 @@ int quip_mm_skinny_group_f16(int32_t mode, const void* const* xs, const void* co
   return mm_skinny_group(mode, xs, qidxs, ys, ns, count, m, k, grid, grid2, resid_scale, stream);
 }
 
+// ---- the routed MLP half of a sparse-MoE block (e8p_skinny_moe.hip, moe_rows.hip.h): pointers and alignment here, shapes
+// in the launchers (BAD_SHAPE before UNSUPPORTED)
+int quip_moe_route_rows_f16(const void* h, const void* ln_weight, const void* router_weight, const void* su_gate,
+                            const void* su_up, void* xs, int32_t* start, int32_t* pair_of, float* weight, int32_t rows,
+                            int32_t hidden, int32_t experts, int32_t top_k, int32_t stacks, int32_t renorm, float eps,
+                            quip_stream_t stream) {
+  if (any_null({h, ln_weight, router_weight, xs, start, pair_of, weight})) return QUIP_ERR_NULL_POINTER;
+  if (any_off({h, ln_weight, router_weight, su_gate, su_up, xs}, 15) || any_off({start, pair_of, weight}, 3))
+    return QUIP_ERR_MISALIGNED;
+  return moe_route_rows_launch(h, ln_weight, router_weight, su_gate, su_up, xs, start, pair_of, weight, rows, hidden, experts,
+                               top_k, stacks, renorm, eps, (hipStream_t)stream);
+}
+
+int quip_moe_mm_skinny_f16(int32_t mode, const void* x, const void* const* qidxs, const void* grid, const float* scale,
+                           const int32_t* start, void* y, int32_t stacks, int32_t experts, int32_t m, int32_t pairs,
+                           int32_t n, int32_t k, quip_stream_t stream) {
+  constexpr CodebookId kOfMode[5] = {kE8P, kE8PRVQ4, kD4, kHI, kE8PRVQ3};
+  if (mode < 0 || mode > 4 || stacks < 1 || stacks > 2 || experts < 1 || m < 1 || pairs < 1 || n < 1 || k < 8)
+    return QUIP_ERR_BAD_SHAPE;
+  if (any_null({x, qidxs, grid, scale, start, y})) return QUIP_ERR_NULL_POINTER;
+  for (int g = 0; g < stacks; ++g)
+    if (!qidxs[g]) return QUIP_ERR_NULL_POINTER;
+  if (any_off({x, qidxs[0], qidxs[stacks - 1]}, 15) || any_off({grid}, 7) || any_off({y, scale, start}, 3))
+    return QUIP_ERR_MISALIGNED;
+  return skinny_moe_launch(kOfMode[mode], x, qidxs, grid, scale, start, y, stacks, experts, m, pairs, n, k, (hipStream_t)stream);
+}
+
+int quip_moe_combine_rows_f16(int32_t mode, const void* t, const void* t2, const void* sv, const void* sv2, const void* su,
+                              const void* residual, void* out, const int32_t* start, const int32_t* pair_of,
+                              const float* weight, int32_t rows, int32_t width, int32_t experts, int32_t top_k, int32_t pairs,
+                              quip_stream_t stream) {
+  if (mode < 0 || mode > 1) return QUIP_ERR_BAD_SHAPE;
+  if (any_null({t, out, start}) || (mode == 0 ? any_null({pair_of, weight}) : any_null({t2}))) return QUIP_ERR_NULL_POINTER;
+  if (any_off({t, t2, sv, sv2, su, residual, out}, 15) || any_off({start, pair_of, weight}, 3)) return QUIP_ERR_MISALIGNED;
+  return moe_rows_launch(mode, t, t2, sv, sv2, su, residual, out, start, pair_of, weight, rows, width, experts, top_k, pairs,
+                         (hipStream_t)stream);
+}
+
 int quip_e8p_mm_batched(const void* x, const void* qidxs, const void* grid, void* y, int64_t m, int32_t n, int32_t k,
                         quip_stream_t stream) {
   return mm_batched(kE8P, x, qidxs, {grid}, y, m, n, k, stream);

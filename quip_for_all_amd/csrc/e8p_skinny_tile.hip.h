@@ -1,8 +1,12 @@
 // The tile body of the skinny products: one column tile (CB column blocks of 32) of one matrix, as the header of
-// e8p_skinny_gemm.hip describes it.  Two kernels are made of it: e8p_skinny_gemm_kernel (e8p_skinny_gemm.hip: one tile
-// per workgroup, GROUP = false) and e8p_skinny_group_kernel (e8p_skinny_group.hip: a workgroup walks tiles of 1..3
-// matrices, GROUP = true).  Per tile both issue the same requests in the same order and add the K slices in the same
-// order, so a column's bits do not depend on which of the two computed it.
+// e8p_skinny_gemm.hip describes it.  Three kernels are made of it: e8p_skinny_gemm_kernel (e8p_skinny_gemm.hip: one tile
+// per workgroup, WALK = 0), e8p_skinny_group_kernel (e8p_skinny_group.hip: a workgroup walks tiles of 1..3 matrices whose
+// operands the host names, WALK = 1) and e8p_skinny_moe_kernel (e8p_skinny_moe.hip: a workgroup walks tiles of the experts
+// that own rows, and reads a tile's rows, codes and row count on the device, WALK = 2).  Per tile all issue the same
+// requests in the same order and add the K slices in the same order, so a column's fp32 sum does not depend on which of
+// them computed it.  (The walk of e8p_skinny_moe_kernel was added to this template -- its preamble, its per-tile operands, its
+// epilogue branch and the loop's condition sit behind `if constexpr (WALK == 2)` -- so the two older kernels are compiled
+// from a changed template; their WALK 0 / 1 paths read as before.)
 #pragma once
 #include "quip_device.hip.h"
 #include "launch.hip.h"
@@ -76,14 +80,30 @@ struct SkinnyGroupArgs {
   float resid_scale;
 };
 
+// The routed products of e8p_skinny_moe_kernel: 1..2 stacks of E code matrices (N, K), the rows of X[g] sorted by expert.
+// Expert e owns rows [start[e], start[e + 1]) of every X[g] / Y[g]; start lives on the device, so the launch is the same
+// whichever experts the rows chose.  Y[g][s] = fp16(scale[g, e] * fp16(X[g][s] . decode(q[g][e])))
+struct SkinnyMoeArgs {
+  const f16* x;              // (G, P, K)
+  const uint16_t* q[2];      // (E, N, K / 8) each
+  f16* y;                    // (G, P, N)
+  const int* start;          // (E + 1)
+  const float* scale;        // (G, E)
+  int G, E, P, N;
+  int M;                     // no expert owns more rows than this (MP was chosen for it)
+};
+
 // CB column blocks of 32 per workgroup, 16 / CB slices of K (16 waves); MP = activation rows staged (16 or 32).
-// GROUP = false: the tile (X, Wc, Y, N, first column col0), M <= 32 rows.  GROUP = true: the tiles blockIdx.x,
-// blockIdx.x + gridDim.x, ... of *ga; the tables are built for the first of them and stay
-template <int CB, int MP, int MODE, bool GROUP>
+// WALK = 0 (false): the tile (X, Wc, Y, N, first column col0), M <= 32 rows.  WALK = 1 (true): the tiles blockIdx.x,
+// blockIdx.x + gridDim.x, ... of *ga; the tables are built for the first of them and stay.  WALK = 2: the same walk over
+// the tiles of *ma, numbered (g, j-th expert that owns rows, column tile) with the column tile fastest
+template <int CB, int MP, int MODE, int WALK>
 __device__ __forceinline__ void skinny_tiles(const f16* __restrict__ X, const uint16_t* __restrict__ Wc,
                                              const uint64_t* __restrict__ grid, f16* __restrict__ Y, int M, int N, int K,
                                              float resid_scale, const uint32_t* __restrict__ grid2, int col0,
-                                             const SkinnyGroupArgs* ga) {
+                                             const SkinnyGroupArgs* ga, const SkinnyMoeArgs* ma = nullptr) {
+  constexpr bool GROUP = WALK != 0;
+  static_assert(WALK != 2 || MODE == 0, "the routed walk addresses E8P12 code rows (K / 8 x 2 bytes)");
   constexpr int NCL = (MODE == 1 || MODE == 3 || MODE == 4) ? 2 : 1;     // code loads per lane and unit (16 bytes; MODE 4: 12)
   constexpr int kRep2 = MODE == 4 ? 8 : kSRep;                           // copies of the sign table
   constexpr int kST3 = kST2 + 256 * 8 * 8;                               // MODE 4: the residual table (256 x 4 bytes x 16 copies)
@@ -97,8 +117,38 @@ __device__ __forceinline__ void skinny_tiles(const f16* __restrict__ X, const ui
   const int cb = wave % CB, ks = wave / CB;
   const int n = lane & 31, kb = lane >> 5;
   int tile = (int)blockIdx.x;
+  // WALK 2: which experts own rows (lane e looks at expert e, E <= 64), the tiles there are, the epilogue's scale
+  uint64_t moe_mask = 0;
+  int moe_ne = 0, moe_ctiles = 1, moe_tiles = 0;
+  float moe_scale = 1.f;
+  if constexpr (WALK == 2) {
+    const int rows_e = lane < ma->E ? ma->start[lane + 1] - ma->start[lane] : 0;
+    moe_mask = __ballot(rows_e > 0);
+    moe_ne = __popcll(moe_mask);
+    moe_ctiles = (ma->N + 32 * CB - 1) / (32 * CB);
+    moe_tiles = ma->G * moe_ne * moe_ctiles;
+    if (tile >= moe_tiles) return;     // (the grid is sized for every expert: the workgroups beyond have no tile)
+  }
+  bool more = false;
   do {     // GROUP: the tiles of this workgroup; else left after the one tile
-  if constexpr (GROUP) {
+  if constexpr (WALK == 2) {
+    // an empty expert has no tile: nothing of it is requested.  All of this is uniform (scalar loads and selects)
+    const int ge = tile / moe_ctiles;
+    const int g = ge >= moe_ne ? 1 : 0;
+    uint64_t mk = moe_mask;
+    for (int i = ge - g * moe_ne; i > 0; --i) mk &= mk - 1;
+    const int e = __builtin_ctzll(mk);
+    // clamped so that whatever `start` holds, rows [s0, s0 + M) lie inside the P rows of X[g] and Y[g]
+    const int s0 = min(max(ma->start[e], 0), ma->P - 1);
+    M = min(max(ma->start[e + 1] - s0, 1), min(ma->M, ma->P - s0));
+    N = ma->N;
+    X = ma->x + ((size_t)g * ma->P + s0) * K;
+    Y = ma->y + ((size_t)g * ma->P + s0) * N;
+    Wc = (g == 0 ? ma->q[0] : ma->q[1]) + (size_t)e * N * (K >> 3);
+    col0 = (tile - ge * moe_ctiles) * (32 * CB);
+    moe_scale = ma->scale[g * ma->E + e];
+  }
+  if constexpr (WALK == 1) {
     // (scalar selects, not indexed: the group stays in the kernel arguments)
     const int g = (tile >= ga->tile0[1] ? 1 : 0) + (tile >= ga->tile0[2] ? 1 : 0);
     X = g == 0 ? ga->x[0] : g == 1 ? ga->x[1] : ga->x[2];
@@ -486,7 +536,15 @@ __device__ __forceinline__ void skinny_tiles(const f16* __restrict__ X, const ui
 #pragma unroll
       for (int s2 = 0; s2 < NKS; ++s2) v += red[((s2 * CB + ocb) * 16 + r) * 64 + lane_r];
       const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane_r >> 5);
-      if (row < M && ocol < N) Y[(size_t)row * N + ocol] = (f16)v;
+      if constexpr (WALK == 2) {
+        // the sum rounded as the single launch stores it, then the module's scale: an fp32 product, rounded to fp32, and
+        // only then to fp16 (left to the compiler the two become one v_fma_mixlo_f16, which rounds once)
+        float scaled = (float)(f16)v * moe_scale;
+        asm volatile("" : "+v"(scaled));
+        if (row < M && ocol < N) Y[(size_t)row * N + ocol] = (f16)scaled;
+      } else {
+        if (row < M && ocol < N) Y[(size_t)row * N + ocol] = (f16)v;
+      }
     }
   }
   if constexpr (GROUP) {
@@ -495,7 +553,9 @@ __device__ __forceinline__ void skinny_tiles(const f16* __restrict__ X, const ui
     __syncthreads();
     tile += (int)gridDim.x;
   }
-  } while (GROUP && tile < ga->tile0[3]);
+  if constexpr (WALK == 1) more = tile < ga->tile0[3];
+  if constexpr (WALK == 2) more = tile < moe_tiles;
+  } while (more);
 }
 
 }  // namespace

@@ -161,6 +161,19 @@ int skinny_gemm_launch(CodebookId cb, const void* x, const void* qidxs, const Co
 bool skinny_group_one_block(int n);      // the single launch's rule: one column block of 32 per workgroup (else two)
 int skinny_group_launch(CodebookId cb, const void* const* xs, const void* const* qidxs, const CodebookArgs& a, void* const* ys,
                         const int* ns, int count, int m, int k, hipStream_t stream);
+// The routed MLP half of a sparse-MoE block at 1..31 rows (e8p_skinny_moe.hip, moe_rows.hip.h).  The router and the sort
+// "by expert, then by row" (start (E + 1), pair_of and weight (rows top_k), the signed rows xs (stacks, rows top_k, hidden));
+// the 1..2 products of the sorted rows against the stacked codes of the experts that own rows, y = scale[g, e] x decode^T;
+// mode 0 the weighted sum of a row's pairs onto the residual, mode 1 the SiLU product between gate / up and down
+int moe_route_rows_launch(const void* h, const void* ln, const void* wg, const void* su0, const void* su1, void* xs,
+                          int32_t* start, int32_t* pair_of, float* weight, int rows, int hidden, int experts, int top_k,
+                          int stacks, int renorm, float eps, hipStream_t stream);
+int skinny_moe_launch(CodebookId cb, const void* x, const void* const* qidxs, const void* grid, const float* scale,
+                      const int32_t* start, void* y, int count, int experts, int m, int pairs, int n, int k,
+                      hipStream_t stream);
+int moe_rows_launch(int mode, const void* t, const void* t2, const void* sv, const void* sv2, const void* su,
+                    const void* residual, void* out, const int32_t* start, const int32_t* pair_of, const float* weight,
+                    int rows, int width, int experts, int top_k, int pairs, hipStream_t stream);
 // bf16 / fp32 (and plain fp16) Walsh-Hadamard transform of the last dimension (hadamard_generic.hip)
 int hadamard_generic_launch(const void* x, void* y, int64_t rows, int n, float scale, int dtype, hipStream_t stream);
 // The attention launches (decode_glue.hip and the headers it includes).  They share their operands: q, k (before the

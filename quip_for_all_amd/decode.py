@@ -31,6 +31,7 @@ from . import score as _score  # (defines quip_lib::nll_rows)
 from . import spec as _spec  # (defines quip_lib::spec_draft / spec_accept_draft)
 from . import token_tail as _token_tail  # noqa: F401  (defines quip_lib::block_engine_token)
 from .codebook import codebook_id
+from .moe import QuantMoeMlp  # (defines quip_lib::moe_route_rows / mm_skinny_moe / moe_combine_rows)
 from .qlinear import (QuantLinear, _engine_had3, chain_planes, chain_supported, ffn_engine, ffn_engine_ok, forward_group,
                       fused_in_supported, gemv_chain, gemv_fused, gemv_group_unfused, gemv_unfused, out_transform_group)
 
@@ -50,6 +51,8 @@ class LlamaShape:
     rms_eps: float = 1e-5
     rope_theta: float = 10000.0
     head_dim: int = None      # unset: hidden // heads; Qwen3 sets its own (q and o are heads * head_dim wide, not hidden)
+    n_experts: int = None     # set: the MLP of every block is a sparse MoE (Mixtral) of n_experts (ffn wide each), top_k per token
+    top_k: int = None
 
     def __post_init__(self):
         if self.head_dim is None:
@@ -98,6 +101,20 @@ def random_quant_linear(in_f, out_f, codebook="E8P12", generator=None, device="c
         layer.Wscale.fill_(1.0 / (wrms * math.sqrt(in_f)))
     layer.wscale_float = float(layer.Wscale)      # quantizer.py:836-837
     return layer.to(device).eval()
+
+
+def random_experts(ql, hidden, ffn, n_experts):
+    """n_experts (w1, w3, w2) triples of random QuantLinear from ql(in, out).  The experts of a checkpoint share their Hadamard
+    factors (quant.get_hadK's tables: one per size), so the factors drawn for the first w1 and w2 are copied to the others"""
+    triples = [(ql(hidden, ffn), ql(hidden, ffn), ql(ffn, hidden)) for _ in range(n_experts)]
+    first = (triples[0][0], triples[0][0], triples[0][2])
+    with torch.no_grad():
+        for t in triples:
+            for m, m0 in zip(t, first):
+                for name in ("had_left", "had_right"):
+                    if m is not m0 and getattr(m0, name) is not None:
+                        getattr(m, name).copy_(getattr(m0, name))
+    return triples
 
 
 def tile_codes(qidxs):
@@ -302,8 +319,14 @@ class LlamaDecoder:
         for _ in range(s.layers):
             self.layers.append(dict(
                 ln1=vec(s.hidden), ln2=vec(s.hidden),
-                q=ql(s.hidden, s.q_width), k=ql(s.hidden, kv), v=ql(s.hidden, kv), o=ql(s.q_width, s.hidden),
-                gate=ql(s.hidden, s.ffn), up=ql(s.hidden, s.ffn), down=ql(s.ffn, s.hidden)))
+                q=ql(s.hidden, s.q_width), k=ql(s.hidden, kv), v=ql(s.hidden, kv), o=ql(s.q_width, s.hidden)))
+            if s.n_experts:
+                # Mixtral's block_sparse_moe in place of gate / up / down (moe.py); the router is drawn behind the experts
+                triples = random_experts(ql, s.hidden, s.ffn, s.n_experts)
+                router = (torch.randn(s.n_experts, s.hidden, generator=g) / 4).to(torch.float16).to(self.dev)
+                self.layers[-1]["moe"] = QuantMoeMlp(router, triples, s.top_k)
+            else:
+                self.layers[-1].update(gate=ql(s.hidden, s.ffn), up=ql(s.hidden, s.ffn), down=ql(s.ffn, s.hidden))
             if qk_norm:
                 # per-head RMSNorm of q and k in front of the rotation (Qwen3); drawn behind the block's other parameters,
                 # and only then: without the flag the random stream is untouched
@@ -316,6 +339,9 @@ class LlamaDecoder:
     # architectures whose decoder block is Llama's: RMSNorm (weight only) -> q / k / v (+ bias) -> rotary -> softmax attention
     # -> o -> residual -> RMSNorm -> SiLU-gated MLP -> residual, embeddings and residuals unscaled
     LLAMA_LIKE = ("llama", "mistral", "qwen2", "qwen3")
+    # ... with a sparse-MoE MLP of Mixtral's kind (block_sparse_moe: softmax router, top-k renormalised, w1 / w3 / w2 experts):
+    # served by from_hf on the stage-wise step (QuantMoeMlp); hf_fast keeps to LLAMA_LIKE.  Qwen3-MoE is not in either
+    MOE_LIKE = ("mixtral",)
 
     @classmethod
     def from_hf(cls, model, max_len=256, device=None, assume_llama_like=False, kv_cache=None):
@@ -332,8 +358,8 @@ class LlamaDecoder:
         dev = torch.device(device) if device is not None else next(model.parameters()).device
         self = cls.__new__(cls)
         mt = getattr(cfg, "model_type", "")
-        if mt not in cls.LLAMA_LIKE and not assume_llama_like:
-            raise NotImplementedError(f"model_type {mt!r}: only {cls.LLAMA_LIKE} are known to have Llama's decoder block "
+        if mt not in cls.LLAMA_LIKE + cls.MOE_LIKE and not assume_llama_like:
+            raise NotImplementedError(f"model_type {mt!r}: only {cls.LLAMA_LIKE + cls.MOE_LIKE} are known to have Llama's decoder block "
                                       "(pass assume_llama_like=True if this one does)")
         if getattr(cfg, "hidden_act", "silu") != "silu":
             raise NotImplementedError(f"hidden_act {cfg.hidden_act!r}: the MLP here is SiLU-gated")
@@ -393,9 +419,12 @@ class LlamaDecoder:
             if inv.numel() != head_dim // 2:
                 raise NotImplementedError(f"rotary_emb.inv_freq has {inv.numel()} entries for head_dim {head_dim}")
             inv_freq, att_scale = inv, float(getattr(rot, "attention_scaling", 1.0) or 1.0)
+        moe = mt in cls.MOE_LIKE
         self.s = LlamaShape(hidden=cfg.hidden_size, ffn=cfg.intermediate_size, layers=cfg.num_hidden_layers,
                             heads=heads, kv_heads=getattr(cfg, "num_key_value_heads", heads) or heads,
-                            vocab=cfg.vocab_size, rms_eps=cfg.rms_norm_eps, rope_theta=float(rope), head_dim=int(head_dim))
+                            vocab=cfg.vocab_size, rms_eps=cfg.rms_norm_eps, rope_theta=float(rope), head_dim=int(head_dim),
+                            n_experts=int(cfg.num_local_experts) if moe else None,
+                            top_k=int(cfg.num_experts_per_tok) if moe else None)
         self.dev, self.max_len = dev, max_len
         h16 = lambda t: t.detach().to(device=dev, dtype=torch.float16).contiguous()  # noqa: E731
         self.embed = h16(model.model.embed_tokens.weight)
@@ -404,12 +433,23 @@ class LlamaDecoder:
         self.layers = []
         self.qk_eps = float(cfg.rms_norm_eps)
         for blk, norms in zip(model.model.layers, qk_norms):
-            a, m = blk.self_attn, blk.mlp
-            mods = dict(q=a.q_proj, k=a.k_proj, v=a.v_proj, o=a.o_proj, gate=m.gate_proj, up=m.up_proj, down=m.down_proj)
+            a = blk.self_attn
+            mods = dict(q=a.q_proj, k=a.k_proj, v=a.v_proj, o=a.o_proj)
+            if not moe:
+                mods.update(gate=blk.mlp.gate_proj, up=blk.mlp.up_proj, down=blk.mlp.down_proj)
             for name, mod in mods.items():
                 if not isinstance(mod, QuantLinear):
                     raise TypeError(f"{name}_proj is {type(mod).__name__}, expected QuantLinear")
                 mod.to(dev).eval()
+            if moe:
+                bsm = blk.block_sparse_moe
+                if len(bsm.experts) != self.s.n_experts:
+                    raise NotImplementedError(f"block_sparse_moe has {len(bsm.experts)} experts, num_local_experts = {self.s.n_experts}")
+                for e in bsm.experts:
+                    for w in (e.w1, e.w3, e.w2):
+                        if isinstance(w, QuantLinear):
+                            w.to(dev).eval()
+                mods["moe"] = QuantMoeMlp.from_hf(bsm, top_k=self.s.top_k)
             self.layers.append(dict(ln1=h16(blk.input_layernorm.weight), ln2=h16(blk.post_attention_layernorm.weight),
                                     **mods))
             if norms is not None:
@@ -507,10 +547,17 @@ class LlamaDecoder:
             raise NotImplementedError(f"q_norm / k_norm with head_dim {s.head_dim}: the norm launches serve 64 and 128")
         self.attn_ws = _R.rope_attn_workspace(s.heads, s.head_dim, self.dev) if self.fused_attention else None
         L0 = self.layers[0]
-        qkv0, gu0 = [L0["q"], L0["k"], L0["v"]], [L0["gate"], L0["up"]]
+        # a sparse-MoE MLP (L["moe"]: moe.QuantMoeMlp) runs on the stage-wise step (_block) only: the chain route, the GEMV
+        # prologue, ffn_engine, the persistent launches, the token tail and the _z attention launch have no routed MLP (not
+        # built) and are off on such a model; single_copy and enable_lora are refused by name
+        self.moe = "moe" in L0
+        if self.moe and self.single_copy:
+            raise NotImplementedError("single_copy: not built for a sparse-MoE model (n_experts)")
+        qkv0, gu0 = [L0["q"], L0["k"], L0["v"]], ([] if self.moe else [L0["gate"], L0["up"]])
         planes_ok = all(hasattr(m.codebook, "mm_planes") and m.codebook.planes_supported(m.q_out_features, m.q_in_features)
                         for m in L0.values() if isinstance(m, QuantLinear))
         # stage-wise step (10 launches per block): chain launches where the shapes allow, else the GEMV prologue
+        planes_ok = planes_ok and not self.moe
         self.chain = (planes_ok and os.environ.get("QUIP_CHAIN", "1") != "0"
                       and chain_supported(qkv0, L0["down"]) and chain_supported(gu0, L0["o"]))
         prologue_ok = (planes_ok and fused_in_supported(qkv0, prev=L0["down"]) and fused_in_supported(gu0, prev=L0["o"]))
@@ -523,6 +570,7 @@ class LlamaDecoder:
                         and self.lora is None
                         and all(ffn_engine_ok(L["gate"], L["up"], L["down"]) for L in self.layers))
         self.ffn_ws = _R.ffn_engine_workspace(s.ffn, L0["gate"].K_right, self.dev) if self.ffn_eng else None
+        self.o_fused, self.qkv_fused = self.o_fused and not self.moe, self.qkv_fused and not self.moe
         # all blocks of a token as ONE persistent launch (csrc/decode_block.hip); QUIP_BLOCK_ENGINE=0 keeps the stage-wise step
         # (E8P12; D4 through the same kernel's one-table mode; E8P12RVQ4B, E8P12RVQ3B and HI as rows of twice the virtual width).
         # What _init_block_engine fills in when every block qualifies:
@@ -539,6 +587,7 @@ class LlamaDecoder:
         if ((self.ffn_eng or gqa_shape or (d4 and self.fused_prologue and self.chain and os.environ.get("QUIP_FFN_ENGINE", "1") != "0"))
                 and os.environ.get("QUIP_BLOCK_ENGINE", "1") != "0" and not self.window     # (its attention walks [0, pos])
                 and not self.qk_norm                # (the persistent launches have no q / k norm: not built)
+                and not self.moe                    # (nor a routed MLP)
                 and self.lora is None):             # (nor an adapter branch)
             self._init_block_engine()
         # q / k / v output transforms inside the attention launch (multi-head attention with a power-of-two hidden <= 4096,
@@ -725,8 +774,12 @@ class LlamaDecoder:
     def algorithmic_bytes_per_token(self):
         b = 0
         for L in self.layers:
-            for k in PROJECTIONS:
-                m = L[k]
+            mods = [L[k] for k in PROJECTIONS if k in L]
+            if "moe" in L:
+                # the experts one token streams (top_k of them) and the router
+                mods += list(L["moe"].experts[0]) * L["moe"].top_k
+                b += L["moe"].router.numel() * 2
+            for m in mods:
                 b += qidxs_nbytes(m) + 2 * (m.in_features + m.out_features)
         return b + self.lm_head.numel() * 2
 
@@ -793,6 +846,9 @@ class LlamaDecoder:
             if t is not None:
                 lo.expand("o", t, [h], adapter)
             h = L["o"].forward_fused(a, residual=h)
+            if "moe" in L:
+                # router, routed experts and the residual add: nine launches for up to 31 rows, nothing read by the host
+                return L["moe"].forward_rows(h, L["ln2"], s.rms_eps)
             t = lo.shrink("gu", h, adapter, rms_weight=L["ln2"], rms_eps=s.rms_eps) if lo else None
             g, u = forward_group([L["gate"], L["up"]], h, rms_weight=L["ln2"], rms_eps=s.rms_eps)
             if t is not None:
@@ -811,6 +867,8 @@ class LlamaDecoder:
         changes; with it and no adapter selected, every result keeps its bits."""
         if self.lora is not None:
             raise RuntimeError("enable_lora: already enabled")
+        if self.moe:
+            raise NotImplementedError("enable_lora: adapters on routed experts (n_experts) are not built")
         lora = _lora.LoraState(self, max_adapters, max_rank)
         for L, lay in zip(self.layers, lora.layers):
             L["lora"] = lay
